@@ -6,12 +6,17 @@ process per GPU (BASELINE.json metric; config = configs[2] "8B+ViT-L/14 bf16 ful
     python bench.py --gpus N --steps 5 --warmup 2          (N > 1: starts the N ranks itself as child processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus 2 --dry-run                     (CPU/gloo rehearsal of the launcher only; never a measurement)
+    python bench.py --full                                 (also the roofline, the all-rows form and the CPU baseline)
+    python bench.py --dump-outputs DIR                     (also write what the last timed step computed to DIR/*.npy)
 
 The job's rank count must equal --gpus or the run exits non-zero.
 
-Prints ONE JSON line on rank 0.  `value` = whole-job samples/s with inputs resident in HBM.  `roofline` = bf16 GEMM
-kernel (the dominant kernel: 96 % of the step's FLOPs) measured live with HIP events on the launch stream;
-`cpu_baseline` = the CPU oracle (oracle/ref_cpu.py) timed on the host cores on a bounded slice of the same workload."""
+Prints ONE JSON line on rank 0.  `value` = whole-job samples/s with inputs resident in HBM; `ms_per_step` = wall time of
+one of the --steps timed steps.  A plain run sets up, warms up, times the steps and prints the line; everything else runs
+only with --full, after the timed steps: `roofline` = bf16 GEMM kernel (the dominant kernel: 96 % of the step's FLOPs)
+measured live with HIP events on the launch stream in one extra instrumented step; `config.all_rows_form` = the same step
+with every row through lm_head; `cpu_baseline` = the CPU oracle (oracle/ref_cpu.py) timed on the host cores on a bounded
+slice of the same workload."""
 import argparse
 import json
 import os
@@ -354,6 +359,35 @@ def cpu_baseline(llm, vis, hidden, workload, budget_layers=8, S=1024, B=2):
                          "seconds": sec1, "flops": fl1})
 
 
+def dump_outputs(out_dir, trainer, loss, max_elems=6_000_000):
+    """--dump-outputs: what the last timed training_step computed, as float32 .npy files in `out_dir`:
+        loss.npy     the loss that step returned
+        params.npy   the parameters after that step's AdamW update (sampled)
+        grads.npy    that step's gradients, at the same positions
+    Sample: every parameter tensor in name order contributes min(numel, 4096) positions (fewer when the model has so many
+    tensors that the two arrays would pass `max_elems` elements in all), drawn with a generator seeded by crc32 of the
+    tensor's name -- the same positions from run to run and build to build, whatever the flat buffer's layout."""
+    import zlib
+    import numpy as np
+    trainer.synchronize()            # the last update runs on a side stream, part of it deferred to the next forward
+    torch.cuda.synchronize()
+    flat = trainer.flat
+    segs = sorted(flat.segments, key=lambda s: s.name)
+    per = max(1, min(4096, max_elems // (2 * len(segs))))
+    idx = []
+    for seg in segs:
+        n = seg.end - seg.start
+        g = torch.Generator().manual_seed(zlib.crc32(seg.name.encode()))
+        pos = torch.arange(n) if n <= per else torch.randint(0, n, (per,), generator=g).sort().values
+        idx.append(pos + seg.start)
+    idx = torch.cat(idx).to(flat.data.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"), flat.data[idx].float().cpu().numpy())
+    if flat.grad is not None:
+        np.save(os.path.join(out_dir, "grads.npy"), flat.grad[idx].float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as so:
@@ -409,7 +443,12 @@ def main():
     ap.add_argument("--padded", action="store_true", help="right-padded batch, lengths U[S/2, S] (SURVEY 8d: the key-mask path); "
                                                           "not the headline configuration")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal on CPU/gloo: no model, no kernels, no measurement")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the GEMM roofline (one instrumented step), "
+                                                        "the all-rows form of the step and the CPU baseline (the --no-* options drop one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:          # bare `python bench.py --gpus N`: become the launcher
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -497,6 +536,11 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer, loss)
+        else:
+            trainer.synchronize()
     fps = 3.0 * flops_per_sample(llm, vis, S, n_img, vocab, llm["hidden_size"]) if args.mode == "FULL" else None
     rows = getattr(batch["labels"], "_mm_loss_rows", None) if trainer.loss_rows_only else None
     fps_exec = fps
@@ -519,11 +563,11 @@ def main():
                                                           "the oracle's own bf16 error; a bf16 pipeline cannot meet 1e-3 against fp32)"}}}
     # the instrumented extra step issues the same gradient-exchange collectives as any other step: EVERY rank runs it
     # (rank 0 alone would leave its all-reduces unmatched and hang); only rank 0 reports
-    r = measure_gemm_roofline(trainer, batch) if not args.no_roofline else None
+    r = measure_gemm_roofline(trainer, batch) if args.full and not args.no_roofline else None
     # the same step in HF's form (every row through the last layer's MLP, the final norm, lm_head and the loss), timed beside the
     # headline so that both numbers come from one process on one box: every rank runs it (collectives), rank 0 reports
     all_rows = None
-    if trainer.loss_rows_only and not args.no_all_rows:
+    if args.full and trainer.loss_rows_only and not args.no_all_rows:
         trainer.loss_rows_only = False
         k2 = max(3, args.steps // 2)
         for _ in range(2):
@@ -580,7 +624,7 @@ def main():
                 roof["whole_step_achieved"] = round(step_tf, 2)
                 roof["whole_step_frac"] = round(step_tf / PEAK_BF16_TFLOPS, 4)
             out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del trainer, model, batch, feed
             torch.cuda.empty_cache()
             c = cpu_baseline(llm, vis, llm["hidden_size"], args.workload)

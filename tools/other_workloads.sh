@@ -9,10 +9,10 @@ O=$R/gpurun_out/other_$tag
 mkdir -p $O
 cd $R
 for wl in llama31_8b_vitl14_s4096_b2_4img qwen2_7b_siglip_so400m_s2048_b4 llama32_1b_vitb32_s2048_b4; do
-  timeout -k 10 300 python3 bench.py --workload $wl --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "FAILED $wl"
+  timeout -k 10 300 python3 bench.py --full --workload $wl --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "FAILED $wl"
   echo "$wl: $(cut -c1-220 $O/bench_$wl.json)"
 done
-timeout -k 10 300 python3 bench.py --mode ALIGNMENT --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_alignment.json 2> $O/bench_alignment.err || echo "FAILED alignment"
+timeout -k 10 300 python3 bench.py --full --mode ALIGNMENT --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_alignment.json 2> $O/bench_alignment.err || echo "FAILED alignment"
 echo "alignment: $(cut -c1-220 $O/bench_alignment.json)"
 timeout -k 10 200 python3 tools/attn_bench.py --quick > $O/attn_quick.log 2>&1; cat $O/attn_quick.log
 timeout -k 10 200 python3 tools/attn_bench.py --ab-q > $O/attn_ab_q.log 2>&1; tail -16 $O/attn_ab_q.log

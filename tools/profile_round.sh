@@ -9,9 +9,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/prof_$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py --steps 10 --warmup 3 > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
+timeout -k 10 400 python3 $R/bench.py --full --steps 10 --warmup 3 > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
 echo "unprofiled: $(cut -c1-160 $O/bench_unprofiled.json)"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-all-rows > $O/bench_profiled.json 2> $O/bench_profiled.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-all-rows > $O/bench_profiled.json 2> $O/bench_profiled.err
 csv=$(find $O/stats -name "*kernel_stats.csv" | head -1)
 cp $csv $O/kernel_stats.csv
 python3 $R/tools/prof_summary.py $O/kernel_stats.csv 5 48 > $O/kernel_summary.txt
