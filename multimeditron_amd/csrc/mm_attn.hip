@@ -14,11 +14,9 @@
 // row-major tiles with a 32-byte XOR swizzle chosen so the transposed reads are conflict free.
 //
 // fp32 variants (parity path only) are plain wave-per-query-row kernels.
-#include <stdlib.h>
+#include <string.h>
 
 #include "mm_common.h"
-#include <type_traits>
-#include <string.h>
 
 namespace {
 
@@ -665,66 +663,12 @@ __global__ __launch_bounds__(64) void attn_bwd_f32_kernel(AttnArgs a, int D) {
 }
 
 // ============================================================================================================
-// D = 128 fast path.  8 waves per workgroup (256 query rows / 256 keys), tiles streamed by LDS-DMA into a 2-deep ring
-// with ONE barrier per tile, 2 waves per SIMD so one wave's softmax VALU overlaps the other's MFMAs.
-// Every tile uses ONE LDS image that serves both row fragments (ds_read_b128) and transposed fragments
-// (ds_read_b64_tr_b16): plain 256-byte rows, 16-byte chunk index XOR ((row&3)<<2 | (row>>2)&3); the DMA destination is
-// linear in lane order, so the XOR is applied to the per-lane SOURCE chunk.
+// D = 128 fast path.  8 waves per workgroup, tiles streamed by LDS-DMA into a ring with ONE barrier per tile, 2 waves per
+// SIMD so one wave's softmax VALU overlaps the other's MFMAs.  Every tile is ONE LDS image (image (a), imga_off below) that
+// serves both row fragments (ds_read_b128) and transposed fragments (ds_read_b64_tr_b16).  Forward: attn_fwd128q_kernel
+// (attn_fwd128p_kernel above 256 Ki keys); backward: attn_bwd_dq128p_kernel, then attn_bwd_dkv128_pairp_kernel.  The
+// variants that lost their A/Bs (plain-row image, one-block and resident-fragment dK/dV) are in git history.
 // ============================================================================================================
-__device__ __forceinline__ int imgb_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int imgb_off(int row, int ch) { return 256 * row + 16 * (ch ^ imgb_swz(row)); }
-
-// DMA ROWS rows x 256 B (row stride in elements) starting at matrix row `row0`; 8 waves, ROWS/32 pieces (4 rows) each
-template <int ROWS, int NW = 8, int NWV_UNUSED = 8>
-__device__ __forceinline__ void imgb_dma(unsigned tile_lds, const SRsrc& rs, int64_t stride, int row0) {
-  const int l = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr int PPW = ROWS / (4 * NW);
-  static_assert(PPW >= 1, "tile too small for this many waves");
-  if (w >= NW) return;      // NW < waves in the workgroup: only the first NW waves issue (staggers SIMD partners)
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int pc = w * PPW + i;
-    const int row = pc * 4 + (l >> 4);
-    const int ch = (l & 15) ^ imgb_swz(row);
-    const unsigned voff = (unsigned)(((int64_t)(row0 + row) * stride) * 2 + ch * 16);
-    lds_dma16(rs, voff, tile_lds + pc * 1024);
-  }
-}
-// same, issued by the NW waves of one TEAM: wt = this wave's index inside its team
-template <int ROWS, int NW>
-__device__ __forceinline__ void imgb_dma_team(unsigned tile_lds, const SRsrc& rs, int64_t stride, int row0, int wt) {
-  const int l = threadIdx.x & 63;
-  constexpr int PPW = ROWS / (4 * NW);
-  static_assert(PPW >= 1, "tile too small for this many waves");
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int pc = wt * PPW + i;
-    const int row = pc * 4 + (l >> 4);
-    const int ch = (l & 15) ^ imgb_swz(row);
-    const unsigned voff = (unsigned)(((int64_t)(row0 + row) * stride) * 2 + ch * 16);
-    lds_dma16(rs, voff, tile_lds + pc * 1024);
-  }
-}
-// row fragment (32 rows x 16 k): lane row = r0 + (l&31), k = kstep*16 + 8*(l>>5) .. +7
-__device__ __forceinline__ bf16x8 imgb_rowfrag(const char* tile, int r0, int kstep) {
-  const int l = threadIdx.x & 63;
-  return *(const bf16x8*)(tile + imgb_off(r0 + (l & 31), kstep * 2 + (l >> 5)));
-}
-// fragment of the transposed tile: A[row = column db*32 + (l&31)][k = tile row], k rows kbase..kbase+15 in the
-// accumulator-compatible order (element j of lane half h <-> tile row kbase + 8*(j>>2) + 4*h + (j&3))
-__device__ __forceinline__ bf16x8 imgb_tfrag(const char* tile, int db, int kbase) {
-  const int l = threadIdx.x & 63;
-  const int h = l >> 5, gi = (l >> 4) & 1, i = l & 15, q = i >> 2, p = i & 3;
-  const int row1 = kbase + 4 * h + q;
-  const int ch = db * 4 + gi * 2 + (p >> 1);
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, tile + imgb_off(row1, ch) + 8 * (p & 1)));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, tile + imgb_off(row1 + 8, ch) + 8 * (p & 1)));
-  bf16x8 o;
-  o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-  o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-  return o;
-}
 __device__ __forceinline__ SRsrc rows_rsrc(const bf16* base, int nrows, int64_t stride) {
   return make_srsrc(base, nrows > 0 ? ((int64_t)(nrows - 1) * stride + 128) * 2 : 0);
 }
@@ -779,173 +723,10 @@ __device__ __forceinline__ void attn_work_item(int id, int nblk, int B, int Hq, 
   }
 }
 
-// NWV waves per workgroup (8: 256 query rows, one workgroup per CU; 4: 128 rows, two independent workgroups per CU)
-template <int INW, int NWV>
-__global__ __launch_bounds__(NWV * 64, 2) void attn_fwd128_kernel(AttnArgs a) {
-  constexpr int QB = NWV * 32;
-  constexpr int BKV = 64, NDS = 8, NDB = 4, TILE = BKV * 256;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 stages][K 16 KiB | V 16 KiB]
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, h = l >> 5;
-  int qblk, b, hq;
-  attn_work_item(blockIdx.x, (a.Sq + QB - 1) / QB, a.B, a.Hq, a.Hkv, a.causal != 0, qblk, b, hq);
-  const int hkv = hq / (a.Hq / a.Hkv);
-  const int q0 = qblk * QB + w * 32;
-  const int qi = q0 + (l & 31);
-  const int shift = a.Skv - a.Sq;
-  const bf16* Q = (const bf16*)a.q + b * a.q_sb + hq * a.q_sh;
-  const SRsrc rk = rows_rsrc((const bf16*)a.k + b * a.k_sb + hkv * a.k_sh, a.Skv, a.k_ss);
-  const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-
-  bf16x8 qf[NDS];
-  {
-    const bf16* qrow = qi < a.Sq ? Q + (int64_t)qi * a.q_ss : nullptr;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) qf[ds] = row_frag_global(qrow, ds);
-  }
-  f32x16 o_acc[NDB];
-#pragma unroll
-  for (int i = 0; i < NDB; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-  const float sc = a.scale * LOG2E;
-
-  int ntiles = (a.Skv + BKV - 1) / BKV;
-  if (a.causal) {
-    const int qmax = min(a.Sq - 1, qblk * QB + QB - 1) + shift;
-    ntiles = qmax < 0 ? 0 : min(ntiles, qmax / BKV + 1);
-  }
-  // per-lane source offsets of this wave's DMA pieces, computed ONCE (they were recomputed for every tile: 176 VALU
-  // instructions per issuing wave and tile); a tile only adds its wave-uniform row offset
-  constexpr int PPW = BKV / (4 * INW);
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  unsigned kofs[PPW], vofs[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int row = (wu * PPW + i) * 4 + (l >> 4);
-    const int ch = (l & 15) ^ imgb_swz(row);
-    kofs[i] = (unsigned)((int64_t)row * a.k_ss * 2 + ch * 16);
-    vofs[i] = (unsigned)((int64_t)row * a.v_ss * 2 + ch * 16);
-  }
-  auto issue = [&](int t) {
-    if (wu >= INW) return;                    // only the first INW waves issue (staggers the two waves of every SIMD)
-    const unsigned st = lds0 + (unsigned)((t & 1) * 2 * TILE) + (unsigned)(wu * PPW) * 1024u;
-    const unsigned tk = (unsigned)((int64_t)t * BKV * a.k_ss * 2), tv = (unsigned)((int64_t)t * BKV * a.v_ss * 2);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) lds_dma16(rk, kofs[i] + tk, st + i * 1024);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) lds_dma16(rv, vofs[i] + tv, st + TILE + i * 1024);
-  };
-  if (ntiles > 0) issue(0);
-  for (int t = 0; t < ntiles; ++t) {
-    const int kv0 = t * BKV;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#ifndef MM_ATTN_DIAG_FWD_NODMA
-    if (t + 1 < ntiles) issue(t + 1);
-#endif
-    // wave-uniform skip: this wave's rows are all beyond Sq, or the whole tile lies above its causal diagonal
-    if (q0 >= a.Sq || (a.causal && kv0 > q0 + 31 + shift)) continue;
-    const char* Kt = smem + (t & 1) * 2 * TILE;
-    const char* Vt = Kt + TILE;
-    bool kvalid = (kv0 + l) < a.Skv;
-    if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + kv0 + l] != 0;
-    const unsigned long long kbits = __ballot(kvalid);
-    const bool need_mask = (kbits != ~0ull) || (a.causal && (kv0 + BKV - 1) > (q0 + shift));
-
-    f32x16 s_acc[2];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s_acc[kb][r] = 0.f;
-#ifdef MM_ATTN_DIAG_FWD_NOQK
-      s_acc[kb] = o_acc[kb];
-#else
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds)
-        s_acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Kt, kb * 32, ds), qf[ds], s_acc[kb], 0, 0, 0);
-#endif
-    }
-    __builtin_amdgcn_s_setprio(0);
-    float mx = -INFINITY;
-#ifdef MM_ATTN_DIAG_FWD_NOSM
-    bf16x8 pf[2][2];
-    float alpha = 1.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pf[kb][r >> 3][r & 7] = (bf16)s_acc[kb][r];
-    if (need_mask) l_run += 1.f;
-#else
-    if (need_mask) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kl = kb * 32 + acc_row(r, h);
-          bool ok = (kbits >> kl) & 1ull;
-          if (a.causal) ok = ok && (kv0 + kl) <= (qi + shift);
-          s_acc[kb][r] = ok ? s_acc[kb][r] : -INFINITY;
-        }
-    }
-    mx = swap32_max(rowmax32(s_acc[0], s_acc[1])) * sc;
-    const float m_new = fmaxf(m_run, mx);
-    const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-    float rs = 0.f;
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[kb][r], sc, -m_safe));
-        rs += p;
-        pf[kb][r >> 3][r & 7] = (bf16)p;
-      }
-    l_run = l_run * alpha + rs;
-    m_run = m_new;
-#endif
-#ifdef MM_ATTN_DIAG_FWD_NOPV
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o_acc[r & 3][r] = o_acc[r & 3][r] * alpha + (float)pf[r & 1][(r >> 3) & 1][r & 7] + (float)pf[(r + 1) & 1][(r >> 3) & 1][r & 7];
-#else
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-          o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Vt, db, kb * 32 + s * 16), pf[kb][s], o_acc[db], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-#endif
-  }
-  const float l_tot = swap32_sum(l_run);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  if (qi < a.Sq) {
-    bf16* orow = (bf16*)a.out + (((int64_t)b * a.Sq + qi) * a.Hq + hq) * 128;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)(o_acc[db][rg * 4 + e] * inv);
-        *(bf16x4*)(orow + db * 32 + 8 * rg + 4 * h) = o;
-      }
-    if (h == 0) a.lse[((int64_t)b * a.Hq + hq) * a.Sq + qi] = l_tot > 0.f ? (m_run + log2f(l_tot)) * LN2 : INFINITY;
-  }
-}
-
 // ---- D = 128 forward, 8 waves, fragments PREFETCHED --------------------------------------------------------------------
-// rocprofv3 on attn_fwd128_kernel: MFMA busy 30 %, and halving its VALU count changed nothing.  The ISA showed why: at 246+
-// VGPRs hipcc keeps ONE register quad for the K fragments, so the QK^T phase is `ds_read_b128 -> s_waitcnt lgkmcnt(0) ->
-// v_mfma` sixteen times over: every MFMA (32 cycles) waits out a whole LDS round trip (>100 cycles), and the wave's partner on
+// rocprofv3 on the earlier (plain-row image) forward: MFMA busy 30 %, and halving its VALU count changed nothing.  The ISA
+// showed why: at 246+ VGPRs hipcc keeps ONE register quad for the K fragments, so the QK^T phase is `ds_read_b128 ->
+// s_waitcnt lgkmcnt(0) -> v_mfma` sixteen times over: every MFMA (32 cycles) waits out a whole LDS round trip (>100 cycles), and the wave's partner on
 // the SIMD is in the same phase.  This kernel (same tile, same arithmetic and rounding points, bit-identical results) fixes
 // the two causes:
 //   * LDS image (a) of the guide (8-row x 64-byte subtiles): every fragment address is a per-lane base + a CONSTANT, so the
@@ -1406,312 +1187,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd128q_kernel(AttnArgs a) {
   }
 }
 
-// dK/dV for D = 128: 4 waves x 32 keys, TWO workgroups per CU.  Register diet that makes 2 waves/SIMD fit: V fragments
-// come from an LDS image of the workgroup's 128 keys (not registers) and the Q / dO tiles arrive by LDS-DMA (no staging
-// registers) into a 2-deep ring, one barrier per query tile.
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv128_kernel(AttnArgs a) {
-  constexpr int BQ = 32, NDS = 8, NDB = 4, QT = BQ * 256;            // 8 KiB per 32-row tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Vimg = smem;                                                   // 128 keys x 256 B
-  char* ring = smem + 128 * 256;                                       // [2 stages][Q 8 KiB | dO 8 KiB]
-  float* rowc = (float*)(smem + 128 * 256 + 4 * QT);                   // [2 stages][lse*log2e (32) | delta (32)]
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, h = l >> 5;
-  const int b = blockIdx.z, hkv = blockIdx.y;
-  const int G = a.Hq / a.Hkv;
-  const int kblk = blockIdx.x * 128;
-  const int k0 = kblk + w * 32;
-  const int ki = k0 + (l & 31);
-  const int shift = a.Skv - a.Sq;
-  const bf16* K = (const bf16*)a.k + b * a.k_sb + hkv * a.k_sh;
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-  {
-    const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-    imgb_dma<128, 4>(lds0, rv, a.v_ss, kblk);
-  }
-  bf16x8 kf[NDS];
-  {
-    const bf16* krow = ki < a.Skv ? K + (int64_t)ki * a.k_ss : nullptr;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) kf[ds] = row_frag_global(krow, ds);
-  }
-  bool kvalid = ki < a.Skv;
-  if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + ki] != 0;
-  const float sc = a.scale * LOG2E;
-  f32x16 dk_acc[NDB], dv_acc[NDB];
-#pragma unroll
-  for (int i = 0; i < NDB; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk_acc[i][r] = 0.f; dv_acc[i][r] = 0.f; }
-
-  int qt0 = 0;
-  if (a.causal) qt0 = max(0, kblk - shift) / BQ;
-  const int nqt = (a.Sq + BQ - 1) / BQ;
-  const int per_head = max(0, nqt - qt0);
-  const int niter = per_head * G;
-  const int64_t do_ss = (int64_t)a.Hq * 128;
-  float rc = 0.f;
-  auto issue = [&](int it) {
-    const int g = it / per_head, qb = (qt0 + it % per_head) * BQ;
-    const int hq = hkv * G + g;
-    const SRsrc rq = rows_rsrc((const bf16*)a.q + b * a.q_sb + hq * a.q_sh, a.Sq, a.q_ss);
-    const SRsrc rdo = rows_rsrc((const bf16*)a.dout + ((int64_t)b * a.Sq * a.Hq + hq) * 128, a.Sq, do_ss);
-    const unsigned st = lds0 + 128 * 256 + (unsigned)((it & 1) * 2 * QT);
-    imgb_dma<BQ, 4>(st, rq, a.q_ss, qb);
-    imgb_dma<BQ, 4>(st + QT, rdo, do_ss, qb);
-    if (threadIdx.x < 64) {
-      const int qq = qb + (threadIdx.x & 31);
-      const int64_t ro = ((int64_t)b * a.Hq + hq) * a.Sq + qq;
-      if (threadIdx.x < 32) rc = qq < a.Sq ? a.lse[ro] * LOG2E : INFINITY;
-      else rc = qq < a.Sq ? a.delta[ro] : 0.f;
-    }
-  };
-  if (niter > 0) {
-    issue(0);
-    if (threadIdx.x < 64) rowc[threadIdx.x] = rc;
-  }
-  for (int it = 0; it < niter; ++it) {
-    const int qb = (qt0 + it % per_head) * BQ;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (it + 1 < niter) issue(it + 1);
-    const char* Qt = ring + (it & 1) * 2 * QT;
-    const char* Ot = Qt + QT;
-    const float* rcs = rowc + (it & 1) * 64;
-    // wave-uniform skip: every key of this wave lies above the causal diagonal of every row of this query tile
-    if (!(a.causal && k0 > qb + BQ - 1 + shift)) {
-      f32x16 s_acc, dp_acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s_acc[r] = 0.f; dp_acc[r] = 0.f; }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) {
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Qt, 0, ds), kf[ds], s_acc, 0, 0, 0);
-        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Ot, 0, ds), imgb_rowfrag(Vimg, w * 32, ds), dp_acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      bf16x8 pf[2], dsf[2];
-      // masks only where they can bite: a padded/out-of-range key in this wave, or a tile that touches the diagonal
-      const bool need_mask = (__ballot(kvalid) != ~0ull) || (a.causal && (k0 + 31) > (qb + shift));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ql = acc_row(r, h);
-        float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[r], sc, -rcs[ql]));
-        if (need_mask) {
-          bool ok = kvalid;
-          if (a.causal) ok = ok && ki <= (qb + ql + shift);
-          p = ok ? p : 0.f;
-        }
-        const float dsv = p * (dp_acc[r] - rcs[32 + ql]) * a.scale;
-        pf[r >> 3][r & 7] = (bf16)p;
-        dsf[r >> 3][r & 7] = (bf16)dsv;
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Ot, db, s * 16), pf[s], dv_acc[db], 0, 0, 0);
-          dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Qt, db, s * 16), dsf[s], dk_acc[db], 0, 0, 0);
-        }
-      __builtin_amdgcn_s_setprio(0);
-    }
-    // row constants of the NEXT tile: their ring slot was last read in iteration it-1, which every wave has left
-    if (it + 1 < niter && threadIdx.x < 64) rowc[((it + 1) & 1) * 64 + threadIdx.x] = rc;
-  }
-  if (ki < a.Skv) {
-    bf16* dkrow = (bf16*)a.dk + b * a.k_sb + hkv * a.k_sh + (int64_t)ki * a.k_ss;
-    bf16* dvrow = (bf16*)a.dv + b * a.v_sb + hkv * a.v_sh + (int64_t)ki * a.v_ss;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 ok_, ov_;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          ok_[e] = (bf16)dk_acc[db][rg * 4 + e];
-          ov_[e] = (bf16)dv_acc[db][rg * 4 + e];
-        }
-        *(bf16x4*)(dkrow + db * 32 + 8 * rg + 4 * h) = ok_;
-        *(bf16x4*)(dvrow + db * 32 + 8 * rg + 4 * h) = ov_;
-      }
-  }
-}
-
-// dK/dV for D = 128, balanced form (used when the GQA group size is even).  Under a causal mask key block j meets
-// (nkb - j) query blocks, a 16:1 spread at S = 2048, and with B*Hkv*nkb = 512 items on 512 workgroup slots the launch
-// lasts as long as block 0.  Here ONE workgroup of 8 waves owns the PAIR of key blocks (j, nkb-1-j), processed one after
-// the other, so every workgroup does the same (nkb+1) block-units; its two 4-wave teams split the query heads of the
-// group (team t: heads t*G/2 ..), each with its own Q/dO ring, and their dK/dV accumulators are summed through LDS at
-// the end of a block (fixed order: deterministic, no atomics, no global partials).  One workgroup per CU, 2 waves/SIMD.
-__global__ __launch_bounds__(512, 2) void attn_bwd_dkv128_pair_kernel(AttnArgs a) {
-  constexpr int BQ = 32, NDS = 8, NDB = 4, QT = BQ * 256;            // 8 KiB per 32-row tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Vimg = smem;                                                   // 128 keys x 256 B
-  const int l = threadIdx.x & 63, h = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: LDS-DMA addresses live in SGPRs
-  const int team = w >> 2, wt = w & 3, tt = threadIdx.x & 255;
-  char* ring = smem + 128 * 256 + team * 4 * QT;                       // per team [2 stages][Q 8 KiB | dO 8 KiB]
-  float* red = (float*)(smem + 128 * 256);                             // 64 KiB = both rings, reused for the team sum
-  float* rowc = (float*)(smem + 128 * 256 + 8 * QT) + team * 128;      // per team [2 stages][lse*log2e (32) | delta (32)]
-  const int b = blockIdx.z, hkv = blockIdx.y;
-  const int G = a.Hq / a.Hkv, GH = G / 2;
-  const int nkb = (a.Skv + 127) / 128;
-  const int shift = a.Skv - a.Sq;
-  const bf16* K = (const bf16*)a.k + b * a.k_sb + hkv * a.k_sh;
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-  const unsigned ring0 = lds0 + 128 * 256 + (unsigned)(team * 4 * QT);
-  const float sc = a.scale * LOG2E;
-  const int nqt = (a.Sq + BQ - 1) / BQ;
-  const int64_t do_ss = (int64_t)a.Hq * 128;
-
-  for (int pass = 0; pass < 2; ++pass) {
-    const int kb = pass == 0 ? (int)blockIdx.x : nkb - 1 - (int)blockIdx.x;
-    if (pass == 1 && kb <= (int)blockIdx.x) break;                    // odd count: the middle block has no partner
-    const int kblk = kb * 128;
-    const int k0 = kblk + wt * 32;
-    const int ki = k0 + (l & 31);
-    {
-      const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-      imgb_dma<128, 8>(lds0, rv, a.v_ss, kblk);
-    }
-    bf16x8 kf[NDS];
-    {
-      const bf16* krow = ki < a.Skv ? K + (int64_t)ki * a.k_ss : nullptr;
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) kf[ds] = row_frag_global(krow, ds);
-    }
-    bool kvalid = ki < a.Skv;
-    if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + ki] != 0;
-    f32x16 dk_acc[NDB], dv_acc[NDB];
-#pragma unroll
-    for (int i = 0; i < NDB; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk_acc[i][r] = 0.f; dv_acc[i][r] = 0.f; }
-
-    int qt0 = 0;
-    if (a.causal) qt0 = max(0, kblk - shift) / BQ;
-    const int per_head = max(0, nqt - qt0);
-    const int niter = per_head * GH;                                   // the same count for both teams
-    float rc = 0.f;
-    auto issue = [&](int it) {
-      const int g = team * GH + it / per_head, qb = (qt0 + it % per_head) * BQ;
-      const int hq = hkv * G + g;
-      const SRsrc rq = rows_rsrc((const bf16*)a.q + b * a.q_sb + hq * a.q_sh, a.Sq, a.q_ss);
-      const SRsrc rdo = rows_rsrc((const bf16*)a.dout + ((int64_t)b * a.Sq * a.Hq + hq) * 128, a.Sq, do_ss);
-      const unsigned st = ring0 + (unsigned)((it & 1) * 2 * QT);
-      imgb_dma_team<BQ, 4>(st, rq, a.q_ss, qb, wt);
-      imgb_dma_team<BQ, 4>(st + QT, rdo, do_ss, qb, wt);
-      if (tt < 64) {
-        const int qq = qb + (tt & 31);
-        const int64_t ro = ((int64_t)b * a.Hq + hq) * a.Sq + qq;
-        if (tt < 32) rc = qq < a.Sq ? a.lse[ro] * LOG2E : INFINITY;
-        else rc = qq < a.Sq ? a.delta[ro] : 0.f;
-      }
-    };
-    if (niter > 0) {
-      issue(0);
-      if (tt < 64) rowc[tt] = rc;
-    }
-    for (int it = 0; it < niter; ++it) {
-      const int qb = (qt0 + it % per_head) * BQ;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (it + 1 < niter) issue(it + 1);
-      const char* Qt = ring + (it & 1) * 2 * QT;
-      const char* Ot = Qt + QT;
-      const float* rcs = rowc + (it & 1) * 64;
-      if (!(a.causal && k0 > qb + BQ - 1 + shift)) {
-        f32x16 s_acc, dp_acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s_acc[r] = 0.f; dp_acc[r] = 0.f; }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ds = 0; ds < NDS; ++ds) {
-          s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Qt, 0, ds), kf[ds], s_acc, 0, 0, 0);
-          dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Ot, 0, ds), imgb_rowfrag(Vimg, wt * 32, ds), dp_acc, 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        bf16x8 pf[2], dsf[2];
-        const bool need_mask = (__ballot(kvalid) != ~0ull) || (a.causal && (k0 + 31) > (qb + shift));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ql = acc_row(r, h);
-          float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[r], sc, -rcs[ql]));
-          if (need_mask) {
-            bool ok = kvalid;
-            if (a.causal) ok = ok && ki <= (qb + ql + shift);
-            p = ok ? p : 0.f;
-          }
-          const float dsv = p * (dp_acc[r] - rcs[32 + ql]) * a.scale;
-          pf[r >> 3][r & 7] = (bf16)p;
-          dsf[r >> 3][r & 7] = (bf16)dsv;
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Ot, db, s * 16), pf[s], dv_acc[db], 0, 0, 0);
-            dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Qt, db, s * 16), dsf[s], dk_acc[db], 0, 0, 0);
-          }
-        __builtin_amdgcn_s_setprio(0);
-      }
-      if (it + 1 < niter && tt < 64) rowc[((it + 1) & 1) * 64 + tt] = rc;
-    }
-    // ---- sum the two teams' accumulators through LDS (team 1 writes, team 0 adds: fixed order), then team 0 stores
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                                   // every wave has left the rings and the V image
-    float* mine = red + (wt * 64) * 64 + l;                            // [wave-in-team][64 values][lane]
-    if (team == 1) {
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[(db * 16 + r) * 64] = dk_acc[db][r];
-    }
-    __syncthreads();
-    if (team == 0) {
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dk_acc[db][r] += mine[(db * 16 + r) * 64];
-    }
-    __syncthreads();
-    if (team == 1) {
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[(db * 16 + r) * 64] = dv_acc[db][r];
-    }
-    __syncthreads();
-    if (team == 0) {
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv_acc[db][r] += mine[(db * 16 + r) * 64];
-      if (ki < a.Skv) {
-        bf16* dkrow = (bf16*)a.dk + b * a.k_sb + hkv * a.k_sh + (int64_t)ki * a.k_ss;
-        bf16* dvrow = (bf16*)a.dv + b * a.v_sb + hkv * a.v_sh + (int64_t)ki * a.v_ss;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            bf16x4 ok_, ov_;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              ok_[e] = (bf16)dk_acc[db][rg * 4 + e];
-              ov_[e] = (bf16)dv_acc[db][rg * 4 + e];
-            }
-            *(bf16x4*)(dkrow + db * 32 + 8 * rg + 4 * h) = ok_;
-            *(bf16x4*)(dvrow + db * 32 + 8 * rg + 4 * h) = ov_;
-          }
-      }
-    }
-    __syncthreads();                                                   // `red` is free again before the next pass's DMA
-  }
-}
-
-// dK/dV for D = 128, paired key blocks, with prefetched fragments.  attn_bwd_dkv128_pair_kernel's ISA had the same disease as
-// the forward (every MFMA behind its own ds_read + lgkmcnt(0), one register quad for all fragments) and a worse one: the 32 row
+// dK/dV for D = 128, paired key blocks, with prefetched fragments.  The earlier (plain-row image) pair kernel's ISA had the
+// same disease as the forward (every MFMA behind its own ds_read + lgkmcnt(0), one register quad for all fragments) and a worse one: the 32 row
 // constants (lse, delta) of a query tile were fetched by 17 ds_read2_b32, each followed by lgkmcnt(0) -- 17 dependent LDS
 // round trips per 32-MFMA iteration; rocprofv3: waves parked 69 % of their cycles.  Here (same arithmetic and rounding, results
 // bit-identical):
@@ -1980,515 +1457,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv128_pairp_kernel(AttnArgs 
   }
 }
 
-// dK/dV for D = 128 with the wave's K and V row fragments RESIDENT in registers (round 4; mm_set_option "attn_dkv_res").
-// attn_bwd_dkv128_pairp_kernel is LDS-port-bound: 19.5 M LDS instructions per launch at B4 S2048 = 77 % of the port's cycles, 48 fragment
-// reads per 32 MFMAs, 16 of them the SAME K / V rows of the wave's 32 keys in every iteration -- and all 256 registers of its
-// two-waves-per-SIMD budget are in use (244 VGPRs), so those fragments cannot stay there.  Here a workgroup is ONE team of four waves, one
-// wave per SIMD with the SIMD's 512 registers: 128 accumulators + 64 of resident K / V fragments + the transients; the team walks ALL the
-// (query head, query tile) items of its key-block pair (the pair kernel's two teams take half each), so the grid is the same and there is
-// no team sum at the end.  32 fragment reads per 32 MFMAs, four waves at the LDS port instead of eight.  Same products and roundings per
-// item; the items of a key block are accumulated in ONE head-major sequence instead of two halves added at the end (low-order bits of
-// dK / dV differ from the pair kernel's; every test compares against the oracle / the fixtures).
-template <int RD>
-__global__ __launch_bounds__(256) void attn_bwd_dkv128_res_kernel(AttnArgs a) {
-  constexpr int BQ = 32, NDB = 4, QT = BQ * 256, IMG = 128 * 256;     // 8 KiB per 32-row tile, 32 KiB per 128-key image
-  extern __shared__ __attribute__((aligned(16))) char smem[];          // [V image | K image | 2 stages x (Q | dO) | row constants]
-  const int l = threadIdx.x & 63, h = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: LDS-DMA addresses live in SGPRs
-  const int wt = w, tt = threadIdx.x;
-  float* rowc = (float*)(smem + 2 * IMG + 4 * QT);                     // [2 stages][lse*log2e (32) | delta (32)]
-  // 1-D grid, XCD-aware: the hardware deals consecutive workgroup ids to the 8 XCDs in turn, and the `npair` workgroups of one
-  // (batch, KV head) stream the SAME Q / dO rows (G heads x Sq x 512 B).  With a (pair, head, batch) grid those workgroups sat
-  // on 8 different XCDs, every L2 saw each tile once and the kernel pulled 4.5x its algorithmic bytes from beyond L2.  Here
-  // group g = (b, hkv) lives on XCD g % 8 and its pairs fill that XCD's consecutive slots (needs B * Hkv % 8 == 0, else the
-  // plain order).
-  const int npair = (((a.Skv + 127) / 128) + 1) / 2, ngroup = a.B * a.Hkv;
-  int pair_i, grp;
-  if ((ngroup & 7) == 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    pair_i = slot % npair;
-    grp = (slot / npair) * 8 + xcd;
-  } else {
-    pair_i = blockIdx.x % npair;
-    grp = blockIdx.x / npair;
-  }
-  const int b = grp / a.Hkv, hkv = grp % a.Hkv;
-  const int G = a.Hq / a.Hkv;
-  const int nkb = (a.Skv + 127) / 128;
-  const int shift = a.Skv - a.Sq;
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-  const unsigned ring0 = lds0 + 2 * IMG;
-  const float sc = a.scale * LOG2E;
-  const int nqt = (a.Sq + BQ - 1) / BQ;
-  const int64_t do_ss = (int64_t)a.Hq * 128;
-  const ImgaBases bases = imga_bases(smem, 0);
-  // per-lane bases: key images at this wave's 32 keys (row fragments), this team's ring (row + transposed fragments)
-  const char* vrow[2] = {bases.kr[0] + 2048 * 4 * wt, bases.kr[1] + 2048 * 4 * wt};
-  const char* ring_r[2] = {bases.kr[0] + 2 * IMG, bases.kr[1] + 2 * IMG};
-  const char* ring_t[2] = {bases.vt[0] + 2 * IMG, bases.vt[1] + 2 * IMG};
-  // DMA source patterns (image (a)): a 1-KiB piece = 8 rows x 128 B, lane pattern s = (piece >> 1) & 1
-  unsigned lk[2], lv[2], lq, ldo;
-  imga_lane_patterns(lk, lv, a.k_ss, a.v_ss);
-  {
-    const int rl = (l >> 2) & 7, cl = 4 * (l >> 5) + ((l & 3) ^ (((wt & 1) << 1) | ((l >> 4) & 1)));   // this wave's ring pieces: 2wt, 2wt+1
-    lq = (unsigned)((int64_t)rl * a.q_ss * 2 + cl * 16);
-    ldo = (unsigned)((int64_t)rl * do_ss * 2 + cl * 16);
-  }
-
-  for (int pass = 0; pass < 2; ++pass) {
-    const int kb = pass == 0 ? pair_i : nkb - 1 - pair_i;
-    if (pass == 1 && kb <= pair_i) break;                    // odd count: the middle block has no partner
-    const int kblk = kb * 128;
-    const int k0 = kblk + wt * 32;
-    const int ki = k0 + (l & 31);
-    {   // V and K images of the 128 keys: 32 pieces each, 8 per wave (four waves)
-      const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-      const SRsrc rk = rows_rsrc((const bf16*)a.k + b * a.k_sb + hkv * a.k_sh, a.Skv, a.k_ss);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int pc = w * 8 + i, prow = kblk + 8 * (pc >> 1);
-        lds_dma16(rv, lv[(i >> 1) & 1] + (unsigned)((int64_t)prow * a.v_ss * 2 + (i & 1) * 128), lds0 + pc * 1024);
-        lds_dma16(rk, lk[(i >> 1) & 1] + (unsigned)((int64_t)prow * a.k_ss * 2 + (i & 1) * 128), lds0 + IMG + pc * 1024);
-      }
-    }
-    bool kvalid = ki < a.Skv;
-    if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + ki] != 0;
-    f32x16 dk_acc[NDB], dv_acc[NDB];
-#pragma unroll
-    for (int i = 0; i < NDB; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk_acc[i][r] = 0.f; dv_acc[i][r] = 0.f; }
-
-    int qt0 = 0;
-    if (a.causal) qt0 = max(0, kblk - shift) / BQ;
-    const int per_head = max(0, nqt - qt0);
-    // the group's (query head, query tile) items in head-major order: all of them
-    const int total = per_head * G, niter = total;
-    constexpr int item0 = 0;
-    float rc = 0.f;
-    auto issue = [&](int it) {
-      const int idx = item0 + it;
-      if (idx >= total || (MM_DKV_DIAG & 1)) return;
-      const int g = idx / per_head, qb = (qt0 + idx % per_head) * BQ;
-      const int hq = hkv * G + g;
-      const SRsrc rq = rows_rsrc((const bf16*)a.q + b * a.q_sb + hq * a.q_sh, a.Sq, a.q_ss);
-      const SRsrc rdo = rows_rsrc((const bf16*)a.dout + ((int64_t)b * a.Sq * a.Hq + hq) * 128, a.Sq, do_ss);
-      const unsigned st = ring0 + (unsigned)((it & 1) * 2 * QT) + (unsigned)(wt * 2) * 1024u;
-      const int prow = qb + 8 * wt;                                    // this wave's two pieces of each tile: rows 8wt .. 8wt+7
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        lds_dma16(rq, lq + (unsigned)((int64_t)prow * a.q_ss * 2 + i * 128), st + i * 1024);
-        lds_dma16(rdo, ldo + (unsigned)((int64_t)prow * do_ss * 2 + i * 128), st + QT + i * 1024);
-      }
-      if (tt < 64) {
-        const int qq = qb + (tt & 31);
-        const int64_t ro = ((int64_t)b * a.Hq + hq) * a.Sq + qq;
-        if (tt < 32) rc = qq < a.Sq ? a.lse[ro] * LOG2E : INFINITY;
-        else rc = qq < a.Sq ? a.delta[ro] : 0.f;
-      }
-    };
-    if (niter > 0) {
-      issue(0);
-      if (tt < 64) rowc[tt] = rc;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the images (and the first tile) have landed ...
-    __builtin_amdgcn_s_barrier();                                      // ... in every wave
-    bf16x8 kres[8], vres[8];                                           // this wave's 32 keys: K / V rows x 16 d per fragment, the whole pass
-#pragma unroll
-    for (int ds = 0; ds < 8; ++ds) {
-      kres[ds] = *(const bf16x8*)(vrow[ds & 1] + IMG + 512 * (ds >> 1));
-      vres[ds] = *(const bf16x8*)(vrow[ds & 1] + 512 * (ds >> 1));
-    }
-    for (int it = 0; it < niter; ++it) {
-      const int qb = (qt0 + (item0 + it) % per_head) * BQ;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (!(MM_DKV_DIAG & 32)) __builtin_amdgcn_s_barrier();
-      // The next tile's DMA (4 pieces per wave) is NOT issued here: in front of the S / dP products it shares the LDS path with
-      // their 32 fragment reads and costs 100-185 cycles per piece (timing build without the DMA: -25 % kernel time).  It is
-      // issued after those products, in front of the VALU-only dS segment (MI355X_MICROARCH.md: 25-60 cycles there).  Its ring
-      // slot was last read in iteration it - 1, which every wave of the team left before this barrier.
-      bool issued = false;
-      if (it + 1 < niter) { issue(it + 1); issued = true; }
-      const int so = (it & 1) * 2 * QT;
-      const float* rcs = rowc + (it & 1) * 64;
-      if (item0 + it < total && !(a.causal && k0 > qb + BQ - 1 + shift)) {
-        // fragment j of the 32 that come from LDS: j < 16: k-step j >> 1, kind j & 1 (0: Q rows, 1: dO rows);
-        //                       j >= 16: d block (j - 16) >> 2, 16-query step ((j - 16) >> 1) & 1, kind (j & 1) (0: dO^T, 1: Q^T)
-        auto frag = [&](int j) -> bf16x8 {
-          if (j < 16) {
-            const int ds = j >> 1, a2 = ds & 1, off = 512 * (ds >> 1);
-            if ((j & 1) == 0) return *(const bf16x8*)(ring_r[a2] + so + off);
-            return *(const bf16x8*)(ring_r[a2] + so + QT + off);
-          }
-          const int jj = j - 16, db = jj >> 2, s16 = (jj >> 1) & 1, kind = jj & 1;
-          const int off = so + (kind == 0 ? QT : 0) + 4096 * s16 + 512 * db;
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, ring_t[0] + off));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, ring_t[1] + off));
-          bf16x8 o;
-          o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-          o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-          return o;
-        };
-        // ONE fresh fragment per MFMA (Q rows for S^T = K Q^T, dO rows for dP^T = V dO^T; K / V rows are resident): RD slots, LA in flight
-        constexpr int LA = RD == 8 ? 6 : 3;
-        f32x16 s_acc, dp_acc;
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        bf16x8 fr[RD];                                                 // ring: fragment j lives in fr[j % RD]
-#pragma unroll
-        for (int j = 0; j < LA; ++j) fr[j] = frag(j);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {                                 // MFMA m uses fragment m and the resident fragment of k-step m >> 1
-          if (m & 1) dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], vres[m >> 1], m > 1 ? dp_acc : zero16, 0, 0, 0);
-          else s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], kres[m >> 1], m > 1 ? s_acc : zero16, 0, 0, 0);
-          if (m + LA < 20) fr[(m + LA) % RD] = frag(m + LA);           // (the last steps fetch the first four transposed fragments, 16 .. 19)
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        // row constants of the lane's 16 query rows: rows 8g + 4h + (0..3), g = 0..3 -> 4 + 4 vectors of 16 bytes
-        f32x4 lsev[4], dltv[4];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          lsev[g4] = *(const f32x4*)(rcs + 8 * g4 + 4 * h);
-          dltv[g4] = *(const f32x4*)(rcs + 32 + 8 * g4 + 4 * h);
-        }
-        bf16x8 pf[2], dsf[2];
-        if (MM_DKV_DIAG & 2) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { pf[r >> 3][r & 7] = (bf16)s_acc[r]; dsf[r >> 3][r & 7] = (bf16)(dp_acc[r] + lsev[r >> 2][r & 3] + dltv[r >> 2][r & 3]); }
-        } else {
-        const bool need_mask = (__ballot(kvalid) != ~0ull) || (a.causal && (k0 + 31) > (qb + shift));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ql = acc_row(r, h);
-          float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[r], sc, -lsev[r >> 2][r & 3]));
-          if (need_mask) {
-            bool ok = kvalid;
-            if (a.causal) ok = ok && ki <= (qb + ql + shift);
-            p = ok ? p : 0.f;
-          }
-          const float dsv = p * (dp_acc[r] - dltv[r >> 2][r & 3]) * a.scale;
-          pf[r >> 3][r & 7] = (bf16)p;
-          dsf[r >> 3][r & 7] = (bf16)dsv;
-        }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {                                 // fragment 16 + m: d block m >> 2, query step (m >> 1) & 1
-          const int db = m >> 2, s16 = (m >> 1) & 1;
-          if (m & 1) dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(16 + m) % RD], dsf[s16], dk_acc[db], 0, 0, 0);
-          else dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(16 + m) % RD], pf[s16], dv_acc[db], 0, 0, 0);
-          if (16 + m + 4 < 32) fr[(16 + m + 4) % RD] = frag(16 + m + 4);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-      }
-      if (!issued && it + 1 < niter) issue(it + 1);                     // a wave that skipped the tile (or the early-issue build)
-      if (it + 1 < niter && tt < 64) rowc[((it + 1) & 1) * 64 + tt] = rc;
-    }
-    // ---- every wave stores the dK / dV rows of its 32 keys
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                                   // every wave has left the ring and the images (the next pass overwrites them)
-    {
-      if (ki < a.Skv) {
-        bf16* dkrow = (bf16*)a.dk + b * a.k_sb + hkv * a.k_sh + (int64_t)ki * a.k_ss;
-        bf16* dvrow = (bf16*)a.dv + b * a.v_sb + hkv * a.v_sh + (int64_t)ki * a.v_ss;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            bf16x4 ok_, ov_;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              ok_[e] = (bf16)dk_acc[db][rg * 4 + e];
-              ov_[e] = (bf16)dv_acc[db][rg * 4 + e];
-            }
-            *(bf16x4*)(dkrow + db * 32 + 8 * rg + 4 * h) = ok_;
-            *(bf16x4*)(dvrow + db * 32 + 8 * rg + 4 * h) = ov_;
-          }
-      }
-    }
-    __syncthreads();                                                   // `red` is free again before the next pass's DMA
-  }
-}
-
-// The same with the items software-pipelined inside the wave (mm_set_option "attn_dkv_res" = 2): iteration `it` runs the S^T / dP^T products
-// of item it + 1 INTERLEAVED with the exp / dS arithmetic of item it (one MFMA, then one of the 16 accumulator elements: the vector ALU works in
-// the matrix pipe's shadow), then the dV / dK products of item it.  The ring has three stages (item it for the transposed fragments, it + 1 for
-// the row fragments, it + 2 landing); fully masked (head, tile) items are not skipped (their p is 0: the sums are unchanged).
-// 4 bytes per lane straight into LDS (lane l lands at lds_addr + 4 l): the row constants of the pipelined dK/dV kernel travel like its tiles,
-// so that no compiler-visible load (and the s_waitcnt vmcnt(0) that would come with its use) sits inside the item loop
-__device__ __forceinline__ void lds_dma4(const SRsrc& r, unsigned voff, unsigned lds_addr) {
-  u32x4 d = {r.w0, r.w1, r.w2, r.w3};
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 4\n\t"
-      "buffer_load_dword %1, %3, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(lds_addr), "s"(d)
-      : "memory");
-}
-
-template <int RD>
-__global__ __launch_bounds__(256) void attn_bwd_dkv128_resp_kernel(AttnArgs a) {
-  constexpr int BQ = 32, NDB = 4, QT = BQ * 256, IMG = 128 * 256;     // 8 KiB per 32-row tile, 32 KiB per 128-key image
-  constexpr int NST = 5, LAT = 4;                                      // ring stages; tiles requested ahead (tile it + LAT during iteration it)
-  extern __shared__ __attribute__((aligned(16))) char smem[];          // [V image | K image | NST stages x (Q | dO) | NST x row constants (lse 32, -, delta 32, -)]
-  const int l = threadIdx.x & 63, h = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: LDS-DMA addresses live in SGPRs
-  const int wt = w, tt = threadIdx.x;
-  const unsigned lds0_early = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-  float* rowc = (float*)(smem + 2 * IMG + NST * 2 * QT);               // [NST stages][lse (32) | unused (32) | delta (32) | unused (32)] floats
-  const unsigned rowc_lds = lds0_early + 2 * IMG + NST * 2 * QT;
-  // 1-D grid, XCD-aware: the hardware deals consecutive workgroup ids to the 8 XCDs in turn, and the `npair` workgroups of one
-  // (batch, KV head) stream the SAME Q / dO rows (G heads x Sq x 512 B).  With a (pair, head, batch) grid those workgroups sat
-  // on 8 different XCDs, every L2 saw each tile once and the kernel pulled 4.5x its algorithmic bytes from beyond L2.  Here
-  // group g = (b, hkv) lives on XCD g % 8 and its pairs fill that XCD's consecutive slots (needs B * Hkv % 8 == 0, else the
-  // plain order).
-  const int npair = (((a.Skv + 127) / 128) + 1) / 2, ngroup = a.B * a.Hkv;
-  int pair_i, grp;
-  if ((ngroup & 7) == 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    pair_i = slot % npair;
-    grp = (slot / npair) * 8 + xcd;
-  } else {
-    pair_i = blockIdx.x % npair;
-    grp = blockIdx.x / npair;
-  }
-  const int b = grp / a.Hkv, hkv = grp % a.Hkv;
-  const int G = a.Hq / a.Hkv;
-  const int nkb = (a.Skv + 127) / 128;
-  const int shift = a.Skv - a.Sq;
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-  const unsigned ring0 = lds0 + 2 * IMG;
-  const float sc = a.scale * LOG2E;
-  const int nqt = (a.Sq + BQ - 1) / BQ;
-  const int64_t do_ss = (int64_t)a.Hq * 128;
-  const ImgaBases bases = imga_bases(smem, 0);
-  // per-lane bases: key images at this wave's 32 keys (row fragments), this team's ring (row + transposed fragments)
-  const char* vrow[2] = {bases.kr[0] + 2048 * 4 * wt, bases.kr[1] + 2048 * 4 * wt};
-  const char* ring_r[2] = {bases.kr[0] + 2 * IMG, bases.kr[1] + 2 * IMG};
-  const char* ring_t[2] = {bases.vt[0] + 2 * IMG, bases.vt[1] + 2 * IMG};
-  // DMA source patterns (image (a)): a 1-KiB piece = 8 rows x 128 B, lane pattern s = (piece >> 1) & 1
-  unsigned lk[2], lv[2], lq, ldo;
-  imga_lane_patterns(lk, lv, a.k_ss, a.v_ss);
-  {
-    const int rl = (l >> 2) & 7, cl = 4 * (l >> 5) + ((l & 3) ^ (((wt & 1) << 1) | ((l >> 4) & 1)));   // this wave's ring pieces: 2wt, 2wt+1
-    lq = (unsigned)((int64_t)rl * a.q_ss * 2 + cl * 16);
-    ldo = (unsigned)((int64_t)rl * do_ss * 2 + cl * 16);
-  }
-
-  for (int pass = 0; pass < 2; ++pass) {
-    const int kb = pass == 0 ? pair_i : nkb - 1 - pair_i;
-    if (pass == 1 && kb <= pair_i) break;                    // odd count: the middle block has no partner
-    const int kblk = kb * 128;
-    const int k0 = kblk + wt * 32;
-    const int ki = k0 + (l & 31);
-    {   // V and K images of the 128 keys: 32 pieces each, 8 per wave (four waves)
-      const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-      const SRsrc rk = rows_rsrc((const bf16*)a.k + b * a.k_sb + hkv * a.k_sh, a.Skv, a.k_ss);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int pc = w * 8 + i, prow = kblk + 8 * (pc >> 1);
-        lds_dma16(rv, lv[(i >> 1) & 1] + (unsigned)((int64_t)prow * a.v_ss * 2 + (i & 1) * 128), lds0 + pc * 1024);
-        lds_dma16(rk, lk[(i >> 1) & 1] + (unsigned)((int64_t)prow * a.k_ss * 2 + (i & 1) * 128), lds0 + IMG + pc * 1024);
-      }
-    }
-    bool kvalid = ki < a.Skv;
-    if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + ki] != 0;
-    f32x16 dk_acc[NDB], dv_acc[NDB];
-#pragma unroll
-    for (int i = 0; i < NDB; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk_acc[i][r] = 0.f; dv_acc[i][r] = 0.f; }
-
-    int qt0 = 0;
-    if (a.causal) qt0 = max(0, kblk - shift) / BQ;
-    const int per_head = max(0, nqt - qt0);
-    // the group's (query head, query tile) items in head-major order: all of them
-    const int total = per_head * G, niter = total;
-    constexpr int item0 = 0;
-    // (head, tile) of the next item to request / to compute: counters instead of idx / per_head and idx % per_head -- two scalar divisions per
-    // item are ~100 instructions that a wave alone on its SIMD cannot hide
-    int is_g = 0, is_q = 0, cq = 0;
-    auto issue = [&](int it) {
-      const int idx = item0 + it;
-      if (idx >= total || (MM_DKV_DIAG & 1)) return;
-      const int g = is_g, qb = (qt0 + is_q) * BQ;
-      if (++is_q == per_head) { is_q = 0; ++is_g; }
-      const int hq = hkv * G + g;
-      const SRsrc rq = rows_rsrc((const bf16*)a.q + b * a.q_sb + hq * a.q_sh, a.Sq, a.q_ss);
-      const SRsrc rdo = rows_rsrc((const bf16*)a.dout + ((int64_t)b * a.Sq * a.Hq + hq) * 128, a.Sq, do_ss);
-      const unsigned st = ring0 + (unsigned)((it % NST) * 2 * QT) + (unsigned)(wt * 2) * 1024u;
-      const int prow = qb + 8 * wt;                                    // this wave's two pieces of each tile: rows 8wt .. 8wt+7
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        lds_dma16(rq, lq + (unsigned)((int64_t)prow * a.q_ss * 2 + i * 128), st + i * 1024);
-        lds_dma16(rdo, ldo + (unsigned)((int64_t)prow * do_ss * 2 + i * 128), st + QT + i * 1024);
-      }
-      if (w == 0) {                                                    // the tile's 32 lse and 32 delta values: two 4-byte-per-lane DMAs (lanes >= 32 out of range)
-        const SRsrc rl = make_srsrc((const float*)a.lse + ((int64_t)b * a.Hq + hq) * a.Sq, (int64_t)a.Sq * 4);      // rows >= Sq read 0 (their Q / dO rows are 0 too)
-        const SRsrc rd = make_srsrc((const float*)a.delta + ((int64_t)b * a.Hq + hq) * a.Sq, (int64_t)a.Sq * 4);
-        const unsigned vo = l < 32 ? (unsigned)(qb + l) * 4u : 0x80000000u;
-        lds_dma4(rl, vo, rowc_lds + (unsigned)((it % NST) * 512));
-        lds_dma4(rd, vo, rowc_lds + (unsigned)((it % NST) * 512 + 256));
-      }
-    };
-#pragma unroll
-    for (int j = 0; j < LAT; ++j)
-      if (j < niter) issue(j);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the images and the first tiles have landed ...
-    __builtin_amdgcn_s_barrier();                                      // ... in every wave
-    bf16x8 kres[8], vres[8];                                           // this wave's 32 keys: K / V rows x 16 d per fragment, the whole pass
-#pragma unroll
-    for (int ds = 0; ds < 8; ++ds) {
-      kres[ds] = *(const bf16x8*)(vrow[ds & 1] + IMG + 512 * (ds >> 1));
-      vres[ds] = *(const bf16x8*)(vrow[ds & 1] + 512 * (ds >> 1));
-    }
-    constexpr int LA = RD == 8 ? 6 : 3;
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 s_cur = zero16, dp_cur = zero16;
-    // row fragment j (< 16) of the tile in ring stage offset `sr`: k-step j >> 1, kind j & 1 (0: Q rows, 1: dO rows);
-    // transposed fragment j (>= 16) of the tile at `stt`: d block (j - 16) >> 2, 16-query step ((j - 16) >> 1) & 1, kind j & 1 (0: dO^T, 1: Q^T)
-    // (the stage offsets are added to the four lane bases ONCE per item -- rr0 / rr1 / rt0 / rt1 below --, so that every read is base + constant:
-    // with `ring + stage + offset` per read the compiler spent two vector adds on each of the 32 transposed reads of an item)
-    const char *rr0 = ring_r[0], *rr1 = ring_r[1], *rt0 = ring_t[0], *rt1 = ring_t[1];
-    auto frag = [&](int j, int, int) -> bf16x8 {
-      if (j < 16) {
-        const int ds = j >> 1, off = 512 * (ds >> 1);
-        const char* rb = (ds & 1) ? rr1 : rr0;
-        if ((j & 1) == 0) return *(const bf16x8*)(rb + off);
-        return *(const bf16x8*)(rb + QT + off);
-      }
-      const int jj = j - 16, db = jj >> 2, s16 = (jj >> 1) & 1, kind = jj & 1;
-      const int off = (kind == 0 ? QT : 0) + 4096 * s16 + 512 * db;
-      const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, rt0 + off));
-      const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(bf16x4, rt1 + off));
-      bf16x8 o;
-      o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-      o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-      return o;
-    };
-    bf16x8 fr[RD];                                                     // ring: fragment j lives in fr[j % RD]
-    if (niter > 0) {                                                   // pipeline prologue: S^T / dP^T of item 0
-#pragma unroll
-      for (int j = 0; j < LA; ++j) fr[j] = frag(j, 0, 0);
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        if (m & 1) dp_cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], vres[m >> 1], m > 1 ? dp_cur : zero16, 0, 0, 0);
-        else s_cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], kres[m >> 1], m > 1 ? s_cur : zero16, 0, 0, 0);
-        if (m + LA < 16) fr[(m + LA) % RD] = frag(m + LA, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    for (int it = 0; it < niter; ++it) {
-      const int qb = (qt0 + cq) * BQ;
-      if (++cq == per_head) cq = 0;
-      // tile it + 1 has landed: what is younger than it in this wave's queue are tiles it + 2 .. it + LAT - 1 (4 DMA pieces each, 6 in wave 0)
-      {
-        const int young = min(niter, it + LAT) - min(niter, it + 2);
-        if (young >= 2) { if (w == 0) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-        else if (young == 1) { if (w == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();                                    // ... in every wave, and every wave has left iteration it - 1 (stage (it + LAT) % NST is free)
-      if (it + LAT < niter) issue(it + LAT);
-      const bool nxt = it + 1 < niter;
-      const int so_c = (it % NST) * 2 * QT, so_n = ((it + 1) % NST) * 2 * QT;
-      rr0 = ring_r[0] + so_n; rr1 = ring_r[1] + so_n; rt0 = ring_t[0] + so_c; rt1 = ring_t[1] + so_c;
-      const float* rcs = rowc + (it % NST) * 128;
-      // row constants of the lane's 16 query rows: rows 8g + 4h + (0..3), g = 0..3 -> 4 + 4 vectors of 16 bytes (read four at a time inside the
-      // element loop instead: 0.683 vs 0.670 ms, the reads then sit on the critical path)
-      f32x4 lsev[4], dltv[4];
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        lsev[g4] = *(const f32x4*)(rcs + 8 * g4 + 4 * h) * LOG2E;
-        dltv[g4] = *(const f32x4*)(rcs + 64 + 8 * g4 + 4 * h);
-      }
-      f32x16 s_nxt = zero16, dp_nxt = zero16;
-      bf16x8 pf[2], dsf[2];
-      // fragment sequence of this iteration: 0 .. 15 = row fragments of item it + 1 (when there is one), 16 .. 31 = transposed fragments of item it
-      if (nxt) {
-#pragma unroll
-        for (int j = 0; j < LA; ++j) fr[j] = frag(j, so_n, so_c);
-      }
-      __builtin_amdgcn_s_setprio(1);
-      // (branch-free bodies: a scalar branch per element ends the basic block, and the compiler then waits lgkmcnt(0) -- the whole fragment
-      // ring -- in front of every MFMA; the mask is a select, and `nxt` picks one of two instantiations per iteration)
-      const bool causal_b = a.causal != 0;
-      const bool need_mask = (__ballot(kvalid) != ~0ull) || (a.causal && (k0 + 31) > (qb + shift));     // wave-uniform: most tiles need none
-      auto bc = [&](auto nxt_c, auto mask_c) {
-        constexpr bool NXT = decltype(nxt_c)::value, MASK = decltype(mask_c)::value;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {                                 // one product of item it + 1, then one accumulator element of item it
-          if constexpr (NXT) {
-            if (m & 1) dp_nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], vres[m >> 1], m > 1 ? dp_nxt : zero16, 0, 0, 0);
-            else s_nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[m % RD], kres[m >> 1], m > 1 ? s_nxt : zero16, 0, 0, 0);
-            if (m + LA < 16) fr[(m + LA) % RD] = frag(m + LA, so_n, so_c);
-          }
-          if (m + LA >= 16 && m + LA < 16 + LA) fr[(m + LA) % RD] = frag(m + LA, so_n, so_c);   // the first LA transposed fragments of item it
-          {
-            const int r = m;
-            float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_cur[r], sc, -lsev[r >> 2][r & 3]));
-            if constexpr (MASK) {
-              const int ql = acc_row(r, h);
-              const bool ok = kvalid && (!causal_b || ki <= (qb + ql + shift));
-              p = ok ? p : 0.f;
-            }
-            const float dsv = p * (dp_cur[r] - dltv[r >> 2][r & 3]) * a.scale;
-            pf[r >> 3][r & 7] = (bf16)p;
-            dsf[r >> 3][r & 7] = (bf16)dsv;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      };
-      if (nxt) { if (need_mask) bc(std::true_type{}, std::true_type{}); else bc(std::true_type{}, std::false_type{}); }
-      else { if (need_mask) bc(std::false_type{}, std::true_type{}); else bc(std::false_type{}, std::false_type{}); }
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {                                   // fragment 16 + m: d block m >> 2, query step (m >> 1) & 1
-        const int db = m >> 2, s16 = (m >> 1) & 1;
-        if (m & 1) dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(16 + m) % RD], dsf[s16], dk_acc[db], 0, 0, 0);
-        else dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[(16 + m) % RD], pf[s16], dv_acc[db], 0, 0, 0);
-        if (16 + m + LA < 32) fr[(16 + m + LA) % RD] = frag(16 + m + LA, so_n, so_c);      // (LA = 6 ahead: a transposed fragment is two LDS reads, ~200 cycles)
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      s_cur = s_nxt;
-      dp_cur = dp_nxt;
-    }
-    // ---- every wave stores the dK / dV rows of its 32 keys
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                                   // every wave has left the ring and the images (the next pass overwrites them)
-    {
-      if (ki < a.Skv) {
-        bf16* dkrow = (bf16*)a.dk + b * a.k_sb + hkv * a.k_sh + (int64_t)ki * a.k_ss;
-        bf16* dvrow = (bf16*)a.dv + b * a.v_sb + hkv * a.v_sh + (int64_t)ki * a.v_ss;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            bf16x4 ok_, ov_;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              ok_[e] = (bf16)dk_acc[db][rg * 4 + e];
-              ov_[e] = (bf16)dv_acc[db][rg * 4 + e];
-            }
-            *(bf16x4*)(dkrow + db * 32 + 8 * rg + 4 * h) = ok_;
-            *(bf16x4*)(dvrow + db * 32 + 8 * rg + 4 * h) = ov_;
-          }
-      }
-    }
-    __syncthreads();                                                   // `red` is free again before the next pass's DMA
-  }
-}
-
 // dQ for D = 128 with prefetched fragments (same treatment as attn_fwd128p_kernel: image (a), base + constant addressing, a
-// 4-deep fragment ring; same arithmetic and rounding as attn_bwd_dq128_kernel, bit-identical results).  Per 32-key step the
-// wave reads 16 row fragments (K for S^T = K.Q^T, V for dP^T = V.dO^T) and 8 transposed K fragments (dQ^T += K^T.dS^T) -- all
+// 4-deep fragment ring; same arithmetic and rounding as the earlier plain-row-image dQ kernel, bit-identical results).  Per
+// 32-key step the wave reads 16 row fragments (K for S^T = K.Q^T, V for dP^T = V.dO^T) and 8 transposed K fragments (dQ^T += K^T.dS^T) -- all
 // 24 are one ring sequence, so the transposed fragments travel under the exponentials.
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq128p_kernel(AttnArgs a) {
   constexpr int BKV = 64, NDS = 8, NDB = 4, TILE = BKV * 256;
@@ -2607,117 +1578,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq128p_kernel(AttnArgs a) {
         dq_acc[(j - 16) >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[j % RD], dsf[(j - 16) & 1], dq_acc[(j - 16) >> 1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_s_setprio(0);
-    }
-  }
-  if (qi < a.Sq) {
-    bf16* drow = (bf16*)a.dq + b * a.q_sb + hq * a.q_sh + (int64_t)qi * a.q_ss;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)dq_acc[db][rg * 4 + e];
-        *(bf16x4*)(drow + db * 32 + 8 * rg + 4 * h) = o;
-      }
-  }
-}
-
-// dQ for D = 128: same shape as the forward fast path (8 waves, 256 query rows, K/V tiles by LDS-DMA, one barrier per
-// tile).  The single K image serves the row fragments of S^T = K.Q^T and the transposed fragments of dQ^T += K^T.dS^T.
-template <int INW>
-__global__ __launch_bounds__(512, 2) void attn_bwd_dq128_kernel(AttnArgs a) {
-  constexpr int BKV = 64, NDS = 8, NDB = 4, TILE = BKV * 256;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 stages][K 16 KiB | V 16 KiB]
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, h = l >> 5;
-  int qblk, b, hq;
-  attn_work_item(blockIdx.x, (a.Sq + 255) / 256, a.B, a.Hq, a.Hkv, a.causal != 0, qblk, b, hq);
-  const int hkv = hq / (a.Hq / a.Hkv);
-  const int q0 = qblk * 256 + w * 32;
-  const int qi = q0 + (l & 31);
-  const int shift = a.Skv - a.Sq;
-  const bf16* Q = (const bf16*)a.q + b * a.q_sb + hq * a.q_sh;
-  const bf16* dO = (const bf16*)a.dout + ((int64_t)b * a.Sq * a.Hq + hq) * 128;
-  const SRsrc rk = rows_rsrc((const bf16*)a.k + b * a.k_sb + hkv * a.k_sh, a.Skv, a.k_ss);
-  const SRsrc rv = rows_rsrc((const bf16*)a.v + b * a.v_sb + hkv * a.v_sh, a.Skv, a.v_ss);
-  const unsigned lds0 = (unsigned)(uintptr_t)LDS_PTR(char, smem);
-
-  bf16x8 qf[NDS], dof[NDS];
-  {
-    const bf16* qrow = qi < a.Sq ? Q + (int64_t)qi * a.q_ss : nullptr;
-    const bf16* drow = qi < a.Sq ? dO + (int64_t)qi * a.Hq * 128 : nullptr;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) {
-      qf[ds] = row_frag_global(qrow, ds);
-      dof[ds] = row_frag_global(drow, ds);
-    }
-  }
-  const float sc = a.scale * LOG2E;
-  float lse2 = INFINITY, dlt = 0.f;
-  if (qi < a.Sq) {
-    lse2 = a.lse[((int64_t)b * a.Hq + hq) * a.Sq + qi] * LOG2E;
-    dlt = a.delta[((int64_t)b * a.Hq + hq) * a.Sq + qi];
-  }
-  f32x16 dq_acc[NDB];
-#pragma unroll
-  for (int i = 0; i < NDB; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq_acc[i][r] = 0.f;
-
-  int ntiles = (a.Skv + BKV - 1) / BKV;
-  if (a.causal) {
-    const int qmax = min(a.Sq - 1, qblk * 256 + 255) + shift;
-    ntiles = qmax < 0 ? 0 : min(ntiles, qmax / BKV + 1);
-  }
-  auto issue = [&](int t) {
-    const unsigned st = lds0 + (unsigned)((t & 1) * 2 * TILE);
-    imgb_dma<BKV, INW>(st, rk, a.k_ss, t * BKV);
-    imgb_dma<BKV, INW>(st + TILE, rv, a.v_ss, t * BKV);
-  };
-  if (ntiles > 0) issue(0);
-  for (int t = 0; t < ntiles; ++t) {
-    const int kv0 = t * BKV;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (t + 1 < ntiles) issue(t + 1);
-    if (q0 >= a.Sq || (a.causal && kv0 > q0 + 31 + shift)) continue;
-    const char* Kt = smem + (t & 1) * 2 * TILE;
-    const char* Vt = Kt + TILE;
-    bool kvalid = (kv0 + l) < a.Skv;
-    if (kvalid && a.kmask) kvalid = a.kmask[(int64_t)b * a.Skv + kv0 + l] != 0;
-    const unsigned long long kbits = __ballot(kvalid);
-    const bool need_mask = (kbits != ~0ull) || (a.causal && (kv0 + BKV - 1) > (q0 + shift));
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      f32x16 s_acc, dp_acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s_acc[r] = 0.f; dp_acc[r] = 0.f; }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) {
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Kt, kb * 32, ds), qf[ds], s_acc, 0, 0, 0);
-        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_rowfrag(Vt, kb * 32, ds), dof[ds], dp_acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      bf16x8 dsf[2];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[r], sc, -lse2));
-        if (need_mask) {
-          const int kl = kb * 32 + acc_row(r, h);
-          bool ok = (kbits >> kl) & 1ull;
-          if (a.causal) ok = ok && (kv0 + kl) <= (qi + shift);
-          p = ok ? p : 0.f;
-        }
-        dsf[r >> 3][r & 7] = (bf16)(p * (dp_acc[r] - dlt) * a.scale);
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-          dq_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(imgb_tfrag(Kt, db, kb * 32 + s * 16), dsf[s], dq_acc[db], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
     }
   }
@@ -3057,146 +1917,47 @@ __global__ void attn_decode_merge_kernel(const float* ws, int nsplit, bf16* out)
   out[(int64_t)row * D + d] = decode_merge_one<D>(ws + (int64_t)row * nsplit * (D + 2), nsplit, d);
 }
 
-int g_attn_fwd_waves = 8;     // waves per workgroup of the D=128 forward (mm_set_option "attn_fwd_waves": 8 or 4)
-int g_attn_fwd_pf = 1;        // D=128 forward with prefetched fragments (attn_fwd128p_kernel; mm_set_option "attn_fwd_pf" 0 = the older kernel)
-int g_attn_fwd_q = 1;         // D=128 forward with the two waves of a SIMD out of phase (attn_fwd128q_kernel; "attn_fwd_q" 0 = attn_fwd128p_kernel)
-int g_attn_dkv_late = 0;      // paired dK/dV kernel: next tile's DMA issued after the S/dP products ("attn_dkv_late" 0 = at the barrier)
-int g_attn_dkv_rd = 8;        // fragment ring slots of attn_bwd_dkv128_pairp_kernel ("attn_dkv_rd": 8 or 4)
-int g_attn_q_issue = 4;       // waves issuing the K/V DMA in attn_fwd128q_kernel ("attn_q_issue": 4 or 8)
-int g_attn_q_rd = 4;          // fragment ring depth of attn_fwd128q_kernel ("attn_q_rd": 4, 6 or 8)
 int g_attn_diag = 0;          // AttnArgs::diag ("attn_diag")
 int g_attn_q_prio = 1;        // s_setprio policy of the out-of-phase kernels (AttnArgs::prio; "attn_q_prio")
 int g_attn_decode_mfma = 1;   // D = 128, G <= 4 decode slices with the scores on MFMA (mm_set_option "attn_decode_mfma"; 0 = attn_decode_partial_kernel)
 int g_attn_decode_wgs = 768;  // workgroups mm_attn_decode_splits aims at (~3 per CU; mm_set_option "attn_decode_wgs")
-int g_attn_dkv_res = 0;       // dK/dV with resident K / V fragments, one wave per SIMD (mm_set_option "attn_dkv_res")
-int g_attn_dkv_pair = 1;      // balanced paired dK/dV kernel (mm_set_option "attn_dkv_pair"; 0 = one key block per workgroup)
-int g_attn_issue_waves = 4;   // waves issuing the K/V DMA in the 8-wave D=128 kernels (mm_set_option "attn_issue_waves")
 
-static bool attn_use_v1() {
-  static const bool v1 = [] { const char* e = getenv("MM_ATTN_KERNEL"); return e && e[0] == 'v'; }();
-  return v1;
+// the D = 128 kernels: 8 waves, dynamic LDS above the 64 KiB default, 1-D grid (the kernel orders its work items)
+template <typename Kernel>
+void launch128(Kernel kern, int64_t nwg, size_t lds, const AttnArgs& a, hipStream_t s) {
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, a);
 }
 
 template <int D>
 int launch_bf16_fwd(const AttnArgs& a, hipStream_t s) {
-  if (D == 128 && !attn_use_v1() && g_attn_fwd_pf && g_attn_fwd_q && g_attn_fwd_waves == 8 && a.Skv <= 256 * 1024) {
-    const size_t lds = 4 * 2 * 64 * 256 + (size_t)((a.Skv + 63) / 64) * 8;       // K/V ring + key-valid bits
+  if constexpr (D == 128) {
     const int64_t nwg = (int64_t)((a.Sq + 255) / 256) * a.Hq * a.B;
     if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-    auto launch = [&](auto kern) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, a);
-    };
-    if (g_attn_q_rd == 8) launch(attn_fwd128q_kernel<8, 4>);
-    else if (g_attn_q_rd == 6) launch(attn_fwd128q_kernel<6, 4>);
-    else if (g_attn_q_issue == 8) launch(attn_fwd128q_kernel<4, 8>);
-    else launch(attn_fwd128q_kernel<4, 4>);
-    MM_CHECK_LAUNCH();
-    return MM_OK;
+    // attn_fwd128q_kernel keeps 8 B of key-valid bits per 64-key tile in LDS beside its 4-slot K/V ring; above 256 Ki keys
+    // they no longer fit, and attn_fwd128p_kernel (3-slot ring, no bits in LDS) is the only kernel that runs for those inputs
+    if (a.Skv <= 256 * 1024) launch128(attn_fwd128q_kernel<4, 4>, nwg, 4 * 2 * 64 * 256 + (size_t)((a.Skv + 63) / 64) * 8, a, s);
+    else launch128(attn_fwd128p_kernel, nwg, 3 * 2 * 64 * 256, a, s);
+  } else {
+    const size_t lds = 2 * 64 * D * 2;
+    dim3 grid((a.Sq + 127) / 128, a.Hq, a.B), block(256);
+    hipLaunchKernelGGL(attn_fwd_kernel<D>, grid, block, lds, s, a);
   }
-  if (D == 128 && !attn_use_v1() && g_attn_fwd_pf && g_attn_fwd_waves == 8) {
-    const size_t lds = 3 * 2 * 64 * 256;
-    const int64_t nwg = (int64_t)((a.Sq + 255) / 256) * a.Hq * a.B;
-    if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-    (void)hipFuncSetAttribute((const void*)attn_fwd128p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_fwd128p_kernel, dim3((unsigned)nwg), dim3(512), lds, s, a);
-    return MM_OK;
-  }
-  if (D == 128 && !attn_use_v1()) {
-    const size_t lds = 2 * 2 * 64 * 256;
-    const int qb = g_attn_fwd_waves * 32;
-    const int64_t nwg = (int64_t)((a.Sq + qb - 1) / qb) * a.Hq * a.B;     // 1-D grid: attn_work_item orders the blocks
-    if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-    dim3 grid((unsigned)nwg), block(g_attn_fwd_waves * 64);
-#define MM_FWD128(...)                                                                                                  \
-  do {                                                                                                                  \
-    auto kfn = attn_fwd128_kernel<__VA_ARGS__>;                                                                         \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-    hipLaunchKernelGGL(kfn, grid, block, lds, s, a);                                                                    \
-  } while (0)
-    if (g_attn_fwd_waves == 4) MM_FWD128(4, 4);
-    else if (g_attn_issue_waves == 4) MM_FWD128(4, 8);
-    else MM_FWD128(8, 8);
-#undef MM_FWD128
-    return MM_OK;
-  }
-  const size_t lds = 2 * 64 * D * 2;
-  dim3 grid((a.Sq + 127) / 128, a.Hq, a.B), block(256);
-  hipLaunchKernelGGL(attn_fwd_kernel<D>, grid, block, lds, s, a);
   return MM_OK;
 }
 template <int D>
 int launch_bf16_bwd(const AttnArgs& a, hipStream_t s) {
-  if (D == 128 && !attn_use_v1()) {
-    const size_t lds = 2 * 2 * 64 * 256;
-    const int64_t nwg = (int64_t)((a.Sq + 255) / 256) * a.Hq * a.B;     // 1-D grid: attn_work_item orders the blocks
-    if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-    dim3 grid((unsigned)nwg), block(512);
-    if (g_attn_fwd_pf) {
-      const size_t lds3 = 3 * 2 * 64 * 256;
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq128p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      hipLaunchKernelGGL(attn_bwd_dq128p_kernel, grid, block, lds3, s, a);
-    } else if (g_attn_issue_waves == 4) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(attn_bwd_dq128_kernel<4>, grid, block, lds, s, a);
-    } else {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(attn_bwd_dq128_kernel<8>, grid, block, lds, s, a);
-    }
+  if constexpr (D == 128) {
+    const int64_t nwg_q = (int64_t)((a.Sq + 255) / 256) * a.Hq * a.B;
+    const int nkb = (a.Skv + 127) / 128;
+    const int64_t nwg_kv = (int64_t)((nkb + 1) / 2) * a.Hkv * a.B;       // one workgroup per key-block pair, any GQA group size
+    if (nwg_q > 0x7FFFFFFF || nwg_kv > 0x7FFFFFFF) return MM_ERR_ARG;
+    launch128(attn_bwd_dq128p_kernel, nwg_q, 3 * 2 * 64 * 256, a, s);
+    launch128(attn_bwd_dkv128_pairp_kernel<8, false>, nwg_kv, 2 * 128 * 256 + 8 * 32 * 256 + 4 * 64 * sizeof(float), a, s);  // V + K images, rings, row constants
   } else {
-    const size_t lds = 3 * 64 * D * 2;
-    dim3 grid((a.Sq + 127) / 128, a.Hq, a.B), block(256);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, grid, block, lds, s, a);
-  }
-  if (D == 128 && !attn_use_v1()) {
-    if ((((a.Hq / a.Hkv) & 1) == 0 || g_attn_fwd_pf) && g_attn_dkv_pair) {      // the prefetching pair kernel splits any group size
-      const int nkb = (a.Skv + 127) / 128;
-      dim3 grid((nkb + 1) / 2, a.Hkv, a.B), block(512);
-      if (g_attn_fwd_pf) {
-        const int64_t nwg = (int64_t)((nkb + 1) / 2) * a.Hkv * a.B;       // 1-D: the kernel deals (pair, head, batch) XCD-aware
-        if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-        grid = dim3((unsigned)nwg);
-        const size_t lds = 2 * 128 * 256 + 8 * 32 * 256 + 4 * 64 * sizeof(float);      // V + K images, rings, row constants
-        auto launch = [&](auto kern) {
-          (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-        };
-        if (g_attn_dkv_res) {                                              // K / V fragments resident, four waves (attn_bwd_dkv128_res_kernel)
-          if (g_attn_dkv_res == 2) {                                       // ... with the items pipelined inside the wave (three ring stages)
-            const size_t lds_p = 2 * 128 * 256 + 5 * 2 * 32 * 256 + 5 * 512;
-            if (g_attn_dkv_rd == 4) {                                     // ("attn_dkv_rd" 4: a 4-slot fragment ring, 3 in flight)
-              auto kern = attn_bwd_dkv128_resp_kernel<4>;
-              (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-              hipLaunchKernelGGL(kern, grid, dim3(256), lds_p, s, a);
-            } else {
-              auto kern = attn_bwd_dkv128_resp_kernel<8>;
-              (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-              hipLaunchKernelGGL(kern, grid, dim3(256), lds_p, s, a);
-            }
-          } else {
-            const size_t lds_r = 2 * 128 * 256 + 4 * 32 * 256 + 2 * 64 * sizeof(float);
-            auto kern = attn_bwd_dkv128_res_kernel<8>;
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds_r, s, a);
-          }
-        } else if (g_attn_dkv_rd == 4) launch(attn_bwd_dkv128_pairp_kernel<4, false>);
-        else if (g_attn_dkv_late) launch(attn_bwd_dkv128_pairp_kernel<8, true>);
-        else launch(attn_bwd_dkv128_pairp_kernel<8, false>);
-      } else {
-        const size_t lds = 128 * 256 + 8 * 32 * 256 + 4 * 64 * sizeof(float);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dkv128_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(attn_bwd_dkv128_pair_kernel, grid, block, lds, s, a);
-      }
-    } else {
-      const size_t lds = 128 * 256 + 4 * 32 * 256 + 2 * 64 * sizeof(float);
-      dim3 grid((a.Skv + 127) / 128, a.Hkv, a.B), block(256);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(attn_bwd_dkv128_kernel, grid, block, lds, s, a);
-    }
-  } else {
-    const size_t lds = 4 * 32 * D * 2 + 64 * sizeof(float);
-    dim3 grid((a.Skv + 127) / 128, a.Hkv, a.B), block(256);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, grid, block, lds, s, a);
+    const size_t lds_dq = 3 * 64 * D * 2, lds_dkv = 4 * 32 * D * 2 + 64 * sizeof(float);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, dim3((a.Sq + 127) / 128, a.Hq, a.B), dim3(256), lds_dq, s, a);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, dim3((a.Skv + 127) / 128, a.Hkv, a.B), dim3(256), lds_dkv, s, a);
   }
   return MM_OK;
 }
@@ -3204,26 +1965,11 @@ int launch_bf16_bwd(const AttnArgs& a, hipStream_t s) {
 }  // namespace
 
 int mm_attn_option(const char* name, int value) {   // reached through mm_set_option (mm_gemm.hip)
-  if (!strcmp(name, "attn_dkv_pair")) { g_attn_dkv_pair = value != 0; return MM_OK; }
-  if (!strcmp(name, "attn_dkv_res")) { if (value < 0 || value > 2) return MM_ERR_ARG; g_attn_dkv_res = value; return MM_OK; }
   if (!strcmp(name, "attn_decode_mfma")) { g_attn_decode_mfma = value != 0; return MM_OK; }
   if (!strcmp(name, "attn_decode_wgs")) { if (value < 1) return MM_ERR_ARG; g_attn_decode_wgs = value; return MM_OK; }
-  if (!strcmp(name, "attn_fwd_pf")) { g_attn_fwd_pf = value != 0; return MM_OK; }
-  if (!strcmp(name, "attn_fwd_q")) { g_attn_fwd_q = value != 0; return MM_OK; }
   if (!strcmp(name, "attn_q_prio")) { g_attn_q_prio = value; return MM_OK; }
-  if (!strcmp(name, "attn_dkv_late")) { g_attn_dkv_late = value != 0; return MM_OK; }
-  if (!strcmp(name, "attn_dkv_rd")) { g_attn_dkv_rd = value == 4 ? 4 : 8; return MM_OK; }
-  if (!strcmp(name, "attn_q_issue")) { g_attn_q_issue = value == 4 ? 4 : 8; return MM_OK; }
-  if (!strcmp(name, "attn_q_rd")) { g_attn_q_rd = value; return MM_OK; }
   if (!strcmp(name, "attn_diag")) { g_attn_diag = value; return MM_OK; }
-  if (!strcmp(name, "attn_fwd_waves")) { if (value != 4 && value != 8) return MM_ERR_ARG; g_attn_fwd_waves = value; return MM_OK; }
   return MM_ERR_ARG;
-}
-
-extern "C" int mm_attn_set_issue_waves(int v) {
-  if (v != 4 && v != 8) return MM_ERR_ARG;
-  g_attn_issue_waves = v;
-  return MM_OK;
 }
 
 static int check_common(int dtype, int B, int Sq, int Skv, int Hq, int Hkv, int D) {

@@ -2284,7 +2284,6 @@ static int g_opt_w4_stagger = 0;    // experiment: see GemmArgs::stagger
 static int g_opt_w4_rowmajor = 1;   // 4-wave kernel: row-major (LDS-transposed, 16-byte) plain epilogue; 0 = the accumulator-layout epilogue (A/B)
 static int g_opt_w4 = [] { const char* e = getenv("MM_GEMM_W4"); return e ? atoi(e) : 1; }();            // (MM_GEMM_W4=0: A/B at step level) NT / NN 256x256 tiles on the 4-wave hand-scheduled kernel (gemm_bf16_w4_kernel); 0 = the 8-wave kernel (A/B)
 
-extern "C" int mm_attn_set_issue_waves(int v);
 int mm_attn_option(const char* name, int value);
 
 extern int g_adamw_blocks;    // mm_optim.hip
@@ -2310,7 +2309,6 @@ extern "C" int mm_w4_diag_read(unsigned* out, int reset) {      // diag builds o
 
 extern "C" int mm_set_option(const char* name, int value) {
   if (!name) return MM_ERR_ARG;
-  if (!strcmp(name, "attn_issue_waves")) return mm_attn_set_issue_waves(value);
   if (!strncmp(name, "attn_", 5)) return mm_attn_option(name, value);
   if (!strcmp(name, "adamw_blocks")) { if (value < 0) return MM_ERR_ARG; g_adamw_blocks = value; return MM_OK; }
   if (!strcmp(name, "gemm_tail")) { g_opt_tail = value != 0; return MM_OK; }

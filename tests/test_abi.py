@@ -38,3 +38,6 @@ def test_argument_validation_without_launch():
     assert L.mm_gemm(0, 0, 16, 16, 16, 16, 3, 16, 8, 16, 8, None, None, 0, 0, None) == -2   # lda not a multiple of 8
     assert L.mm_attn_fwd(0, 16, 16, 16, 1, 8, 8, 2, 1, 32, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, 0, 1.0, 16, 16, None) == -3
     assert L.mm_error_string(-2).decode().startswith("alignment")
+    # the attention kernels' removed A/B switches are unknown names now (MM_ERR_ARG)
+    assert L.mm_set_option(b"attn_dkv_res", 1) == -1
+    assert L.mm_set_option(b"attn_fwd_pf", 0) == -1

@@ -399,7 +399,7 @@ ATTN_CASES = [
     (1, 384, 384, 8, 2, 128, True, False),
     (2, 1, 77, 4, 2, 64, True, True),
     (1, 40, 104, 2, 1, 128, True, False),
-    (1, 300, 300, 7, 1, 128, True, False),       # Qwen2-7B's odd GQA group (28/4 = 7): one-key-block dK/dV kernel
+    (1, 300, 300, 7, 1, 128, True, False),       # Qwen2-7B's odd GQA group (28/4 = 7) through the paired dK/dV kernel
     (2, 640, 640, 4, 2, 128, True, True),        # 5 key blocks: odd count through the paired dK/dV kernel
     (3, 729, 729, 2, 2, 128, False, False),      # SigLIP-so400m token count, non-causal (padded 72-wide heads run here)
 ]
@@ -458,19 +458,10 @@ def test_attention_fwd_bwd(K, dtype, case):
     assert rel(dv.float(), vf.grad) < gtol, "dv"
 
 
-@pytest.mark.parametrize("mode", [1, 2])
-@pytest.mark.parametrize("case", [c for c in ATTN_CASES if c[5] == 128])
-def test_attention_bwd_resident_kv(K, case, mode):
-    """mm_set_option("attn_dkv_res", 1 | 2): the D = 128 dK/dV kernel with the wave's K / V fragments resident in registers (four waves, one per
-    SIMD: attn_bwd_dkv128_res_kernel; 2 = attn_bwd_dkv128_resp_kernel, the items software-pipelined inside the wave over a three-stage ring)
-    against the same fp32 reference as the shipped pair kernel.  (Round 4: both correct, 1.5x / 1.1x the pair kernel's time, so they stay
-    options)"""
-    from multimeditron_amd._lib import lib
-    assert lib().mm_set_option(b"attn_dkv_res", mode) == 0
-    try:
-        test_attention_fwd_bwd(K, torch.bfloat16, case)
-    finally:
-        assert lib().mm_set_option(b"attn_dkv_res", 0) == 0
+def test_attention_long_kv(K):
+    """More than 256 Ki keys: the D = 128 forward runs attn_fwd128p_kernel (attn_fwd128q_kernel's key-valid bits no longer fit
+    in LDS).  Sq != Skv, GQA, causal with a shift.  bf16 only: the fp32 kernels refuse more than 12 000 keys."""
+    test_attention_fwd_bwd(K, torch.bfloat16, (1, 64, 262_208, 2, 1, 128, True, False))
 
 
 @pytest.mark.parametrize("case", [(4, 2051, 32, 8, 128, True), (2, 77, 4, 2, 64, True), (1, 300, 7, 1, 128, False),

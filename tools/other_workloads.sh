@@ -15,7 +15,6 @@ done
 timeout -k 10 300 python3 bench.py --full --mode ALIGNMENT --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_alignment.json 2> $O/bench_alignment.err || echo "FAILED alignment"
 echo "alignment: $(cut -c1-220 $O/bench_alignment.json)"
 timeout -k 10 200 python3 tools/attn_bench.py --quick > $O/attn_quick.log 2>&1; cat $O/attn_quick.log
-timeout -k 10 200 python3 tools/attn_bench.py --ab-q > $O/attn_ab_q.log 2>&1; tail -16 $O/attn_ab_q.log
 timeout -k 10 300 python3 tools/decode_bench.py > $O/decode.log 2>&1; tail -5 $O/decode.log
 timeout -k 10 120 python3 tools/rowwise_bench.py > $O/rowwise.log 2>&1; cat $O/rowwise.log
 timeout -k 10 300 python3 tools/gemv_bench.py 4 16 > $O/gemv.txt 2>&1; tail -12 $O/gemv.txt

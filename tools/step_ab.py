@@ -39,15 +39,15 @@ def endless():
         yield host_batch
 
 
-OPTION_DEFAULTS = {"adamw_blocks": 0, "attn_q_rd": 4, "attn_q_prio": 1, "attn_diag": 0, "gemm_kernel": 0, "gemm_small": -1,
-                   "gemm_issue_waves": 4, "attn_issue_waves": 4, "attn_fwd_waves": 8}      # everything else is an on/off switch, default 1
+OPTION_DEFAULTS = {"adamw_blocks": 0, "attn_q_prio": 1, "attn_diag": 0, "gemm_kernel": 0, "gemm_small": -1,
+                   "gemm_issue_waves": 4}      # everything else is an on/off switch, default 1
 res = {v: [] for v in args.variants}
 for r in range(args.rounds):
     for v in args.variants:
         saved, opts = {}, []
         for kv in v.split(","):
             k, val = kv.split("=")
-            if k.startswith("opt:"):            # a libmmhip switch (mm_set_option), e.g. opt:attn_fwd_pf=0
+            if k.startswith("opt:"):            # a libmmhip switch (mm_set_option), e.g. opt:attn_q_prio=0
                 from multimeditron_amd._lib import lib
                 assert lib().mm_set_option(k[4:].encode(), int(val)) == 0, k
                 opts.append(k[4:])
