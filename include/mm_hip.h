@@ -263,6 +263,25 @@ int mm_argmax_softmax(int dtype, const void* logits, int rows, int V, int ld, fl
 int mm_argmax_softmax_ws_bytes(int rows, int V);
 int mm_argmax_softmax_split(int dtype, const void* logits, int rows, int V, int ld, float temperature, int64_t* out, void* ws,
                             void* stream);
+/* Seeded next-token sampling (generate(do_sample=True, top_k=, top_p=, min_p=, seed=); HF warper order temperature -> top-k ->
+ * top-p -> min-p, HF:generation/utils.py).  Per row r of logits [rows, ld] (V valid columns), in fp32:
+ *   1. x_v = float(logit_v) / T;  m = max_v x_v;  w_v = exp(x_v - m)
+ *   2. top-k (0 or >= V: off): keep x_v >= x_(k), the k-th largest value; ties at it are all kept (TopKLogitsWarper)
+ *   3. top-p (1: off), over the set kept so far with mass Z_K: keep v iff sum of w_u over kept u with x_u > x_v < top_p * Z_K
+ *      (TopPLogitsWarper, min_tokens_to_keep = 1, ties resolved by value: kept together); the maximum is always kept
+ *   4. min-p (0: off): keep v iff w_v >= min_p  (p_v >= min_p * p_max, MinPLogitsWarper)
+ *   5. u = (philox4x32_10(call = r, offset, seed).x >> 8) * 2^-24 in [0, 1), t = u * Z with Z the kept mass: the token is the
+ *      smallest kept index v (vocabulary order) whose cumulative kept mass C(v) > t; if rounding leaves none, the last kept one
+ *   6. x = -inf is never drawn; a row without a finite logit is out of contract but still gets an index in [0, V)
+ *   7. bitwise deterministic: the mass is fixed point (w * 2^38 as an integer; sums exact in any order), no float atomics
+ * thresh (may be NULL): the smallest kept x of each row.  ws: mm_sample_ws_bytes(rows, V) bytes, 16-byte aligned; V <= 2^24.
+ * MM_ERR_ARG before any launch for T <= 0, top_k < 0, top_p outside (0, 1] or NaN, min_p outside [0, 1], ld < V, rows < 0 or
+ * a workspace that is too small.  No allocation, copy or synchronisation inside (capturable).
+ * mm_sample_uniforms: the u of step 5 for rows 0 .. rows-1 (tests).                                                       */
+int mm_sample_ws_bytes(int rows, int V, int64_t* bytes);
+int mm_sample(int dtype, const void* logits, int rows, int V, int ld, float temperature, int top_k, float top_p, float min_p,
+              int64_t seed, int64_t offset, int64_t* out, float* thresh, void* ws, int64_t ws_bytes, void* stream);
+int mm_sample_uniforms(int64_t seed, int64_t offset, int rows, float* u, void* stream);
 /* generate()'s per-token bookkeeping ON the device (the reference syncs per token: model.py:618-625,637-638): id = finished[b]
  * ? eos : tok[b]; finished[b] |= id == eos; out[b, col] = id; next_ids[b] = id (the next step's embedding lookup).       */
 int mm_decode_select(const int64_t* tok, unsigned char* finished, int64_t eos, int B, int64_t* out, int ld_out, int col,

@@ -24,25 +24,6 @@
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------- Philox4x32-10
-struct U4 { unsigned x, y, z, w; };
-
-__host__ __device__ inline unsigned mulhi32(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
-
-__host__ __device__ inline U4 philox4x32_10(unsigned long long call, unsigned long long offset, unsigned long long seed) {
-  unsigned c0 = (unsigned)call, c1 = (unsigned)(call >> 32), c2 = (unsigned)offset, c3 = (unsigned)(offset >> 32);
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = mulhi32(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = mulhi32(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = h1 ^ c1 ^ k0, n1 = l1, n2 = h0 ^ c3 ^ k1, n3 = l0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
-
 // keep <=> random word >= p * 2^32 (P(keep) = 1 - p up to 2^-32)
 __host__ __device__ inline unsigned drop_threshold(float p) {
   const double t = (double)p * 4294967296.0;

@@ -611,6 +611,42 @@ def argmax_softmax(logits2d, V, temperature):
     return out
 
 
+def _i64(v):
+    """the 64-bit pattern of a Python int as a C int64_t (a seed may be given as any non-negative int below 2**64)"""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def sample_ws(rows, V, device):
+    """workspace of mm_sample for `rows` rows of V logits (reusable across calls of that size)."""
+    import ctypes
+    nb = ctypes.c_int64(0)
+    call("mm_sample_ws_bytes", int(rows), int(V), ctypes.byref(nb))
+    return torch.empty((nb.value + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def sample(logits2d, V, temperature, top_k=0, top_p=1.0, min_p=0.0, seed=0, offset=0, thresh=False, ws=None, out=None):
+    """seeded temperature -> top-k -> top-p -> min-p draw per row (contract: mm_sample in include/mm_hip.h).  Returns the
+    int64 token ids [rows], or (ids, smallest kept x per row) when thresh.  ws: sample_ws(rows, V, device), owned by the caller."""
+    rows = logits2d.shape[0]
+    assert logits2d.stride(-1) == 1
+    if ws is None:
+        ws = sample_ws(rows, V, logits2d.device)
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits2d.device)
+    th = torch.empty(rows, dtype=torch.float32, device=logits2d.device) if thresh else None
+    call("mm_sample", dt(logits2d), _p(logits2d), rows, V, logits2d.stride(0), float(temperature), min(int(top_k), V), float(top_p),
+         float(min_p), _i64(seed), _i64(offset), _p(out), _p(th), _p(ws), ws.numel() * 8, _stream())
+    return (out, th) if thresh else out
+
+
+def sample_uniforms(seed, offset, rows, device="cuda"):
+    """the uniforms u of mm_sample's draws for rows 0 .. rows-1 (tests)."""
+    u = torch.empty(rows, dtype=torch.float32, device=device)
+    call("mm_sample_uniforms", _i64(seed), _i64(offset), rows, _p(u), _stream())
+    return u
+
+
 def expert_fuse(x, gate, idx, mode, backward=False, E=None):
     """MoE fusion (see mm_expert_fuse).  forward: x [E, n, L] -> [n, L] (mode 0) / [n, J, L] (mode 1); backward: x = dout ->
     dX [E, n, L] (zeros outside the listed experts)."""

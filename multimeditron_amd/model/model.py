@@ -438,10 +438,41 @@ class MultiModalModelForCausalLM(nn.Module):
                               **kwargs)
 
     def generate(self, batch: Dict[str, Any], max_new_tokens=512, temperature=0.1, do_sample=True, sync_every: int = 16,
-                 **kwargs) -> torch.Tensor:
+                 top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                 seed: Optional[int] = None, generator: Optional[torch.Generator] = None, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
+
+        Sampling (do_sample=True) takes one of two paths:
+          - none of top_k / top_p / min_p / seed / generator given: torch.softmax + torch.multinomial, the reference-compatible
+            consumer of torch's global RNG (the same torch seed gives the reference's draws);
+          - any of them given: the device sampler mm_sample (temperature -> top-k -> top-p -> min-p, HF warper order; contract in
+            include/mm_hip.h), step i drawing with Philox offset i and call = row.  `seed` is used as given; without it one int64
+            is drawn from `generator` (torch's default CPU generator when None), so torch.manual_seed still fixes the ids.
+            top_k = 0, top_p = 1 and min_p = 0 switch a warper off.
+        Whether the device sampler should become the default is a separate decision."""
+        device_sample = do_sample and any(a is not None for a in (top_k, top_p, min_p, seed, generator))
+        if device_sample:
+            top_k = 0 if top_k is None else top_k
+            top_p = 1.0 if top_p is None else top_p
+            min_p = 0.0 if min_p is None else min_p
+            if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+                raise ValueError(f"top_k must be an int >= 0, got {top_k!r}")
+            if not (isinstance(top_p, (int, float)) and 0.0 < float(top_p) <= 1.0):
+                raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+            if not (isinstance(min_p, (int, float)) and 0.0 <= float(min_p) <= 1.0):
+                raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64):
+                raise ValueError(f"seed must be an int in [0, 2**64), got {seed!r}")
+            if seed is None:
+                gdev = generator.device if generator is not None else "cpu"
+                seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
+        return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
+                              (top_k, top_p, min_p, seed) if device_sample else None)
+
+    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler) -> torch.Tensor:
+        """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
         Here the chosen id, the eos bookkeeping and the next embedding lookup stay on the device (mm_decode_select +
@@ -472,6 +503,8 @@ class MultiModalModelForCausalLM(nn.Module):
             next_ids = torch.empty(B, dtype=torch.int64, device=dev)
             steps = 0
             emb = self.model.get_input_embeddings()
+            sample_ws = K.sample_ws(B, V, dev) if sampler is not None else None       # once per call
+            tok_buf = torch.empty(B, dtype=torch.int64, device=dev) if sampler is not None else None
             for i in range(max_new_tokens):
                 if i > 0:
                     position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
@@ -479,7 +512,11 @@ class MultiModalModelForCausalLM(nn.Module):
                 out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
                                  past_key_values=cache, use_cache=True, logits_to_keep=1)
                 logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
-                if do_sample:
+                if sampler is not None:
+                    k_, p_, mp_, sd_ = sampler
+                    tok = K.sample(logits2d, V, temperature, top_k=k_, top_p=p_, min_p=mp_, seed=sd_, offset=i, ws=sample_ws,
+                                   out=tok_buf)
+                elif do_sample:
                     probs = torch.softmax(logits2d.float() / temperature, dim=-1)
                     tok = torch.multinomial(probs, num_samples=1).view(B)
                 else:

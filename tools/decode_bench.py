@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
-   python tools/decode_bench.py [B] [S] [new_tokens]"""
+   python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7]
+--sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
+the greedy selection."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,6 +11,14 @@ from multimeditron_amd.model.model import MultimodalConfig, MultiModalModelForCa
 from multimeditron_amd.model.modalities import ImageConfig
 from multimeditron_amd.model.presets import resolve_llm_config, resolve_vision_config
 
+SAMPLE = None
+if "--sample" in sys.argv:
+    i = sys.argv.index("--sample")
+    SAMPLE = {}
+    for kv in sys.argv[i + 1].split(","):
+        k, val = kv.split("=")
+        SAMPLE[k] = int(val) if k in ("top_k", "seed") else float(val)
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 33
@@ -27,7 +37,13 @@ batch["attention_mask"] = torch.ones(B, S, dtype=torch.long, device="cuda")
 def run(n):
     torch.cuda.synchronize()
     t = time.perf_counter()
-    ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False)
+    if SAMPLE is None:
+        ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False)
+    else:
+        kw = dict(SAMPLE)
+        T = kw.pop("T", 1.0)
+        kw.setdefault("seed", 0)
+        ids = model.generate(batch, max_new_tokens=n, temperature=T, do_sample=True, **kw)
     torch.cuda.synchronize()
     return time.perf_counter() - t, ids
 
@@ -37,5 +53,5 @@ t1, _ = run(1)
 tn, ids = run(N)
 per_tok = (tn - t1) / (N - 1)
 wbytes = sum(p.numel() for p in model.model.parameters()) * 2
-print(f"B={B} S={S}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
+print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
       f"weight stream {wbytes / per_tok / 1e12:.2f} TB/s of 8 (floor {wbytes / 8e12 * 1e3:.2f} ms/token)  ids {tuple(ids.shape)}")

@@ -1,0 +1,52 @@
+#!/usr/bin/env python3
+"""mm_sample alone on the decoder's vocabulary (V = 128 258, bf16 logits) beside the greedy selection mm_argmax_softmax_split on the
+same rows (run on the GPU box).  HIP events around 200 back-to-back calls after 20 warm-up calls.
+   python tools/sample_bench.py [--iters N]"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from multimeditron_amd import kernels as K
+
+CONFIGS = [("plain", dict()), ("top_k=50", dict(top_k=50)), ("top_p=0.95", dict(top_p=0.95)),
+           ("top_k=50+top_p=0.9", dict(top_k=50, top_p=0.9))]
+
+
+def timed(fn, iters, warmup=20):
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters          # us per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--V", type=int, default=128258)
+    args = ap.parse_args()
+    V, ld = args.V, (args.V + 63) // 64 * 64
+    torch.manual_seed(0)
+    for rows in (1, 4, 16):
+        buf = (torch.randn(rows, ld, device="cuda") * 3).to(torch.bfloat16)
+        lg = buf[:, :V]
+        ws = K.sample_ws(rows, V, "cuda")
+        out = torch.empty(rows, dtype=torch.int64, device="cuda")
+        greedy = timed(lambda: K.argmax_softmax(lg, V, 0.7), args.iters)
+        line = [f"rows={rows:2d}  argmax_softmax_split {greedy:6.1f} us"]
+        for name, kw in CONFIGS:
+            us = timed(lambda: K.sample(lg, V, 0.7, seed=1, offset=0, ws=ws, out=out, **kw), args.iters)
+            line.append(f"{name} {us:6.1f} us")
+        print(" | ".join(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
