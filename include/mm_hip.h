@@ -188,7 +188,11 @@ int mm_rope_apply(int dtype, void* x, int T, int nheads, int D, int ld, const fl
 /* ---- attention: HF:llama:191-213 (eager softmax attention, GQA via repeat_kv), HF:clip:280-334 ------------
  * q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] with element strides (batch, seq, head); D contiguous; D in {64,128} for
  * MM_BF16 (MFMA path), any D<=256 for MM_F32.  key_mask [B,Skv] int64 (1 = attend) or NULL.  causal aligns the
- * LAST query with the LAST key (q position = i + Skv - Sq).  out [B,Sq,Hq,D] contiguous; lse [B,Hq,Sq] f32.     */
+ * LAST query with the LAST key (q position = i + Skv - Sq).  out [B,Sq,Hq,D] contiguous; lse [B,Hq,Sq] f32.
+ * Sq > Skv is allowed: under causal the first Sq - Skv queries then see no key.  A query row with no visible key (causal
+ * and/or key_mask) gives out = 0 and lse = +inf, never NaN, and dq = 0 in mm_attn_bwd; a key no query sees gets dk = dv = 0.
+ * Known limit of the MM_BF16 D = 128 kernels: a buffer resource spans at most 4 GiB of one head's K or V rows
+ * ((Skv - 1) * k_ss * 2 bytes), about 349 k keys in the Llama fused qkv layout.                                 */
 int mm_attn_fwd(int dtype, const void* q, const void* k, const void* v, int B, int Sq, int Skv, int Hq, int Hkv, int D,
                 int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb,
                 int64_t v_ss, int64_t v_sh, const int64_t* key_mask, int causal, float scale, void* out, float* lse,

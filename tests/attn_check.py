@@ -1,0 +1,324 @@
+"""Attention checker: an fp64 reference with per-element error scales, the output contract, and guarded launches.
+
+`reference` runs in float64 on the device of its operands, on the SAME bf16- or fp32-rounded q/k/v/dout the kernels read.
+Besides out, lse (natural log), dq, dk and dv it returns an error scale E for every element, built only from absolute values
+of fp64 terms (nothing is fitted to kernel output).  A kernel result passes when |got - ref| <= c * u * E elementwise, with u
+the unit roundoff of the dtype (2^-8 bf16, 2^-24 fp32) and c a per-path constant (`C` below); where E = 0 the result must be
+exact (rows with no visible key: out = 0, lse = +inf, dq = 0; masked keys: dk = dv = 0).
+
+The rounding points of the bf16 kernels (mm_attn.hip) and the term of E that covers each:
+  forward   scores S = Q.K^T in fp32 (exact bf16 products), p = exp2(S*scale*log2e - m) in fp32, l summed from the fp32 p,
+            P rounded to bf16 before O += P.V, out = bf16(O / l)                      -> E_o  = P.|V|   (P rounding + out rounding)
+  backward  delta = rowsum(out * dO) from the bf16 `out`                           -> |o|.|dO| term of E_dS (carried as E_o.|dO|)
+            p = exp2(S*scale*log2e - lse*log2e), dP = dO.V^T in fp32
+            dV += bf16(P)^T.dO                                                   -> E_dv = P^T.|dO|
+            dS = bf16(P * (dP - delta) * scale)                                  -> E_dS = P o (|dP| + |delta| + E_o.|dO| row sums)
+            dQ = dS.K, dK = dS^T.Q (fp32 accumulation), every output rounded to bf16 -> E_dq = scale E_dS.|K|, E_dk = scale E_dS^T.|Q|
+The fp32 kernels have no bf16 rounding point, and their largest error is the fp32 score itself (a D-term dot product, and the
+exponent argument S*scale - lse): each P carries a relative error of ~u32 * A with A = sqrt(D) * scale * |Q|.|K|^T + |lse|.
+That enters every scale as P -> P o (1 + kappa * A) (plus kappa * |o| * rowsum(P o A) for out and kappa * sqrt(D) * P o |dO|.|V|^T
+for dP), with kappa = u32 / u: 1 for fp32, 2^-16 for bf16 (negligible there).  lse is fp32 in both paths and is checked with
+u32 against E_lse = |lse| + rowsum(P o A) + sqrt(visible keys) (the fp32 sum of l).
+
+The bound is a worst-case (sum of |terms|) bound: it is rigorous, and so it loses power as 1/sqrt(n) on long rows -- a
+single-key error in a row of n keys moves out by ~1/n of a value while E_o stays ~mean|v|.  tests/test_attn_check_cpu.py shows
+at which sizes the usual kernel mistakes are flagged."""
+import atexit
+import json
+import math
+import os
+
+import torch
+
+LOG2E = 1.4426950408889634
+U = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}
+U32 = 2.0 ** -24
+
+# c per launch path and quantity: the smallest power of two >= 2x the worst err / (u E) measured on the MI355X over the
+# cases of tests/test_attention_contract_gpu.py (the PR description lists the measured ratios)
+C = {
+    "bf16-d128": {"out": 4.0, "lse": 1.0, "dq": 1.0, "dk": 1.0, "dv": 4.0},        # measured 1.71, 0.30, 0.45, 0.49, 1.85
+    # attn_fwd128p_kernel, one case (test_attention_long_kv): measured 0.013, 0.054, 0.002, 0.23, 1.17; its siblings' constants
+    "bf16-d128-long": {"out": 4.0, "lse": 1.0, "dq": 1.0, "dk": 1.0, "dv": 4.0},
+    "bf16-d64": {"out": 4.0, "lse": 1.0, "dq": 1.0, "dk": 2.0, "dv": 4.0},         # measured 1.58, 0.38, 0.43, 0.59, 1.79
+    "f32": {"out": 2.0, "lse": 2.0, "dq": 0.25, "dk": 0.25, "dv": 2.0},            # measured 0.59, 0.75, 0.10, 0.09, 0.62
+}
+
+# worst err / (u E) seen per (path, quantity) in this process; MM_ATTN_RATIO_LOG=<file> writes them out at exit
+RATIOS = {}
+
+
+def _dump_ratios(path):
+    with open(path, "w") as f:
+        json.dump({f"{p}/{n}": v for (p, n), v in sorted(RATIOS.items())}, f, indent=1)
+
+
+if os.environ.get("MM_ATTN_RATIO_LOG"):
+    atexit.register(_dump_ratios, os.environ["MM_ATTN_RATIO_LOG"])
+
+SENTINEL = {torch.bfloat16: 0x7FC1, torch.float32: 0x7FC10000}   # quiet NaNs with a payload no kernel produces
+
+
+def path_of(dtype, D, Skv):
+    if dtype == torch.float32:
+        return "f32"
+    if D == 64:
+        return "bf16-d64"
+    return "bf16-d128" if Skv <= 256 * 1024 else "bf16-d128-long"
+
+
+def visible(key_mask, causal, B, Sq, Skv, device):
+    """[B, Sq, Skv] bool: key j is visible to query i (causal: j <= i + Skv - Sq, the ABI's alignment; covers Sq > Skv)."""
+    allowed = torch.ones(B, Sq, Skv, dtype=torch.bool, device=device)
+    if causal:
+        allowed &= (torch.arange(Skv, device=device)[None, :] <= torch.arange(Sq, device=device)[:, None] + (Skv - Sq))[None]
+    if key_mask is not None:
+        allowed &= (key_mask.to(device) != 0)[:, None, :]
+    return allowed
+
+
+def reference(q, k, v, dout, key_mask, causal, scale, backward=True):
+    """fp64 on q's device.  q/dout [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] (any strides).  Returns a dict with out, lse [B,Hq,Sq],
+    dq, dk, dv (fp64, the operands' layouts) and their error scales E_out, E_lse, E_dq, E_dk, E_dv, plus rows [B,Sq]
+    (the query has at least one visible key) and keys [B,Skv] (the key is visible to at least one query)."""
+    B, Sq, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    dev = q.device
+    kappa = U32 / U[q.dtype]
+    rt = math.sqrt(D)
+    f64 = dict(dtype=torch.float64, device=dev)
+    r = {n: torch.zeros(B, Sq, Hq, D, **f64) for n in ("out", "E_out", "dq", "E_dq")}
+    r.update({n: torch.zeros(B, Skv, Hkv, D, **f64) for n in ("dk", "E_dk", "dv", "E_dv")})
+    r["lse"] = torch.full((B, Hq, Sq), math.inf, **f64)
+    r["E_lse"] = torch.zeros(B, Hq, Sq, **f64)
+    allowed = visible(key_mask, causal, B, Sq, Skv, dev)
+    r["rows"] = allowed.any(-1)
+    r["keys"] = allowed.any(1)
+    for b in range(B):
+        al = allowed[b]
+        nvis = al.sum(-1).double()                                      # [Sq]
+        for hkv in range(Hkv):
+            hs = slice(hkv * G, (hkv + 1) * G)
+            Q = q[b, :, hs].double().permute(1, 0, 2)                   # [G, Sq, D]
+            Kt, V = k[b, :, hkv].double(), v[b, :, hkv].double()         # [Skv, D]
+            S = (Q @ Kt.t() * scale).masked_fill(~al, -math.inf)
+            m = S.amax(-1, keepdim=True) if Skv else torch.full((G, Sq, 1), -math.inf, **f64)
+            m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+            e = torch.exp(S - m)
+            del S
+            lsum = e.sum(-1, keepdim=True)
+            P = e / torch.where(lsum > 0, lsum, torch.ones_like(lsum))
+            del e
+            lse = torch.where(lsum > 0, m + torch.log(lsum), torch.full_like(m, math.inf))
+            lse_fin = torch.where(lsum > 0, lse, torch.zeros_like(lse))
+            O = P @ V
+            PA = P * (rt * scale * (Q.abs() @ Kt.abs().t()) + lse_fin.abs())
+            Pw = P + kappa * PA
+            PA_sum = PA.sum(-1, keepdim=True)
+            del PA
+            E_o = Pw @ V.abs() + kappa * O.abs() * PA_sum
+            r["out"][b, :, hs] = O.permute(1, 0, 2)
+            r["E_out"][b, :, hs] = E_o.permute(1, 0, 2)
+            r["lse"][b, hs] = lse[..., 0]
+            r["E_lse"][b, hs] = (lse_fin.abs() + PA_sum)[..., 0] + nvis.sqrt()[None]
+            if not backward:
+                continue
+            dO = dout[b, :, hs].double().permute(1, 0, 2)
+            dP = dO @ V.t()
+            delta = (O * dO).sum(-1, keepdim=True)
+            E_delta = (E_o * dO.abs()).sum(-1, keepdim=True)
+            dS = P * (dP - delta)
+            E_dS = Pw * (dP.abs() + delta.abs()) + P * E_delta + kappa * rt * P * (dO.abs() @ V.abs().t())
+            del dP
+            r["dq"][b, :, hs] = (scale * dS @ Kt).permute(1, 0, 2)
+            r["E_dq"][b, :, hs] = (scale * E_dS @ Kt.abs()).permute(1, 0, 2)
+            r["dk"][b, :, hkv] = scale * (dS.transpose(1, 2) @ Q).sum(0)
+            r["E_dk"][b, :, hkv] = scale * (E_dS.transpose(1, 2) @ Q.abs()).sum(0)
+            r["dv"][b, :, hkv] = (P.transpose(1, 2) @ dO).sum(0)
+            r["E_dv"][b, :, hkv] = (Pw.transpose(1, 2) @ dO.abs()).sum(0)
+            del dS, E_dS, P, Pw
+    return r
+
+
+def _where(kind, idx, shape):
+    """Human-readable location of flat index idx in a tensor of `kind` ('q': [B,Sq,Hq,D], 'k': [B,Skv,Hkv,D], 'lse': [B,Hq,Sq])
+    with its tile coordinates (32- and 256-row query blocks, 64- and 128-key blocks)."""
+    coords = []
+    for n in reversed(shape):
+        coords.append(idx % n)
+        idx //= n
+    coords = coords[::-1]
+    if kind == "lse":
+        b, h, row = coords
+        return f"(b={b}, row={row}, head={h}) [q32 tile {row // 32}, q256 block {row // 256}]"
+    b, row, h, d = coords
+    if kind == "q":
+        return f"(b={b}, row={row}, head={h}, d={d}) [q32 tile {row // 32}, q256 block {row // 256}]"
+    return f"(b={b}, key={row}, kvhead={h}, d={d}) [k64 tile {row // 64}, k128 block {row // 128}]"
+
+
+def check(name, got, ref, E, c, u, kind, path=None):
+    """|got - ref| <= c u E elementwise; exact where E = 0 (ref is then 0, or +inf for lse).  Returns the worst err / (u E)
+    and records it in RATIOS[(path, name)].  On failure the message names the worst element and its tiles."""
+    g = got.detach().to(ref.device, torch.float64)
+    exact = E == 0
+    if kind == "lse":
+        exact = exact | torch.isinf(ref)
+    bad_exact = exact & ~(g == ref)
+    nonfinite = ~torch.isfinite(g) & ~exact
+    if bool(nonfinite.any()):
+        i = int(nonfinite.reshape(-1).nonzero()[0])
+        raise AssertionError(f"{name}: non-finite {float(g.reshape(-1)[i])} at {_where(kind, i, g.shape)}, "
+                             f"ref {float(ref.reshape(-1)[i]):.6g} ({int(nonfinite.sum())} such elements)")
+    if bool(bad_exact.any()):
+        i = int(bad_exact.reshape(-1).nonzero()[0])
+        raise AssertionError(f"{name}: {float(g.reshape(-1)[i]):.6g} where exactly {float(ref.reshape(-1)[i])} is required "
+                             f"(no visible key / masked key / E = 0) at {_where(kind, i, g.shape)} "
+                             f"({int(bad_exact.sum())} such elements)")
+    err = torch.where(exact, torch.zeros_like(g), (g - ref).abs())
+    ratio = err / (u * torch.where(exact, torch.ones_like(E), E))
+    if ratio.numel() == 0:
+        return 0.0
+    i = int(ratio.reshape(-1).argmax())
+    worst = float(ratio.reshape(-1)[i])
+    if path is not None:
+        RATIOS[(path, name)] = max(RATIOS.get((path, name), 0.0), worst)
+    if not worst <= c:
+        nbad = int((ratio > c).sum())
+        raise AssertionError(f"{name}: err/(u E) = {worst:.3g} > c = {c} at {_where(kind, i, g.shape)}: got "
+                             f"{float(g.reshape(-1)[i]):.6g}, ref {float(ref.reshape(-1)[i]):.6g}, c u E = "
+                             f"{c * u * float(E.reshape(-1)[i]):.3g} ({nbad} elements over the bound)")
+    return worst
+
+
+def check_all(res, ref, dtype, path, c=None, backward=True):
+    """Every quantity of `res` (dict with out, lse and, for backward, dq, dk, dv) against `ref`; returns {name: worst ratio}."""
+    c = c or C[path]
+    u = U[dtype]
+    out = {"out": check("out", res["out"], ref["out"], ref["E_out"], c["out"], u, "q", path),
+           "lse": check("lse", res["lse"], ref["lse"], ref["E_lse"], c["lse"], U32, "lse", path)}
+    if backward:
+        out["dq"] = check("dq", res["dq"], ref["dq"], ref["E_dq"], c["dq"], u, "q", path)
+        out["dk"] = check("dk", res["dk"], ref["dk"], ref["E_dk"], c["dk"], u, "k", path)
+        out["dv"] = check("dv", res["dv"], ref["dv"], ref["E_dv"], c["dv"], u, "k", path)
+    return out
+
+
+def check_contract(res, ref, backward=True):
+    """The output contract: rows with no visible key give out == 0, lse == +inf, dq == 0 exactly; keys no query
+    sees (masked) give dk == dv == 0 exactly; every output is finite (lse: finite or +inf)."""
+    rows, keys = ref["rows"].to(res["out"].device), ref["keys"].to(res["out"].device)
+    out, lse = res["out"], res["lse"]
+    dead = ~rows                                                        # [B, Sq]
+    assert bool(torch.isfinite(out).all()), "out has non-finite values"
+    assert bool((out[dead] == 0).all()), "out != 0 on a row with no visible key"
+    assert bool(torch.isinf(lse.transpose(1, 2)[dead]).all()) and bool((lse.transpose(1, 2)[dead] > 0).all()), \
+        "lse != +inf on a row with no visible key"
+    assert bool(torch.isfinite(lse.transpose(1, 2)[rows]).all()), "lse not finite on a row with visible keys"
+    if backward:
+        dq, dk, dv = res["dq"], res["dk"], res["dv"]
+        for n, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+            assert bool(torch.isfinite(t).all()), f"{n} has non-finite values"
+        assert bool((dq[dead] == 0).all()), "dq != 0 on a row with no visible key"
+        assert bool((dk[~keys] == 0).all()) and bool((dv[~keys] == 0).all()), "dk/dv != 0 on a key no query sees"
+
+
+# ---- guarded launches through the C ABI --------------------------------------------------------------------------------
+def _ints(t):
+    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+class Guarded:
+    """One storage of `numel` elements between guard bands of `pad` elements, all filled with the sentinel NaN.  `view`
+    places a strided view at an element offset into the storage (as the operand it mirrors sits in its own storage);
+    `verify` asserts that every element outside the views is bit-unchanged and that no sentinel is left inside them."""
+
+    def __init__(self, numel, dtype, device, pad=512):
+        self.dtype, self.pad = dtype, pad
+        self.buf = torch.empty(pad + numel + pad, dtype=dtype, device=device)
+        _ints(self.buf).fill_(SENTINEL[dtype])
+        self.covered = torch.zeros(self.buf.numel(), dtype=torch.bool, device=device)
+        self.views = []
+
+    def view(self, shape, stride, offset=0):
+        v = self.buf.as_strided(shape, stride, self.pad + offset)
+        self.covered.as_strided(shape, stride, self.pad + offset).fill_(True)
+        self.views.append(v)
+        return v
+
+    def verify(self, name):
+        iv = _ints(self.buf)
+        s = SENTINEL[self.dtype]
+        guard_bad = (~self.covered) & (iv != s)
+        if bool(guard_bad.any()):
+            i = int(guard_bad.nonzero()[0])
+            raise AssertionError(f"{name}: write outside the output at storage element {i - self.pad} "
+                                 f"(storage [0, {self.buf.numel() - 2 * self.pad}), {int(guard_bad.sum())} elements)")
+        left = self.covered & (iv == s)
+        if bool(left.any()):
+            i = int(left.nonzero()[0])
+            raise AssertionError(f"{name}: {int(left.sum())} output elements never written (first at storage element "
+                                 f"{i - self.pad})")
+
+
+def grad_views(views, zero=()):
+    """Gradient buffers with the SAME strides and offsets as the operand views (the ABI's rule), in guarded storages that mirror
+    the operands' storages: views that share a storage (the fused qkv buffer) share one guarded storage, so the columns
+    between the q, k and v sections and the rows past a prefix view are guards.  Views named in `zero` are zero-filled."""
+    stores, out = {}, []
+    for i, x in enumerate(views):
+        key = x.untyped_storage().data_ptr()
+        if key not in stores:
+            stores[key] = Guarded(x.untyped_storage().nbytes() // x.element_size(), x.dtype, x.device)
+        g = stores[key].view(x.shape, x.stride(), x.storage_offset())
+        if i in zero:
+            g.zero_()
+        out.append(g)
+    return out, list(stores.values())
+
+
+def _dt(dtype):
+    return 0 if dtype == torch.bfloat16 else 1
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _s3(t):
+    return t.stride(0), t.stride(1), t.stride(2)
+
+
+def run_fwd(q, k, v, key_mask, causal, scale, stream=None):
+    """mm_attn_fwd with out / lse inside guarded storages; returns (out, lse, [guards])."""
+    from multimeditron_amd._lib import call
+    B, Sq, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    go = Guarded(B * Sq * Hq * D, q.dtype, q.device)
+    gl = Guarded(B * Hq * Sq, torch.float32, q.device)
+    out = go.view((B, Sq, Hq, D), (Sq * Hq * D, Hq * D, D, 1))
+    lse = gl.view((B, Hq, Sq), (Hq * Sq, Sq, 1))
+    st = stream if stream is not None else torch.cuda.current_stream()
+    call("mm_attn_fwd", _dt(q.dtype), _p(q), _p(k), _p(v), B, Sq, Skv, Hq, Hkv, D, *_s3(q), *_s3(k), *_s3(v), _p(key_mask),
+         int(causal), float(scale), _p(out), _p(lse), st.cuda_stream)
+    return out, lse, [("out", go), ("lse", gl)]
+
+
+def run_bwd(q, k, v, out, dout, lse, key_mask, causal, scale, stream=None):
+    """mm_attn_bwd with dq/dk/dv as guarded views mirroring q/k/v (fp32: dk/dv zero-filled, as the ABI requires);
+    returns (dq, dk, dv, [guards])."""
+    from multimeditron_amd._lib import call
+    B, Sq, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    (dq, dk, dv), stores = grad_views([q, k, v], zero=(1, 2) if q.dtype == torch.float32 else ())
+    delta = torch.empty(B * Hq * Sq, dtype=torch.float32, device=q.device)
+    st = stream if stream is not None else torch.cuda.current_stream()
+    call("mm_attn_bwd", _dt(q.dtype), _p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), B, Sq, Skv, Hq, Hkv, D, *_s3(q),
+         *_s3(k), *_s3(v), _p(key_mask), int(causal), float(scale), _p(dq), _p(dk), _p(dv), _p(delta), st.cuda_stream)
+    return dq, dk, dv, [(f"dq/dk/dv storage {i}", g) for i, g in enumerate(stores)]
+
+
+def verify_guards(guards):
+    for name, g in guards:
+        g.verify(name)

@@ -456,6 +456,12 @@ def test_attention_fwd_bwd(K, dtype, case):
     assert rel(dq.float().cpu()[valid], qf.grad[valid]) < gtol, "dq"
     assert rel(dk.float(), kf.grad) < gtol, "dk"
     assert rel(dv.float(), vf.grad) < gtol, "dv"
+    # per element against the fp64 reference, and the output contract on the rows / keys the rel-L2 above leaves out
+    from tests import attn_check as AC
+    ref64 = AC.reference(qv, kv, vv, do.cuda(), mg, causal, scale)
+    res = dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv)
+    AC.check_contract(res, ref64)
+    AC.check_all(res, ref64, dtype, AC.path_of(dtype, D, Skv))
 
 
 def test_attention_long_kv(K):

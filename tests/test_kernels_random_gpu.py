@@ -111,6 +111,12 @@ def test_attention_random(K, case):      # noqa: F811
         assert close(dq.float(), qf.grad), case
         assert close(dk.float(), kf.grad), case
         assert close(dv.float(), vf.grad), case
+    # per element against the fp64 reference, and the output contract (rows with no visible key included)
+    from tests import attn_check as AC
+    ref64 = AC.reference(qd, kd, vd, do.cuda(), mg, causal, scale)
+    res = dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv)
+    AC.check_contract(res, ref64)
+    AC.check_all(res, ref64, dtype, AC.path_of(dtype, D, Skv))
 
 
 # ---- row-wise kernels on the widths the supported models use (and a few odd ones) ---------------------------------------
