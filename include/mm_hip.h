@@ -55,14 +55,21 @@ const char* mm_error_string(int code);
  * epilogue in the accumulator layout), "gemm_w4_shuffle" (0; 1 = the plain epilogue by register lane exchange instead of the LDS round trip: bit-identical, measured equal),
  * "gemm_w4_group_m", "gemm_w4_stagger" / "gemm_w4_stagger_slots" (experiments).  Unknown names return MM_ERR_ARG.   */
 int mm_set_option(const char* name, int value);
-/* current value of a "gemm_*" switch (so that a caller that flips one temporarily can restore what it found) */
+/* current value of a "gemm_*" switch (so that a caller that flips one temporarily can restore what it found); also
+ * "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged kernel (also the
+ * fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10 the 4-wave
+ * 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the decode
+ * fusions), 30 the fp32 kernel */
 int mm_get_option(const char* name, int* value);
 
 /* ---- GEMM: every nn.Linear / Conv2d(k=s) on the path -------------------------------------
  * replaces F.linear in mlp.py:33-39, HF:clip:280-384 (q/k/v/out/fc1/fc2), HF:clip:152-158 (patch conv as
  * GEMM), HF:llama:163-176,232-244,480 (gate/up/down, q/k/v/o, lm_head) and their autograd backward.
- * Requirements: lda, ldb, ldc, ldr multiples of 8 elements; pointers 16-byte aligned; for a K-contiguous
- * operand whose K is not a multiple of 8 the row padding up to the next multiple of 8 must hold zeros.   */
+ * Requirements (MM_BF16): lda, ldb multiples of 8 elements and A, B 16-byte aligned; ldc (and ldr with MM_EPI_RESIDUAL)
+ * multiples of 4 and C 8-byte aligned -- with ldc, ldr, N multiples of 8 and C, residual, bias 16-byte aligned the 256x256
+ * kernel stores row-major 16-byte groups, otherwise 8-byte ones; for a K-contiguous operand whose K is not a multiple of 8
+ * the row padding up to the next multiple of 8 must hold zeros (nothing beyond it is read).  Epilogue order, all in fp32
+ * with ONE rounding to bf16 at the store: acc (+ bias) (activation) (+ residual) (+ C).                                  */
 int mm_gemm(int dtype, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
             void* C, int ldc, const void* bias, const void* residual, int ldr, int epilogue, void* stream);
 

@@ -2278,7 +2278,12 @@ static int g_opt_w4_group_m = 8;    // experiment: GROUP_M of the 4-wave kernel'
 static int g_opt_w4_stream = 1;     // 4-wave kernel: wait-free plain epilogue (0 = gemm_epilogue_plain_pipe, A/B)
 static int g_opt_w4_shuffle = 0;    // GemmArgs::shuffle (measured equal to the LDS form within +-0.5 %: DESIGN.md section 4, the round-4 list, item 8)
 static int g_opt_w4_diag_epi = 0;   // MM_W4_DIAG builds: GemmArgs::diag_epi
-static int g_last_kernel = -1;      // which kernel the last bf16 mm_gemm* call launched: 10 = the 4-wave 256x256 kernel, 0..5 = v1 / the 8-wave DMA tiles, 20 = skinny
+// which kernel the last mm_gemm* / mm_decode_* call launched (mm_get_option "gemm_last_kernel"; -1 before the first):
+//   0 gemm_bf16_kernel (v1, 128x128 register staged; also the fallback when a K-strided operand or C passes the 32-bit offsets)
+//   1..5 gemm_bf16_dma_kernel tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64
+//   10 gemm_bf16_w4_kernel (4-wave 256x256)     20 gemm_skinny_kernel     21 gemv_stream_kernel (M <= 16 NT, decode fusions)
+//   30 gemm_f32_kernel
+static int g_last_kernel = -1;
 static int g_opt_w4_stagger_slots = 4;
 static int g_opt_w4_stagger = 0;    // experiment: see GemmArgs::stagger
 static int g_opt_w4_rowmajor = 1;   // 4-wave kernel: row-major (LDS-transposed, 16-byte) plain epilogue; 0 = the accumulator-layout epilogue (A/B)
@@ -2509,6 +2514,7 @@ template <int MODE>
 static int gemv_stream_launch(const SkinnyArgs& g, unsigned nblk, hipStream_t s) {
   if (!gemv_stream_fits(g.M, g.K)) return MM_ERR_UNSUPPORTED;
   if (g.norm_w && (g.K > 8192 || !mm_aligned16(g.norm_w))) return MM_ERR_UNSUPPORTED;
+  g_last_kernel = 21;
   const size_t lds = (size_t)g.M * g.K * 2;
   // persistent grid: as many workgroups as the chip holds at once (2 per CU by registers, fewer when x takes most of the LDS)
   static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
@@ -2758,6 +2764,7 @@ static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
       }
     }
   } else if (dtype == MM_F32) {
+    g_last_kernel = 30;
     g.nbm = (M + 63) / 64;
     g.nbn = (N + 63) / 64;
     dim3 grid((unsigned)(g.nbm * g.nbn)), block(256);

@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import gemm_check as GC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -130,6 +132,9 @@ def test_gemm_layouts(K, dtype, layout, shape):
     torch.cuda.synchronize()
     assert out.shape == (M, N)
     assert rel(out.float(), ref) < TOL[dtype]
+    assert GC.last_kernel() == (GC.expected_kernel(lay, M, N, Kd) if dtype == torch.bfloat16 else GC.F32)
+    if dtype == torch.bfloat16:
+        GC.check_random("C", out, a, b)
 
 
 DMA_SHAPES = [(256, 256, 64), (300, 520, 192), (1028, 1024, 640), (129, 72, 1088), (513, 264, 200), (2048, 512, 2056),
@@ -165,10 +170,13 @@ def test_gemm_dma_kernels_forced(K, variant, layout, shape):
     try:
         out = K.gemm(lay, A, B, M, N, Kd, ldc_pad=True)
         torch.cuda.synchronize()
+        kid = GC.last_kernel()
     finally:
         assert lib().mm_set_option(b"gemm_kernel", 0) == 0
     assert out.shape == (M, N)
     assert rel(out.float(), ref) < TOL[dtype]
+    assert kid == GC.expected_kernel(lay, M, N, Kd, forced=variant)
+    GC.check_random("C", out, a, b)
 
 
 @pytest.mark.parametrize("layout", ["NT", "NN", "TN"])
@@ -200,11 +208,13 @@ def test_gemm_half_tile_round(K, layout, shape):
         for tail in (1, 0):
             assert lib().mm_set_option(b"gemm_tail", tail) == 0
             outs.append(K.gemm(lay, A, B, M, N, Kd, ldc_pad=True).clone())
+            assert GC.last_kernel() == GC.expected_kernel(lay, M, N, Kd, forced=3) == GC.W4
         torch.cuda.synchronize()
     finally:
         lib().mm_set_option(b"gemm_kernel", 0)
         lib().mm_set_option(b"gemm_tail", 1)
     assert rel(outs[0].float(), ref) < TOL[dtype]
+    GC.check_random("C", outs[0], a, b)
     assert torch.equal(outs[0], outs[1])        # same products in the same K order: bit-identical to the unsplit schedule
 
 
@@ -219,6 +229,8 @@ def test_gemm_skinny_decode(K, shape):
     ref = a.float() @ w.float().t()
     out = K.linear_fwd(a.cuda(), w.cuda(), ldc_pad=True)
     assert rel(out.float(), ref) < TOL[dtype]
+    assert GC.last_kernel() == GC.expected_kernel(GC.NT, M, N, Kd) == GC.GEMV
+    GC.check_random("C", out, a, w)
     ref2 = F.gelu(ref + bias.float()) + res.float()
     rp = torch.zeros(M, (N + 63) // 64 * 64, dtype=dtype)
     rp[:, :N] = res
@@ -362,9 +374,15 @@ def test_gemm_epilogues(K, dtype):
     for name, (kw, ref) in cases.items():
         out = K.gemm(0, a.cuda(), w.cuda(), M, N, Kd, **kw)
         assert rel(out.float(), ref) < TOL[dtype], name
+        assert GC.last_kernel() == (GC.expected_kernel(0, M, N, Kd, acts="act" in kw) if dtype == torch.bfloat16 else GC.F32), name
+        if dtype == torch.bfloat16 and "act" not in kw:
+            epi = (GC.EPI_BIAS if "bias" in kw else 0) | (GC.EPI_RESIDUAL if "residual" in kw else 0)
+            GC.check_random(name, out, a, w, epi, bias=bias, res=res)
     c0 = rnd((M, N), dtype, 7)
     out = K.gemm(0, a.cuda(), w.cuda(), M, N, Kd, out=c0.cuda().clone(), accumulate=True)
     assert rel(out.float(), base + c0.float()) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        GC.check_random("accumulate", out, a, w, GC.EPI_ACCUMULATE, c0=c0)
     cs = torch.empty(N, dtype=dtype, device="cuda")
     K.colsum(res.cuda(), cs, False)
     assert rel(cs.float(), res.float().sum(0)) < TOL[dtype]

@@ -9,6 +9,8 @@ import torch.nn.functional as F  # noqa: F401
 
 from tests.test_kernels_gpu import TOL, attn_ref, rel, rnd, K  # noqa: F401  (K: the kernels fixture)
 
+from tests import gemm_check as GC
+
 pytestmark = pytest.mark.gpu
 _rng = random.Random(20260131)
 
@@ -55,10 +57,13 @@ def test_gemm_random(K, case):      # noqa: F811
     try:
         out = K.gemm(lay, A, B, M, N, Kd, bias=bias.cuda() if bias is not None else None, residual=res, ldc_pad=True)
         torch.cuda.synchronize()
+        kid = GC.last_kernel()
     finally:
         lib().mm_set_option(b"gemm_kernel", 0)
     assert out.shape == (M, N)
     assert rel(out.float(), ref) < TOL[dtype], case
+    assert kid == GC.expected_kernel(lay, M, N, Kd, forced=variant), case
+    GC.check_random(str(case), out, a, b, (GC.EPI_BIAS | GC.EPI_RESIDUAL) if with_epi else 0, bias=bias, res=res)
 
 
 def _attn_cases(n):
