@@ -218,6 +218,30 @@ int mm_attn_bwd(int dtype, const void* q, const void* k, const void* v, const vo
 int mm_rope_append(int dtype, void* x, int T, int Hq, int Hkv, int D, int ld, const float* cos_t, const float* sin_t,
                    void* kdst, void* vdst, int64_t dstride, void* stream);
 
+/* ---- Qwen3 per-head q/k RMSNorm + RoPE (HF 5.15 models/qwen3/modeling_qwen3.py:50-64,237-257):
+ * q = RoPE(q_norm(q_proj(h).view(.., Hq, D))), k = RoPE(k_norm(k_proj(h).view(.., Hkv, D))), w_q / w_k [D].  bf16 or f32; D in
+ * {64, 128} (MM_ERR_UNSUPPORTED otherwise).  cos_t / sin_t: mm_rope_table's [T, D/2] tables.
+ * mm_qk_norm_rope_fwd: x = the q|k heads [T, (Hq+Hkv)*D] (row stride ld_in; the q|k columns of the fused projection output)
+ *   -> out [T, (Hq+Hkv)*D] (row stride ld_out) and rstd [T, Hq+Hkv] f32 (may be NULL).  Per head: fp32 sum of squares (any order),
+ *   rstd = rsqrtf(ss/D + eps), y = bf16(w * bf16(x*rstd)) (mm_rmsnorm_fwd's rounding points), then mm_rope_apply's rotation of y:
+ *   given the kernel's own rstd, out is bit-identical to that chain followed by mm_rope_apply.  out == x (with ld_out == ld_in)
+ *   runs in place: every lane stores only the elements it loaded.
+ * mm_qk_norm_rope_bwd: dqk = d(out) (row stride ld_dqk), x / rstd as in forward -> dx (row stride ld_dx; the q|k columns of the
+ *   projection's dqkv, nothing else is written): inverse RoPE, then mm_rmsnorm_bwd's dx = rstd*(g - xhat*mean(g*xhat)), g = dy*w.
+ *   dwq_partial / dwk_partial [mm_qk_norm_bwd_blocks(T), D] f32 (reduce with mm_reduce_partials): deterministic, no atomics;
+ *   both NULL skips dw (frozen norms; dx is still written).
+ * mm_qk_norm_rope_append: decode step: the forward in place on the q|k heads of x [T, (Hq+2Hkv)*D] (row stride ld) plus the append
+ *   of the normed, roped k heads and the v heads to the KV cache rows kdst / vdst, as mm_rope_append.  Same head code as the forward:
+ *   bit-identical to mm_qk_norm_rope_fwd in place followed by the cache copy.                                                   */
+int mm_qk_norm_rope_fwd(int dtype, const void* x, int ld_in, int T, int Hq, int Hkv, int D, const void* w_q, const void* w_k, float eps,
+                        const float* cos_t, const float* sin_t, void* out, int ld_out, float* rstd, void* stream);
+int mm_qk_norm_bwd_blocks(int T);
+int mm_qk_norm_rope_bwd(int dtype, const void* dqk, int ld_dqk, const void* x, int ld_x, int T, int Hq, int Hkv, int D, const void* w_q,
+                        const void* w_k, const float* rstd, const float* cos_t, const float* sin_t, void* dx, int ld_dx, float* dwq_partial,
+                        float* dwk_partial, void* stream);
+int mm_qk_norm_rope_append(int dtype, void* x, int T, int Hq, int Hkv, int D, int ld, const void* w_q, const void* w_k, float eps,
+                           const float* cos_t, const float* sin_t, void* kdst, void* vdst, int64_t dstride, void* stream);
+
 /* ---- decode-step fusions on the weight-streaming GEMM (KV-cache decode of `generate`, reference model.py:595-602; M = batch <= 16;
  * MM_BF16).  Each replaces a GEMM + the tiny launches around it in HF's LlamaDecoderLayer (HF:llama:284-325) with the arithmetic
  * and rounding points of the separate kernels (same bits).  `in_norm_w` (may be NULL) / `eps`: the RMSNorm IN FRONT of the projection

@@ -357,10 +357,18 @@ def rope_attention(qkv, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale):
 class QKVRopeAttentionFn(torch.autograd.Function):
     """The decoder's attention front half as ONE node: fused q|k|v projection with RoPE in its epilogue (mm_gemm_rope_fwd; the
     projection + mm_rope_apply when a shape does not qualify: same bits), then flash attention.  h [T, H] -> out [T, Hq*D].
-    Backward = attention backward, inverse RoPE on d(q|k) in place, then the projection's wgrad / bias / dgrad (LinearFn's)."""
+    Backward = attention backward, inverse RoPE on d(q|k) in place, then the projection's wgrad / bias / dgrad (LinearFn's).
+
+    qkn = (q_norm weight, k_norm weight, eps) (Qwen3): the projection (never the RoPE epilogue), then the per-head RMSNorm + RoPE of
+    q|k into a separate buffer `qk` (the raw values stay in qkv for backward, v is read where it is), then attention on q / k of qk
+    and v of qkv.  Backward: attention writes d(q|k) into dqk (qk's strides) and dv into dqkv, mm_qk_norm_rope_bwd fills the q|k
+    columns of dqkv (and the norm weights' gradients), then the projection's backward as above."""
 
     @staticmethod
-    def forward(ctx, h, dummy, wg: ParamGroup, bg: Optional[ParamGroup], cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale):
+    def forward(ctx, h, dummy, wg: ParamGroup, bg: Optional[ParamGroup], cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn=None):
+        if qkn is not None:
+            return QKVRopeAttentionFn._forward_qk_norm(ctx, h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn)
+        ctx.qkn = None
         w = wg.tensor()
         b = bg.tensor() if bg is not None else None
         W = (Hq + 2 * Hkv) * D
@@ -379,7 +387,56 @@ class QKVRopeAttentionFn(torch.autograd.Function):
         return out.view(B * S, Hq * D)
 
     @staticmethod
+    def _forward_qk_norm(ctx, h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn):
+        assert cos is not None, "the q/k norm path always applies RoPE"
+        qn, kn, eps = qkn
+        qkv = K.linear_fwd(h, wg.tensor(), bias=bg.tensor() if bg is not None else None)
+        qk, rstd = K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, qn.data, kn.data, eps, cos, sin)
+        q = qk[:, : Hq * D].view(B, S, Hq, D)
+        k = qk[:, Hq * D:].view(B, S, Hkv, D)
+        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
+        out, lse = K.attn_fwd(q, k, v, key_mask, causal, scale)
+        ctx.dims = (B, S, Hq, Hkv, D, causal, scale)
+        ctx.wg, ctx.bg, ctx.qkn = wg, bg, (qn, kn)
+        ctx.save_for_backward(h, qkv, out, lse, cos, sin, key_mask, qk, rstd)
+        return out.view(B * S, Hq * D)
+
+    @staticmethod
+    def _backward_qk_norm(ctx, dout):
+        h, qkv, out, lse, cos, sin, key_mask, qk, rstd = ctx.saved_tensors
+        B, S, Hq, Hkv, D, causal, scale = ctx.dims
+        wg, bg = ctx.wg, ctx.bg
+        qn, kn = ctx.qkn
+        f32 = qkv.dtype == torch.float32          # the fp32 attention backward accumulates with atomics
+        dqkv = torch.zeros_like(qkv) if f32 else torch.empty_like(qkv)
+        dqk = torch.zeros_like(qk) if f32 else torch.empty_like(qk)
+        dq = dqk[:, : Hq * D].view(B, S, Hq, D)
+        dk = dqk[:, Hq * D:].view(B, S, Hkv, D)
+        dv = dqkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
+        q = qk[:, : Hq * D].view(B, S, Hq, D)
+        k = qk[:, Hq * D:].view(B, S, Hkv, D)
+        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
+        K.attn_bwd(q, k, v, out, dout.contiguous().view(B, S, Hq, D), lse, key_mask, causal, scale, dq, dk, dv)
+        del dq, dk
+        want_dw = qn.requires_grad or kn.requires_grad
+        dwq, dwk = K.qk_norm_rope_bwd(dqk, qkv, B * S, Hq, Hkv, D, qn.data, kn.data, rstd, cos, sin, dqkv, want_dw=want_dw)
+        for p, part in ((qn, dwq), (kn, dwk)):
+            if p.requires_grad:
+                g, acc = grad_target(p)
+                K.reduce_partials(part, g, acc)
+                _ready(p)
+        if bg is not None and bg.requires_grad:
+            g, acc = bg.grad_target()
+            K.colsum(dqkv, g, acc)
+            bg.ready()
+        _wgrad(dqkv, h, wg)
+        dh = K.linear_dgrad(dqkv, wg.tensor()) if ctx.needs_input_grad[0] else None
+        return (dh,) + (None,) * 14
+
+    @staticmethod
     def backward(ctx, dout):
+        if ctx.qkn is not None:
+            return QKVRopeAttentionFn._backward_qk_norm(ctx, dout)
         h, qkv, out, lse, cos, sin, key_mask = ctx.saved_tensors
         B, S, Hq, Hkv, D, causal, scale = ctx.dims
         wg, bg = ctx.wg, ctx.bg
@@ -400,12 +457,13 @@ class QKVRopeAttentionFn(torch.autograd.Function):
             bg.ready()
         _wgrad(dqkv, h, wg)
         dh = K.linear_dgrad(dqkv, wg.tensor()) if ctx.needs_input_grad[0] else None
-        return (dh,) + (None,) * 13
+        return (dh,) + (None,) * 14
 
 
-def qkv_rope_attention(h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, dummy=None):
+def qkv_rope_attention(h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, dummy=None, qkn=None):
+    """qkn: optional (q_norm weight, k_norm weight, eps) of a Qwen3 layer (per-head RMSNorm of q and k in front of RoPE)."""
     return QKVRopeAttentionFn.apply(h, dummy, as_group(wg), as_group(bg) if bg is not None else None, cos, sin, key_mask, B, S, Hq, Hkv, D,
-                                    causal, scale)
+                                    causal, scale, qkn)
 
 
 class HeadPadFn(torch.autograd.Function):

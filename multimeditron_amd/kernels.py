@@ -433,6 +433,43 @@ def rope_append_(qkv, B, Hq, Hkv, D, cos, sin, kcache, vcache, pos):
     return qkv
 
 
+def qk_norm_rope_fwd(qkv, T, Hq, Hkv, D, w_q, w_k, eps, cos, sin, out=None, want_rstd=True):
+    """Qwen3: per-head RMSNorm (w_q / w_k) + RoPE of the q|k heads of qkv [T, >= (Hq+Hkv)*D] (row stride qkv.stride(0)).
+    out: None -> a new [T, (Hq+Hkv)*D] buffer; out is qkv -> in place.  -> (qk, rstd [T, Hq+Hkv] f32 or None)."""
+    assert qkv.stride(-1) == 1 and w_q.is_contiguous() and w_k.is_contiguous()
+    if out is None:
+        out = torch.empty((T, (Hq + Hkv) * D), dtype=qkv.dtype, device=qkv.device)
+    rstd = torch.empty((T, Hq + Hkv), dtype=torch.float32, device=qkv.device) if want_rstd else None
+    call("mm_qk_norm_rope_fwd", dt(qkv), _p(qkv), qkv.stride(0), T, Hq, Hkv, D, _p(w_q), _p(w_k), float(eps), _p(cos), _p(sin), _p(out),
+         out.stride(0), _p(rstd), _stream())
+    return out, rstd
+
+
+def qk_norm_bwd_blocks(T):
+    return _lib.lib().mm_qk_norm_bwd_blocks(T)
+
+
+def qk_norm_rope_bwd(dqk, qkv, T, Hq, Hkv, D, w_q, w_k, rstd, cos, sin, dqkv, want_dw=True):
+    """Writes d(raw q|k) into the q|k columns of dqkv (nothing else).  -> (dwq_partial, dwk_partial) [nblk, D] f32, or (None, None)."""
+    assert dqk.stride(-1) == 1 and qkv.stride(-1) == 1 and dqkv.stride(-1) == 1 and rstd.is_contiguous()
+    dwq = dwk = None
+    if want_dw:
+        nb = qk_norm_bwd_blocks(T)
+        dwq = torch.empty((nb, D), dtype=torch.float32, device=qkv.device)
+        dwk = torch.empty((nb, D), dtype=torch.float32, device=qkv.device)
+    call("mm_qk_norm_rope_bwd", dt(qkv), _p(dqk), dqk.stride(0), _p(qkv), qkv.stride(0), T, Hq, Hkv, D, _p(w_q), _p(w_k), _p(rstd), _p(cos),
+         _p(sin), _p(dqkv), dqkv.stride(0), _p(dwq), _p(dwk), _stream())
+    return dwq, dwk
+
+
+def qk_norm_rope_append_(qkv, B, Hq, Hkv, D, w_q, w_k, eps, cos, sin, kcache, vcache, pos):
+    """decode step (Qwen3): per-head norm + RoPE of q/k in place + write the normed, roped k and v to cache[:, pos]."""
+    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
+    call("mm_qk_norm_rope_append", dt(qkv), _p(qkv), B, Hq, Hkv, D, qkv.stride(0), _p(w_q), _p(w_k), float(eps), _p(cos), _p(sin),
+         _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0), _stream())
+    return qkv
+
+
 # ------------------------------------------------------------------------------------------------ attention
 def _strides3(t):  # t: [B, S, H, D] view
     assert t.dim() == 4 and t.stride(3) == 1

@@ -1,10 +1,12 @@
-"""Llama / Qwen2 decoder on libmmhip kernels: the MI355X replacement for the HF `AutoModelForCausalLM` the
+"""Llama / Qwen2 / Qwen3 decoder on libmmhip kernels: the MI355X replacement for the HF `AutoModelForCausalLM` the
 reference constructs at model.py:253-260 and calls at model.py:517-526 (forward) and :595-602 (decode).
 
 Semantics follow HF transformers 5.15.0 (models/llama/modeling_llama.py): RMSNorm :53-70, RoPE :113-160 (+ llama3
 inv_freq scaling modeling_rope_utils.py:641-662), GQA softmax attention :191-281, SwiGLU MLP :163-176, pre-norm
 residual layer :284-325, final norm + lm_head :413,480, shifted CE loss/loss_utils.py:36-71.  Qwen2 = same graph with
-biased q/k/v projections.  Parameter names equal HF's so reference checkpoints interchange.
+biased q/k/v projections.  Qwen3 = Llama with a per-head RMSNorm of q and k (`q_norm` / `k_norm`, weights [head_dim]) between
+the projection and RoPE (HF 5.15 models/qwen3/modeling_qwen3.py:50-64,237-257).  Parameter names equal HF's so reference
+checkpoints interchange.
 
 Data layout: activations are [B*S, features] row-major in HBM; q/k/v come out of ONE fused GEMM as a
 [B*S, (Hq+2Hkv)*D] buffer that RoPE rewrites in place and the attention kernel reads through strides; gate/up come
@@ -36,6 +38,7 @@ class LLMConfig:
     rms_norm_eps: float = 1e-5
     tie_word_embeddings: bool = False
     attention_bias: bool = False
+    qk_norm: bool = False              # Qwen3: RMSNorm over every q and k head before RoPE
     max_position_embeddings: int = 131072
     rope_parameters: Dict[str, Any] = field(default_factory=lambda: {"rope_type": "default", "rope_theta": 10000.0})
 
@@ -53,6 +56,12 @@ class LLMConfig:
         kw["rope_parameters"] = rp
         if mt.startswith("qwen2"):
             kw["attention_bias"] = True          # Qwen2 hard-codes biased q/k/v (HF:models/qwen2)
+        if mt.startswith("qwen3"):
+            if mt != "qwen3":
+                raise NotImplementedError(f"model_type {mt!r}: only dense Qwen3 decoders are supported")
+            if "sliding_attention" in (d.get("layer_types") or ()):
+                raise NotImplementedError("Qwen3 sliding-window attention layers are not supported")
+            kw["qk_norm"] = True                 # Qwen3: q_norm / k_norm per head (HF:models/qwen3:237-257)
         if not kw.get("head_dim"):
             kw["head_dim"] = kw.get("hidden_size", 4096) // kw.get("num_attention_heads", 32)
         return cls(**kw)
@@ -90,6 +99,12 @@ class Attention(nn.Module):
         self.o_proj = Linear(self.Hq * D, H, bias=False, dtype=dtype, device=device)
         self._wqkv = Fm.ParamGroup([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight])
         self._bqkv = Fm.ParamGroup([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]) if b else None
+        self.q_norm = Norm(D, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device) if cfg.qk_norm else None
+        self.k_norm = Norm(D, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device) if cfg.qk_norm else None
+
+    def qkn(self):
+        """(q_norm weight, k_norm weight, eps) of a Qwen3 layer, else None."""
+        return None if self.q_norm is None else (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps)
 
 
 class MLP(nn.Module):
@@ -122,7 +137,10 @@ class DecoderLayer(nn.Module):
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         h, _ = K.rmsnorm_fwd(x, self.input_layernorm.weight, self.input_layernorm.eps)
         qkv = K.linear_fwd(h, a._wqkv.tensor(), bias=a._bqkv.tensor() if a._bqkv is not None else None)
-        K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, cache.k, cache.v, cache.len)
+        if a.q_norm is not None:
+            K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, cache.k, cache.v, cache.len)
+        else:
+            K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, cache.k, cache.v, cache.len)
         cache.len += 1
         o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
         x = K.linear_fwd(o.view(B, Hq * D), a.o_proj.weight, residual=x)
@@ -154,7 +172,7 @@ class DecoderLayer(nn.Module):
 
     def can_decode_step_fused(self, x, B, S, cache):
         a = self.self_attn
-        return (self.can_decode_step(x, B, S, cache) and a.D == 128 and K.decode_fusions() and x.shape[-1] <= 8192 and self.mlp.I % 4 == 0
+        return (self.can_decode_step(x, B, S, cache) and a.D == 128 and a.q_norm is None and K.decode_fusions() and x.shape[-1] <= 8192 and self.mlp.I % 4 == 0
                 and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
                 and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.input_layernorm.bias is None)
 
@@ -169,7 +187,7 @@ class DecoderLayer(nn.Module):
         h, x = self.input_layernorm(x)
         if cache is None:      # projection (+ RoPE in its epilogue) + attention as one autograd node
             o = Fm.qkv_rope_attention(h, a._wqkv, a._bqkv, cos, sin, key_mask, B, S, a.Hq, a.Hkv, a.D, True, a.D ** -0.5,
-                                      dummy=grad_dummy(a.q_proj.weight))
+                                      dummy=grad_dummy(a.q_proj.weight), qkn=a.qkn())
         else:
             qkv = Fm.linear(h, a._wqkv, a._bqkv, dummy=grad_dummy(a.q_proj.weight))
             o = cache.attend(qkv, cos, sin, key_mask, B, S, a)
@@ -193,7 +211,10 @@ class LayerKVCache:
     def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         W = (Hq + 2 * Hkv) * D
-        K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
+        if a.q_norm is not None:       # in place: prefill keeps no backward
+            K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, out=qkv, want_rstd=False)
+        else:
+            K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
         q = qkv[:, : Hq * D].view(B, S, Hq, D)
         kn = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
         vn = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)

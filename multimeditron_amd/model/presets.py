@@ -19,6 +19,13 @@ LLM_PRESETS: Dict[str, Dict[str, Any]] = {
                                     num_attention_heads=28, num_key_value_heads=4, head_dim=128, vocab_size=152064,
                                     rms_norm_eps=1e-6, tie_word_embeddings=False,
                                     rope_parameters={"rope_type": "default", "rope_theta": 1000000.0}),
+    # Qwen3-4B-Instruct-2507 (the reference's cookbook/sft/single_clip/two_phase_alignment/config_alignment_generalist_qwen.yaml):
+    # values from the public model card's config.json.  There is no hub access in this build, so this entry is the only copy:
+    # a local checkpoint directory's config.json takes precedence (resolve_llm_config).
+    "Qwen/Qwen3-4B-Instruct-2507": dict(model_type="qwen3", hidden_size=2560, intermediate_size=9728, num_hidden_layers=36,
+                                         num_attention_heads=32, num_key_value_heads=8, head_dim=128, vocab_size=151936,
+                                         rms_norm_eps=1e-6, tie_word_embeddings=True, max_position_embeddings=262144,
+                                         rope_parameters={"rope_type": "default", "rope_theta": 5000000.0}),
 }
 for _alias, _name in (("meta-llama/Llama-3.1-8B", "meta-llama/Llama-3.1-8B-Instruct"),
                       ("meta-llama/Llama-3.2-1B", "meta-llama/Llama-3.2-1B-Instruct"),

@@ -10,7 +10,7 @@ init), inputs, per-stage activations, logits, loss, selected grads, greedy token
 collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 
 Import recipe = SURVEY.md Appendix A (three harness-side shims, none edits the reference).
-The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 modules as called
+The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 modules as called
 by the reference at model.py:433-444,517-526,595-640 and image_modality.py:130-137.
 """
 import io
@@ -28,7 +28,7 @@ import torch
 import transformers
 from transformers import (AutoConfig, AutoModel, AutoModelForCausalLM, AutoProcessor,  # noqa: F401
                           CLIPConfig, CLIPImageProcessorPil, CLIPModel, LlamaConfig,
-                          PreTrainedTokenizerFast, Qwen2Config)
+                          PreTrainedTokenizerFast, Qwen2Config, Qwen3Config)
 from safetensors.torch import save_file
 
 REF_SRC = "/root/reference/src/multimeditron"
@@ -111,6 +111,36 @@ def qwen2_cfg():
                        num_key_value_heads=1, vocab_size=128, rms_norm_eps=1e-6, max_position_embeddings=32768,
                        tie_word_embeddings=True, use_sliding_window=False,
                        rope_parameters={"rope_type": "default", "rope_theta": 1000000.0})
+
+
+def qwen3_cfg():
+    """Qwen3 (per-head q_norm / k_norm in front of RoPE) at head_dim 128 with GQA 4:1, so that the D = 128 attention kernels and
+    the fused q/k norm + RoPE kernels both run; tied embeddings as Qwen3-4B."""
+    return Qwen3Config(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=1,
+                       head_dim=128, vocab_size=128, rms_norm_eps=1e-6, tie_word_embeddings=True,
+                       rope_parameters={"rope_type": "default", "rope_theta": 1000000.0})
+
+
+SHARD_BYTES = 960 * 1024     # every committed file stays below 1 MiB
+
+
+def save_sharded(tensors, name, kind):
+    """-> the file names written: {name}.{kind}.safetensors when it fits SHARD_BYTES, else {name}.{kind}.{i}.safetensors (i = 0..),
+    tensors packed in key order.  tests read them back through the `shards` entry of the fixture's meta.json."""
+    shards, cur, size = [], {}, 0
+    for k in sorted(tensors):
+        t = tensors[k].contiguous()
+        n = t.numel() * t.element_size()
+        if cur and size + n > SHARD_BYTES:
+            shards.append(cur)
+            cur, size = {}, 0
+        cur[k] = t
+        size += n
+    shards.append(cur)
+    files = [f"{name}.{kind}.safetensors"] if len(shards) == 1 else [f"{name}.{kind}.{i}.safetensors" for i in range(len(shards))]
+    for f, sh in zip(files, shards):
+        save_file(sh, os.path.join(OUT, f))
+    return files
 
 
 def randomize_(model, seed):
@@ -256,7 +286,7 @@ def run_case(model, batch, tag, out, do_grads=True, do_generate=False):
             out[f"{tag}.greedy_T{T}"] = ids.clone()
 
 
-def model_fixture(name, llm_cfg, seed, long_seq=False):
+def model_fixture(name, llm_cfg, seed, long_seq=False, sharded=False):
     with tempfile.TemporaryDirectory() as tmp:
         model = build_model(llm_cfg, seed, tmp)
         out = {}
@@ -276,12 +306,18 @@ def model_fixture(name, llm_cfg, seed, long_seq=False):
                     or "position_ids" in n or "post_layernorm" in n:
                 continue
             w[n] = p.detach().to(torch.bfloat16).contiguous().clone()
-        save_file(w, os.path.join(OUT, f"{name}.weights.safetensors"))
-        save_file({k: v.contiguous() for k, v in out.items()}, os.path.join(OUT, f"{name}.vectors.safetensors"))
+        shards = None
+        if sharded:
+            shards = {"weights": save_sharded(w, name, "weights"), "vectors": save_sharded(out, name, "vectors")}
+        else:
+            save_file(w, os.path.join(OUT, f"{name}.weights.safetensors"))
+            save_file({k: v.contiguous() for k, v in out.items()}, os.path.join(OUT, f"{name}.vectors.safetensors"))
         meta = dict(name=name, vision=VIS, llm=llm_cfg.to_dict(), vocab_size=VOCAB, eos_token_idx=EOS,
                     image_start=IMG_START, image_end=IMG_END, attachment=ATTACH, num_patches=P,
                     transformers=transformers.__version__, torch=torch.__version__,
                     cases=sorted({k.split(".")[0] for k in out}))
+        if shards:
+            meta["shards"] = shards
         meta["llm"] = {k: v for k, v in meta["llm"].items()
                        if isinstance(v, (int, float, str, bool, dict, type(None), list))}
         with open(os.path.join(OUT, f"{name}.meta.json"), "w") as f:
@@ -786,7 +822,7 @@ def collator_fixture():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["llama", "trunc", "qwen2", "llama_d128", "siglip", "moe", "moe_pep", "collator", "ckpt"]
+    which = sys.argv[1:] or ["llama", "trunc", "qwen2", "llama_d128", "qwen3", "siglip", "moe", "moe_pep", "collator", "ckpt"]
     if "llama" in which:
         model_fixture("tiny_clip_llama", llama_cfg(), 100)
     if "trunc" in which:
@@ -795,6 +831,9 @@ if __name__ == "__main__":
         model_fixture("tiny_clip_qwen2", qwen2_cfg(), 200)
     if "llama_d128" in which:
         model_fixture("tiny_clip_llama_d128", llama_d128_cfg(), 400, long_seq=True)
+    if "qwen3" in which:    # sharded: every file below 1 MiB
+        model_fixture("tiny_clip_qwen3", qwen3_cfg(), 900, sharded=True)
+        model_fixture("tiny_clip_qwen3_long", qwen3_cfg(), 910, long_seq=True, sharded=True)
     if "siglip" in which:
         siglip_fixture()
     if "moe" in which:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Small HBM-bound kernels in isolation at the shapes of the 8B step (decoder rows 8192 x 4096, ViT-L rows 1028 x 1024/4096):
 time per launch and the bytes each must move, so that an in-step duration (rocprofv3, other streams sharing the chip) can be
-told from the kernel's own speed."""
+told from the kernel's own speed.  Also Qwen3's fused per-head q/k RMSNorm + RoPE at the Qwen3-4B step's shape."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -49,6 +49,24 @@ def main():
     x = torch.randn(1028, 4096, device=dev).to(bf)
     timeit("gelu_fwd(quick) 1028x4096", lambda: K.gelu_fwd(x, 1), 2 * x.numel() * 2)
     timeit("gelu_bwd(quick) 1028x4096", lambda: K.gelu_bwd(x, x, 1), 3 * x.numel() * 2)
+    # Qwen3's per-head q/k norm + RoPE at the 4B step's shape (T = 8192 tokens, 32 + 8 heads x 128 inside a 48-head qkv row),
+    # next to the RoPE alone on the same heads (the Llama path's separate pass)
+    T, Hq, Hkv, D = 8192, 32, 8, 128
+    nh, W = Hq + Hkv, (Hq + 2 * Hkv) * D
+    qkv = torch.randn(T, W, device=dev).to(bf)
+    wq, wk = torch.ones(D, device=dev, dtype=bf), torch.ones(D, device=dev, dtype=bf)
+    cos, sin = K.rope_table(torch.arange(T, device=dev), torch.rand(D // 2, device=dev), True)
+    qk, rstd = K.qk_norm_rope_fwd(qkv, T, Hq, Hkv, D, wq, wk, 1e-6, cos, sin)
+    tab = 2 * T * (D // 2) * 4
+    timeit(f"qk_norm_rope_fwd {T}x{nh}x{D}", lambda: K.qk_norm_rope_fwd(qkv, T, Hq, Hkv, D, wq, wk, 1e-6, cos, sin, out=qk),
+           2 * T * nh * D * 2 + T * nh * 4 + tab)
+    dqkv = torch.empty_like(qkv)
+    timeit(f"qk_norm_rope_bwd {T}x{nh}x{D}", lambda: K.qk_norm_rope_bwd(qk, qkv, T, Hq, Hkv, D, wq, wk, rstd, cos, sin, dqkv),
+           3 * T * nh * D * 2 + T * nh * 4 + tab)
+    dwq, _ = K.qk_norm_rope_bwd(qk, qkv, T, Hq, Hkv, D, wq, wk, rstd, cos, sin, dqkv)
+    out = torch.zeros(D, device=dev, dtype=bf)
+    timeit(f"reduce_partials {dwq.shape[0]}x{D} (x2 per layer)", lambda: K.reduce_partials(dwq, out, True), dwq.numel() * 4)
+    timeit(f"rope_apply {T}x{nh}x{D} (Llama path)", lambda: K.rope_apply_(qkv, T, nh, D, W, cos, sin), 2 * T * nh * D * 2 + tab)
     x = torch.empty(1 << 28, device=dev, dtype=bf)
     timeit("torch zero_ 512 MB", lambda: x.zero_(), x.numel() * 2, it=10)
 
