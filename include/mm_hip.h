@@ -97,16 +97,6 @@ int mm_gemm_act_fwd(int dtype, int M, int N, int K, const void* X, int ldx, cons
 int mm_gemm_swiglu_bwd(int dtype, int M, int I, int H, const void* dY, int lddy, const void* Wd, int ldw, const void* GU,
                        int ldgu, void* dGU, int lddgu, void* stream);
 
-/* a GEMM that also returns the sum of squares of what it stores: the call overwrites the first n <= capacity partials and leaves
- * the others alone; on a buffer the caller zeroed beforehand they sum to sum(C^2) over the bf16 values written (after
- * MM_EPI_ACCUMULATE, the only epilogue allowed).  For the weight gradients, so that the global gradient norm of `max_grad_norm`
- * clipping (config_alignment.yaml:49 -> HF Trainer -> torch.nn.utils.clip_grad_norm_) can be assembled per GEMM.  Deterministic:
- * fixed slot per workgroup, no atomics.  Implemented as the GEMM followed by a reduction pass over C (the in-epilogue form cost
- * every GEMM more than it saved: csrc/mm_gemm.hip).  mm_gemm_sumsq_slots -> the capacity to provide for a problem.               */
-int mm_gemm_sumsq_slots(int dtype, int layout, int M, int N, int K, int64_t* slots);
-int mm_gemm_sumsq(int dtype, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                  int epilogue, float* partials, int64_t capacity, void* stream);
-
 /* column sums: out[N] (+)= sum_m X[m,n]   (bias gradients)                                           */
 int mm_colsum(int dtype, const void* X, int M, int N, int ldx, void* out, int accumulate, void* stream);
 
@@ -405,21 +395,12 @@ int mm_image_resample_v_norm(const void* tmp_u8, int r0, int nrows, int cw, cons
 /* ---- utilities ---------------------------------------------------------------------------------------------------- */
 int mm_cast(int src_dtype, int dst_dtype, const void* src, void* dst, int64_t n, void* stream);
 int mm_fill_zero(void* p, int64_t bytes, void* stream);
+int mm_device_cu_count(void);                        /* compute units of the current device (-1: no device) */
 
 /* ---- diagnostics (tests only): raw lane maps of ds_read_b64_tr_b16 and the bf16 MFMAs ------------------------------
  * tr_read: img = 4096 bf16 copied to LDS; lane l reads at byte address addr[l]; out[l*4+j] = its j-th element.
  * mfma: shape 32 -> v_mfma_f32_32x32x16_bf16 (out 64x16 f32), 16 -> v_mfma_f32_16x16x32_bf16 (out 64x4 f32);
  *       a/b = 64 lanes x 8 bf16 fragments.                                                                         */
-/* Streams restricted to a subset of the CUs (no reference counterpart: the reference leaves kernel placement to PyTorch).  `mask`:
- * bit i of word i / 32 enables CU i (hipExtStreamCreateWithCUMask).  The Trainer runs AdamW and the deferred weight-gradient GEMMs
- * on such streams so that the small kernels of the modality tower they overlap always find free CUs.  mm_debug_cu_probe: where
- * the workgroups of a launch on `stream` ran (XCC_ID and HW_ID registers), for tools/cumask_probe.py.                            */
-int mm_stream_create_cu_mask(const unsigned* mask, int nwords, void** stream);
-int mm_stream_priority_range(int* least, int* greatest);
-int mm_stream_create_priority(int priority, void** stream);
-int mm_stream_destroy(void* stream);
-int mm_device_cu_count(void);
-int mm_debug_cu_probe(void* out_u32, int n_wg, int threads, int64_t spin_ticks, void* stream);
 int mm_debug_tr_read(const void* img_bf16_4096, const void* lane_byte_addr_i32_64, void* out_bf16_256, void* stream);
 int mm_debug_mfma(int shape, const void* a_frag_bf16_512, const void* b_frag_bf16_512, void* out_f32, void* stream);
 

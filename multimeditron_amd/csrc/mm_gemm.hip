@@ -52,10 +52,8 @@ struct GemmArgs {
   // per-token tables rope_cos / rope_sin [M, 64] f32 (0 = no rotation).  The B tile's rows are gathered so that a lane owns
   // columns d and d + 64 of a head (rope_row).
   const float* rope_cos; const float* rope_sin; int rope_cols;
-  // sum of squares of what the epilogue stores (mm_gemm_sumsq, EK = 5): per output tile 16 slots = [column half][wave]; a full
-  // 256x256 tile fills half 0 and zeroes half 1, the half tiles of the last round fill their own half: the slot of a value does
-  // not depend on how the tiles were scheduled (persistent / one tile per workgroup, tail split or not).
-  float* ss;
+  float* unused_ptr;            // no kernel reads it: it keeps the kernel-argument offsets of the fields below, on which the 4-wave
+                                // kernels' scalar register allocation was tuned (without it the RoPE instantiation spills differently)
   int group_m;                  // 4-wave kernel: GROUP_M of the tile order (8)
   int stream_epi;               // 4-wave kernel: the plain epilogue without waits between its stores (gemm_epilogue_plain_stream)
   int shuffle;                  // 4-wave kernel: plain stores by register lane exchange instead of the LDS round trip (w4_shuffle_half)
@@ -311,10 +309,9 @@ __device__ __forceinline__ void gemm_epilogue_swiglu_bwd(const GemmArgs& g, f32x
 // keeps the scalar path.
 constexpr unsigned EPI_OOB = 0xFFFFFFFFu;
 
-template <int MREP, int NREP, bool SUMSQ = false>
-__device__ __forceinline__ void gemm_epilogue_plain_pipe(const GemmArgs& g, f32x4 (&acc)[MREP][NREP], int mw, int nw, int ss_slot = 0, int lane = -1) {
+template <int MREP, int NREP>
+__device__ __forceinline__ void gemm_epilogue_plain_pipe(const GemmArgs& g, f32x4 (&acc)[MREP][NREP], int mw, int nw, int lane = -1) {
   const int l = lane >= 0 ? lane : (int)(threadIdx.x & 63);      // lane: the caller's (opaque) copy of the lane index, see gemm_bf16_w4_kernel
-  float ssq = 0.f;
   mw = __builtin_amdgcn_readfirstlane(mw);
   nw = __builtin_amdgcn_readfirstlane(nw);
   const int epi = g.epi;
@@ -349,7 +346,6 @@ __device__ __forceinline__ void gemm_epilogue_plain_pipe(const GemmArgs& g, f32x
     }
   };
   request(0, 0);
-  const unsigned row_lim = rows > 0 ? (unsigned)((rows < MREP * 16 ? rows : MREP * 16) * g.ldc) * 2u : 0u;      // wave-uniform: byte offset of the first row >= M
 #pragma unroll
   for (int i = 0; i < MREP; ++i) {
     if (i + 1 < MREP) request(i + 1, (i + 1) & 1);
@@ -374,13 +370,6 @@ __device__ __forceinline__ void gemm_epilogue_plain_pipe(const GemmArgs& g, f32x
       bf16x4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = (bf16)v[r];
-      if constexpr (SUMSQ) {      // of the bf16 values as stored; a row >= M or a column >= N holds whatever the operand tiles'
-                                  // neighbours hold (only the STORE is range-checked), so both are masked here
-        if (colb[j] != EPI_OOB && rowc < row_lim) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ssq = __builtin_fmaf((float)o[r], (float)o[r], ssq);
-        }
-      }
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rc, colb[j] == EPI_OOB ? EPI_OOB : rowc + colb[j], 0, 0);
     }
   }
@@ -401,19 +390,10 @@ __device__ __forceinline__ void gemm_epilogue_plain_pipe(const GemmArgs& g, f32x
               if (has_bias) v += (float)bias[n + r];
               if (has_res) v += (float)((const bf16*)g.residual)[(int64_t)m * g.ldr + n + r];
               if (has_acc) v += (float)cp[r];
-              const bf16 ob = (bf16)v;
-              cp[r] = ob;
-              if constexpr (SUMSQ) ssq = __builtin_fmaf((float)ob, (float)ob, ssq);
+              cp[r] = (bf16)v;
             }
         }
       }
-    }
-  }
-  if constexpr (SUMSQ) {
-    ssq = wave_sum(ssq);
-    if (l == 0) {
-      g.ss[ss_slot] = ssq;
-      if (ss_slot >= 0 && NREP == 4) g.ss[ss_slot + 8] = 0.f;      // a full tile (NREP == 4) also zeroes its second-half slot
     }
   }
 }
@@ -542,7 +522,7 @@ __device__ __forceinline__ void gemm_epilogue_ek0(const GemmArgs& g, f32x4 (&acc
   if (!g.pipe) { gemm_epilogue_plain<MREP, NREP, false, false>(g, acc, mw, nw, lane); return; }
 #endif
 #if MM_GEMM_EPI_PIPE
-  gemm_epilogue_plain_pipe<MREP, NREP>(g, acc, mw, nw, 0, lane);
+  gemm_epilogue_plain_pipe<MREP, NREP>(g, acc, mw, nw, lane);
 #else
   gemm_epilogue_plain<MREP, NREP, false, false>(g, acc, mw, nw, lane);
 #endif
@@ -566,26 +546,6 @@ template <int MREP, int NREP, bool ALLOW_PRE = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[MREP][NREP], int mw, int nw) {
   if (g.epi & MM_EPI_SWIGLU_BWD) gemm_epilogue_swiglu_bwd<MREP, NREP>(g, acc, mw, nw);
   else gemm_epilogue_plain<MREP, NREP, ALLOW_PRE>(g, acc, mw, nw);
-}
-
-// sum of squares of a bf16 [M, N] matrix with leading dimension ld -> partial[blockIdx.x] (mm_gemm_sumsq's second pass)
-__global__ __launch_bounds__(256) void sumsq2d_kernel(const bf16* C, int M, int N, int ld, float* partial) {
-  __shared__ float red[8];
-  float s = 0.f;
-  const int64_t nv = (int64_t)M * (N / 4);                   // N % 4 == 0 is guaranteed by ldc % 4 == 0 ... checked by the host
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / (N / 4), c = (i % (N / 4)) * 4;
-    const bf16x4 v = *(const bf16x4*)(C + r * ld + c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s = __builtin_fmaf((float)v[k], (float)v[k], s);
-  }
-  if ((N & 3) && blockIdx.x == 0)
-    for (int64_t i = threadIdx.x; i < (int64_t)M * (N & 3); i += 256) {
-      const float q = (float)C[(i / (N & 3)) * ld + (N & ~3) + i % (N & 3)];
-      s = __builtin_fmaf(q, q, s);
-    }
-  s = block_sum_256(s, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 template <bool A_KC, bool B_KC>
@@ -1071,9 +1031,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel(GemmArgs g) {
     else if constexpr (EK == 3) gemm_epilogue_swiglu<MREP, NREP>(g, acc, m0 + wm * (BM_ / WGM), n0 + wn * (BN_ / WGN / 2));
     else if constexpr (EK == 2) gemm_epilogue_ek2<MREP, NREP>(g, acc, m0 + wm * (BM_ / WGM), n0 + wn * (BN_ / WGN));
     else if constexpr (EK == 0) gemm_epilogue_ek0<MREP, NREP>(g, acc, m0 + wm * (BM_ / WGM), n0 + wn * (BN_ / WGN));
-    else if constexpr (EK == 5)
-      gemm_epilogue_plain_pipe<MREP, NREP, true>(g, acc, m0 + wm * (BM_ / WGM), n0 + wn * (BN_ / WGN),
-                                                 __builtin_amdgcn_readfirstlane(((m0 / BM_) * g.nbn + n0 / BN_) * 16 + w));
     else gemm_epilogue_plain<MREP, NREP, (BM_ * BN_ <= 128 * 128) && EK == 1, EK == 1>(g, acc, m0 + wm * (BM_ / WGM), n0 + wn * (BN_ / WGN));
     tile = next;
     m0 = nm0;
@@ -1147,9 +1104,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel(GemmArgs g) {
       }
       if constexpr (EK == 2) gemm_epilogue_ek2<MREP, NREPH>(g, acch, hm0 + wm * (BM_ / WGM), hn0 + wn * (BNH / WGN));
       else if constexpr (EK == 0) gemm_epilogue_ek0<MREP, NREPH>(g, acch, hm0 + wm * (BM_ / WGM), hn0 + wn * (BNH / WGN));
-      else if constexpr (EK == 5)
-        gemm_epilogue_plain_pipe<MREP, NREPH, true>(g, acch, hm0 + wm * (BM_ / WGM), hn0 + wn * (BNH / WGN),
-                                                    __builtin_amdgcn_readfirstlane((hm * g.nbn + hn) * 16 + ((int)blockIdx.x & 1) * 8 + w));
       else gemm_epilogue_plain<MREP, NREPH, false, EK == 1>(g, acch, hm0 + wm * (BM_ / WGM), hn0 + wn * (BNH / WGN));
     }
   }
@@ -2436,63 +2390,6 @@ extern "C" int mm_gemm_swiglu_bwd(int dtype, int M, int I, int H, const void* dY
   return gemm_launch(g, dtype, MM_GEMM_NN, (hipStream_t)stream);
 }
 
-// C = A.B (any layout, MM_EPI_ACCUMULATE allowed) followed by the sum of squares of the stored bf16 values: partials[0 .. n)
-// (n = mm_gemm_sumsq_slots <= capacity) are OVERWRITTEN, the rest is left alone; the caller zeroes the buffer once so that
-// sum(partials[0 .. capacity)) = sum(C^2) (clip_grad_norm_'s global norm assembled per weight-gradient GEMM, reference
-// config_alignment.yaml:49).  Round 2 first computed the sum INSIDE the GEMM epilogue (one FMA per stored element, a slot per
-// wave): that made the gradient-norm sweep unnecessary but lengthened every wgrad GEMM by more than the sweep costs
-// (399.6 vs 395.5 ms/step), and merely compiling the path into the kernel cost every OTHER GEMM 1.6 %.  It is a second,
-// bandwidth-bound pass over C now (C is L2/MALL-hot right after the GEMM); same ABI, same results up to summation order.
-static int sumsq_blocks(int64_t M, int64_t N) {
-  const int64_t v = (M * N / 4 + 255) / 256;
-  return (int)(v < 1 ? 1 : (v > 1024 ? 1024 : v));
-}
-// slots of the in-epilogue form: 16 per 256x256 output tile
-static int64_t sumsq_tile_slots(int64_t M, int64_t N) { return ((M + 255) / 256) * ((N + 255) / 256) * 16; }
-
-extern "C" int mm_gemm_sumsq_slots(int dtype, int layout, int M, int N, int K, int64_t* slots) {
-  if (!slots || M <= 0 || N <= 0 || K < 0 || layout < 0 || layout > 2) return MM_ERR_ARG;
-  if (dtype != MM_BF16) return MM_ERR_UNSUPPORTED;
-  const int64_t a = sumsq_blocks(M, N), b = sumsq_tile_slots(M, N);
-  *slots = a > b ? a : b;                      // whichever form a call takes fits
-  return MM_OK;
-}
-
-// Round 3: the sum is taken INSIDE the epilogue again, but in an instantiation of its own (EK = 5, the TN 256x256 kernel the
-// decoder's weight gradients run): round 2's first cut had the extra FMA inlined into the shared epilogue, where it cost every
-// other GEMM 1.6 %; the second cut (GEMM + a reduction pass over C) was neutral against the gradient-norm sweep it replaces.
-// Other shapes / layouts keep the two-pass form.  Either way partials[0 .. n) are OVERWRITTEN (n <= mm_gemm_sumsq_slots).
-extern "C" int mm_gemm_sumsq(int dtype, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
-                             int ldc, int epilogue, float* partials, int64_t capacity, void* stream) {
-  if (M < 0 || N < 0 || K < 0 || layout < 0 || layout > 2) return MM_ERR_ARG;
-  if (dtype != MM_BF16) return MM_ERR_UNSUPPORTED;
-  if (!A || !B || !C || !partials || capacity <= 0 || (epilogue & ~MM_EPI_ACCUMULATE)) return MM_ERR_ARG;
-  if (M == 0 || N == 0) return hipMemsetAsync(partials, 0, (size_t)capacity * sizeof(float), (hipStream_t)stream) == hipSuccess ? MM_OK : MM_ERR_LAUNCH;
-  int64_t need = 0;
-  mm_gemm_sumsq_slots(dtype, layout, M, N, K, &need);
-  if (capacity < need) return MM_ERR_ARG;
-  GemmArgs g{M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, epilogue};
-  static const bool in_epi = [] { const char* e = getenv("MM_SUMSQ_EPILOGUE"); return !e || e[0] != '0'; }();
-  if (in_epi && layout == MM_GEMM_TN) {
-    g.ss = partials;
-    const int rc = gemm_launch(g, dtype, layout, (hipStream_t)stream);
-    if (rc == MM_OK) {                         // slots beyond the tiles' (the two-pass count may be larger) must read zero
-      const int64_t used = sumsq_tile_slots(M, N);
-      if (need > used && hipMemsetAsync(partials + used, 0, (size_t)(need - used) * sizeof(float), (hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
-      return MM_OK;
-    }
-    if (rc != MM_ERR_UNSUPPORTED) return rc;
-    g.ss = nullptr;
-  }
-  const int nb = sumsq_blocks(M, N);
-  const int rc = gemm_launch(g, dtype, layout, (hipStream_t)stream);
-  if (rc != MM_OK) return rc;
-  hipLaunchKernelGGL(sumsq2d_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const bf16*)C, M, N, ldc, partials);
-  if (need > nb && hipMemsetAsync(partials + nb, 0, (size_t)(need - nb) * sizeof(float), (hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
-  MM_CHECK_LAUNCH();
-  return MM_OK;
-}
-
 // ---- decode-step entry points (KV-cache decode of generate, reference model.py:595-602: M = batch <= 16 rows) ------------------
 static int skinny_common(int dtype, int M, int K, const void* X, int ldx, const void* W, int ldw, int64_t wrows) {
   if (dtype != MM_BF16) return MM_ERR_UNSUPPORTED;
@@ -2650,7 +2547,7 @@ static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
       const int64_t rem4 = g_opt_persist ? nwg % ncu : 0;
       const bool tail4 = g_opt_tail && !g.swi_I && !g.rope_cols && !(epilogue & MM_EPI_SWIGLU_BWD) && rem4 > 0 && 2 * rem4 <= ncu;
       g_last_kernel = variant;
-      if (g_opt_w4 && variant == 2 && K >= 192 && !g.ss && !acts) {
+      if (g_opt_w4 && variant == 2 && K >= 192 && !acts) {
         g_last_kernel = 10;
         int64_t nb4 = g_opt_persist ? (nwg < (int64_t)ncu ? nwg : (int64_t)ncu) : nwg;
         if (tail4) {
@@ -2722,11 +2619,7 @@ static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
     else MM_LAUNCH_ONE(AKC, BKC, 256, 256, 2, 2, 8, EK);                                                                 \
   } while (0)
       // epilogue kind = kernel instantiation: the SwiGLU ones exist for the layout their entry point uses only
-      if (g.ss) {                                                         // mm_gemm_sumsq in the epilogue: TN, 256x256
-        if (layout != MM_GEMM_TN || variant != 2 || (epilogue & ~MM_EPI_ACCUMULATE)) return MM_ERR_UNSUPPORTED;
-        if (g_opt_issue_waves == 4) MM_LAUNCH_ONE(false, false, 256, 256, 2, 2, 4, 5);
-        else MM_LAUNCH_ONE(false, false, 256, 256, 2, 2, 8, 5);
-      } else if (g.rope_cols) {                                           // mm_gemm_rope_fwd: NT, 256x256
+      if (g.rope_cols) {                                           // mm_gemm_rope_fwd: NT, 256x256
         if (layout != MM_GEMM_NT) return MM_ERR_ARG;
         if (g_opt_issue_waves == 4) MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 4, 4);
         else MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 8, 4);
@@ -2750,7 +2643,6 @@ static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
 #undef MM_LAUNCH_ONE
 #undef MM_LAUNCH_DMA
     } else {
-      if (g.ss) return MM_ERR_UNSUPPORTED;
       g.nbm = (M + BM - 1) / BM;
       g.nbn = (N + BN - 1) / BN;
       const int64_t nwg = (int64_t)g.nbm * g.nbn;

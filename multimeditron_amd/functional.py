@@ -51,14 +51,13 @@ def _ready(p):
 _defer = None
 
 
-def set_wgrad_deferral(stream, params, immediate=()):
-    """stream: side HIP stream for the deferred GEMMs; params: the first Parameter of every deferred group (held weakly);
-    immediate: first Parameters of groups whose wgrad GEMM is not held back but launched AT ONCE on the side stream (it then
-    runs beside the input-gradient chain of the main stream instead of in front of it).  stream=None disables."""
+def set_wgrad_deferral(stream, params):
+    """stream: side HIP stream for the deferred GEMMs; params: the first Parameter of every deferred group (held weakly).
+    stream=None disables."""
     import weakref
     global _defer
     _defer = None if stream is None else {"stream": stream, "params": {id(p): weakref.ref(p) for p in params}, "items": [],
-                                          "event": None, "now": {id(p): weakref.ref(p) for p in immediate}}
+                                          "event": None}
 
 
 def _is_deferred(p):
@@ -66,45 +65,15 @@ def _is_deferred(p):
     return r is not None and r() is p        # the weak reference guards against id() reuse by a later model
 
 
-def _wgrad_on_side(dy, x, wg):
-    """Launch one wgrad GEMM on the side stream now, ordered after everything the main stream has been given so far."""
-    from ._lib import get_option, lib
-    d = _defer
-    main, side = torch.cuda.current_stream(), d["stream"]
-    ev0 = torch.cuda.Event()
-    ev0.record(main)
-    side.wait_event(ev0)
-    persist = get_option("gemm_persist")
-    lib().mm_set_option(b"gemm_persist", 0)          # one tile per workgroup: fills the CUs the main stream's tails leave
-    try:
-        with torch.cuda.stream(side):
-            dy.record_stream(side)
-            x.record_stream(side)
-            g, acc = wg.grad_target()
-            K.linear_wgrad(dy, x, g, acc, sumsq=wg.sumsq_slots())
-            wg.ready()
-            ev = torch.cuda.Event()
-            ev.record(side)
-    finally:
-        lib().mm_set_option(b"gemm_persist", persist)
-    d["event"] = ev
-
-
 def _wgrad(dy, x, wg):
-    """The weight-gradient GEMM of one parameter group: now on this stream, now on the side stream, or held back."""
+    """The weight-gradient GEMM of one parameter group: now on this stream, or held back."""
     if not wg.requires_grad:
         return
-    if _defer is not None:
-        key = id(wg.params[0])
-        r = _defer["now"].get(key)
-        if r is not None and r() is wg.params[0]:
-            _wgrad_on_side(dy, x, wg)
-            return
-        if _is_deferred(wg.params[0]):
-            _defer["items"].append((dy, x, wg))
-            return
+    if _is_deferred(wg.params[0]):
+        _defer["items"].append((dy, x, wg))
+        return
     g, acc = wg.grad_target()
-    K.linear_wgrad(dy, x, g, acc, sumsq=wg.sumsq_slots())
+    K.linear_wgrad(dy, x, g, acc)
     wg.ready()
 
 
@@ -118,17 +87,15 @@ def flush_deferred_wgrads():
         from ._lib import get_option, lib
         main, side = torch.cuda.current_stream(), d["stream"]
         side.wait_stream(main)
-        import os
         persist = get_option("gemm_persist")         # restore what the trainer / the user had set, not a constant
-        # one tile per workgroup: shares the chip with the other stream's kernels (MM_DEFER_PERSIST=1: keep the persistent grid)
-        lib().mm_set_option(b"gemm_persist", 1 if os.environ.get("MM_DEFER_PERSIST", "0") == "1" else 0)
+        lib().mm_set_option(b"gemm_persist", 0)      # one tile per workgroup: shares the chip with the other stream's kernels
         try:
             with torch.cuda.stream(side):
                 for dy, x, wg in d["items"]:
                     dy.record_stream(side)
                     x.record_stream(side)
                     g, acc = wg.grad_target()
-                    K.linear_wgrad(dy, x, g, acc, sumsq=wg.sumsq_slots())
+                    K.linear_wgrad(dy, x, g, acc)
                     wg.ready()
                 ev = torch.cuda.Event()
                 ev.record(side)
@@ -187,11 +154,6 @@ class ParamGroup:
     def ready(self):
         for p in self.params:
             _ready(p)
-
-    def sumsq_slots(self):
-        """fp32 partial buffer the trainer attached to this group's first parameter (`_mm_ss`): the wgrad GEMM then also
-        produces the group's sum of squares for the global gradient norm.  None = not requested."""
-        return getattr(self.params[0], "_mm_ss", None)
 
 
 def as_group(p):

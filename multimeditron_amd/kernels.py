@@ -40,9 +40,9 @@ def pad8(n: int) -> int:
 # ------------------------------------------------------------------------------------------------ GEMM
 def gemm(layout: int, a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, out: Optional[torch.Tensor] = None,
          bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: int = 0,
-         accumulate: bool = False, ldc_pad: bool = False, sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+         accumulate: bool = False, ldc_pad: bool = False) -> torch.Tensor:
     """Raw GEMM on 2-D row-major tensors (strides taken from .stride(0)).  Returns C [M, N] (a view of a padded
-    buffer when ldc_pad).  sumsq: fp32 partial buffer -> mm_gemm_sumsq (the GEMM also leaves sum(C^2) there)."""
+    buffer when ldc_pad)."""
     assert a.dim() == 2 and b.dim() == 2 and a.stride(1) == 1 and b.stride(1) == 1
     if out is None:
         if ldc_pad:
@@ -60,11 +60,6 @@ def gemm(layout: int, a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, 
         assert residual.stride(-1) == 1
     if accumulate:
         epi |= EPI_ACCUMULATE
-    if sumsq is not None:
-        assert bias is None and residual is None and act == 0
-        call("mm_gemm_sumsq", dt(a), layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), epi, _p(sumsq),
-             sumsq.numel(), _stream())
-        return out
     call("mm_gemm", dt(a), layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), _p(bias),
          _p(residual), residual.stride(0) if residual is not None else 0, epi, _stream())
     return out
@@ -101,20 +96,11 @@ def linear_dgrad(dy2d, w, out=None):
     return gemm(GEMM_NN, dy2d, w, M, K, N, out=out)
 
 
-def linear_wgrad(dy2d, x2d, out, accumulate, sumsq=None):
-    """dw[N,K] (+)= dy[M,N]^T @ x[M,K].  sumsq: fp32 partial buffer -> the GEMM also leaves sum(dw^2) there (mm_gemm_sumsq)."""
+def linear_wgrad(dy2d, x2d, out, accumulate):
+    """dw[N,K] (+)= dy[M,N]^T @ x[M,K]."""
     M, N = dy2d.shape
     K = x2d.shape[1]
-    if dy2d.dtype != torch.bfloat16:
-        sumsq = None
-    return gemm(GEMM_TN, dy2d, x2d, N, K, M, out=out, accumulate=accumulate, sumsq=sumsq)
-
-
-def gemm_sumsq_slots(layout, M, N, K):
-    import ctypes
-    n = ctypes.c_int64(0)
-    call("mm_gemm_sumsq_slots", MM_BF16, layout, M, N, K, ctypes.byref(n))
-    return n.value
+    return gemm(GEMM_TN, dy2d, x2d, N, K, M, out=out, accumulate=accumulate)
 
 
 import os as _os
@@ -760,71 +746,3 @@ def cast(src, dtype):
     call("mm_cast", dt(src), _DT[dtype], _p(src), _p(dst), src.numel(), _stream())
     return dst
 
-
-# ------------------------------------------------------------------------------------------------ CU-masked streams
-def cu_mask_words(n_enabled: int, ncu: int = 256, scheme: str = "hash"):
-    """Bit mask (list of uint32 words) with `n_enabled` of `ncu` CUs on.  The disabled CUs are spread so that every XCD and shader
-    engine loses about the same number whichever way the driver numbers CUs ("hash": the D smallest of (173 i) mod 256, a
-    permutation that is even both over i mod 8 and over i // 32; "stride": every (ncu / D)-th)."""
-    n_enabled = max(1, min(int(n_enabled), ncu))
-    D = ncu - n_enabled
-    if scheme == "stride":
-        off = {int((k + 0.5) * ncu / D) for k in range(D)} if D else set()
-    else:
-        off = set(sorted(range(ncu), key=lambda i: ((i * 173) % 256, i))[:D])
-    words = [0] * ((ncu + 31) // 32)
-    for i in range(ncu):
-        if i not in off:
-            words[i // 32] |= 1 << (i % 32)
-    return words
-
-
-_masked_streams = {}
-
-
-def masked_stream(n_enabled: int, scheme: str = "hash", tag: str = ""):
-    """A torch stream object over a HIP stream whose kernels run on `n_enabled` CUs only (cached per process; never destroyed: the
-    Trainer keeps them for its lifetime)."""
-    import ctypes
-    ncu = _lib.lib().mm_device_cu_count()
-    key = (torch.cuda.current_device(), int(n_enabled), scheme, tag)
-    st = _masked_streams.get(key)
-    if st is None:
-        words = cu_mask_words(n_enabled, ncu, scheme)
-        arr = (ctypes.c_uint32 * len(words))(*words)
-        out = ctypes.c_void_p()
-        call("mm_stream_create_cu_mask", ctypes.cast(arr, ctypes.c_void_p), len(words), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p))
-        st = torch.cuda.ExternalStream(out.value)
-        _masked_streams[key] = st
-    return st
-
-
-def priority_stream(priority: int, tag: str = ""):
-    """A torch stream object over a HIP stream of the given priority (lower number = served first; cached per process)."""
-    import ctypes
-    key = (torch.cuda.current_device(), "prio", int(priority), tag)
-    st = _masked_streams.get(key)
-    if st is None:
-        out = ctypes.c_void_p()
-        call("mm_stream_create_priority", int(priority), ctypes.cast(ctypes.pointer(out), ctypes.c_void_p))
-        st = _masked_streams[key] = torch.cuda.ExternalStream(out.value)
-    return st
-
-
-def stream_priority_range():
-    import ctypes
-    lo, hi = ctypes.c_int(), ctypes.c_int()
-    call("mm_stream_priority_range", ctypes.cast(ctypes.pointer(lo), ctypes.c_void_p), ctypes.cast(ctypes.pointer(hi), ctypes.c_void_p))
-    return lo.value, hi.value
-
-
-def cu_probe(n_wg, threads, spin_ticks, stream=None):
-    """-> int64 [n_wg, 2] (XCC id, HW_ID register) of a spinning launch on `stream` (default: the current stream)."""
-    out = torch.zeros((n_wg, 2), dtype=torch.int32, device="cuda")
-    s = stream.cuda_stream if stream is not None else _stream()
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    call("mm_debug_cu_probe", _p(out), n_wg, threads, int(spin_ticks), s)
-    if stream is not None:
-        torch.cuda.current_stream().wait_stream(stream)
-    return out.cpu().long() & 0xFFFFFFFF

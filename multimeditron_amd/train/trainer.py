@@ -75,9 +75,6 @@ def scheduled_lr(kind: str, step: int, total: int, base_lr: float, min_lr: float
     raise ValueError(f"lr_scheduler_type {kind!r}: expected one of {LR_SCHEDULES}")
 
 
-_SIDE_CUS_DEFAULT = {"MM_ADAMW_CUS": 0, "MM_DEFER_CUS": 0}      # CUs a side burst may use (0 = all): see MultimodalTrainer._side_stream
-
-
 class MultimodalTrainer:
     def __init__(self, model, training_mode: TrainingMode = TrainingMode.ALIGNMENT, learning_rate: float = 1e-4,
                  weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 1.0,
@@ -118,23 +115,7 @@ class MultimodalTrainer:
         self._setup_state()
         self._setup_optimizer_pipeline()
         self._setup_wgrad_deferral()
-        self._setup_early_gradnorm()
-
-    def _side_stream(self, env: str, priority: int = 0):
-        """The HIP stream of a burst that runs beside a chain of small modality-tower kernels (AdamW beside the next ViT forward,
-        the deferred wgrad GEMMs beside the ViT backward).  `env` names the number of CUs the burst may use (kernels.masked_stream:
-        hipExtStreamCreateWithCUMask, the CUs left out spread evenly over the XCDs): the chain then always finds free CUs instead
-        of waiting for a CU to drain.  0 / unset = every CU (a plain stream)."""
-        n = int(os.environ.get(env, str(_SIDE_CUS_DEFAULT.get(env, 0))))
-        if n > 0 and torch.cuda.is_available():
-            return K.masked_stream(n, tag=env)
-        # MM_ADAMW_PRIO / MM_DEFER_PRIO: a HIP stream priority (experiment).  Round 4, with the update as short workgroups: the LOWEST priority for
-        # AdamW costs 30 ms per step (377 vs 348: the decoder's GEMMs overtake it and then wait for it); the image tower on a HIGHEST-priority
-        # stream of its own (tried as MM_VIT_PRIO, removed) costs 43 ms (386 vs 343: its backward then preempts the weight-gradient GEMMs)
-        lowprio = os.environ.get(env.replace("_CUS", "_PRIO"))
-        if lowprio is not None and torch.cuda.is_available():
-            return K.priority_stream(int(lowprio), tag=env)
-        return torch.cuda.Stream(priority=priority)
+        self._setup_gradnorm_chunks()
 
     def _setup_wgrad_deferral(self):
         """Hold back the weight-gradient GEMMs of the first decoder layers (the last to run in backward) and launch them on a
@@ -149,150 +130,46 @@ class MultimodalTrainer:
         tail = any(p.requires_grad for mod in getattr(self.model, "modalities_with_projection", ())
                    for n, p in mod.named_parameters() if not n.startswith(("projector.", "projectors.")))
         layers = getattr(getattr(self.model.model, "model", None), "layers", None)
-        side = os.environ.get("MM_WGRAD_SIDE", "0") == "1" and self.world == 1
-        if ((n <= 0 or not tail) and not side) or layers is None or not torch.cuda.is_available():
+        if n <= 0 or not tail or layers is None or not torch.cuda.is_available():
             Fm.set_wgrad_deferral(None, ())
             return
-        def firsts(ls):
-            out = []
-            for layer in ls:
-                a, m = layer.self_attn, layer.mlp
-                for group in (a._wqkv, Fm.as_group(a.o_proj.weight), m._wgu, Fm.as_group(m.down_proj.weight)):
-                    if group.requires_grad:
-                        out.append(group.params[0])
-            return out
+        ids = []                                     # the first parameter of every trainable GEMM group of layers 0..n-1
+        for layer in list(layers)[:n]:
+            a, m = layer.self_attn, layer.mlp
+            for group in (a._wqkv, Fm.as_group(a.o_proj.weight), m._wgu, Fm.as_group(m.down_proj.weight)):
+                if group.requires_grad:
+                    ids.append(group.params[0])
+        self._wgrad_stream = torch.cuda.Stream(priority=0)
+        Fm.set_wgrad_deferral(self._wgrad_stream, ids)
 
-        if not tail:
-            n = 0
-        ids = firsts(list(layers)[:n])
-        # MM_WGRAD_SIDE=1 (experiment): the wgrad GEMMs of the OTHER decoder layers (and an untied lm_head) are not held back but
-        # launched at once on the side stream, beside the main stream's input-gradient chain
-        now = []
-        if os.environ.get("MM_WGRAD_SIDE", "0") == "1":
-            now = firsts(list(layers)[n:])
-            head = getattr(self.model.model, "lm_head", None)
-            if head is not None and head.weight.requires_grad and head.weight is not self.model.model.get_input_embeddings().weight:
-                now.append(head.weight)
-        prio = int(os.environ.get("MM_WGRAD_SIDE_PRIO", "0"))
-        self._wgrad_stream = self._side_stream("MM_DEFER_CUS", priority=prio)
-        Fm.set_wgrad_deferral(self._wgrad_stream, ids, immediate=now)
-
-    def _setup_early_gradnorm(self):
+    def _setup_gradnorm_chunks(self):
         """Global gradient norm (clip_grad_norm_): how the sum of squares of 16.7 GB of gradients is taken.
 
-        DEFAULT: one sweep (`sumsq_kernel`, 5.4 TB/s = 3.1 ms) over the trainable ranges after backward, partials summed in a
-        fixed order by the finish kernel.  Two ways to hide those 3 ms were built, measured on the 8B step with
-        tools/step_ab.py (same box, same process, interleaved) and found to COST time; they stay behind switches:
-          * MM_FUSED_NORM=1 -- the decoder's weight-gradient GEMMs (97 % of the parameters) and an untied lm_head report the sum of
-            squares of what they store (`mm_gemm_sumsq`, per-workgroup slots: no atomics, bit-reproducible) and only the rest is
-            swept: 399.6 vs 395.5 ms/step when the sum was taken inside the GEMM epilogue (an extra convert + FMA per stored
-            element lengthened every wgrad GEMM by more than the sweep it replaced, and the inlined path cost every other GEMM
-            1.6 %: csrc/mm_gemm.hip).  `mm_gemm_sumsq` is now the GEMM followed by a reduction pass over its output.
-          * MM_EARLY_NORM=1 -- each decoder layer swept on a side stream as soon as its wgrads are enqueued, under the rest
-            of backward: 409.2 vs 404.8 ms/step: the sweep's HBM reads slow the GEMMs they run beside.
-        One GPU only in both cases: under data parallelism a gradient is final only after its bucket's all-reduce."""
-        self._norm_chunks = [(s, e, None) for s, e, _ in self.ranges]       # (start, end, trigger param id or None)
-        if self.shard_optim:       # after the reduce-scatter a rank holds final gradients for its own pieces only
-            self._norm_chunks = [(a, b, None) for a, b, _, _, _, _ in self.pieces]
-        self._norm_triggers: Dict[int, int] = {}
-        self._norm_stream = None
-        self._ss = None
-        for seg in self.flat.segments:                  # slots of an earlier trainer on this model are void
-            if hasattr(seg.param, "_mm_ss"):
-                del seg.param._mm_ss
-        layers = getattr(getattr(self.model.model, "model", None), "layers", None)
-        # (one GPU only: with a sharded optimiser step, also at world == 1 under MM_FORCE_EXCHANGE, the norm is assembled over the
-        # rank's PIECES, whose positions the sharded step indexes -- the two experiments would replace that list)
-        fused = os.environ.get("MM_FUSED_NORM", "0") == "1" and self.flat.dtype == torch.bfloat16 and not self.shard_optim
-        early = os.environ.get("MM_EARLY_NORM", "0") == "1" and not self.shard_optim
-        if self.world > 1 or layers is None or not torch.cuda.is_available() or not (fused or early):
-            self._alloc_norm_partials()
-            return
-        seg_of = {id(sg.param): sg for sg in self._trainable}
-        covered = []                                     # (start, end, trigger id) of the ranges NOT swept at the end
-        groups = []                                      # (first param, [params]) whose wgrad GEMM produces its own sum of squares
-        for layer in layers:
-            a, m = layer.self_attn, layer.mlp
-            mats = [a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight, m.up_proj.weight,
-                    m.down_proj.weight]
-            if not all(id(p) in seg_of for p in mats):
-                continue
-            sgs = [seg_of[id(p)] for p in mats]
-            if any((x.end + 7) // 8 * 8 != y.start for x, y in zip(sgs[:-1], sgs[1:])):
-                continue                                                   # not contiguous in the flat buffer: swept at the end
-            if fused:
-                groups += [mats[0:3], mats[3:4], mats[4:6], mats[6:7]]
-            elif Fm._is_deferred(a.q_proj.weight):
-                continue
-            covered.append((sgs[0].start, (sgs[-1].end + 7) // 8 * 8, id(a.v_proj.weight)))     # q/k/v wgrad = the layer's last write
-        head = getattr(self.model.model, "lm_head", None)
-        emb = self.model.model.get_input_embeddings().weight
-        if head is not None and head.weight is not emb and id(head.weight) in seg_of:
-            sg = seg_of[id(head.weight)]
-            covered.append((sg.start, (sg.end + 7) // 8 * 8, id(head.weight)))
-            if fused:
-                groups.append([head.weight])
-        late = []
-        for s0, e0, _ in self.ranges:
-            cur = s0
-            for a0, b0, _t in sorted(x for x in covered if s0 <= x[0] and x[1] <= e0):
-                if a0 > cur:
-                    late.append((cur, a0, None))
-                cur = b0
-            if cur < e0:
-                late.append((cur, e0, None))
-        if fused and groups:
-            from .._lib import GEMM_TN
-            sizes = [K.gemm_sumsq_slots(GEMM_TN, sum(p.shape[0] for p in g), g[0].shape[1], 4096) for g in groups]
-            self._ss = torch.zeros(sum(sizes), dtype=torch.float32, device=self.flat.device)
-            off = 0
-            for g, n in zip(groups, sizes):
-                g[0]._mm_ss = self._ss[off:off + n]        # functional.ParamGroup.sumsq_slots() hands it to the wgrad GEMM
-                off += n
-            self._norm_chunks = late
-        elif early and covered:
-            self._norm_chunks = covered + late
-            self._norm_triggers = {t: i for i, (_, _, t) in enumerate(covered)}
-            self._norm_stream = torch.cuda.Stream()
-        self._alloc_norm_partials()
-
-    def _alloc_norm_partials(self):
-        self._norm_slots = []
+        One sweep (`sumsq_kernel`, 5.4 TB/s = 3.1 ms) over the trainable ranges after backward -- under the sharded optimiser, over
+        the pieces whose final gradients this rank holds after the reduce-scatter -- with the partials summed in a fixed order by
+        the finish kernel.  Two ways to hide those 3 ms were built, measured on the 8B step with tools/step_ab.py (same box, same
+        process, interleaved), found to COST time and removed:
+          * the sum of squares taken by the decoder's weight-gradient GEMMs themselves (97 % of the parameters), only the rest
+            swept: 399.6 vs 395.5 ms/step inside the GEMM epilogue (an extra convert + FMA per stored element lengthened every
+            wgrad GEMM by more than the sweep it replaced); as an epilogue instantiation of its own, 384.6 vs 382.4.
+          * each decoder layer swept on a side stream as soon as its wgrads are enqueued, under the rest of backward: 409.2 vs
+            404.8 ms/step: the sweep's HBM reads slow the GEMMs they run beside."""
+        if self.shard_optim:
+            self._norm_chunks = [(a, b) for a, b, _, _, _, _ in self.pieces]
+        else:
+            self._norm_chunks = [(s, e) for s, e, _ in self.ranges]
+        self._norm_slots = []                          # (offset, count) of every chunk's partials in the finish kernel's buffer
         off = 0
-        for s, e, _ in self._norm_chunks:
+        for s, e in self._norm_chunks:
             nb = int(min(1024, max(1, (e - s) // 65536)))
             self._norm_slots.append((off, nb))
             off += nb
-        # one buffer for the finish kernel: [partials of the swept chunks | the wgrad GEMMs' slots]
-        n_ss = self._ss.numel() if self._ss is not None else 0
-        buf = torch.zeros(off + n_ss, dtype=torch.float32, device=self.flat.device)
-        if n_ss:
-            old = self._ss
-            self._ss = buf[off:]
-            for seg in self._trainable:                         # re-point the views handed out above into the joint buffer
-                v = getattr(seg.param, "_mm_ss", None)
-                if v is not None and v.untyped_storage().data_ptr() == old.untyped_storage().data_ptr():
-                    o0 = v.storage_offset() - old.storage_offset()
-                    seg.param._mm_ss = self._ss[o0:o0 + v.numel()]
-        self._norm_partial = buf
-        self._norm_done = set()
-        self._norm_armed = False
+        self._norm_partial = torch.zeros(off, dtype=torch.float32, device=self.flat.device)
 
     def _norm_chunk(self, i):
-        s, e, _ = self._norm_chunks[i]
+        s, e = self._norm_chunks[i]
         off, nb = self._norm_slots[i]
         K.gradnorm_partial(self.flat.grad[s:e], self._norm_partial[off:off + nb])
-        self._norm_done.add(i)
-
-    def _norm_on_ready(self, key: int):
-        i = self._norm_triggers.get(key)
-        if i is None or not self._norm_armed or i in self._norm_done:
-            return
-        ev = torch.cuda.Event()
-        ev.record()                                   # everything enqueued so far (this layer's wgrads included)
-        self._norm_stream.wait_event(ev)
-        with torch.cuda.stream(self._norm_stream):
-            self._norm_chunk(i)
 
     # ------------------------------------------------------------------ setup
     def _set_mode(self):
@@ -342,8 +219,8 @@ class MultimodalTrainer:
             n_state = sum(e - s for s, e, _ in self.ranges)
         # bf16 models keep the fp32 master weight as (the bf16 parameter itself, an int16 remainder): `self.master` then holds the
         # remainders (mm_adamw_step_split: 26 B instead of 28 B of traffic per parameter, no second copy of the weights).  fp32
-        # models (the parity path) and MM_ADAMW_SPLIT=0 keep a separate fp32 master.
-        self.split_master = flat.dtype == torch.bfloat16 and flat.data.is_cuda and os.environ.get("MM_ADAMW_SPLIT", "1") != "0"
+        # models (the parity path) keep a separate fp32 master.
+        self.split_master = flat.dtype == torch.bfloat16 and flat.data.is_cuda
         self.master = (torch.zeros(n_state, dtype=torch.int16, device=dev) if self.split_master      # master == parameter: remainder 0
                        else torch.empty(n_state, dtype=torch.float32, device=dev))
         self.m = torch.zeros(n_state, dtype=torch.float32, device=dev)
@@ -393,16 +270,11 @@ class MultimodalTrainer:
         last = self._micro == self.accum - 1
         if first:
             self.flat.attach_grads(fresh=True)       # no memset: the first wgrad of the step overwrites
-            if self._ss is not None:
-                self._ss.zero_()                     # the wgrad GEMMs overwrite their own slots; the rest must read 0
         ex = self.exchanger
         ex.begin_step(exchange_this_step=last)
-        self._norm_done = set()
-        self._norm_armed = last and bool(self._norm_triggers)      # a gradient is final only in the last micro-batch
 
-        def on_ready(p, _ex=ex.on_ready, _nr=self._norm_on_ready):
+        def on_ready(p, _ex=ex.on_ready):
             _ex(id(p))
-            _nr(id(p))
 
         Fm.set_grad_ready_hook(on_ready)
         try:
@@ -439,10 +311,25 @@ class MultimodalTrainer:
         """AdamW is HBM-bound (30 B/param), the forward pass is MFMA-bound: run the update of step n on a side HIP stream
         while step n+1's forward runs, block by block in FORWARD order (vision tower, projector, embedding, decoder layers,
         final norm, lm_head).  A forward pre-hook on each block makes the compute stream wait for that block's update
-        event, and the compute stream waits for the last event before the next backward writes gradients."""
+        event, and the compute stream waits for the last event before the next backward writes gradients.
+
+        Why beside the ViT forward: a kernel trace (tools/stream_time.py) shows that AdamW's grid-striding workgroups, launched
+        at the end of the step, fill every wave slot while the next step's ViT forward runs: each of the ViT's ~350 short kernels
+        waits for slots (attention 402 us instead of 11, GELU 277 instead of 9, LayerNorm 134 instead of 12): 33 ms on the compute
+        stream for 5 ms of work.  Launching the decoder's share of the update (97 % of the parameters, 43 ms of HBM streaming)
+        from the NEXT forward instead, at the moment its host code reaches the first decoder layer, was built, measured
+        (tools/step_ab.py, same process) and removed: 401.6 ms/step deferred vs 394.2 as is.  Beside the decoder's GEMMs the
+        update costs MORE: the 256x256 GEMM's LDS-DMA stream shares HBM with 5 TB/s of optimizer traffic and loses about 0.8 ms
+        per ms of update, wherever the update is placed; the ViT forward, being launch-latency-bound, is the cheapest thing to
+        run it beside.  (A smaller update grid, `mm_set_option("adamw_blocks", 512)`: 388.6-393.8 vs 394.2, inside the noise;
+        round 4: a LARGER grid -- 262 144, one vector per thread, now the library's default -- is 8-18 % faster stand-alone and
+        2.7 ms per step: csrc/mm_optim.hip.)  The update therefore costs the step about 35 of its 44 ms on this chip; fewer bytes
+        per parameter (28 now) is what would lower it.  HIP stream priorities for the side bursts were measured as well (round 4,
+        with the update as short workgroups) and removed: the LOWEST priority for AdamW costs 30 ms per step (377 vs 348: the
+        decoder's GEMMs overtake it and then wait for it); the image tower on a HIGHEST-priority stream of its own costs 43 ms
+        (386 vs 343: its backward then preempts the weight-gradient GEMMs)."""
         import re
         self._blocks = []          # [(module or None, [(start, end, decay, state_off)])] in forward order
-        self._defer_from, self._deferred = None, None
         self._hooks = []
         self._pending = {}
         self._all_done = None
@@ -468,11 +355,6 @@ class MultimodalTrainer:
         groups: Dict[str, List] = {}
         for seg in self._trainable:
             groups.setdefault(block_key(seg.name), []).append(seg)
-        # MM_ADAMW_DEFER=1 (default off, measured slower): the decoder's blocks are not launched with the rest at the end of
-        # the step but when the NEXT forward reaches the first decoder layer -- see _launch_deferred
-        defer = os.environ.get("MM_ADAMW_DEFER", "0") == "1"
-        self._defer_from: Optional[int] = None
-        self._deferred = None
 
         def order(key):    # forward order: modality towers (embeddings, pre-norm, layers, projector), then the LLM
             llm = key.startswith("model.")
@@ -494,16 +376,13 @@ class MultimodalTrainer:
                 else:
                     runs.append([sg.start, end, sg.decay])
             self._blocks.append((self._hook_module(key), [(a, b, d, st_off(a)) for a, b, d in runs]))
-            if self._defer_from is None and defer and order(key)[0] >= 11 and self._blocks[-1][0] is not None:
-                self._defer_from = len(self._blocks) - 1            # first decoder layer: see _launch_deferred
         covered = sum(b - a for _, rs in self._blocks for a, b, _, _ in rs)
         assert covered == sum(e - s0 for s0, e, _ in self.ranges), "optimizer pipeline must cover every trainable range"
-        self._opt_stream = self._side_stream("MM_ADAMW_CUS")
+        self._opt_stream = torch.cuda.Stream(priority=0)
         self._pending: Dict[int, torch.cuda.Event] = {}
         self._all_done: Optional[torch.cuda.Event] = None
         self._hooks = []
         self._unfired: List[int] = []
-        self._deferred_mods = set() if self._defer_from is None else {id(m) for m, _ in self._blocks[self._defer_from:] if m is not None}
         hooked = set()
         for mod, _ in self._blocks:
             if mod is not None and id(mod) not in hooked:      # several blocks may share one call site (ViT embeddings.*)
@@ -526,7 +405,7 @@ class MultimodalTrainer:
             return (1 if llm else 0, 1 if (llm and decay) else 0, bk.start)
 
         self._bucket_order = sorted(range(len(ex.buckets)), key=order)
-        self._opt_stream = self._side_stream("MM_ADAMW_CUS") if torch.cuda.is_available() and self.flat.device.type == "cuda" else None
+        self._opt_stream = torch.cuda.Stream(priority=0) if torch.cuda.is_available() and self.flat.device.type == "cuda" else None
 
         def block_key(name):
             m = re.match(r"(.*?layers\.\d+)\.", name)
@@ -632,43 +511,7 @@ class MultimodalTrainer:
             key = key.rsplit(".", 1)[0] if "." in key else ""
         return None
 
-    def _launch_deferred(self):
-        """MM_ADAMW_DEFER=1 (an experiment that LOST; off by default): the decoder's share of the update (97 % of the
-        parameters, 43 ms of HBM streaming) launched from the NEXT forward at the moment its host code reaches the first decoder
-        layer, ordered after everything the compute stream has been given so far, instead of at the end of the step.
-        Motivation: a kernel trace (tools/stream_time.py) shows that AdamW's 2048 grid-striding workgroups, launched at the end
-        of the step, fill every wave slot while the next step's ViT forward runs: each of the ViT's ~350 short kernels waits
-        for slots (attention 402 us instead of 11, GELU 277 instead of 9, LayerNorm 134 instead of 12): 33 ms on the compute
-        stream for 5 ms of work.  Measured (tools/step_ab.py, same process): 401.6 ms/step deferred vs 394.2 as is.  Beside the
-        decoder's GEMMs the update costs MORE: the 256x256 GEMM's LDS-DMA stream shares HBM with 5 TB/s of optimizer traffic and
-        loses about 0.8 ms per ms of update, wherever the update is placed; the ViT forward, being launch-latency-bound, is the
-        cheapest thing to run it beside.  (A smaller update grid, `mm_set_option("adamw_blocks", 512)`: 388.6-393.8 vs 394.2,
-        inside the noise; round 4: a LARGER grid -- 262 144, one vector per thread, now the library's default --
-        is 8-18 % faster stand-alone and 2.7 ms per step: csrc/mm_optim.hip.)  The update therefore costs the step about 35 of its 44 ms on this chip; fewer bytes per parameter
-        (28 now) is what would lower it."""
-        upd = self._deferred
-        if upd is None:
-            return
-        self._deferred = None
-        main, side = torch.cuda.current_stream(), self._opt_stream
-        ev0 = torch.cuda.Event()
-        ev0.record(main)
-        side.wait_event(ev0)
-        with torch.cuda.stream(side):
-            for mod, runs in self._blocks[self._defer_from:]:
-                for s, e, decay, off in runs:
-                    upd(s, e, decay, off)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                if mod is not None:
-                    self._pending[id(mod)] = ev
-            self._all_done = ev
-        if any(mod is None for mod, _ in self._blocks[self._defer_from:]):
-            main.wait_event(self._all_done)
-
     def _wait_block(self, mod, _inputs):
-        if self._deferred is not None and id(mod) in self._deferred_mods:
-            self._launch_deferred()
         ev = self._pending.pop(id(mod), None)
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
@@ -682,8 +525,6 @@ class MultimodalTrainer:
                 torch.cuda.current_stream().wait_event(self._all_done)
                 self._all_done = None
             return
-        if getattr(self, "_deferred", None) is not None:
-            self._launch_deferred()                           # no forward reached the decoder since the last step
         if getattr(self, "_all_done", None) is not None:
             # blocks whose hook did not fire in the forward that just ran (legitimate for a tower the batch never entered;
             # a bug if forward read them: tests/test_trainer_gpu.py checks this list is empty for an image batch)
@@ -695,16 +536,11 @@ class MultimodalTrainer:
     def _optimizer_step(self):
         self.step_count += 1
         lr = scheduled_lr(self.lr_scheduler_type, self.step_count - 1, self.max_steps, self.lr, self.min_lr, self.warmup)
-        g = self.flat.grad
-        self._norm_armed = False
         if self.shard_optim:
             self._optimizer_step_sharded(lr)
             return
-        if self._norm_stream is not None and self._norm_done:
-            torch.cuda.current_stream().wait_stream(self._norm_stream)     # the chunks summed under backward
         for i in range(len(self._norm_chunks)):
-            if i not in self._norm_done:
-                self._norm_chunk(i)
+            self._norm_chunk(i)
         total = K.gradnorm_finish(self._norm_partial, self.max_grad_norm if self.max_grad_norm else 0.0)
         self.last_grad_norm = total
 
@@ -718,10 +554,9 @@ class MultimodalTrainer:
         main = torch.cuda.current_stream()
         side = self._opt_stream
         side.wait_stream(main)                               # gradients (and their all-reduce) are complete
-        now = self._blocks if self._defer_from is None else self._blocks[:self._defer_from]
         with torch.cuda.stream(side):
             ev = None
-            for mod, runs in now:
+            for mod, runs in self._blocks:
                 for s, e, decay, off in runs:
                     upd(s, e, decay, off)
                 ev = torch.cuda.Event()
@@ -730,10 +565,8 @@ class MultimodalTrainer:
                     self._pending[id(mod)] = ev
             self._all_done = ev
         # blocks without a hookable module: wait for them right away
-        if ev is not None and any(mod is None for mod, _ in now):
+        if ev is not None and any(mod is None for mod, _ in self._blocks):
             main.wait_event(self._all_done)
-        if self._defer_from is not None:
-            self._deferred = upd                              # the decoder's blocks: launched by the next forward (_launch_deferred)
 
     def synchronize(self):
         """Make the compute stream wait for the in-flight optimiser update (call before reading parameters)."""
@@ -742,7 +575,7 @@ class MultimodalTrainer:
             K.embed_check_pending()          # and surface an out-of-range token id of the steps so far (IndexError, as torch)
 
     def close(self):
-        """Detach from the model (forward hooks, deferred-wgrad registration, gradient-norm slots) and release the optimiser
+        """Detach from the model (forward hooks, deferred-wgrad registration) and release the optimiser
         state, so that another trainer can be built on the same model (the hooks otherwise keep this one alive)."""
         self._wait_optimizer()
         for h in getattr(self, "_hooks", []):
@@ -750,10 +583,7 @@ class MultimodalTrainer:
         self._hooks = []
         Fm.set_wgrad_deferral(None, ())
         Fm.set_grad_ready_hook(None)
-        for seg in self.flat.segments:
-            if hasattr(seg.param, "_mm_ss"):
-                del seg.param._mm_ss
-        self.master = self.m = self.v = self._norm_partial = self._ss = None
+        self.master = self.m = self.v = self._norm_partial = None
         self._blocks = []
         if getattr(self, "comm", None) is not None:
             self.comm.close()

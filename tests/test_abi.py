@@ -41,3 +41,15 @@ def test_argument_validation_without_launch():
     # the attention kernels' removed A/B switches are unknown names now (MM_ERR_ARG)
     assert L.mm_set_option(b"attn_dkv_res", 1) == -1
     assert L.mm_set_option(b"attn_fwd_pf", 0) == -1
+
+
+def test_removed_entry_points_are_gone():
+    """The in-GEMM gradient-norm sums and the CU-masked / priority stream constructors (rejected experiments: DESIGN.md section 6)
+    left the ABI: neither declared by the header nor exported by the library."""
+    removed = ("mm_gemm_sumsq", "mm_gemm_sumsq_slots", "mm_stream_create_cu_mask", "mm_stream_create_priority",
+               "mm_stream_priority_range", "mm_debug_cu_probe")
+    protos = _lib.parse_header()
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name in removed:
+        assert name not in protos, f"include/mm_hip.h still declares {name}"
+        assert not hasattr(L, name), f"libmmhip.so still exports {name}"

@@ -75,6 +75,9 @@ CASES += [  # the 4-wave kernel's schedules and epilogue forms
     dict(kid=GC.DMA64x128, layout=TN, M=200, N=136, K=256, epi="plain", place="tight", opts={}, tag="default small_variant"),
     dict(kid=GC.DMA128, layout=NN, M=2048, N=1024, K=640, epi="bias", place="tight", opts={}, tag="default small_variant"),
     dict(kid=GC.V1, layout=NT, M=2048, N=2688, K=256, epi="plain", place="tight", opts={}, tag="default small_variant"),
+    # weight-gradient GEMMs (TN, accumulate into C) on both 256x256 kernels
+    dict(kid=GC.DMA256x256, layout=TN, M=4100, N=4100, K=264, epi="accumulate", place="slice", opts=dict(gemm_kernel=3, gemm_w4=0), tag="wgrad"),
+    dict(kid=GC.W4, layout=TN, M=4000, N=3304, K=320, epi="accumulate", place="tight", opts=dict(gemm_kernel=3), tag="wgrad"),
 ]
 SKINNY_SHAPES = [(1, 130, 64), (4, 6144, 256), (16, 1000, 200), (7, 72, 1088), (3, 1028, 203), (5, 266, 72), (2, 512, 4104)]
 GEMV_SHAPES = [(1, 130, 64), (4, 6144, 256), (16, 1000, 200), (7, 72, 1088), (3, 1028, 128), (5, 266, 72), (2, 512, 4104)]
@@ -450,30 +453,3 @@ def test_offset_thresholds(what, layout, M, N, K, lda, ldb, kid):
     GC.check_exact(what, C, GC.rne_bf16(ref))
     del A, B
     torch.cuda.empty_cache()
-
-
-def test_sumsq_tn_exact():
-    """mm_gemm_sumsq (TN, the in-epilogue sum of squares of the 8-wave 256x256 kernel): C exact, guards intact, persist on / off
-    bit-identical, and the partials sum to the exact sum of squares of the stored bf16 values."""
-    M, N, K = 4100, 4100, 264
-    p = GC.exact_problem(M, N, K, "cuda", 17)
-    A, B = GC.operands(TN, p["A"], p["B"])
-    from multimeditron_amd import kernels
-    slots = kernels.gemm_sumsq_slots(TN, M, N, K)
-    outs = []
-    for persist in (1, 0):
-        C, g = GC.out_view(M, N, "slice")
-        C.copy_(p["c0"].to(torch.bfloat16))
-        part = torch.zeros(slots, device="cuda")
-        with GC.options(gemm_persist=persist):
-            got = _call("mm_gemm_sumsq", 0, TN, M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(),
-                        C.stride(0), GC.EPI_ACCUMULATE, part.data_ptr(), slots, _s())
-        assert got == GC.DMA256x256
-        g.verify("C")
-        outs.append((C.clone(), part))
-    want = GC.rne_bf16(GC.exact_reference(p, GC.EPI_ACCUMULATE))
-    GC.check_exact("C", outs[0][0], want)
-    GC.check_exact("C persist 0", outs[1][0], want)
-    ss = float((want.double() ** 2).sum())
-    for _, part in outs:
-        assert math.isfinite(float(part.sum())) and abs(float(part.double().sum()) - ss) <= 1e-5 * ss

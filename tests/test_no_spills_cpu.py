@@ -40,11 +40,6 @@ def test_hot_kernels_use_no_scratch(fname):
         for hot in HOT[fname]:
             if hot in name:
                 seen.add(hot)
-                if "gemm_bf16_dma_kernel" in name and name.endswith("ELi5EEEvNS_8GemmArgsE"):
-                    # the sum-of-squares epilogue (mm_gemm_sumsq in the GEMM, MM_FUSED_NORM=1: a rejected experiment, off by default --
-                    # DESIGN.md section 6): 8 bytes/lane since GemmArgs grew in round 4; not on the step's path
-                    assert scratch <= 16, f"{name}: {scratch} bytes/lane of scratch"
-                    continue
                 assert scratch == 0, f"{name}: {scratch} bytes/lane of scratch"
     assert seen == set(HOT[fname]), sorted(set(HOT[fname]) - seen)
 

@@ -96,32 +96,22 @@ def test_optimizer_overlap_hooks_cover_every_block(golden_dir, tmp_path, name):
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("variant", ["fused", "early", "sweep"])
-def test_gradnorm_assembly_equals_full_norm(golden_dir, tmp_path, monkeypatch, variant):
-    """The global grad norm is assembled from the wgrad GEMMs' own sum-of-squares slots (mm_gemm_sumsq: decoder matrices,
-    lm_head) plus a sweep of the rest ("fused", MM_FUSED_NORM=1), or from per-layer sweeps under backward ("early", an experiment
-    kept behind MM_EARLY_NORM=1), or from one sweep ("sweep", the default since both alternatives measured slower).  Each must equal the norm of the complete flat gradient and be
-    identical run to run (fixed slots, fixed summation order); deferred and immediate wgrads both take part."""
+def test_gradnorm_assembly_equals_full_norm(golden_dir, tmp_path, monkeypatch):
+    """The global grad norm is assembled from one sweep over the trainable ranges (the two alternatives that were built -- the
+    wgrad GEMMs' own sums of squares, per-layer sweeps under backward -- measured slower and were removed).  It must equal the
+    norm of the complete flat gradient and be identical run to run (fixed slots, fixed summation order); deferred and immediate
+    wgrads both take part."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     monkeypatch.setenv("MM_DEFER_WGRAD_LAYERS", "1")          # layer 0's wgrads deferred (side stream), layer 1's immediate
-    monkeypatch.setenv("MM_FUSED_NORM", "1" if variant == "fused" else "0")
-    monkeypatch.setenv("MM_EARLY_NORM", "1" if variant == "early" else "0")
     from multimeditron_amd.train.trainer import MultimodalTrainer, TrainingMode
     meta, w, v = R.load_golden("tiny_clip_llama", golden_dir)
     norms = []
     for rep in range(2):
         model = build_from_golden(meta, w, tmp_path / f"m{rep}", "bfloat16")
         tr = MultimodalTrainer(model, training_mode=TrainingMode.FULL, learning_rate=0.0, weight_decay=0.0, max_grad_norm=1.0)
-        if variant == "fused":
-            assert tr._ss is not None and tr._ss.numel() > 0 and not tr._norm_triggers
-            fused_elems = sum(e - s for s, e, _ in tr.ranges) - sum(e - s for s, e, _ in tr._norm_chunks)
-            assert fused_elems > 0.5 * sum(p.numel() for p in model.model.model.layers.parameters())
-        elif variant == "early":
-            assert tr._norm_triggers and tr._ss is None
-        else:
-            assert tr._ss is None and not tr._norm_triggers and len(tr._norm_chunks) == len(tr.ranges)
-        spans = sorted((s, e) for s, e, _ in tr._norm_chunks)
+        assert len(tr._norm_chunks) == len(tr.ranges)
+        spans = sorted(tr._norm_chunks)
         assert all(a[1] <= b[0] for a, b in zip(spans[:-1], spans[1:])), "chunks overlap"
         for _ in range(2):                                     # twice: slots are reused step after step
             tr.training_step(to_device(R.golden_batch(v, "right")))
@@ -130,9 +120,53 @@ def test_gradnorm_assembly_equals_full_norm(golden_dir, tmp_path, monkeypatch, v
         g = tr.flat.grad
         ref = torch.sqrt(sum((g[s:e].double() ** 2).sum() for s, e, _ in tr.ranges))
         got = tr.last_grad_norm[0].double()
-        assert abs(float(got) - float(ref)) < 1e-5 * float(ref), (variant, float(got), float(ref))
+        assert abs(float(got) - float(ref)) < 1e-5 * float(ref), (float(got), float(ref))
         norms.append(tr.last_grad_norm.clone())
     assert torch.equal(norms[0], norms[1])
+
+
+REMOVED_SWITCHES = {   # environment variables of the overlap experiments that were removed, each at its old "on" value
+    "MM_FUSED_NORM": "1", "MM_EARLY_NORM": "1", "MM_ADAMW_DEFER": "1", "MM_ADAMW_SPLIT": "0", "MM_ADAMW_CUS": "224",
+    "MM_DEFER_CUS": "224", "MM_ADAMW_PRIO": "1", "MM_DEFER_PRIO": "1", "MM_WGRAD_SIDE": "1", "MM_WGRAD_SIDE_PRIO": "-1",
+    "MM_DEFER_PERSIST": "1", "MM_SUMSQ_EPILOGUE": "0",
+}
+
+
+def test_removed_switches_are_inert(golden_dir, tmp_path, monkeypatch):
+    """The step has one schedule: with any of the removed variables set, the norm chunk list, the optimizer blocks, `split_master`,
+    the set of deferred weight gradients and the two side streams are those of a clean environment, every block's update is
+    launched at the end of the step, and one step gives the same loss and gradient norm bit for bit."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from multimeditron_amd import functional as Fm
+    from multimeditron_amd.train.trainer import MultimodalTrainer, TrainingMode
+    meta, w, v = R.load_golden("tiny_clip_llama", golden_dir)
+    for name in REMOVED_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("MM_DEFER_WGRAD_LAYERS", "1")          # a non-empty deferral set on the two-layer model
+
+    def schedule(tag):
+        model = build_from_golden(meta, w, tmp_path / tag, "bfloat16")
+        tr = MultimodalTrainer(model, training_mode=TrainingMode.FULL, learning_rate=1e-3, max_grad_norm=1.0)
+        names = {id(sg.param): sg.name for sg in tr._trainable}
+        sig = dict(chunks=list(tr._norm_chunks), blocks=[runs for _, runs in tr._blocks], split=tr.split_master,
+                   master=tr.master.dtype, deferred=sorted(names[k] for k in Fm._defer["params"]),
+                   streams=[(type(st).__name__, st.priority) for st in (tr._opt_stream, tr._wgrad_stream)])
+        loss = tr.training_step(to_device(R.golden_batch(v, "right")))
+        sig["launched"] = len(tr._pending)                     # blocks whose update is already on the side stream
+        tr.synchronize()
+        torch.cuda.synchronize()
+        sig["loss"], sig["norm"] = float(loss), float(tr.last_grad_norm[0])
+        tr.close()
+        return sig
+
+    clean = schedule("clean")
+    assert clean["split"] and clean["master"] == torch.int16 and clean["deferred"] and clean["blocks"]
+    assert clean["launched"] > 0
+    for name, value in REMOVED_SWITCHES.items():
+        monkeypatch.setenv(name, value)
+        assert schedule(name) == clean, name
+        monkeypatch.delenv(name)
 
 
 @pytest.mark.parametrize("dtype", ["bfloat16", "float32"])

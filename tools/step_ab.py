@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-box, same-process A/B of training-step variants selected by environment switches (box-to-box variance is +-3-5 %,
 run-to-run on one box ~1 %: decisions need interleaved rounds in ONE process, guide rule 24).
-    python tools/step_ab.py [--rounds 3] [--steps 8] "MM_FUSED_NORM=1" "MM_FUSED_NORM=0" ["A=1,B=2" ...]
+    python tools/step_ab.py [--rounds 3] [--steps 8] "MM_LOSS_ROWS=1" "MM_LOSS_ROWS=0" ["A=1,B=2" ...]
 The 8B model is built once; every variant gets a fresh MultimodalTrainer (the switches are read at construction / call time)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
