@@ -153,7 +153,11 @@ int mm_rows_select(int dtype, const void* src, int64_t ld_src, const int* map, i
                    int64_t ld_dst, void* stream);
 
 /* ---- norms ------------------------------------------------------------------------------------------
- * RMSNorm: HF:llama:53-70.  rstd[M] f32 is saved for backward.                                            */
+ * Widths (all four norm entries): H % 8 == 0 for MM_BF16, H % 4 == 0 for MM_F32 (MM_ERR_ALIGN otherwise), and a row of at most
+ * 256 * 8 sixteen-byte vectors: H <= 16384 for MM_BF16, H <= 8192 for MM_F32 (MM_ERR_UNSUPPORTED above).  M == 0 writes nothing.
+ * RMSNorm: HF:llama:53-70.  rstd[M] f32 is saved for backward.  Rounding points (T = the storage type): fp32 sum of squares (any
+ * order), rstd = rsqrtf(ss / H + eps), y = T(w * f32(T(x * rstd))): the normalised value is rounded to T BEFORE the weight
+ * multiply, as HF's `weight * hidden_states.to(input_dtype)`.  Given the kernel's own rstd, y is bit-identical to that chain.   */
 int mm_rmsnorm_fwd(int dtype, const void* x, const void* w, int M, int H, float eps, void* y, float* rstd, void* stream);
 /* dx = rstd*(g - xhat*mean(g*xhat)) (+ dres), g = dy*w;  dw_partial[nblk,H] f32 (nblk = mm_norm_bwd_blocks(M)).
  * dres (optional, [M,H]) is the gradient arriving through the residual branch that shares x: fusing the add here
@@ -175,7 +179,8 @@ int mm_reduce_partials2(int dtype, const float* partial0, const float* partial1,
 /* ---- RoPE: HF:llama:113-160 (rotate_half form) --------------------------------------------------------
  * cos/sin tables [T, D/2] f32 from position_ids and inv_freq (HF:llama:113-127; llama3 scaling is applied by
  * the caller to inv_freq, HF:modeling_rope_utils.py:641-662).  round_bf16: round cos/sin to bf16 (HF casts them
- * to the activation dtype).                                                                               */
+ * to the activation dtype).  The angle is ONE fp32 product float(position) * inv_freq[j] (HF's fp32 matmul of a single term);
+ * the tables are cosf / sinf of that fp32 angle, so they follow the angle's rounding at large positions, as HF's do.           */
 int mm_rope_table(const int64_t* position_ids, const float* inv_freq, int T, int half, int round_bf16, float* cos_t,
                   float* sin_t, void* stream);
 /* in place on x viewed as [T, nheads, D] with row stride ld (elements); inverse=1 applies the adjoint          */
@@ -262,7 +267,9 @@ int mm_attn_decode(int dtype, const void* q, const void* k, const void* v, int B
                    void* stream);
 
 /* ---- activations -----------------------------------------------------------------------------------------
- * SwiGLU: HF:llama:163-176.  gu [M, 2I] = [gate | up] from the fused gate/up GEMM; out [M,I] = silu(gate)*up     */
+ * SwiGLU: HF:llama:163-176.  gu [M, 2I] = [gate | up] from the fused gate/up GEMM; out [M,I] = silu(gate)*up.
+ * Rounding points of the forward (T = the storage type): out = T(f32(T(silu(gate))) * up): silu(gate) is rounded to T BEFORE the
+ * multiply by up, as HF's act_fn(gate_proj(x)) * up_proj(x) in the storage dtype.  The backward rounds each output once.        */
 int mm_swiglu_fwd(int dtype, const void* gu, int M, int I, void* out, void* stream);
 int mm_swiglu_bwd(int dtype, const void* gu, const void* dout, int M, int I, void* dgu, void* stream);
 /* kind: 0 = erf GELU (mlp.py:35,37), 1 = quick GELU (HF:clip fc1).  x is the pre-activation.                       */
@@ -273,15 +280,24 @@ int mm_gelu_bwd(int dtype, int kind, const void* x, const void* dy, int64_t n, v
 int mm_add(int dtype, const void* a, const void* b, int64_t n, void* y, void* stream);
 
 /* ---- loss: HF:loss/loss_utils.py:36-71 --------------------------------------------------------------------------
- * logits [T, ld] (V valid columns); labels already shifted by the caller; ignore_index = -100.
+ * logits [T, ld] (V valid columns; [V, ld) is never read); labels already shifted by the caller; ignore_index = -100.
+ * Which rows are live, one rule for the three kernels: a NEGATIVE label (-100, and any other negative value) is ignored: its
+ * loss_row is 0, its dlogits row is 0 and it is not counted.  A label in [0, V) is live and counted.  A label >= V is a caller
+ * error that is not diagnosed: the row gives no loss and no gradient (mm_ce_fwd / mm_ce_bwd see V) but mm_ce_reduce, which
+ * does not know V, counts it.  The callers in functional.py produce -100 or token ids below V only.
+ * -inf logits (masked vocabulary entries) count as exp = 0 wherever they stand in the row; a row needs at least one finite logit
+ * and a finite logit at its label (otherwise lse / loss_row are -inf / NaN: out of contract).
  * fwd: lse[T] f32, loss_row[T] f32 (0 for ignored rows).  loss = sum(loss_row)/count is reduced by mm_ce_reduce.    */
 int mm_ce_fwd(int dtype, const void* logits, int T, int V, int ld, const int64_t* labels, float* lse, float* loss_row, void* stream);
-/* out[0] = sum(loss_row)/max(count,1), out[1] = count (number of labels != -100)                                   */
+/* out[0] = sum(loss_row)/max(count,1), out[1] = count (number of labels >= 0; see the rule above)                    */
 int mm_ce_reduce(const float* loss_row, const int64_t* labels, int T, float* out, void* stream);
 /* dlogits[t,v] = (exp(logit - lse[t]) - [v==label]) * gscale[0] / count, 0 for ignored rows and for v in [V, ld)    */
 int mm_ce_bwd(int dtype, const void* logits, int T, int V, int ld, const int64_t* labels, const float* lse,
               const float* loss_and_count, const float* gscale, void* dlogits, void* stream);
-/* next-token selection of model.py:607-621: argmax(softmax(logits/T)) over the LAST dim, first max wins          */
+/* next-token selection of model.py:607-621: argmax(softmax(logits/T)) over the LAST dim, first max wins.
+ * Rounding points (T = the storage type), chosen so that ties resolve as torch.argmax over the softmax tensor in the logits
+ * dtype does: s = T(x / temperature) (fp32 division), p = T(exp(s - max s) / sum exp(s - max s)) with fp32 softmax arithmetic,
+ * result = the FIRST index of the maximum of p.  temperature > 0 (MM_ERR_ARG otherwise); any row stride ld >= V.              */
 int mm_argmax_softmax(int dtype, const void* logits, int rows, int V, int ld, float temperature, int64_t* out, void* stream);
 /* the same selection for long rows, the vocabulary cut into chunks over many workgroups (3 short launches instead of one block per
  * row sweeping 128 258 logits three times); ws: mm_argmax_softmax_ws_bytes(rows, V) bytes, 8-byte aligned                     */

@@ -443,6 +443,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* logits, int V, int
     for (int k = 0; k < VN; ++k)
       if (e + k < V) lm = fmaxf(lm, v.get(k));
     const float nm = fmaxf(mx, lm);
+    if (nm == -INFINITY) continue;   // nothing finite yet (a run of -inf logits): exp(-inf - -inf) would be NaN; (mx, sm) stay (-inf, 0)
     float add = 0.f;
 #pragma unroll
     for (int k = 0; k < VN; ++k)

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import gemm_check as GC
+from tests import rowwise_check as RC
 
 pytestmark = pytest.mark.gpu
 
@@ -560,6 +561,15 @@ def test_norms(K, dtype, H):
     K.reduce_partials(dwp, dw, False)
     assert rel(dx.float(), xf.grad + dres.float()) < tol * 2     # fused residual-gradient add
     assert rel(dw.float(), wf.grad) < tol * 2
+    # per element against fp64, the saved statistics included, and the documented rounding chain exactly
+    xd, wd, bd, dyd = x.cuda(), w.cuda(), b.cuda(), dy.cuda()
+    GC.check_exact("rmsnorm chain", y, RC.rmsnorm_chain(xd, wd, rstd))
+    y64, Ey, r64, Er = RC.rmsnorm_fwd_reference(xd, wd, 1e-5)
+    RC.bound("rstd", "rmsnorm.rstd", dtype, rstd, r64, Er, u=RC.U32)
+    RC.bound("y", "rmsnorm.y", dtype, y, y64, Ey)
+    dx64, Edx, dw64, Edw = RC.rmsnorm_bwd_reference(dyd, xd, wd, rstd, dres.cuda())
+    RC.bound("dx", "rmsnorm.dx", dtype, dx, dx64, Edx)
+    RC.bound("dw", "rmsnorm.dw", dtype, dw, dw64, Edw)
     # LayerNorm
     xf, wf, bf = (t.float().clone().requires_grad_(True) for t in (x, w, b))
     ref = F.layer_norm(xf, (H,), wf, bf, 1e-5)
@@ -573,6 +583,14 @@ def test_norms(K, dtype, H):
     assert rel(dx.float(), xf.grad) < tol * 2
     assert rel(dw.float(), wf.grad) < tol * 2
     assert rel(db.float(), bf.grad) < tol * 2
+    y64, Ey, m64, Em, r64, Er = RC.layernorm_fwd_reference(xd, wd, bd, 1e-5)
+    RC.bound("mean", "layernorm.mean", dtype, mean, m64, Em, u=RC.U32)
+    RC.bound("rstd", "layernorm.rstd", dtype, rstd, r64, Er, u=RC.U32)
+    RC.bound("y", "layernorm.y", dtype, y, y64, Ey)
+    dx64, Edx, dw64, Edw, db64, Edb = RC.layernorm_bwd_reference(dyd, xd, wd, mean, rstd)
+    RC.bound("dx", "layernorm.dx", dtype, dx, dx64, Edx)
+    RC.bound("dw", "layernorm.dw", dtype, dw, dw64, Edw)
+    RC.bound("db", "layernorm.db", dtype, db, db64, Edb)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -587,6 +605,9 @@ def test_rope(K, dtype, D):
     cos, sin = ang.cos(), ang.sin()
     cg, sg = K.rope_table(pos.cuda(), inv.cuda(), False)
     assert rel(cg, cos) < 1e-5 and rel(sg, sin) < 1e-5
+    c64, s64, Ec, Es, u = RC.rope_table_reference(pos.cuda(), inv.cuda(), False)
+    RC.bound("cos", "rope_table", torch.float32, cg, c64, Ec, u=u)
+    RC.bound("sin", "rope_table", torch.float32, sg, s64, Es, u=u)
 
     def ref_rot(x, inverse=False):  # x [T, h, D]
         c = torch.cat([cos, cos], -1)[:, None]
@@ -600,8 +621,14 @@ def test_rope(K, dtype, D):
     ref = qkv.float().clone()
     ref[:, : (Hq + Hkv) * D] = ref_rot(ref[:, : (Hq + Hkv) * D].view(B * S, Hq + Hkv, D)).reshape(B * S, -1)
     assert rel(g.float(), ref) < TOL[dtype]
+    r64, E = RC.rope_reference(qkv.cuda(), cg, sg, Hq + Hkv, D)
+    RC.bound("rope", "rope", dtype, g, r64, E)
+    GC.check_exact("v columns", g[:, (Hq + Hkv) * D:], qkv.cuda()[:, (Hq + Hkv) * D:])
+    roped = g.clone()
     K.rope_apply_(g, B * S, Hq + Hkv, D, W, cg, sg, inverse=True)
     assert rel(g.float(), qkv.float()) < TOL[dtype] * 2
+    r64, E = RC.rope_reference(roped, cg, sg, Hq + Hkv, D, inverse=True)
+    RC.bound("rope inverse", "rope", dtype, g, r64, E)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -612,16 +639,28 @@ def test_activations(K, dtype):
     ref = F.silu(guf[:, :I]) * guf[:, I:]
     ref.backward(dout.float())
     tol = TOL[dtype]
-    assert rel(K.swiglu_fwd(gu.cuda(), I).float(), ref.detach()) < tol
-    assert rel(K.swiglu_bwd(gu.cuda(), dout.cuda(), I).float(), guf.grad) < tol * 2
+    out, dgu = K.swiglu_fwd(gu.cuda(), I), K.swiglu_bwd(gu.cuda(), dout.cuda(), I)
+    assert rel(out.float(), ref.detach()) < tol
+    assert rel(dgu.float(), guf.grad) < tol * 2
+    r64, E = RC.swiglu_fwd_reference(gu.cuda(), I)
+    RC.bound("swiglu_fwd", "swiglu_fwd", dtype, out, r64, E)
+    r64, E = RC.swiglu_bwd_reference(gu.cuda(), dout.cuda(), I)
+    RC.bound("swiglu_bwd", "swiglu_bwd", dtype, dgu, r64, E)
     x, dy = rnd((1000 + 3,), dtype, 43, 2.0), rnd((1000 + 3,), dtype, 44)
     for kind, fn in [(0, F.gelu), (1, lambda t: t * torch.sigmoid(1.702 * t)), (2, lambda t: F.gelu(t, approximate="tanh"))]:
         xf = x.float().clone().requires_grad_(True)
         r = fn(xf)
         r.backward(dy.float())
-        assert rel(K.gelu_fwd(x.cuda(), kind).float(), r.detach()) < tol
-        assert rel(K.gelu_bwd(x.cuda(), dy.cuda(), kind).float(), xf.grad) < tol * 2
-    assert rel(K.add(x.cuda(), dy.cuda()).float(), x.float() + dy.float()) < tol
+        yg, dxg = K.gelu_fwd(x.cuda(), kind), K.gelu_bwd(x.cuda(), dy.cuda(), kind)
+        assert rel(yg.float(), r.detach()) < tol
+        assert rel(dxg.float(), xf.grad) < tol * 2
+        r64, E = RC.gelu_fwd_reference(x.cuda(), kind)
+        RC.bound(f"gelu_fwd {kind}", "gelu_fwd", dtype, yg, r64, E)
+        r64, E = RC.gelu_bwd_reference(x.cuda(), dy.cuda(), kind)
+        RC.bound(f"gelu_bwd {kind}", "gelu_bwd", dtype, dxg, r64, E)
+    s = K.add(x.cuda(), dy.cuda())
+    assert rel(s.float(), x.float() + dy.float()) < tol
+    GC.check_exact("add", s, (x.float() + dy.float()).to(dtype).cuda())
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -667,6 +706,7 @@ def test_cross_entropy(K, dtype, V):
     K.ce_bwd(buf[:, :V], V, labels.cuda(), lse, lc, None, d[:, :V])
     assert rel(d[:, :V].float(), lf.grad) < (2e-5 if dtype == torch.float32 else 1e-2)
     assert torch.all(d[:, V:] == 0)
+    RC.check_ce(dtype, logits.cuda(), labels.cuda(), lse, lc, d, None)
     for T_ in (0.1, 0.7):
         got = K.argmax_softmax(buf[:, :V], V, T_).cpu()
         want = torch.argmax(torch.softmax(logits / T_, dim=-1), dim=-1)   # in the logits dtype, as model.py:607-621

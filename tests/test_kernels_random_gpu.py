@@ -10,6 +10,7 @@ import torch.nn.functional as F  # noqa: F401
 from tests.test_kernels_gpu import TOL, attn_ref, rel, rnd, K  # noqa: F401  (K: the kernels fixture)
 
 from tests import gemm_check as GC
+from tests import rowwise_check as RC
 
 pytestmark = pytest.mark.gpu
 _rng = random.Random(20260131)
@@ -149,6 +150,15 @@ def test_norms_random(K, case):      # noqa: F811
     K.reduce_partials(dwp, dw, False)
     assert rel(dx.float(), xf.grad + add) < tol * 2, case
     assert float((dw.float().cpu() - wf.grad).norm()) <= tol * 3 * float(wf.grad.norm()) + 1e-3, case
+    # per element against fp64, the saved statistics included, and the documented rounding chain exactly
+    xd, wd, bd, dyd, rd = x.cuda(), w.cuda(), b.cuda(), dy.cuda(), dres.cuda() if with_res else None
+    GC.check_exact("rmsnorm chain", y, RC.rmsnorm_chain(xd, wd, rstd))
+    y64, Ey, r64, Er = RC.rmsnorm_fwd_reference(xd, wd, 1e-6)
+    RC.bound("rstd", "rmsnorm.rstd", dtype, rstd, r64, Er, u=RC.U32)
+    RC.bound("y", "rmsnorm.y", dtype, y, y64, Ey)
+    dx64, Edx, dw64, Edw = RC.rmsnorm_bwd_reference(dyd, xd, wd, rstd, rd)
+    RC.bound("dx", "rmsnorm.dx", dtype, dx, dx64, Edx)
+    RC.bound("dw", "rmsnorm.dw", dtype, dw, dw64, Edw)
     xf, wf, bf = (t.float().clone().requires_grad_(True) for t in (x, w, b))
     ref = F.layer_norm(xf, (H,), wf, bf, 1e-6)
     ref.backward(dy.float())
@@ -161,6 +171,14 @@ def test_norms_random(K, case):      # noqa: F811
     assert rel(dx.float(), xf.grad + add) < tol * 2, case
     assert float((dw.float().cpu() - wf.grad).norm()) <= tol * 3 * float(wf.grad.norm()) + 1e-3, case
     assert float((db.float().cpu() - bf.grad).norm()) <= tol * 3 * float(bf.grad.norm()) + 1e-3, case
+    y64, Ey, m64, Em, r64, Er = RC.layernorm_fwd_reference(xd, wd, bd, 1e-6)
+    RC.bound("mean", "layernorm.mean", dtype, mean, m64, Em, u=RC.U32)
+    RC.bound("rstd", "layernorm.rstd", dtype, rstd, r64, Er, u=RC.U32)
+    RC.bound("y", "layernorm.y", dtype, y, y64, Ey)
+    dx64, Edx, dw64, Edw, db64, Edb = RC.layernorm_bwd_reference(dyd, xd, wd, mean, rstd, rd)
+    RC.bound("dx", "layernorm.dx", dtype, dx, dx64, Edx)
+    RC.bound("dw", "layernorm.dw", dtype, dw, dw64, Edw)
+    RC.bound("db", "layernorm.db", dtype, db, db64, Edb)
 
 
 @pytest.mark.parametrize("case", [(_rng.choice([1, 7, 33, 130]), _rng.choice([8, 136, 4304, 8192, 14336, 18944])) for _ in range(8)])
@@ -171,8 +189,14 @@ def test_swiglu_random(K, case):      # noqa: F811
     guf = gu.float().clone().requires_grad_(True)
     ref = F.silu(guf[:, :I]) * guf[:, I:]
     ref.backward(dout.float())
-    assert rel(K.swiglu_fwd(gu.cuda(), I).float(), ref.detach()) < TOL[dtype]
-    assert rel(K.swiglu_bwd(gu.cuda(), dout.cuda(), I).float(), guf.grad) < TOL[dtype] * 2
+    out, dgu = K.swiglu_fwd(gu.cuda(), I), K.swiglu_bwd(gu.cuda(), dout.cuda(), I)
+    assert rel(out.float(), ref.detach()) < TOL[dtype]
+    assert rel(dgu.float(), guf.grad) < TOL[dtype] * 2
+    r64, E = RC.swiglu_fwd_reference(gu.cuda(), I)
+    RC.bound("swiglu_fwd", "swiglu_fwd", dtype, out, r64, E)
+    RC.swiglu_chain_check("swiglu_fwd chain", gu.cuda(), out, I)
+    r64, E = RC.swiglu_bwd_reference(gu.cuda(), dout.cuda(), I)
+    RC.bound("swiglu_bwd", "swiglu_bwd", dtype, dgu, r64, E)
 
 
 @pytest.mark.parametrize("case", [(_rng.choice([1, 9, 40]), _rng.choice([2, 130, 1000, 32000, 128258, 152066]), _rng.choice([torch.bfloat16, torch.float32]))
@@ -198,5 +222,6 @@ def test_cross_entropy_random(K, case):      # noqa: F811
         K.ce_bwd(buf[:, :V], V, labels.cuda(), lse, lc, None, d[:, :V])
         assert rel(d[:, :V].float(), lf.grad) < (2e-5 if dtype == torch.float32 else 1e-2), case
         assert torch.all(d[:, V:] == 0)
+        RC.check_ce(dtype, logits.cuda(), labels.cuda(), lse, lc, d, None)
     got = K.argmax_softmax(buf[:, :V], V, 0.1).cpu()
     assert torch.equal(got, torch.argmax(torch.softmax(logits / 0.1, dim=-1), dim=-1)), case
