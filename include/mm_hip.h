@@ -360,6 +360,37 @@ int mm_xattn_bwd(int dtype, const void* q, const void* k, const void* v, const v
 int mm_dropout(int dtype, const void* x, int64_t n, float p, int64_t seed, int64_t offset, void* y, void* stream);
 int mm_dropout_mask(int64_t seed, int64_t offset, int64_t n, float p, void* mask_u8, void* stream);
 
+/* ---- MoE image modality: the gating network, a ResNet-50 in eval mode (moe/gating.py:37-89 = torchvision resnet50 with an E-way
+ * fc; model/modalities/gating.py).  Activations are NHWC: the channel dimension is contiguous, so every filter tap of every
+ * pixel is a run of 16-byte vectors.  Storage type T = bf16 (MM_BF16, fp32 accumulation) or fp32 (MM_F32, the parity path).
+ * mm_nchw_to_nhwc: pixels f32 [n, C, H, W] -> out T [n, H, W, Cpad], channels C .. Cpad-1 written as zeros (the stem's 3 -> 8
+ *   padding; its weight is zero-padded to match).  Cpad >= C and Cpad % 8 == 0 (bf16) / % 4 (f32), out 16-byte aligned
+ *   (MM_ERR_ALIGN otherwise).
+ * mm_conv2d_nhwc_fwd: y[n, Ho, Wo, Cout] = act(conv(x[n, H, W, Cin], w[Cout, R, R, Cin]) * scale[Cout] + shift[Cout]
+ *   (+ residual[n, Ho, Wo, Cout])), Ho = (H + 2 pad - R) / stride + 1 (Wo alike), zero padding, act = ReLU (relu != 0) or nothing;
+ *   w is the filter packed [Cout, R, S, Cin] (K = R*S*Cin contiguous), scale / shift are fp32 (eval-mode BatchNorm as a per-channel
+ *   affine: it is NOT folded into the weights), residual may be NULL.  An implicit GEMM with M = n*Ho*Wo, N = Cout, K = R*R*Cin
+ *   (MM_BF16: v_mfma_f32_32x32x16_bf16); out-of-image taps count as zeros and nothing outside x is read.  Rounding points: exact
+ *   bf16 products accumulated in fp32 (any order), then acc * scale + shift (one fma) (+ residual) (ReLU) in fp32 and ONE rounding
+ *   to T at the store (mm_gemm's epilogue rule).  R in {1, 3, 7}, stride in {1, 2}, pad in {0, 1, 3} (MM_ERR_UNSUPPORTED otherwise);
+ *   Cin % 8 == 0, Cout % 64 == 0 and x, w, scale, shift, residual, y 16-byte aligned (MM_ERR_ALIGN otherwise); M <= 2^31 - 257 and
+ *   Cout * K < 2^31 (MM_ERR_UNSUPPORTED above); a filter larger than the padded image is MM_ERR_ARG.  M is arbitrary (ragged last
+ *   tiles).  All checks come before any launch.
+ * mm_maxpool2d_nhwc: y[n, Ho, Wo, C] = max over the 3x3 window, stride 2, pad 1 (Ho = (H - 1) / 2 + 1): ResNet's pool.  Padding
+ *   taps do not take part in the maximum.  C % 8 == 0 (bf16) / % 4 (f32), x and y 16-byte aligned (MM_ERR_ALIGN otherwise).
+ * mm_gate_head: the tail of the network in one launch (avgpool + fc + softmax + topk, gating.py:85-87).  x T [n, HW, C];
+ *   pooled = fp32 mean over HW (sum in order, times 1/HW; NOT rounded to T); logits[n, E] = T(pooled . fc_w[E, C]^T + fc_b) with
+ *   an fp32 dot product; weights[n, E] = T(softmax_fp32(float(logits))): the softmax of the ROUNDED logits, as softmax(logits) in
+ *   the model dtype; topk_idx int64 [n, top_k] = indices of the top_k largest (rounded) logits, descending, the lower index first
+ *   on ties.  fc_w, fc_b, logits, weights are T.  1 <= top_k <= E (MM_ERR_ARG otherwise); E <= 64 and C <= 8192
+ *   (MM_ERR_UNSUPPORTED above); C % 8 == 0 (bf16) / % 4 (f32), x and fc_w 16-byte aligned (MM_ERR_ALIGN otherwise).           */
+int mm_nchw_to_nhwc(int dtype, const float* pixels, int n, int C, int H, int W, int Cpad, void* out, void* stream);
+int mm_conv2d_nhwc_fwd(int dtype, const void* x, int n, int H, int W, int Cin, const void* w, int Cout, int R, int stride, int pad,
+                       const float* scale, const float* shift, const void* residual, int relu, void* y, void* stream);
+int mm_maxpool2d_nhwc(int dtype, const void* x, int n, int H, int W, int C, void* y, void* stream);
+int mm_gate_head(int dtype, const void* x, int n, int HW, int C, const void* fc_w, const void* fc_b, int E, int top_k, void* logits,
+                 void* weights, int64_t* topk_idx, void* stream);
+
 /* ---- optimizer: AdamW (config_alignment.yaml:38-59 -> torch.optim.AdamW semantics) + grad-norm clip ----------------
  * sumsq partial: out[blk] = sum g^2 over a slice; mm_gradnorm_finish: total[0] = sqrt(sum) ; clip coef in total[1]  */
 int mm_gradnorm_partial(int dtype, const void* g, int64_t n, float* partial, int nblk, void* stream);

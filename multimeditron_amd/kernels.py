@@ -746,3 +746,56 @@ def cast(src, dtype):
     call("mm_cast", dt(src), _DT[dtype], _p(src), _p(dst), src.numel(), _stream())
     return dst
 
+
+
+# ------------------------------------------------------------------------------------------------ gating network (NHWC conv)
+def nchw_to_nhwc(pixels: torch.Tensor, cpad: int, dtype: torch.dtype) -> torch.Tensor:
+    """fp32 pixels [n, C, H, W] -> [n, H, W, cpad] in `dtype`, channels C .. cpad-1 zero."""
+    assert pixels.dtype == torch.float32 and pixels.dim() == 4 and pixels.is_contiguous()
+    n, C, H, W = pixels.shape
+    out = torch.empty((n, H, W, cpad), dtype=dtype, device=pixels.device)
+    call("mm_nchw_to_nhwc", _DT[dtype], _p(pixels), n, C, H, W, cpad, _p(out), _stream())
+    return out
+
+
+def conv_out_size(size: int, R: int, stride: int, pad: int) -> int:
+    return (size + 2 * pad - R) // stride + 1
+
+
+def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int, pad: int,
+                residual: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [n, Ho, Wo, Cout] = act(conv(x [n, H, W, Cin], w [Cout, R, R, Cin]) * scale + shift (+ residual)); scale / shift fp32."""
+    assert x.dim() == 4 and w.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype
+    n, H, W, Cin = x.shape
+    Cout, R = w.shape[0], w.shape[1]
+    assert w.shape[2] == R and w.shape[3] == Cin and scale.dtype == torch.float32 and shift.dtype == torch.float32
+    Ho, Wo = conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad)
+    if out is None:
+        out = torch.empty((n, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
+    call("mm_conv2d_nhwc_fwd", dt(x), _p(x), n, H, W, Cin, _p(w), Cout, R, stride, pad, _p(scale), _p(shift), _p(residual),
+         int(relu), _p(out), _stream())
+    return out
+
+
+def maxpool2d_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3 / stride 2 / pad 1 max pool on [n, H, W, C]."""
+    assert x.dim() == 4 and x.is_contiguous()
+    n, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((n, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
+    call("mm_maxpool2d_nhwc", dt(x), _p(x), n, H, W, C, _p(out), _stream())
+    return out
+
+
+def gate_head(x: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, top_k: int):
+    """x [n, HW, C] -> (logits [n, E], topk_idx int64 [n, top_k], weights [n, E]): mean over HW, fc, softmax, top-k in one launch."""
+    assert x.dim() == 3 and x.is_contiguous() and fc_w.is_contiguous() and fc_w.dtype == x.dtype and fc_b.dtype == x.dtype
+    n, HW, C = x.shape
+    E = fc_w.shape[0]
+    logits = torch.empty((n, E), dtype=x.dtype, device=x.device)
+    weights = torch.empty((n, E), dtype=x.dtype, device=x.device)
+    topk = torch.empty((n, top_k), dtype=torch.int64, device=x.device)
+    call("mm_gate_head", dt(x), _p(x), n, HW, C, _p(fc_w), _p(fc_b), E, top_k, _p(logits), _p(weights), _p(topk), _stream())
+    return logits, topk, weights

@@ -18,9 +18,12 @@ and fuses in the LLM's embedding space; its cross-attention therefore has `hidde
 shipped recipe (cookbook/sft/moe/*/attn/pep: 4096 / 8), 96 in the shared-projector one (768 / 8).  Neither is a flash-kernel
 width; both run on the one-pass cross-attention kernel `mm_xattn_*` (csrc/mm_xattn.hip: up to 512 keys, head widths up to 512).
 
-NOT built: the reference's `GatingNetwork` is a torchvision ResNet-50 (moe/gating.py:37-89); torchvision is
-absent and a ResNet is outside the hot path.  `gating_network` is therefore a plug: any callable with the reference's output
-contract `pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  The experts run side by side, each on its own HIP
+The gate (reference moe/gating.py:37-89, a torchvision ResNet-50 with an E-way fc) is `modalities/gating.py`: the same key set
+on libmmhip's NHWC convolution kernels, built from `config.gating_path` when that is a directory holding a `config.json`
+(`GatingNetwork.from_pretrained`), as the submodule `gating_network`: frozen, eval mode always, outside the optimiser.  A
+`gating_network=` argument wins over the path, and may be any callable with the reference's output contract
+`pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  NOT built: training the gate in FULL mode
+(train-mode BatchNorm, a ResNet backward).  The experts run side by side, each on its own HIP
 stream (`_run_experts`); a grouped multi-expert GEMM launch would be the step after that.  `CrossAttention`'s two dropouts
 (p = 0.1 on the attention probabilities and on the output projection, active in the reference whenever the module trains) are
 Philox-based: eval mode equals the reference, train mode equals it in distribution (torch's generator cannot be reproduced)."""
@@ -38,6 +41,7 @@ from ..presets import resolve_preprocessor_config, resolve_vision_config
 from ..projectors.mlp import MLPProjector
 from ..vision import VisionConfig, VisionTransformer
 from .base import AutoModality, BaseModality, BaseModalityConfig, BaseModalityProcessor
+from .gating import GatingNetwork, is_gate_dir
 from .image_modality import ClipImagePreprocessor
 
 
@@ -407,9 +411,50 @@ def _expert_stream(device, e):
     return _EXPERT_STREAMS[key]
 
 
+def _resolve_gate(config, gating_network, dtype, device):
+    """The `gating_network=` argument wins; otherwise a `gating_path` that is a directory with a config.json is the reference's
+    `GatingNetwork.from_pretrained(config.gating_path)` (image_modality_moe.py:123), in the modality's dtype and device; anything
+    else leaves the plug empty."""
+    if gating_network is None and is_gate_dir(getattr(config, "gating_path", None)):
+        gating_network = GatingNetwork.from_pretrained(config.gating_path, dtype=dtype, device=device)
+    return gating_network
+
+
+_NO_GATE = ("{cls} needs a gating network: set `gating_path` to a directory written by GatingNetwork.save_pretrained / the "
+            "reference (config.json + model.safetensors, keys resnet.*), or assign `modality.gating_network = fn` with "
+            "fn(pixels [n,3,H,W]) -> (logits, topk_indices, weights [n, E]) (reference moe/gating.py:73-89).")
+
+
+class _FrozenGate:
+    """The gate stays frozen and in eval mode whatever the training mode (the reference trains it in FULL mode,
+    image_modality_moe.py:233-241: a stated deviation)."""
+    _warned_frozen_gate = False
+
+    def _keep_gate_frozen(self, warn=False):
+        g = getattr(self, "gating_network", None)
+        if not isinstance(g, nn.Module):
+            return
+        g.eval()
+        for p in g.parameters():
+            p.requires_grad = False
+        if warn and not _FrozenGate._warned_frozen_gate:
+            import warnings
+            _FrozenGate._warned_frozen_gate = True
+            warnings.warn("the MoE gating network stays frozen (eval-mode BatchNorm, no gradient): training the gate is not built")
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self._keep_gate_frozen()
+        return self
+
+    def unfreeze_all(self):
+        super().unfreeze_all()
+        self._keep_gate_frozen()
+
+
 @AutoModality.register("moe_meditron_clip")             # applied last: the config class keeps the reference's model_type
 @AutoModality.register("moe_meditron_clip_shared")      # alias: the name the shipped recipes use (cookbook/sft/moe/*/*/shared/config.yaml),
-class MOEImageModality(BaseModality):                   # which the reference itself does not register (image_modality_moe.py:89)
+class MOEImageModality(_FrozenGate, BaseModality):      # which the reference itself does not register (image_modality_moe.py:89)
     config_class = MOEImageConfig
     preprocessor_class = MOEImageProcessor
 
@@ -431,6 +476,7 @@ class MOEImageModality(BaseModality):                   # which the reference it
         self._num_patches_per_entry = vis0.num_patches
         self.generalist_idx = config.generalist_idx
         self.fusion_method = config.fusion_method.replace("-", "_")
+        gating_network = _resolve_gate(config, gating_network, dtype, device)
         self.gating_network = gating_network
         names = list(getattr(getattr(gating_network, "config", None), "class_names", []) or [])
         if names:                                                        # reference :118-131: gate class order -> expert order
@@ -454,10 +500,7 @@ class MOEImageModality(BaseModality):                   # which the reference it
 
     def gate_weights(self, pixels: torch.Tensor) -> torch.Tensor:
         if self.gating_network is None:
-            raise NotImplementedError(
-                "MOEImageModality needs a gating network: the reference's GatingNetwork is a torchvision ResNet-50, which is not "
-                "part of this build.  Assign `modality.gating_network = fn` with fn(pixels [n,3,H,W]) -> (logits, topk_indices, "
-                "weights [n, E]) (reference moe/gating.py:73-89).")
+            raise NotImplementedError(_NO_GATE.format(cls="MOEImageModality"))
         _logits, _topk, weights = self.gating_network(pixels)
         w = weights.to(device=self.device, dtype=torch.float32)
         return w.index_select(-1, self._gating_to_expert_perm.to(w.device)).contiguous()      # reference :171-173, :185-186
@@ -492,12 +535,14 @@ class MOEImageModality(BaseModality):                   # which the reference it
             for p in e.parameters():
                 p.requires_grad = False
         self.modality_frozen = True
+        self._keep_gate_frozen()
 
     def unfreeze_modality_embedder(self):
         for e in self.experts:
             for p in e.parameters():
                 p.requires_grad = True
         self.modality_frozen = False
+        self._keep_gate_frozen(warn=True)
 
     def unfreeze_projection(self):
         for p in self.projector.parameters():
@@ -522,7 +567,7 @@ class MOEImageProcessorPEP(MOEImageProcessor):
 
 
 @AutoModality.register("moe_meditron_clip_pep")
-class MOEImageModalityPEP(BaseModality):
+class MOEImageModalityPEP(_FrozenGate, BaseModality):
     """reference image_modality_moe_pep.py:91-288: experts -> one projector PER expert -> fusion in the projected space."""
     config_class = MOEImageConfigPEP
     preprocessor_class = MOEImageProcessorPEP
@@ -549,6 +594,7 @@ class MOEImageModalityPEP(BaseModality):
         self._num_patches_per_entry = vis0.num_patches
         self.generalist_idx = config.generalist_idx
         self.fusion_method = config.fusion_method.replace("-", "_")
+        gating_network = _resolve_gate(config, gating_network, dtype, device)
         self.gating_network = gating_network
         names = list(getattr(getattr(gating_network, "config", None), "class_names", []) or [])
         if names:
@@ -574,9 +620,7 @@ class MOEImageModalityPEP(BaseModality):
         pixels = pixels.to(self.device, non_blocking=True)
         n, E = pixels.shape[0], len(self.experts)
         if self.gating_network is None:
-            raise NotImplementedError(
-                "MOEImageModalityPEP needs a gating network: assign `modality.gating_network = fn` with fn(pixels [n,3,H,W]) -> "
-                "(logits, topk_indices, weights [n, E]) (reference moe/gating.py:73-89; its ResNet-50 is not part of this build).")
+            raise NotImplementedError(_NO_GATE.format(cls="MOEImageModalityPEP"))
         _logits, _topk, weights = self.gating_network(pixels)
         w_raw = weights.to(device=self.device, dtype=torch.float32).contiguous()          # gate order, as weighted_average uses it (:214)
         outs = _run_experts(self.experts, pixels, post=lambda e, tok: self.projectors[e](tok))      # [n, P, H] each
@@ -605,12 +649,14 @@ class MOEImageModalityPEP(BaseModality):
             for p in e.parameters():
                 p.requires_grad = False
         self.modality_frozen = True
+        self._keep_gate_frozen()
 
     def unfreeze_modality_embedder(self):
         for e in self.experts:
             for p in e.parameters():
                 p.requires_grad = True
         self.modality_frozen = False
+        self._keep_gate_frozen(warn=True)
 
     def unfreeze_projection(self):
         for p in self.projectors.parameters():

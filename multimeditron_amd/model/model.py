@@ -157,6 +157,8 @@ class MultiModalModelForCausalLM(nn.Module):
                 module.weight.fill_(1.0)
                 if module.bias is not None:
                     module.bias.zero_()
+            elif getattr(module, "_mm_pretrained", False):
+                pass                                                  # the MoE gate: built by its own from_pretrained, never re-initialised
             else:
                 for n, p in module.named_parameters(recurse=False):   # class/position embeddings, patch conv
                     p.normal_(mean=0.0, std=std)
@@ -176,8 +178,8 @@ class MultiModalModelForCausalLM(nn.Module):
                 out.append(("model." + n, p, "llm", hf_decays("model." + n, owner.get(id(p)))))
         for i, m in enumerate(self.modalities_with_projection):
             for n, p in m.named_parameters():
-                if id(p) in seen:
-                    continue
+                if id(p) in seen or n.startswith("gating_network."):     # the MoE gate is frozen: outside the flat buffer,
+                    continue                                              # the gradient buckets and the optimiser
                 seen.add(id(p))
                 comp = f"projector{i}" if n.startswith("projector.") else f"encoder{i}"
                 full = f"modalities_with_projection.{i}.{n}"
@@ -202,9 +204,19 @@ class MultiModalModelForCausalLM(nn.Module):
         self._flat = None            # views into the old flat buffer are gone: re-pack lazily
         return out
 
+    def _checkpoint_tensors(self):
+        """What a checkpoint holds: every parameter, and the persistent buffers (the MoE gate's BatchNorm statistics, integer
+        `num_batches_tracked` included: the reference's state dict carries them)."""
+        own = dict(self.named_parameters())
+        sd_keys = set(self.state_dict().keys())
+        for k, b in self.named_buffers():
+            if k in sd_keys and k not in own:
+                own[k] = b
+        return own
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         sd = dict(state_dict)
-        own = dict(self.named_parameters())
+        own = self._checkpoint_tensors()
         # the reference keeps the whole CLIPModel; accept and ignore its unused towers / buffers
         unused = [k for k in sd if k not in own and any(t in k for t in ("text_model", "text_projection", "visual_projection",
                                                                          "logit_scale", "position_ids", "post_layernorm"))]
@@ -242,7 +254,7 @@ class MultiModalModelForCausalLM(nn.Module):
                 json.dump(self._llm_cfg.to_dict(), f, indent=2)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
-        names = [(k, v) for k, v in self.named_parameters()]
+        names = list(self._checkpoint_tensors().items())
         shards, cur, cur_bytes = [], [], 0
         for k, v in names:
             nb = v.numel() * v.element_size()
@@ -279,7 +291,7 @@ class MultiModalModelForCausalLM(nn.Module):
             files = ["model.safetensors"]
         else:
             raise FileNotFoundError(f"{path}: neither model.safetensors nor model.safetensors.index.json")
-        own = dict(self.named_parameters())
+        own = self._checkpoint_tensors()
         seen, unexpected = set(), []
         tied = self._llm_cfg.tie_word_embeddings
         with torch.no_grad():
