@@ -1,10 +1,9 @@
 """Attention checker: an fp64 reference with per-element error scales, the output contract, and guarded launches.
 
 `reference` runs in float64 on the device of its operands, on the SAME bf16- or fp32-rounded q/k/v/dout the kernels read.
-Besides out, lse (natural log), dq, dk and dv it returns an error scale E for every element, built only from absolute values
-of fp64 terms (nothing is fitted to kernel output).  A kernel result passes when |got - ref| <= c * u * E elementwise, with u
-the unit roundoff of the dtype (2^-8 bf16, 2^-24 fp32) and c a per-path constant (`C` below); where E = 0 the result must be
-exact (rows with no visible key: out = 0, lse = +inf, dq = 0; masked keys: dk = dv = 0).
+Besides out, lse (natural log), dq, dk and dv it returns the error scale E of every element for the rule of tests/kernel_check.py
+(c per path: `C` below).  E = 0, where the result must be exact: rows with no visible key (out = 0, lse = +inf, dq = 0) and masked
+keys (dk = dv = 0).
 
 The rounding points of the bf16 kernels (mm_attn.hip) and the term of E that covers each:
   forward   scores S = Q.K^T in fp32 (exact bf16 products), p = exp2(S*scale*log2e - m) in fp32, l summed from the fp32 p,
@@ -23,16 +22,14 @@ u32 against E_lse = |lse| + rowsum(P o A) + sqrt(visible keys) (the fp32 sum of 
 The bound is a worst-case (sum of |terms|) bound: it is rigorous, and so it loses power as 1/sqrt(n) on long rows -- a
 single-key error in a row of n keys moves out by ~1/n of a value while E_o stays ~mean|v|.  tests/test_attn_check_cpu.py shows
 at which sizes the usual kernel mistakes are flagged."""
-import atexit
-import json
+import functools
 import math
-import os
 
 import torch
 
+from tests.kernel_check import U, U32, Guarded, RatioLog, check_bound, coords, dt, ptr, verify_guards  # noqa: F401
+
 LOG2E = 1.4426950408889634
-U = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}
-U32 = 2.0 ** -24
 
 # c per launch path and quantity: the smallest power of two >= 2x the worst err / (u E) measured on the MI355X over the
 # cases of tests/test_attention_contract_gpu.py (the PR description lists the measured ratios)
@@ -45,18 +42,7 @@ C = {
 }
 
 # worst err / (u E) seen per (path, quantity) in this process; MM_ATTN_RATIO_LOG=<file> writes them out at exit
-RATIOS = {}
-
-
-def _dump_ratios(path):
-    with open(path, "w") as f:
-        json.dump({f"{p}/{n}": v for (p, n), v in sorted(RATIOS.items())}, f, indent=1)
-
-
-if os.environ.get("MM_ATTN_RATIO_LOG"):
-    atexit.register(_dump_ratios, os.environ["MM_ATTN_RATIO_LOG"])
-
-SENTINEL = {torch.bfloat16: 0x7FC1, torch.float32: 0x7FC10000}   # quiet NaNs with a payload no kernel produces
+RATIOS = RatioLog("MM_ATTN_RATIO_LOG")
 
 
 def path_of(dtype, D, Skv):
@@ -144,52 +130,20 @@ def reference(q, k, v, dout, key_mask, causal, scale, backward=True):
 def _where(kind, idx, shape):
     """Human-readable location of flat index idx in a tensor of `kind` ('q': [B,Sq,Hq,D], 'k': [B,Skv,Hkv,D], 'lse': [B,Hq,Sq])
     with its tile coordinates (32- and 256-row query blocks, 64- and 128-key blocks)."""
-    coords = []
-    for n in reversed(shape):
-        coords.append(idx % n)
-        idx //= n
-    coords = coords[::-1]
     if kind == "lse":
-        b, h, row = coords
+        b, h, row = coords(idx, shape)
         return f"(b={b}, row={row}, head={h}) [q32 tile {row // 32}, q256 block {row // 256}]"
-    b, row, h, d = coords
+    b, row, h, d = coords(idx, shape)
     if kind == "q":
         return f"(b={b}, row={row}, head={h}, d={d}) [q32 tile {row // 32}, q256 block {row // 256}]"
     return f"(b={b}, key={row}, kvhead={h}, d={d}) [k64 tile {row // 64}, k128 block {row // 128}]"
 
 
 def check(name, got, ref, E, c, u, kind, path=None):
-    """|got - ref| <= c u E elementwise; exact where E = 0 (ref is then 0, or +inf for lse).  Returns the worst err / (u E)
-    and records it in RATIOS[(path, name)].  On failure the message names the worst element and its tiles."""
-    g = got.detach().to(ref.device, torch.float64)
-    exact = E == 0
-    if kind == "lse":
-        exact = exact | torch.isinf(ref)
-    bad_exact = exact & ~(g == ref)
-    nonfinite = ~torch.isfinite(g) & ~exact
-    if bool(nonfinite.any()):
-        i = int(nonfinite.reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: non-finite {float(g.reshape(-1)[i])} at {_where(kind, i, g.shape)}, "
-                             f"ref {float(ref.reshape(-1)[i]):.6g} ({int(nonfinite.sum())} such elements)")
-    if bool(bad_exact.any()):
-        i = int(bad_exact.reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: {float(g.reshape(-1)[i]):.6g} where exactly {float(ref.reshape(-1)[i])} is required "
-                             f"(no visible key / masked key / E = 0) at {_where(kind, i, g.shape)} "
-                             f"({int(bad_exact.sum())} such elements)")
-    err = torch.where(exact, torch.zeros_like(g), (g - ref).abs())
-    ratio = err / (u * torch.where(exact, torch.ones_like(E), E))
-    if ratio.numel() == 0:
-        return 0.0
-    i = int(ratio.reshape(-1).argmax())
-    worst = float(ratio.reshape(-1)[i])
-    if path is not None:
-        RATIOS[(path, name)] = max(RATIOS.get((path, name), 0.0), worst)
-    if not worst <= c:
-        nbad = int((ratio > c).sum())
-        raise AssertionError(f"{name}: err/(u E) = {worst:.3g} > c = {c} at {_where(kind, i, g.shape)}: got "
-                             f"{float(g.reshape(-1)[i]):.6g}, ref {float(ref.reshape(-1)[i]):.6g}, c u E = "
-                             f"{c * u * float(E.reshape(-1)[i]):.3g} ({nbad} elements over the bound)")
-    return worst
+    """The rule on one quantity (lse: exact also where ref = +inf, a row with no visible key); recorded in RATIOS[(path, name)];
+    a failure names the element's tiles."""
+    return check_bound(name, got, ref, E, c, u, key=path and (path, name), log=RATIOS, where=functools.partial(_where, kind),
+                       exact=torch.isinf(ref) if kind == "lse" else None)
 
 
 def check_all(res, ref, dtype, path, c=None, backward=True):
@@ -225,43 +179,6 @@ def check_contract(res, ref, backward=True):
 
 
 # ---- guarded launches through the C ABI --------------------------------------------------------------------------------
-def _ints(t):
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-class Guarded:
-    """One storage of `numel` elements between guard bands of `pad` elements, all filled with the sentinel NaN.  `view`
-    places a strided view at an element offset into the storage (as the operand it mirrors sits in its own storage);
-    `verify` asserts that every element outside the views is bit-unchanged and that no sentinel is left inside them."""
-
-    def __init__(self, numel, dtype, device, pad=512):
-        self.dtype, self.pad = dtype, pad
-        self.buf = torch.empty(pad + numel + pad, dtype=dtype, device=device)
-        _ints(self.buf).fill_(SENTINEL[dtype])
-        self.covered = torch.zeros(self.buf.numel(), dtype=torch.bool, device=device)
-        self.views = []
-
-    def view(self, shape, stride, offset=0):
-        v = self.buf.as_strided(shape, stride, self.pad + offset)
-        self.covered.as_strided(shape, stride, self.pad + offset).fill_(True)
-        self.views.append(v)
-        return v
-
-    def verify(self, name):
-        iv = _ints(self.buf)
-        s = SENTINEL[self.dtype]
-        guard_bad = (~self.covered) & (iv != s)
-        if bool(guard_bad.any()):
-            i = int(guard_bad.nonzero()[0])
-            raise AssertionError(f"{name}: write outside the output at storage element {i - self.pad} "
-                                 f"(storage [0, {self.buf.numel() - 2 * self.pad}), {int(guard_bad.sum())} elements)")
-        left = self.covered & (iv == s)
-        if bool(left.any()):
-            i = int(left.nonzero()[0])
-            raise AssertionError(f"{name}: {int(left.sum())} output elements never written (first at storage element "
-                                 f"{i - self.pad})")
-
-
 def grad_views(views, zero=()):
     """Gradient buffers with the SAME strides and offsets as the operand views (the ABI's rule), in guarded storages that mirror
     the operands' storages: views that share a storage (the fused qkv buffer) share one guarded storage, so the columns
@@ -278,14 +195,6 @@ def grad_views(views, zero=()):
     return out, list(stores.values())
 
 
-def _dt(dtype):
-    return 0 if dtype == torch.bfloat16 else 1
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _s3(t):
     return t.stride(0), t.stride(1), t.stride(2)
 
@@ -300,8 +209,8 @@ def run_fwd(q, k, v, key_mask, causal, scale, stream=None):
     out = go.view((B, Sq, Hq, D), (Sq * Hq * D, Hq * D, D, 1))
     lse = gl.view((B, Hq, Sq), (Hq * Sq, Sq, 1))
     st = stream if stream is not None else torch.cuda.current_stream()
-    call("mm_attn_fwd", _dt(q.dtype), _p(q), _p(k), _p(v), B, Sq, Skv, Hq, Hkv, D, *_s3(q), *_s3(k), *_s3(v), _p(key_mask),
-         int(causal), float(scale), _p(out), _p(lse), st.cuda_stream)
+    call("mm_attn_fwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), B, Sq, Skv, Hq, Hkv, D, *_s3(q), *_s3(k), *_s3(v), ptr(key_mask),
+         int(causal), float(scale), ptr(out), ptr(lse), st.cuda_stream)
     return out, lse, [("out", go), ("lse", gl)]
 
 
@@ -314,11 +223,6 @@ def run_bwd(q, k, v, out, dout, lse, key_mask, causal, scale, stream=None):
     (dq, dk, dv), stores = grad_views([q, k, v], zero=(1, 2) if q.dtype == torch.float32 else ())
     delta = torch.empty(B * Hq * Sq, dtype=torch.float32, device=q.device)
     st = stream if stream is not None else torch.cuda.current_stream()
-    call("mm_attn_bwd", _dt(q.dtype), _p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), B, Sq, Skv, Hq, Hkv, D, *_s3(q),
-         *_s3(k), *_s3(v), _p(key_mask), int(causal), float(scale), _p(dq), _p(dk), _p(dv), _p(delta), st.cuda_stream)
+    call("mm_attn_bwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), B, Sq, Skv, Hq, Hkv, D, *_s3(q),
+         *_s3(k), *_s3(v), ptr(key_mask), int(causal), float(scale), ptr(dq), ptr(dk), ptr(dv), ptr(delta), st.cuda_stream)
     return dq, dk, dv, [(f"dq/dk/dv storage {i}", g) for i, g in enumerate(stores)]
-
-
-def verify_guards(guards):
-    for name, g in guards:
-        g.verify(name)

@@ -5,23 +5,18 @@ corrupted references on the CPU to show which kernel mistakes it rejects.
 y[n, Ho, Wo, Cout] = act(conv(x[n, H, W, Cin], w[Cout, R, S, Cin]) * scale + shift (+ residual)), computed in float64 on the SAME
 storage-rounded x, w, residual and fp32 scale / shift the kernel reads.
 
-Random family: |got - ref| <= c u E per element, u = the storage type's unit roundoff, and
+Random family: the rule of tests/kernel_check.py (`check`, c in `C` below) with
     E = |ref| + K (u32 / u) |scale| (|x| (*) |w|),      K = R S Cin,   (*) = the same convolution on absolute values:
 the one rounding at the store (|ref|) plus a worst-case bound on the fp32 accumulation of K exact products carried through the
-scale.  Nothing in E is fitted to kernel output.  c follows the project's rule: the smallest power of two >= 2x the worst
-err / (u E) measured on the MI355X over the cases of tests/test_conv_contract_gpu.py (`C` below, measured ratios beside it).
+scale.
 
 Exact family: integer x and w with |.| <= 4, a power-of-two scale per channel, integer shift and residual, so that every fp32
 partial sum in any order is exact (`exact_reference` asserts it: the sum of |terms| stays below 2^24 and the fp64 result is an fp32
 number).  The bf16 result must then equal bf16(fp64) bit for bit and the fp32 result the fp64 value."""
-import atexit
-import json
-import os
-
 import torch
 import torch.nn.functional as F
 
-from tests.attn_check import Guarded, U, U32
+from tests.kernel_check import U, U32, Guarded, RatioLog, check_bits, check_bound
 
 # c per storage type and quantity (conv: the six contract cases; head: mm_gate_head's logits and weights); measured worst
 # err / (u E) on the MI355X beside each
@@ -29,16 +24,7 @@ C = {
     "bf16": {"conv": 2.0, "logits": 2.0, "weights": 2.0},                    # measured 0.979, 0.835, 0.527
     "f32": {"conv": 0.125, "logits": 2.0 ** -11, "weights": 2.0 ** -11},     # measured 0.0318, 1.68e-4, 1.56e-4 (K and C + HW are worst-case factors)
 }
-RATIOS = {}
-
-
-def _dump_ratios(path):
-    with open(path, "w") as f:
-        json.dump({f"{p}/{n}": v for (p, n), v in sorted(RATIOS.items())}, f, indent=1)
-
-
-if os.environ.get("MM_CONV_RATIO_LOG"):
-    atexit.register(_dump_ratios, os.environ["MM_CONV_RATIO_LOG"])
+RATIOS = RatioLog("MM_CONV_RATIO_LOG")
 
 
 def path_of(dtype):
@@ -82,43 +68,13 @@ def exact_reference(x, w, scale, shift, residual, relu, stride, pad):
 
 
 def check(name, got, ref, E, c, u, path=None, quantity="conv"):
-    """|got - ref| <= c u E elementwise (exact where E = 0); returns the worst err / (u E) and records it in RATIOS."""
-    g = got.detach().to(ref.device, torch.float64)
-    assert g.shape == ref.shape, f"{name}: shape {tuple(g.shape)} != {tuple(ref.shape)}"
-    if not bool(torch.isfinite(g).all()):
-        i = int((~torch.isfinite(g)).reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: non-finite output at flat index {i}")
-    exact = E == 0
-    if bool((exact & (g != ref)).any()):
-        raise AssertionError(f"{name}: {int((exact & (g != ref)).sum())} elements differ where E = 0")
-    ratio = torch.where(exact, torch.zeros_like(g), (g - ref).abs() / (u * torch.where(exact, torch.ones_like(E), E)))
-    if ratio.numel() == 0:
-        return 0.0
-    i = int(ratio.reshape(-1).argmax())
-    worst = float(ratio.reshape(-1)[i])
-    if path is not None:
-        RATIOS[(path, quantity)] = max(RATIOS.get((path, quantity), 0.0), worst)
-    print(f"{name}: worst err/(u E) = {worst:.4g} (c = {c})")
-    if not worst <= c:
-        idx = []
-        for n in reversed(ref.shape):
-            idx.append(i % n)
-            i //= n
-        raise AssertionError(f"{name}: err/(u E) = {worst:.3g} > c = {c} at {tuple(idx[::-1])}: got {float(g.reshape(-1)[ratio.reshape(-1).argmax()]):.6g}, "
-                             f"ref {float(ref.reshape(-1)[ratio.reshape(-1).argmax()]):.6g} ({int((ratio > c).sum())} elements over the bound)")
-    return worst
+    """The rule; the worst err / (u E) is recorded in RATIOS[(path, quantity)]."""
+    return check_bound(name, got, ref, E, c, u, key=path and (path, quantity), log=RATIOS)
 
 
 def check_exact(name, got, ref):
-    """The exact family: got == T(ref) bit for bit (ref is an fp32 number, so the rounding to T is a single one)."""
-    want = ref.to(torch.float32).to(got.dtype)
-    g = got.detach().to(ref.device)
-    assert g.shape == want.shape, f"{name}: shape {tuple(g.shape)} != {tuple(want.shape)}"
-    bad = ~((g == want) & (torch.signbit(g.float()) == torch.signbit(want.float())) | ((g == 0) & (want == 0)))
-    if bool(bad.any()):
-        i = int(bad.reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: {int(bad.sum())} elements differ from the exact result; first at flat index {i}: got "
-                             f"{float(g.reshape(-1)[i])}, want {float(want.reshape(-1)[i])}")
+    """The exact family: got == T(ref) (ref is an fp32 number, so the rounding to T is a single one), a zero of either sign."""
+    check_bits(name, got, ref.to(torch.float32).to(got.dtype), zero_sign=False)
 
 
 # ---- operands -----------------------------------------------------------------------------------------------------------

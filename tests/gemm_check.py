@@ -1,6 +1,6 @@
 """GEMM checker: exact and per-element fp64 references, guarded operand / output placement, and the launch path a call took.
 
-Two families of data, as for attention (tests/attn_check.py), but for the linear paths the check can be EXACT:
+Two families of data; for the linear paths the check can be EXACT:
 
 Exact family (`exact_problem`).  A and B hold small integers (|a|, |b| <= 8) and every row of A / column of B (row of the
 [N, K] operand) is scaled by its own power of two, so the data is asymmetric: a swapped row / column, a transposed block or a
@@ -13,8 +13,7 @@ and the check is bitwise equality of every element (`check_exact`).  The fp32 GE
 
 Random family (`bound_reference`).  Normal operands; the error scale E is built from absolute fp64 terms, one per rounding
 point: |ref| for the final bf16 rounding and K * (u32 / u) * |A|.|B| for the fp32 accumulation (one fma per product,
-cdna_hip_programming.md "FP32-input MFMA").  A result passes when |got - ref| <= c u E elementwise (`check_bound`), c per path
-(`C`): the smallest power of two >= 2x the worst ratio measured on the MI355X, the rule of attn_check.C.
+cdna_hip_programming.md "FP32-input MFMA").  `check_bound` is the rule of tests/kernel_check.py with c per path (`C`).
 MM_GEMM_RATIO_LOG=<file> writes the worst ratio per path at exit.
 
 Non-linear epilogues (activation, SwiGLU, RoPE, the RMSNorm prologue of the decode fusions) are checked with `check_bound`
@@ -22,27 +21,22 @@ against an fp64 reference that takes the documented bf16 rounding points of mm_h
 where they are exactly reproducible (PRE, GU, the bf16 GEMM output before RoPE); E then carries the remaining function
 error (a few fp32 ulps of each operand) and the rounding points in between.
 
-Placement.  Outputs live in NaN-sentinel storages (`Guarded` of attn_check): `out_view` places C tight (ldc = N), at a
+Placement.  Outputs live in NaN-sentinel storages (`Guarded`): `out_view` places C tight (ldc = N), at a
 padded ldc (the logits' layout), as a column slice of a wider buffer (the fused qkv / gate|up layout) -- always with rows past
 M in the same storage.  Inputs: K-contiguous operands have zeros in [K, pad8(K)) and NaN beyond, K-strided ones NaN in the
 padding columns and in rows past K, bias and residual NaN past N (`kc_storage`, `ks_storage`, ...).  A read outside the
 contract that reaches a stored element then fails the exact check; a write outside the output fails Guarded.verify.
 
 `last_kernel()` is mm_get_option("gemm_last_kernel"): every case states the kernel id it expects (see mm_hip.h)."""
-import atexit
-import contextlib
-import ctypes
-import json
 import math
-import os
 
 import torch
 
-from tests.attn_check import SENTINEL, Guarded  # noqa: F401  (re-exported: one sentinel / guard for every checker)
+from tests import kernel_check as KC
+from tests.kernel_check import U32, Guarded, get_option, ptr, sentinel_fill, stream
 
 BF = torch.bfloat16
-U_BF = 2.0 ** -8
-U32 = 2.0 ** -24
+U_BF = KC.U[BF]
 NT, NN, TN = 0, 1, 2
 EPI_BIAS, EPI_GELU_ERF, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_ACCUMULATE, EPI_GELU_TANH = 1, 2, 4, 8, 16, 32
 ACTS = {EPI_GELU_ERF: "erf", EPI_QUICK_GELU: "quick", EPI_GELU_TANH: "tanh"}
@@ -61,16 +55,7 @@ C = {
 }
 
 # worst err / (u E) seen per path in this process; MM_GEMM_RATIO_LOG=<file> writes them out at exit
-RATIOS = {}
-
-
-def _dump_ratios(path):
-    with open(path, "w") as f:
-        json.dump(dict(sorted(RATIOS.items())), f, indent=1)
-
-
-if os.environ.get("MM_GEMM_RATIO_LOG"):
-    atexit.register(_dump_ratios, os.environ["MM_GEMM_RATIO_LOG"])
+RATIOS = KC.RatioLog("MM_GEMM_RATIO_LOG")
 
 
 def pad8(n):
@@ -146,16 +131,8 @@ def _where(idx, shape):
 
 
 def check_exact(name, got, want):
-    """Bitwise equality of every element (got, want: the same dtype; NaN never equals)."""
-    g = got.detach()
-    w = want.to(g.device)
-    assert g.shape == w.shape, f"{name}: shape {tuple(g.shape)} != {tuple(w.shape)}"
-    iv = lambda t: t.contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
-    bad = iv(g) != iv(w)
-    if bool(bad.any()):
-        i = int(bad.reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: {int(bad.sum())} of {bad.numel()} elements differ from the exact result; first at "
-                             f"{_where(i, g.shape)}: got {float(g.reshape(-1)[i])!r}, want {float(w.reshape(-1)[i])!r}")
+    """Bitwise equality of every element (got, want: the same dtype)."""
+    KC.check_bits(name, got, want, where=_where)
 
 
 # ---- random family -------------------------------------------------------------------------------------------------------
@@ -177,32 +154,8 @@ def bound_reference(a, b, epi=0, bias=None, res=None, c0=None):
 
 
 def check_bound(name, got, ref, E, c, path=None, u=U_BF):
-    """|got - ref| <= c u E elementwise (every element finite).  Returns the worst err / (u E), recorded in RATIOS[path]."""
-    g = got.detach().to(ref.device, torch.float64)
-    assert g.shape == ref.shape, f"{name}: shape {tuple(g.shape)} != {tuple(ref.shape)}"
-    fin = torch.isfinite(g)
-    if not bool(fin.all()):
-        i = int((~fin).reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: non-finite {float(g.reshape(-1)[i])} at {_where(i, g.shape)} "
-                             f"({int((~fin).sum())} such elements)")
-    err = (g - ref).abs()
-    zero = E == 0
-    bad_zero = zero & (err != 0)
-    if bool(bad_zero.any()):
-        i = int(bad_zero.reshape(-1).nonzero()[0])
-        raise AssertionError(f"{name}: {float(g.reshape(-1)[i])} where exactly 0 is required at {_where(i, g.shape)}")
-    ratio = torch.where(zero, torch.zeros_like(err), err / (u * torch.where(zero, torch.ones_like(E), E)))
-    if ratio.numel() == 0:
-        return 0.0
-    i = int(ratio.reshape(-1).argmax())
-    worst = float(ratio.reshape(-1)[i])
-    if path is not None:
-        RATIOS[path] = max(RATIOS.get(path, 0.0), worst)
-    if not worst <= c:
-        raise AssertionError(f"{name}: err/(u E) = {worst:.3g} > c = {c} at {_where(i, g.shape)}: got "
-                             f"{float(g.reshape(-1)[i]):.6g}, ref {float(ref.reshape(-1)[i]):.6g} "
-                             f"({int((ratio > c).sum())} elements over the bound)")
-    return worst
+    """The rule; the worst err / (u E) is recorded in RATIOS[path], a failure names the element's tiles."""
+    return KC.check_bound(name, got, ref, E, c, u, key=path, log=RATIOS, where=_where)
 
 
 # ---- non-linear references (fp64 of the function; E: its fp32 error + the documented bf16 rounding points) ---------------
@@ -279,17 +232,12 @@ def norm_E(xn, b):
 
 
 # ---- placement ------------------------------------------------------------------------------------------------------------
-def _nan_fill(t):
-    t.view(torch.int16 if t.dtype == BF else torch.int32).fill_(SENTINEL[t.dtype])
-    return t
-
-
 def kc_storage(vals, dtype=BF, ld=None, extra_rows=8):
     """A K-contiguous operand [R, K] in a storage [R + extra_rows, ld]: zeros in [K, pad8(K)), NaN from pad8(K) to ld and in
     the rows past R.  -> the [R, K] view (stride ld)."""
     R, K = vals.shape
     ld = ld or pad8(K) + 16
-    buf = _nan_fill(torch.empty(R + extra_rows, ld, dtype=dtype, device=vals.device))
+    buf = sentinel_fill(torch.empty(R + extra_rows, ld, dtype=dtype, device=vals.device))
     buf[:R, K:pad8(K)] = 0
     buf[:R, :K] = vals.to(dtype)
     return buf[:R, :K]
@@ -300,14 +248,14 @@ def ks_storage(vals, dtype=BF, ld=None, extra_rows=72):
     K-step read past K meets NaN, not zeros).  -> the [K, X] view (stride ld)."""
     K, X = vals.shape
     ld = ld or pad8(X) + 8
-    buf = _nan_fill(torch.empty(K + extra_rows, ld, dtype=dtype, device=vals.device))
+    buf = sentinel_fill(torch.empty(K + extra_rows, ld, dtype=dtype, device=vals.device))
     buf[:K, :X] = vals.to(dtype)
     return buf[:K, :X]
 
 
 def vec_storage(vals, dtype=BF, extra=64):
     """bias [N] followed by NaN."""
-    buf = _nan_fill(torch.empty(vals.numel() + extra, dtype=dtype, device=vals.device))
+    buf = sentinel_fill(torch.empty(vals.numel() + extra, dtype=dtype, device=vals.device))
     buf[:vals.numel()] = vals.to(dtype)
     return buf[:vals.numel()]
 
@@ -316,7 +264,7 @@ def rows_storage(vals, dtype=BF, ld=None, extra_rows=8):
     """residual [M, N] in a storage [M + extra_rows, ld] with NaN past N and past M."""
     M, N = vals.shape
     ld = ld or pad8(N) + 8
-    buf = _nan_fill(torch.empty(M + extra_rows, ld, dtype=dtype, device=vals.device))
+    buf = sentinel_fill(torch.empty(M + extra_rows, ld, dtype=dtype, device=vals.device))
     buf[:M, :N] = vals.to(dtype)
     return buf[:M, :N]
 
@@ -340,48 +288,15 @@ def out_view(M, N, placement, dtype=BF, device="cuda", extra_rows=8):
 
 
 # ---- launches -------------------------------------------------------------------------------------------------------------
-def _lib():
-    from multimeditron_amd._lib import lib
-    return lib()
-
-
-def get_option(name):
-    v = ctypes.c_int(0)
-    assert _lib().mm_get_option(name.encode(), ctypes.byref(v)) == 0, name
-    return v.value
-
-
 def last_kernel():
     return get_option("gemm_last_kernel")
-
-
-# options without a getter: their library defaults
-_DEFAULTS = {"gemm_w4_big": 4, "gemm_w4_stream": 1, "gemm_small": -1, "gemm_epi_pipe": 1}
-
-
-@contextlib.contextmanager
-def options(**kw):
-    """Set mm_set_option switches for the block and restore what was there."""
-    old = {}
-    for k, v in kw.items():
-        old[k] = _DEFAULTS[k] if k in _DEFAULTS else get_option(k)
-        assert _lib().mm_set_option(k.encode(), int(v)) == 0, (k, v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            _lib().mm_set_option(k.encode(), v)
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
 
 
 def gemm(layout, a, b, M, N, K, c, bias=None, res=None, epi=0, dtype=BF):
     """mm_gemm on storage views (a, b as laid out for `layout`, c the output view); -> the kernel id it launched."""
     from multimeditron_amd._lib import call
-    call("mm_gemm", 0 if dtype == BF else 1, layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0),
-         _p(bias), _p(res), res.stride(0) if res is not None else 0, epi, torch.cuda.current_stream().cuda_stream)
+    call("mm_gemm", KC.dt(dtype), layout, M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(c), c.stride(0),
+         ptr(bias), ptr(res), res.stride(0) if res is not None else 0, epi, stream())
     return last_kernel()
 
 

@@ -1,9 +1,7 @@
 """Row-wise kernel checker (csrc/mm_rowwise.hip): fp64 references with per-element error scales, asymmetric problems, guarded launches.
 
-Every reference takes the STORED operands (bf16 / fp32 tensors, any device) and returns (ref, E) in fp64.  A result passes when
-|got - ref| <= c u E per element (gemm_check.check_bound), u = 2^-8 for a bf16 output and 2^-24 for an fp32 one.  E is a sum of
-absolute terms, one per rounding point the kernel has; fp32 terms enter a bf16 output's E scaled by U32 / u.  The rounding points,
-read off mm_rowwise.hip (T = storage type, everything else fp32):
+Every reference takes the STORED operands (bf16 / fp32 tensors, any device) and returns (ref, E) in fp64 for the rule of
+tests/kernel_check.py (`bound`).  The rounding points, read off mm_rowwise.hip (T = storage type, everything else fp32):
 
   rmsnorm_fwd   ss = sum x^2 (depth norm_depth) -> ss / H -> + eps -> rsqrtf = rstd;  y = T(w * f32(T(x * rstd))): two roundings to T
   rmsnorm_bwd   xh = x rstd;  dot = sum(g w xh) / H (norm_depth);  dx = T(rstd (g w - xh dot) + dres);  dw = reduce(sum_rows g xh)
@@ -32,11 +30,12 @@ kernel measure well below 1; a bf16 output measures just under 1 (half an ulp of
 import torch
 
 from tests import gemm_check as GC
-from tests.gemm_check import FUNC, RATIOS, SENTINEL, U32, U_BF, Guarded, check_bound, check_exact, pad64  # noqa: F401
+from tests.gemm_check import FUNC, RATIOS, check_exact, pad64  # noqa: F401  (the row-wise ratios go into the GEMM log)
+from tests.kernel_check import U, U32, Guarded, check_bound, sentinel_fill
 
 BF, F32 = torch.bfloat16, torch.float32
+U_BF = U[BF]
 VN = {BF: 8, F32: 4}
-U = {BF: U_BF, F32: U32}
 NAME = {BF: "bf16", F32: "f32"}
 ROWS_PER_BLOCK = 16                  # NORM_BWD_ROWS_PER_BLOCK
 ARGMAX_CHUNK = 4096
@@ -80,8 +79,9 @@ def path(kernel, dtype):
 
 
 def bound(name, kernel, dtype, got, ref, E, u=None):
-    """check_bound with the kernel's c, recorded under rowwise.<kernel>.<dtype>."""
-    return check_bound(name, got, ref.to(got.device), E.to(got.device), c_of(kernel, dtype), path(kernel, dtype), u=U[dtype] if u is None else u)
+    """The rule with the kernel's c, recorded under rowwise.<kernel>.<dtype>."""
+    return check_bound(name, got, ref.to(got.device), E.to(got.device), c_of(kernel, dtype), U[dtype] if u is None else u,
+                       key=path(kernel, dtype), log=RATIOS)
 
 
 # ---- launch geometry mirrored from mm_rowwise.hip ------------------------------------------------------------------------------
@@ -170,7 +170,7 @@ def ce_problem(T, V, dtype, device, seed, scale=2.0):
 def logits_storage(x, ld, extra_rows=4):
     """logits [T, V] in a [T + extra_rows, ld] storage with NaN sentinels in [V, ld) and in the rows past T -> the [T, V] view."""
     T, V = x.shape
-    buf = GC._nan_fill(torch.empty(T + extra_rows, ld, dtype=x.dtype, device=x.device))
+    buf = sentinel_fill(torch.empty(T + extra_rows, ld, dtype=x.dtype, device=x.device))
     buf[:T, :V] = x
     return buf[:T, :V]
 
@@ -178,7 +178,7 @@ def logits_storage(x, ld, extra_rows=4):
 def rows_storage(x, extra_rows=4):
     """a contiguous [M, H] operand followed by rows of NaN sentinels (rows past M are not read)."""
     M, H = x.shape
-    buf = GC._nan_fill(torch.empty(M + extra_rows, H, dtype=x.dtype, device=x.device))
+    buf = sentinel_fill(torch.empty(M + extra_rows, H, dtype=x.dtype, device=x.device))
     buf[:M] = x
     return buf[:M]
 
@@ -499,29 +499,7 @@ def argmax_tie_rows(V, dtype):
     return rows
 
 
-# ---- launches through the C ABI (outputs in caller-made views, return codes handed back) -----------------------------------------
-def _lib():
-    from multimeditron_amd._lib import lib
-    return lib()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def dt(dtype):
-    return 0 if dtype == BF else 1
-
-
-def p_(t):
-    return t.data_ptr() if t is not None else None
-
-
-def rc(name, *args):
-    """the raw return code of an entry point on the current stream (no exception)."""
-    return getattr(_lib(), name)(*args, _stream())
-
-
+# ---- outputs in caller-made views -----------------------------------------------------------------------------------------------
 def guarded(shape, dtype, ld=None, extra_rows=0, device="cuda"):
     """an output [R, W] with row stride ld (default W) and `extra_rows` spare rows in a NaN-sentinel storage; 1-D for a 1-D shape.
     -> (view, Guarded)."""

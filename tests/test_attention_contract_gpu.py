@@ -3,7 +3,7 @@
 Paths (launch_bf16_fwd / launch_bf16_bwd / mm_attn_bwd): bf16 D = 128 (attn_fwd128q_kernel, attn_fwd128p_kernel above 256 Ki keys,
 attn_bwd_dq128p_kernel, attn_bwd_dkv128_pairp_kernel), bf16 D = 64 (attn_fwd_kernel<64>, attn_bwd_dq_kernel<64>,
 attn_bwd_dkv_kernel<64>), fp32 (attn_fwd_f32_kernel, attn_bwd_f32_kernel, both forms of attn_delta_kernel).  Every launch writes
-into guarded storages (tests/attn_check.py: Guarded) and every case checks the output contract.  Then the exact invariances:
+into guarded storages (tests/kernel_check.py: Guarded) and every case checks the output contract.  Then the exact invariances:
 the work mapping (batch split, KV-head permutation), masked padding keys, and repeat determinism with a GEMM running beside."""
 import pytest
 import torch

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import conv_check as CC
-from tests.attn_check import Guarded, U
+from tests.kernel_check import Guarded, U
 
 DTYPES = [torch.bfloat16, torch.float32]
 

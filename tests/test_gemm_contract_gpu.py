@@ -14,6 +14,7 @@ import torch
 
 from tests import gemm_check as GC
 from tests.gemm_check import NN, NT, TN
+from tests.kernel_check import dt, options, ptr, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -135,7 +136,7 @@ def _run(c, p, A, B, bias, res, dtype, epi, opts):
     C, guard = GC.out_view(c["M"], c["N"], c["place"], dtype)
     if epi & GC.EPI_ACCUMULATE:
         C.copy_(p["c0"].to(dtype))
-    with GC.options(**opts):
+    with options(**opts):
         kid = GC.gemm(c["layout"], A, B, c["M"], c["N"], c["K"], C, bias, res, epi, dtype)
     torch.cuda.synchronize()
     guard.verify(f"C ({c['place']})")
@@ -168,10 +169,6 @@ def _call(name, *args):
     return GC.last_kernel()
 
 
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
 @pytest.mark.parametrize("kind", ["erf", "quick", "tanh"])
 @pytest.mark.parametrize("M,N,K,flags,kid,opts", [
     (300, 136, 72, GC.EPI_BIAS, GC.DMA64x128, {}), (1028, 1024, 1024, GC.EPI_BIAS | GC.EPI_RESIDUAL, GC.DMA64x128, {}),
@@ -185,10 +182,10 @@ def test_gemm_act_fwd_keeps_pre(kind, M, N, K, flags, kid, opts):
     PRE, gp = GC.out_view(M, N, "slice")
     ACT, ga = GC.out_view(M, N, "pad64" if N % 8 else "tight")
     epi = flags | {"erf": GC.EPI_GELU_ERF, "quick": GC.EPI_QUICK_GELU, "tanh": GC.EPI_GELU_TANH}[kind]
-    with GC.options(**opts):
-        got = _call("mm_gemm_act_fwd", 0, M, N, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), GC._p(bias),
-                    PRE.data_ptr(), PRE.stride(0), ACT.data_ptr(), ACT.stride(0), GC._p(res), res.stride(0) if res is not None else 0,
-                    epi, _s())
+    with options(**opts):
+        got = _call("mm_gemm_act_fwd", 0, M, N, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), ptr(bias),
+                    PRE.data_ptr(), PRE.stride(0), ACT.data_ptr(), ACT.stride(0), ptr(res), res.stride(0) if res is not None else 0,
+                    epi, stream())
     assert got == kid
     gp.verify("PRE")
     ga.verify("ACT")
@@ -212,9 +209,9 @@ def test_gemm_swiglu_fwd_bwd(M, I, K, opts, kid, kid_bwd):
     for persist in (1, 0):
         GU, gg = GC.out_view(M, 2 * I, "slice")
         ACT, ga = GC.out_view(M, I, "pad64")
-        with GC.options(gemm_persist=persist, **opts):
+        with options(gemm_persist=persist, **opts):
             got = _call("mm_gemm_swiglu_fwd", 0, M, I, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), GU.data_ptr(),
-                        GU.stride(0), ACT.data_ptr(), ACT.stride(0), _s())
+                        GU.stride(0), ACT.data_ptr(), ACT.stride(0), stream())
         assert got == kid
         gg.verify("GU")
         ga.verify("ACT")
@@ -232,9 +229,9 @@ def test_gemm_swiglu_fwd_bwd(M, I, K, opts, kid, kid_bwd):
     bw = []
     for persist in (1, 0):
         dGU, gd = GC.out_view(M, 2 * I, "tight")
-        with GC.options(gemm_persist=persist, **opts):
+        with options(gemm_persist=persist, **opts):
             got = _call("mm_gemm_swiglu_bwd", 0, M, I, H, dY.data_ptr(), dY.stride(0), Wd.data_ptr(), Wd.stride(0), GUs.data_ptr(),
-                        GUs.stride(0), dGU.data_ptr(), dGU.stride(0), _s())
+                        GUs.stride(0), dGU.data_ptr(), dGU.stride(0), stream())
         assert got == kid_bwd
         gd.verify("dGU")
         bw.append(dGU.clone())
@@ -262,9 +259,9 @@ def test_gemm_rope_fwd(M, Hq, Hkv, K, bias, opts, kid):
     outs = []
     for persist in (1, 0):
         Q, gq = GC.out_view(M, N, "slice")
-        with GC.options(gemm_persist=persist, **opts):
-            got = _call("mm_gemm_rope_fwd", 0, M, N, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), GC._p(b), Q.data_ptr(),
-                        Q.stride(0), cols, D, cos.data_ptr(), sin.data_ptr(), _s())
+        with options(gemm_persist=persist, **opts):
+            got = _call("mm_gemm_rope_fwd", 0, M, N, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), ptr(b), Q.data_ptr(),
+                        Q.stride(0), cols, D, cos.data_ptr(), sin.data_ptr(), stream())
         assert got == kid
         gq.verify("QKV")
         outs.append(Q.clone())
@@ -290,7 +287,7 @@ def test_decode_linear(M, N, K, norm):
     nw = _norm_w(K, 1) if norm else None
     C, gc_ = GC.out_view(M, N, "pad64" if N % 4 else "slice")
     assert _call("mm_decode_linear", 0, M, N, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), b.data_ptr(), res.data_ptr(),
-                 res.stride(0), C.data_ptr(), C.stride(0), GC._p(nw), 1e-5, _s()) == GC.GEMV
+                 res.stride(0), C.data_ptr(), C.stride(0), ptr(nw), 1e-5, stream()) == GC.GEMV
     gc_.verify("C")
     if not norm:
         GC.check_exact("C", C, GC.rne_bf16(GC.exact_reference(p, GC.EPI_BIAS | GC.EPI_RESIDUAL)))
@@ -308,7 +305,7 @@ def test_decode_gateup_swiglu(M, I, K, norm):
     nw = _norm_w(K, 2) if norm else None
     ACT, ga = GC.out_view(M, I, "slice")
     assert _call("mm_decode_gateup_swiglu", 0, M, I, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), ACT.data_ptr(),
-                 ACT.stride(0), GC._p(nw), 1e-5, _s()) == GC.GEMV
+                 ACT.stride(0), ptr(nw), 1e-5, stream()) == GC.GEMV
     ga.verify("ACT")
     if not norm:
         gu = GC.rne_bf16(GC.exact_reference(p)).double()
@@ -344,9 +341,9 @@ def test_decode_qkv_rope_append(M, Hq, Hkv, K, bias, norm):
     kc = gk.buf[gk.pad:gk.pad + M * Smax * Hkv * D].view(M, Smax, Hkv, D)
     vc = gv.buf[gv.pad:gv.pad + M * Smax * Hkv * D].view(M, Smax, Hkv, D)
     krow, vrow = (gg.view((M, Hkv * D), (Smax * Hkv * D, 1), pos * Hkv * D) for gg in (gk, gv))
-    assert _call("mm_decode_qkv_rope_append", 0, M, Hq, Hkv, D, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), GC._p(b),
+    assert _call("mm_decode_qkv_rope_append", 0, M, Hq, Hkv, D, K, X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), ptr(b),
                  Q.data_ptr(), Q.stride(0), cos.data_ptr(), sin.data_ptr(), kc[:, pos].data_ptr(), vc[:, pos].data_ptr(),
-                 kc.stride(0), GC._p(nw), 1e-6, _s()) == GC.GEMV
+                 kc.stride(0), ptr(nw), 1e-6, stream()) == GC.GEMV
     gq.verify("QKV")
     gk.verify("k cache")
     gv.verify("v cache")
@@ -382,7 +379,7 @@ def test_colsum_exact(dtype, M, N, acc):
     if acc:
         base = p["c0"][0] * 2.0 ** 6
         out.copy_(base.to(dtype))
-    _call("mm_colsum", 0 if dtype == torch.bfloat16 else 1, X.data_ptr(), M, N, X.stride(0), out.data_ptr(), int(acc), _s())
+    _call("mm_colsum", dt(dtype), X.data_ptr(), M, N, X.stride(0), out.data_ptr(), int(acc), stream())
     g.verify("colsum out")
     ref = p["res"].sum(0) + base
     assert float(((p["res"].abs().sum(0) + base.abs()) / (p["q"].min(0).values)).max()) < 2 ** 24

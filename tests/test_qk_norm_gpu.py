@@ -4,8 +4,8 @@ Forward: given the kernel's own rstd, the output must be BIT-identical to the do
 fp32 product, one rounding), bf16(w * that) (a product of two bf16 values, exact in fp32, one rounding), then mm_rope_apply with
 the same tables -- taken here in torch + the existing mm_rope_apply.  Against mm_rmsnorm_fwd on a contiguous [T*H, D] copy +
 mm_rope_apply: bit-identical on every head whose rstd agrees, last-bit differences on the others only.  rstd against fp64.
-Backward: per-element fp64 bounds |got - ref| <= c u E (tests/gemm_check.check_bound) with E built from absolute terms; dx lands in
-a NaN-sentinel storage (attn_check.Guarded) that also holds the v columns and row padding, which must stay untouched.  The dw
+Backward: per-element fp64 bounds |got - ref| <= c u E (tests/kernel_check.check_bound) with E built from absolute terms; dx lands in
+a NaN-sentinel storage (kernel_check.Guarded) that also holds the v columns and row padding, which must stay untouched.  The dw
 partials are bit-identical across reruns.  Decode: the append kernel is bit-identical to the forward in place + the cache copy."""
 import ctypes
 import os
@@ -14,7 +14,7 @@ import re
 import pytest
 import torch
 
-from tests.gemm_check import U32, U_BF, Guarded, check_bound
+from tests.kernel_check import U, U32, Guarded, check_bound
 
 BF = torch.bfloat16
 EPS = 1e-6
@@ -168,7 +168,7 @@ def test_backward_fp64_bounds_and_determinism(dtype, D, Hq, Hkv, T):
     dwq, dwk = K.qk_norm_rope_bwd(dqk, qkv, T, Hq, Hkv, D, wq, wk, rstd, cos, sin, dx)
     torch.cuda.synchronize()
     gdx.verify("dqkv")
-    u = U_BF if dtype == BF else U32
+    u = U[dtype]
     ref, Ef, rq, rk, Sq, Sk = backward_reference(qkv, dqk, wq, wk, cos, sin, T, Hq, Hkv, D)
     check_bound("dx", dx, ref, ref.abs() + (D + 16) * (U32 / u) * Ef, C_BWD, u=u)
     nblk = K.qk_norm_bwd_blocks(T)

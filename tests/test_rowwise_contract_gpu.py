@@ -10,7 +10,9 @@ import torch
 
 from tests import gemm_check as GC
 from tests import rowwise_check as RC
-from tests.rowwise_check import BF, F32, U32, VN, check_exact, dt, guarded, p_, rc
+from tests.kernel_check import SENTINEL, dt, lib, rc
+from tests.kernel_check import ptr as p_
+from tests.rowwise_check import BF, F32, U32, VN, check_exact, guarded
 
 pytestmark = pytest.mark.gpu
 DTYPES = [BF, F32]
@@ -48,7 +50,7 @@ def f(x):
 def untouched(*guards):
     for g in guards:
         iv = g.buf.view(torch.int16 if g.dtype == BF else torch.int32)
-        assert bool((iv == RC.SENTINEL[g.dtype]).all()), "a refused or empty call wrote to its output"
+        assert bool((iv == SENTINEL[g.dtype]).all()), "a refused or empty call wrote to its output"
 
 
 def ids(v):
@@ -77,7 +79,7 @@ def rms_case(dtype, H, M, with_res, eps, seed):
     RC.bound(tag + " rstd", "rmsnorm.rstd", dtype, rstd, r64, Er, u=U32)
     RC.bound(tag + " y", "rmsnorm.y", dtype, y, y64, Ey)
     nblk = RC.norm_blocks(M)
-    assert RC._lib().mm_norm_bwd_blocks(M) == nblk
+    assert lib().mm_norm_bwd_blocks(M) == nblk
     dx, gdx = guarded((M, H), dtype, extra_rows=2)
     dwp, gdw = guarded((nblk, H), F32, extra_rows=1)
     res = dres if with_res else None
@@ -504,7 +506,7 @@ def test_argmax_constructed_ties_one_launch_and_split(dtype, V):
             for split in (False, True):
                 out = torch.full((R + 2,), -7, dtype=torch.int64, device=DEV)
                 if split:
-                    nb = RC._lib().mm_argmax_softmax_ws_bytes(R, V)
+                    nb = lib().mm_argmax_softmax_ws_bytes(R, V)
                     ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=DEV)
                     assert rc("mm_argmax_softmax_split", dt(dtype), p_(lg), R, V, ld, f(temp), p_(out), p_(ws)) == RC.OK
                 else:
