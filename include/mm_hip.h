@@ -102,38 +102,58 @@ int mm_colsum(int dtype, const void* X, int M, int N, int ldx, void* out, int ac
 
 /* ids outside [0, vocab): *flag (device int, sticky) = 1.  nn.Embedding raises for them (model.py:433 embeds every id of the
  * batch before the splice); mm_embed_splice_fwd reads row 0 instead of out of bounds, so the caller checks this flag (the
- * Python layer reads it one call later, without a stall, and raises IndexError).                                           */
+ * Python layer reads it one call later, without a stall, and raises IndexError).  The flag is only ever set to 1: the
+ * caller zeroes it, and a later call with good ids leaves a 1 in place.  T == 0: nothing is launched.                       */
 int mm_embed_check_ids(const int64_t* ids, int T, int64_t vocab, int* flag, void* stream);
 
 /* ---- embed + modality splice: model.py:433-444 ---------------------------------------------------
  * out[t,:] = proj[src[t],:] if src[t] >= 0 else emb[ids[t],:]; src is built from (batch_idx, token_range)
- * by mm_splice_build_map (last writer wins, like index_put).                                         */
+ * by mm_splice_build_map (last writer wins, like index_put).
+ * Contract (tests/test_embed_contract_gpu.py):
+ *   mm_splice_build_map writes all of src_map[0, T): -1, or the LARGEST source index i whose position
+ *     pos(i) = batch_idx[i] * S + token_range[i] equals t.  A position outside [0, T) is dropped.  token_range is not
+ *     checked against S: a value outside [0, S) lands in a neighbouring batch row (callers keep 0 <= token_range < S).
+ *   mm_embed_splice_fwd copies rows bit for bit; an id outside [0, vocab) reads row 0 (see mm_embed_check_ids).  H % vn == 0
+ *     (vn = 8 bf16, 4 fp32) and emb, proj, out 16-byte aligned, else MM_ERR_ALIGN; a src_map without proj is MM_ERR_ARG.
+ *     Every row of out is written exactly once and nothing behind row T - 1.                            */
 int mm_splice_build_map(const int64_t* batch_idx, const int64_t* token_range, int n_mod, int S, int T,
                         int32_t* src_map, void* stream);
 int mm_embed_splice_fwd(int dtype, const void* emb, int64_t vocab, int H, const int64_t* ids, const void* proj,
                         const int32_t* src_map, int T, void* out, void* stream);
 /* token order for the embedding gradient (depends on ids / src_map only, so it is built at forward time): a stable
  * sort of the T tokens by id; tokens overwritten by a modality row or with an id outside [0, vocab) sort last and get no
- * gradient.  order/skey: int32 [order_elems]; key_ws: int32 [T] workspace; sizes from mm_embed_sort_sizes.            */
+ * gradient.  order/skey: int32 [order_elems]; key_ws: int32 [T] workspace; sizes from mm_embed_sort_sizes.
+ * Contract: order[0, T) = the stable sort of the tokens by (key, t), key = id or 0x7fffffff for a token that gets no gradient;
+ * order[T, order_elems) is NOT written (and never read for a token); skey[0, order_elems) = the sorted keys followed by
+ * 0x7fffffff, order_elems = (ceil(T / 32) + 1) * 32.  The same permutation on every launch.                            */
 int mm_embed_sort_sizes(int T, int H, int64_t* order_elems, int64_t* scratch_floats);
 int mm_embed_sort(const int64_t* ids, const int32_t* src_map, int T, int64_t vocab, int32_t* key_ws, int32_t* order,
                   int32_t* skey, void* stream);
 /* backward (autograd of model.py:433-444): dproj[i,:] = dE[pos(i),:]; demb[id,:] (+)= sum of dE[t,:] over the tokens t
  * with ids[t] == id that were NOT overwritten -- summed in fp32 in ascending token order, rounded once, one write per
  * touched row: bitwise reproducible, no atomics.  accumulate = 0 overwrites the touched rows (the caller has zeroed
- * demb), 1 adds to what demb holds (tied lm_head gradient, gradient accumulation).  scratch: fp32 [scratch_floats].   */
+ * demb), 1 adds to what demb holds (tied lm_head gradient, gradient accumulation).  scratch: fp32 [scratch_floats].
+ * Contract: a row of demb that no valid token touches keeps its bits in both modes.  A row's sum takes at most 32 adds inside
+ * a chunk of 32 sorted positions plus one per further chunk its run spans; its value does not depend on what scratch held (two
+ * slots per chunk, each read only after this call wrote it).  dproj[i] is a bit copy of dE[pos(i)] for the source that owns its
+ * position and exactly zero for a lost duplicate or a dropped position; dproj needs batch_idx, token_range and src_map, demb
+ * needs ids, order, skey and scratch (MM_ERR_ARG).  H % vn == 0, dE, demb and scratch 16-byte aligned (MM_ERR_ALIGN).       */
 int mm_embed_splice_bwd(int dtype, const void* dE, int H, const int64_t* ids, const int32_t* src_map, int T,
                         const int64_t* batch_idx, const int64_t* token_range, int n_mod, int S, void* dproj,
                         void* demb, int64_t vocab, const int32_t* order, const int32_t* skey, float* scratch,
                         int accumulate, void* stream);
 
 /* ---- ViT patch embedding glue: HF:clip:138-218 -----------------------------------------------------
- * patchify: pixels f32 [n,3,Himg,Wimg] -> patches [n*P, Kpad] (k = c*ps*ps + py*ps + px, zero padded)     */
+ * patchify: pixels f32 [n,3,Himg,Wimg] -> patches [n*P, Kpad] (k = c*ps*ps + py*ps + px, zero padded)
+ * P = (Himg / ps) * (Wimg / ps), patch (row r, column q) of the grid in row r * (Wimg / ps) + q; each element is the pixel rounded
+ * once to the dtype, columns [3 ps^2, Kpad) are exactly zero, a ragged border (Himg % ps rows, Wimg % ps columns) is dropped.  */
 int mm_patchify(int dtype, const float* pixels, int n, int himg, int wimg, int ps, int kpad, void* patches, void* stream);
-/* x[n,0,:] = cls + pos[0]; x[n,1+p,:] = patch_out[n*P+p,:] + pos[1+p]                                    */
+/* x[n,0,:] = cls + pos[0]; x[n,1+p,:] = patch_out[n*P+p,:] + pos[1+p]: one fp32 add rounded once (no alignment rule)  */
 int mm_vit_embed_fwd(int dtype, const void* patch_out, const void* cls, const void* pos, int n, int P, int D,
                      void* x, void* stream);
-/* dpatch_out = dx[:,1:,:]; dcls (+)= sum_n dx[n,0]; dpos (+)= sum_n dx[n]                                  */
+/* dpatch_out = dx[:,1:,:] (bit copy); dcls (+)= sum_n dx[n,0]; dpos (+)= sum_n dx[n]: the fp32 sum over the images in
+ * index order, + the old value when accumulate, rounded once.  Each of the three outputs may be NULL (skipped); without
+ * accumulate the old contents of dcls / dpos are not read.                                                 */
 int mm_vit_embed_bwd(int dtype, const void* dx, int n, int P, int D, void* dpatch_out, void* dcls, void* dpos,
                      int accumulate, void* stream);
 /* dst[n,P,D] = src[n,1+P,D][:,1:,:] (image_modality.py:133) and its adjoint (zero CLS row)                */
@@ -141,7 +161,12 @@ int mm_vit_embed_bwd(int dtype, const void* dx, int n, int P, int D, void* dpatc
  * mm_bcast_add: y[n,L] = x[n,L] + b[L]  (learned positions added to every image; HF:siglip SiglipVisionEmbeddings)
  * mm_head_pad:  inverse = 0: dst[rows, nheads*dpad] = src[rows, nheads*d] with each head zero-padded to dpad;
  *               inverse = 1: dst[rows, nheads*d] = the first d columns of every head of src[rows, nheads*dpad].
- *               Zero columns change neither q.k nor p.v, so attention on the padded heads is exact.                  */
+ *               Zero columns change neither q.k nor p.v, so attention on the padded heads is exact.
+ * Contract of the movers (bcast_add, head_pad, drop_cls, rows_select): rows are bit copies, mm_bcast_add is one fp32 add rounded
+ * once; widths (L, d, dpad, D, ld_src, ld_dst) % vn == 0 and every pointer 16-byte aligned, else MM_ERR_ALIGN; dpad < d is
+ * MM_ERR_ARG, a dtype other than MM_BF16 / MM_F32 is MM_ERR_UNSUPPORTED for bcast_add and head_pad.  mm_head_pad writes the
+ * whole padded head (zeros in [d, dpad)); its inverse does not read the pad.  mm_rows_select writes dst[r, 0:D) only (columns
+ * [D, ld_dst) stay untouched, ld < D is MM_ERR_ALIGN).  An empty call (n, rows or n_dst == 0) launches nothing.            */
 int mm_bcast_add(int dtype, const void* x, const void* b, int n, int64_t L, void* y, void* stream);
 int mm_head_pad(int dtype, const void* src, int64_t rows, int nheads, int d, int dpad, void* dst, int inverse, void* stream);
 int mm_drop_cls_fwd(int dtype, const void* src, int n, int P, int D, void* dst, void* stream);
@@ -392,10 +417,25 @@ int mm_gate_head(int dtype, const void* x, int n, int HW, int C, const void* fc_
                  void* weights, int64_t* topk_idx, void* stream);
 
 /* ---- optimizer: AdamW (config_alignment.yaml:38-59 -> torch.optim.AdamW semantics) + grad-norm clip ----------------
- * sumsq partial: out[blk] = sum g^2 over a slice; mm_gradnorm_finish: total[0] = sqrt(sum) ; clip coef in total[1]  */
+ * sumsq partial: out[blk] = sum g^2 over a slice; mm_gradnorm_finish: total[0] = sqrt(sum) ; clip coef in total[1]
+ * Contract (tests/test_optim_contract_gpu.py):
+ *   mm_gradnorm_partial writes every partial[0, nblk): 16-byte vector j of g goes to block (j / 256) % nblk, the scalar tail
+ *     [vn (n / vn), n) to block 0, a block without work writes exactly 0 (so does every block for n == 0).  g 16-byte aligned
+ *     (MM_ERR_ALIGN); nblk <= 0, n < 0 or a NULL pointer is MM_ERR_ARG.  The same bits on every launch.
+ *   mm_gradnorm_finish: total[1] = min(1, max_norm / (total[0] + 1e-6f)) for max_norm > 0, else exactly 1.  All-zero gradients
+ *     give total = {0, 1}.                                                                                              */
 int mm_gradnorm_partial(int dtype, const void* g, int64_t n, float* partial, int nblk, void* stream);
 int mm_gradnorm_finish(const float* partial, int nblk, float max_norm, float* total, void* stream);
-/* p (param dtype), g (param dtype), master/m/v f32.  clip = device scalar (total+1) or NULL.                          */
+/* p (param dtype), g (param dtype), master/m/v f32.  clip = mm_gradnorm_finish's total (clip[1] is read, clip[0] is not) or
+ * NULL for a coefficient of 1.  One step of torch.optim.AdamW on g * clip[1]: decoupled decay w (1 - lr wd), eps outside the
+ * root, bias corrections bc = 1.0f - powf(beta, (float) step) evaluated in fp32 on the host -- with beta2 = 0.999 that value is
+ * off from the exact one by about 1e-5 relative at steps 2 and 3 (an error of half an ulp of beta^step, amplified by
+ * beta^step / bc = 499), 3e-7 at step 10, nothing at step 1 and from about step 1000; half of it reaches the update.
+ * Contract: master, m, v are updated in place for all n elements (4 per thread, the tail [4 (n / 4), n) by block 0); p is
+ * written, never read: p = RNE_bf16(master) (MM_BF16) or the master's bits (MM_F32).  g = m = v = 0 leaves m, v at 0 and gives
+ * master (1 - lr wd).  All five pointers 16-byte aligned (MM_ERR_ALIGN); step < 1, n < 0 or a NULL pointer is MM_ERR_ARG; n == 0
+ * returns MM_OK and touches nothing.  MM_ADAMW_NT=0 (read once per process) selects plain instead of non-temporal accesses
+ * for bf16; mm_set_option "adamw_blocks" caps the grid (0 = default), the kernel then strides.                             */
 int mm_adamw_step(int dtype, void* p, const void* g, float* master, float* m, float* v, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, const float* clip, void* stream);
 
@@ -419,7 +459,13 @@ int mm_comm_finalize(void* comm);
 /* AdamW with the fp32 master weight held as (bf16 parameter, int16 remainder): master_bits = (p_bits << 16) + lo, p = RNE(master).
  * Same update as mm_adamw_step (MM_BF16), 26 B instead of 28 B of HBM traffic per parameter and no separate fp32 copy; one
  * remainder value in 2^17 (+0x8000, a round-to-even tie) is stored as 0x7FFF, i.e. the master moves by one fp32 ulp there.
- * mm_master_split / mm_master_join convert between that form and an fp32 master (optimiser checkpoints keep fp32).              */
+ * mm_master_split / mm_master_join convert between that form and an fp32 master (optimiser checkpoints keep fp32).
+ * Contract: d = master_bits - (p_bits << 16) lies in [-0x8000, 0x8000]; lo = min(d, 0x7FFF).  d = +0x8000 happens exactly when
+ * the low half is 0x8000 under an even upper half (the tie that rounds down); join(split(w)) is then one fp32 ulp below w, and
+ * equals w bit for bit everywhere else -- denormals, a mantissa carry into the exponent, values that round to bf16 infinity
+ * and infinity itself included (a NaN may come back quieted).  join is plain integer arithmetic on any (p, lo).
+ * mm_adamw_step_split: m, v 16-byte aligned, p, g and lo 8-byte aligned (MM_ERR_ALIGN); otherwise mm_adamw_step's rules.
+ * mm_master_split / mm_master_join: n < 0 or, for n > 0, a NULL pointer is MM_ERR_ARG; no alignment rule.                       */
 int mm_adamw_step_split(void* p_bf16, const void* g_bf16, void* lo_i16, float* m, float* v, int64_t n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, int step, const float* clip, void* stream);
 int mm_master_split(const float* master, int64_t n, void* p_bf16, void* lo_i16, void* stream);

@@ -168,7 +168,7 @@ def rc(name, *args):
 
 
 # options without a getter: their library defaults
-_DEFAULTS = {"gemm_w4_big": 4, "gemm_w4_stream": 1, "gemm_small": -1, "gemm_epi_pipe": 1}
+_DEFAULTS = {"gemm_w4_big": 4, "gemm_w4_stream": 1, "gemm_small": -1, "gemm_epi_pipe": 1, "adamw_blocks": 0}
 
 
 @contextlib.contextmanager

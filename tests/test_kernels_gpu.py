@@ -10,8 +10,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import embed_check as EC
 from tests import gemm_check as GC
+from tests import optim_check as OC
 from tests import rowwise_check as RC
+from tests.kernel_check import check_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -729,6 +732,10 @@ def test_embed_splice(K, dtype):
     assert torch.equal(out.float().cpu(), ref.reshape(B * S, H))
     out2 = K.embed_splice_fwd(emb.cuda(), ids.cuda().reshape(-1), None, None)
     assert torch.equal(out2.float().cpu(), e.reshape(B * S, H))
+    idc = ids.cuda().reshape(-1)
+    assert torch.equal(m, EC.build_map_reference(bi.cuda(), tr.cuda(), S, B * S))
+    check_bits("embed_splice_fwd", out, EC.splice_fwd_reference(emb.cuda(), idc, proj.cuda(), m))
+    check_bits("embed_splice_fwd without a map", out2, EC.splice_fwd_reference(emb.cuda(), idc, None, None))
     # backward
     dE = rnd((B * S, H), dtype, 64)
     ef = emb.float().clone().requires_grad_(True)
@@ -743,11 +750,14 @@ def test_embed_splice(K, dtype):
     assert torch.equal(dproj.float().cpu(), pf.grad)
     # fp32 sums rounded once: fp32 path exact to fp32 rounding, bf16 path within one bf16 rounding of the fp32 sum
     assert rel(demb.float(), ef.grad) < (1e-6 if dtype == torch.float32 else 4e-3)
+    check_bits("dproj", dproj, EC.dproj_reference(dE.cuda(), bi.cuda(), tr.cuda(), S, m))
+    EC.check_demb("embed_splice_bwd", dE.cuda(), idc, m, V, torch.zeros_like(demb), 0, demb)
     # accumulate onto an existing gradient (tied lm_head wgrad / gradient accumulation)
     base = rnd((V, H), dtype, 65)
     demb2 = base.clone().cuda()
     K.embed_splice_bwd(dE.cuda(), ids.cuda().reshape(-1), m, bi.cuda(), tr.cuda(), S, None, demb2, order, skey, accumulate=True)
     assert rel(demb2.float(), base.float() + ef.grad) < (1e-6 if dtype == torch.float32 else 4e-3)
+    EC.check_demb("embed_splice_bwd accumulate", dE.cuda(), idc, m, V, base.cuda(), 1, demb2)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -783,6 +793,9 @@ def test_embed_grad_heavy_repeats_fp32_and_deterministic(K, dtype, T, V, H, spli
     got = outs[0].double().cpu()
     err = float((got - ref).norm() / ref.norm())
     assert err < (1e-6 if dtype == torch.float32 else 4e-3), err
+    EC.check_demb(f"embed grad T={T} V={V} H={H}", dEc, idc, m, V, torch.zeros_like(outs[0]), 0, outs[0])
+    o_ref, k_ref = EC.sort_reference(idc, m, V)
+    assert torch.equal(order[:T], o_ref) and torch.equal(skey, k_ref)
     # the order really is the stable sort by (id, token)
     o = order[:T].cpu().long()
     k = torch.where(keep, ids, torch.full_like(ids, 2 ** 31 - 1))
@@ -798,6 +811,7 @@ def test_vit_glue(K, dtype):
     ref = F.conv2d(pix.to(dtype).float(), w.float(), stride=ps).flatten(2).transpose(1, 2)   # [n,P,Dv]
     kpad = (3 * ps * ps + 63) // 64 * 64
     patches = K.patchify(pix.cuda(), ps, kpad, dtype)
+    check_bits("patchify", patches, EC.patchify_reference(pix.cuda(), ps, kpad, dtype))
     wp = torch.zeros(Dv, kpad, dtype=dtype)
     wp[:, : 3 * ps * ps] = w.reshape(Dv, -1)
     po = K.linear_fwd(patches, wp.cuda())
@@ -806,6 +820,7 @@ def test_vit_glue(K, dtype):
     x = K.vit_embed_fwd(po, cls.cuda(), pos.cuda(), n, P)
     refx = torch.cat([cls.float().expand(n, 1, Dv), po.float().cpu().view(n, P, Dv)], 1) + pos.float()
     assert rel(x.float(), refx) < TOL[dtype]
+    check_bits("vit_embed_fwd", x, EC.vit_embed_fwd_reference(po.view(n, P, Dv), cls.cuda(), pos.cuda()))
     d = K.drop_cls_fwd(x)
     assert torch.equal(d.cpu(), x[:, 1:].cpu())
     db = K.drop_cls_bwd(d)
@@ -817,6 +832,9 @@ def test_vit_glue(K, dtype):
     assert torch.equal(dpatch.view(n, P, Dv).cpu(), dx[:, 1:].cpu())
     assert rel(dcls.float(), dx.float().cpu()[:, 0].sum(0)) < TOL[dtype]
     assert rel(dpos.float(), dx.float().cpu().sum(0)) < TOL[dtype]
+    _, dcls_ref, dpos_ref = EC.vit_embed_bwd_reference(dx, None, None, False)
+    check_bits("vit_embed_bwd dcls", dcls, dcls_ref)
+    check_bits("vit_embed_bwd dpos", dpos, dpos_ref)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -832,13 +850,18 @@ def test_adamw_and_gradnorm(K, dtype):
     total = K.gradnorm([g.cuda()], 1.0)
     nrm = float(g.float().norm())
     assert abs(float(total[0]) - nrm) < 1e-3 * nrm
+    OC.check_gradnorm("gradnorm", g.cuda(), 1024, 1.0, total)
+    hyper = OC.Hyper(1e-2, 0.9, 0.95, 1e-8, 0.01)
     coef = min(1.0, 1.0 / (nrm + 1e-6))
     ref_p = torch.nn.Parameter(p.float().clone())
     opt = torch.optim.AdamW([ref_p], lr=1e-2, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.01)
     for step in (1, 2, 3):
         ref_p.grad = g.float() * coef
         opt.step()
+        before = {"g": g.cuda(), "m": m.clone(), "v": v.clone(), "w": master.clone()}
         K.adamw_step(pg, g.cuda(), master, m, v, 1e-2, 0.9, 0.95, 1e-8, 0.01, step, clip=total)
+        OC.check_adamw(f"adamw_step step {step}", before, {"m": m, "v": v, "master": master, "p": pg}, hyper, step, float(total[1]),
+                       "bf16" if dtype == torch.bfloat16 else "f32")
     assert rel(master, ref_p.detach()) < 1e-5
     assert rel(pg.float(), ref_p.detach()) < (1e-5 if dtype == torch.float32 else 5e-3)
 
@@ -858,8 +881,11 @@ def test_adamw_split_master_equals_fp32_master(K):
         g = (torch.randn(n, generator=g0) * (0.01 * step)).to(torch.bfloat16).cuda()
         total = K.gradnorm([g], 1.0)
         K.adamw_step(p_a, g, master, m_a, v_a, 3e-3, 0.9, 0.95, 1e-8, 0.01, step, clip=total)
+        before = {"g": g, "m": m_b.clone(), "v": v_b.clone(), "w": OC.join_reference(p_b, lo)}
         K.adamw_step_split(p_b, g, lo, m_b, v_b, 3e-3, 0.9, 0.95, 1e-8, 0.01, step, clip=total)
         torch.cuda.synchronize()
+        OC.check_adamw(f"adamw_step_split step {step}", before, {"m": m_b, "v": v_b, "p": p_b, "lo": lo},
+                       OC.Hyper(3e-3, 0.9, 0.95, 1e-8, 0.01), step, float(total[1]), "split")
         assert torch.equal(p_a, p_b), step
         joined = K.master_join(p_b, lo)
         ulp = (joined.view(torch.int32).long() - master.view(torch.int32).long()).abs()
@@ -871,6 +897,9 @@ def test_adamw_split_master_equals_fp32_master(K):
     assert torch.equal(p2, p_b) and torch.equal(lo2, lo)
     K.master_split(master, p2, lo2)
     assert torch.equal(p2, p_a)                                                     # p = round-to-nearest-even(master)
+    p_ref, lo_ref = OC.split_reference(master)
+    assert torch.equal(p2.view(torch.int16), p_ref.view(torch.int16)) and torch.equal(lo2, lo_ref)
+    check_bits("master_join", K.master_join(p2, lo2), OC.join_reference(p_ref, lo_ref))
 
 
 @pytest.mark.parametrize("M,I,Kd", [(512, 256, 128), (300, 128, 64), (1024, 384, 320), (2048, 14336 // 8, 512)])
