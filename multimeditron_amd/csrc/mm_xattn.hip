@@ -14,7 +14,7 @@
 // backward, deterministic (no atomics): kernel 1 per query tile recomputes P, forms dS and dQ (same shape as the forward) and
 // leaves P_drop^T and dS^T [key][q] in a workspace; kernel 2 per 64 keys sums dV = P_drop^T dO and dK = dS^T Q over the queries.
 // Dropout: Philox4x32-10 keyed by (seed, offset); the keep bit of probability (row, key) is component (key & 3) of call
-// row * KP/4 + key/4 (KP = keys rounded up to 16), so forward, backward, the fp32 kernels and mm_dropout_mask agree bit for bit.
+// row * KP/4 + key/4 (KP = keys rounded up to 32), so forward, backward, the fp32 kernels and mm_dropout_mask agree bit for bit.
 //
 // fp32 (parity path): plain wave-per-query kernels, exact fp32 chains, same dropout stream, no atomics either.
 #include <stdlib.h>

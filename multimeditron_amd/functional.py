@@ -475,7 +475,7 @@ def next_dropout_stream():
 class CrossAttentionFn(torch.autograd.Function):
     """Non-causal attention of Nq queries over Nkv keys/values with separate inputs (model/attention.py:79-96 between the
     projections): q2d [n*Nq, h*d], kv2d [n*Nkv, 2*h*d] (k | v, one fused projection output) -> [n*Nq, h*d].
-    drop_p > 0: dropout on the attention probabilities (attention.py:40,91).  Up to 512 keys the one-pass kernel mm_xattn_* runs
+    drop_p > 0: dropout on the attention probabilities (attention.py:40,91).  Up to 1024 keys the one-pass kernel mm_xattn_* runs
     (any head width up to 512: the reference's recipes use 96 and 512); beyond that the flash kernels (d in {64, 128}, no dropout)."""
 
     @staticmethod
@@ -492,7 +492,7 @@ class CrossAttentionFn(torch.autograd.Function):
             out, lse = K.xattn_fwd(q, k, v, scale, drop_p, seed, off)
         else:
             if drop_p > 0.0:
-                raise NotImplementedError(f"attention dropout over {Nkv} keys: mm_xattn_* holds a query's scores in registers (<= 512 keys)")
+                raise NotImplementedError(f"attention dropout over {Nkv} keys: mm_xattn_* holds a query's scores in registers (<= 1024 keys)")
             out, lse = K.attn_fwd(q, k, v, None, False, scale)
         ctx.dims = (n, Nq, Nkv, heads, d, scale, drop_p, seed, off, small)
         ctx.save_for_backward(q2d, kv2d, out, lse)

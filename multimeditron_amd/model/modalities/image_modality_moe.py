@@ -16,7 +16,7 @@ Parameter names equal the reference's (`experts.{e}.*`, `cross_attn.{q,k,v}_proj
 `moe_meditron_clip_pep` (per-expert projection) gives every expert its own MLP projector (`projectors.{e}.projection.{0,2,4}`)
 and fuses in the LLM's embedding space; its cross-attention therefore has `hidden_size / cross_attn_heads`-wide heads: 512 in the
 shipped recipe (cookbook/sft/moe/*/attn/pep: 4096 / 8), 96 in the shared-projector one (768 / 8).  Neither is a flash-kernel
-width; both run on the one-pass cross-attention kernel `mm_xattn_*` (csrc/mm_xattn.hip: up to 512 keys, head widths up to 512).
+width; both run on the one-pass cross-attention kernel `mm_xattn_*` (csrc/mm_xattn.hip: up to 1024 keys, head widths up to 512).
 
 The gate (reference moe/gating.py:37-89, a torchvision ResNet-50 with an E-way fc) is `modalities/gating.py`: the same key set
 on libmmhip's NHWC convolution kernels, built from `config.gating_path` when that is a directory holding a `config.json`

@@ -1,5 +1,5 @@
 """What every kernel checker shares: the acceptance rule, bitwise equality, the ratio log, guarded storages and the C-ABI shims.
-The checkers (attn_check, gemm_check, rowwise_check, conv_check) build the references and the error scales; nothing here knows a
+The checkers (attn_check, xattn_check, gemm_check, rowwise_check, conv_check) build the references and the error scales; nothing here knows a
 kernel family.
 
 The rule (`check_bound`).  A reference is computed in float64 from the SAME storage-rounded operands the kernel reads, together
@@ -115,7 +115,8 @@ def sentinel_fill(t):
 class Guarded:
     """One storage of `numel` elements between guard bands of `pad` elements, all filled with the sentinel NaN.  `view`
     places a strided view at an element offset into the storage (as the operand it mirrors sits in its own storage);
-    `verify` asserts that every element outside the views is bit-unchanged and that no sentinel is left inside them."""
+    `verify` asserts that every element outside the views is bit-unchanged and that no sentinel is left inside them
+    (require_written=False: only the former, for a scratch buffer whose interior a kernel may leave partly unwritten)."""
 
     def __init__(self, numel, dtype, device, pad=512):
         self.dtype, self.pad = dtype, pad
@@ -129,7 +130,7 @@ class Guarded:
         self.views.append(v)
         return v
 
-    def verify(self, name):
+    def verify(self, name, require_written=True):
         iv = _ints(self.buf)
         s = SENTINEL[self.dtype]
         guard_bad = (~self.covered) & (iv != s)
@@ -138,15 +139,16 @@ class Guarded:
             raise AssertionError(f"{name}: write outside the output at storage element {i - self.pad} "
                                  f"(storage [0, {self.buf.numel() - 2 * self.pad}), {int(guard_bad.sum())} elements)")
         left = self.covered & (iv == s)
-        if bool(left.any()):
+        if require_written and bool(left.any()):
             i = int(left.nonzero()[0])
             raise AssertionError(f"{name}: {int(left.sum())} output elements never written (first at storage element "
                                  f"{i - self.pad})")
 
 
 def verify_guards(guards):
-    for name, g in guards:
-        g.verify(name)
+    """guards: (name, Guarded) or (name, Guarded, require_written) entries"""
+    for name, g, *opt in guards:
+        g.verify(name, *opt)
 
 
 # ---- the C ABI: argument shims, raw return codes, option switches --------------------------------------------------------------

@@ -112,6 +112,11 @@ def test_guard_bands_and_unwritten_elements(dtype):
     KC.sentinel_fill(g.buf[64 + 3 + 20:64 + 3 + 21])
     with pytest.raises(AssertionError, match="1 output elements never written"):
         g.verify("y")
+    g.verify("y", require_written=False)                        # a scratch buffer: only the bands are held
+    KC.verify_guards([("y", g, False)])
+    g.buf[5] = 0.0
+    with pytest.raises(AssertionError, match="write outside the output"):
+        KC.verify_guards([("y", g, False)])
 
 
 def test_ratio_log_keeps_the_maximum_and_dumps_at_exit(tmp_path, monkeypatch):

@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+from tests.xattn_check import dropout_keep, keep_mask
+
 pytestmark = pytest.mark.gpu
 
 
@@ -78,6 +80,8 @@ def test_xattn_matches_float64_restatement(shape, dtype, p):
                 dkv2d[:, C:].view(n, Nkv, H, D))
     torch.cuda.synchronize()
     mask = _mask(K, seed, off, n, H, Nq, Nkv, p) if p > 0 else None
+    if p > 0:       # the mask the kernels list is the documented one (tests/xattn_check.py computes it on the CPU)
+        assert torch.equal(mask.bool().cpu(), keep_mask(seed, off, n, H, Nq, Nkv, p))
     o_ref, dq_ref, dk_ref, dv_ref = _ref(q, k, v, do, scale, mask, p)
     tol = 2e-2 if dtype == torch.bfloat16 else 1e-4
     assert torch.isfinite(dq2d.float()).all() and torch.isfinite(dkv2d.float()).all()          # every gradient element was written
@@ -123,6 +127,7 @@ def test_dropout_keep_rate_and_adjoint():
         x = torch.randn(1000, 77, device="cuda").to(dtype)       # 77000 elements: not a multiple of 4
         y = K.dropout(x, p, 7, 3)
         keep = K.dropout_mask(7, 3, x.numel(), p).view_as(x).bool()
+        assert torch.equal(keep.cpu().view(-1), dropout_keep(7, 3, x.numel(), p))
         want = torch.where(keep, (x.float() / (1 - p)), torch.zeros((), device="cuda")).to(dtype)
         assert torch.equal(y, want)
 
