@@ -416,6 +416,67 @@ int mm_maxpool2d_nhwc(int dtype, const void* x, int n, int H, int W, int C, void
 int mm_gate_head(int dtype, const void* x, int n, int HW, int C, const void* fc_w, const void* fc_b, int E, int top_k, void* logits,
                  void* weights, int64_t* topk_idx, void* stream);
 
+/* ---- MoE image modality: pieces of TRAINING the gating network (reference image_modality_moe.py:233-241 unfreezes it in FULL
+ * mode): BatchNorm with batch statistics, forward and backward, the max-pool's backward, the convolutions' data and weight gradients
+ * and the gradient of the fusion with respect to the gate weights.  T as above; every
+ * entry point checks all its arguments before any launch, uses no atomics and gives the same bits on every launch.
+ * mm_bn_train_fwd: z T [M, C] is the raw convolution output (mm_conv2d_nhwc_fwd with scale 1, shift 0, no residual, no ReLU: one
+ *   rounding to T), M = n*Ho*Wo.  From the STORED z, in fp32: mean[C], the biased var[C] (never formed as E[z^2] - mean^2: each
+ *   workgroup owns 512 rows of a 64- (bf16) / 32- (f32) channel slab and writes its own mean and its sum of squared deviations from
+ *   THAT mean; the slabs are then merged in row order with the pairwise update of Chan, Golub & LeVeque 1979), invstd =
+ *   1 / sqrt(var + eps); y = T(act(fma((z - mean) * invstd, gamma, beta) (+ residual))), fp32 inside, ONE rounding; act = ReLU
+ *   (relu != 0) or nothing.  Summation depth: no column sum passes through more than 21 + ceil(M / 512) additions (16 in a thread,
+ *   5 levels of a tree over the workgroup's 32 row groups, then the workgroups in order); tests/conv_train_check.py builds its error
+ *   scale on that figure.  mean / invstd (fp32) are written for the backward.  gamma, beta, residual, y are T.  Running statistics
+ *   (all three pointers may be NULL together: then none is touched) follow torch.nn.BatchNorm2d: running = (1 - momentum) * running +
+ *   momentum * batch in fp32 from the stored T value, stored back in T, with the UNBIASED variance M2 / (M - 1);
+ *   num_batches_tracked[0] += 1 (int64).  M < 2 is MM_ERR_ARG.  C % 64 == 0 and z, y, residual, gamma, beta, running_*, ws 16-byte
+ *   aligned (MM_ERR_ALIGN otherwise); ws of mm_bn_train_ws_bytes(M, C) bytes (MM_ERR_ARG when smaller).
+ * mm_bn_train_bwd: with g = dy * [y > 0] (relu != 0; y is the forward's stored output) or g = dy, and xhat = (z - mean) * invstd
+ *   in fp32: dbeta = T(sum g), dgamma = T(sum g * xhat) (fp32 column sums of the depth above), dz = T(gamma * invstd * (g -
+ *   sum g / M - xhat * sum(g xhat) / M)), and, where dres is not NULL (the unit had a residual input), dres = T(g): the bits of dy
+ *   or zero.  Two column reductions in one pass, a merge, one elementwise pass.  Same alignment rules and workspace size.
+ * mm_maxpool2d_nhwc_bwd: the backward of mm_maxpool2d_nhwc in gather form.  dx[n, h, w, c] = T(fp32 sum, in (ho, wo) row-major
+ *   order, of dy[n, ho, wo, c] over the at most four windows whose maximum (n, h, w, c) is).  The maximum of a window is its FIRST
+ *   maximal element in row-major window order (torch's CPU rule; post-ReLU zeros tie all the time); padding taps never win; an
+ *   element that wins no window gets exactly +0.  x is the forward's input.  Alignment as the forward.
+ * mm_expert_fuse_gate_bwd: d(loss) / d(gate) of mm_expert_fuse.  dgate fp32 [n, E]; experts not listed in idx get exactly 0.
+ *   d[j] = sum over L of float(dout[.]) * float(X[idx[j], n, .]) (exact products, fp32 accumulation in a fixed order; dout is
+ *   [n, L] in mode 0 and [n, J, L] in mode 1).  mode 0: dgate[n, idx[j]] += d[j] in the order of j.  mode 1: with w' = the softmax
+ *   over the J listed weights as the forward computes it, dgate[n, idx[j]] += w'[j] * (d[j] - sum_k w'[k] d[k]).  One pass over X
+ *   and dout: L is split over workgroups (fp32 partials in ws, merged in order).  ws of mm_expert_fuse_gate_bwd_ws_bytes bytes;
+ *   argument rules as mm_expert_fuse, dgate and ws 16-byte aligned.
+ * mm_conv2d_nhwc_dgrad: dx[n, h, w, cin] = T(sum over taps (r, s) and couts of dz[n, ho, wo, cout] * w[cout, r, s, cin] (+ addend[n,
+ *   h, w, cin])), the taps being those with ho * stride - pad + r == h and wo * stride - pad + s == w inside the output image.
+ *   H, W are the INPUT extents (Ho, Wo follow as in the forward); wp is the filter packed [Cin, R, S, Cout].  Exact products,
+ *   fp32 accumulation (any order), the optional addend (the join of a residual branch with its identity path) added in fp32, ONE
+ *   rounding.  An input pixel that no output reads gets exactly +0 (or the addend).  MM_BF16: the gather form of the forward's
+ *   implicit GEMM on v_mfma_f32_32x32x16_bf16; a tap whose output coordinate is fractional or outside the image is a zero fragment
+ *   and is never loaded.  R in {1, 3} (7 is MM_ERR_UNSUPPORTED: the stem needs no data gradient), stride in {1, 2}; Cin % 64 == 0,
+ *   Cout % 8 == 0, all pointers 16-byte aligned (MM_ERR_ALIGN).
+ * mm_conv2d_nhwc_wgrad: dw[cout, r, s, cin] (packed [Cout, R, S, Cin] as the forward's filter) = T(sum over output pixels m of
+ *   dz[m, cout] * x[m @ (r, s), cin]), out-of-image taps as zeros.  The pixels are split into runs of 1024 (one workgroup row each,
+ *   fp32 partials [splits, Cout, K] in ws), the runs are then added in a fixed order (mm_reduce_partials) and rounded ONCE.  MM_BF16:
+ *   both MFMA operands are read transposed from row-staged LDS tiles (ds_read_b64_tr_b16).  R in {1, 3, 7}, stride in {1, 2};
+ *   Cin % 8 == 0 (zero input channels, the stem's 3 -> 8 padding, give exactly 0), Cout % 64 == 0; ws of
+ *   mm_conv2d_nhwc_wgrad_ws_bytes bytes = 4 * Cout * K * ceil(n Ho Wo / 1024) (MM_ERR_ARG when smaller).                          */
+int mm_conv2d_nhwc_dgrad(int dtype, const void* dz, int n, int H, int W, int Cin, const void* wp, int Cout, int R, int stride, int pad,
+                         const void* addend, void* dx, void* stream);
+int mm_conv2d_nhwc_wgrad_ws_bytes(int n, int H, int W, int Cin, int Cout, int R, int stride, int pad, int64_t* bytes);
+int mm_conv2d_nhwc_wgrad(int dtype, const void* dz, const void* x, int n, int H, int W, int Cin, int Cout, int R, int stride, int pad,
+                         void* dw, void* ws, int64_t ws_bytes, void* stream);
+int mm_bn_train_ws_bytes(int M, int C, int64_t* bytes);
+int mm_bn_train_fwd(int dtype, const void* z, int M, int C, const void* gamma, const void* beta, const void* residual, int relu,
+                    float eps, float momentum, void* y, float* mean, float* invstd, void* running_mean, void* running_var,
+                    int64_t* num_batches_tracked, void* ws, int64_t ws_bytes, void* stream);
+int mm_bn_train_bwd(int dtype, const void* dy, const void* y, const void* z, int M, int C, const float* mean, const float* invstd,
+                    const void* gamma, int relu, void* dz, void* dres, void* dgamma, void* dbeta, void* ws, int64_t ws_bytes,
+                    void* stream);
+int mm_maxpool2d_nhwc_bwd(int dtype, const void* x, const void* dy, int n, int H, int W, int C, void* dx, void* stream);
+int mm_expert_fuse_gate_bwd_ws_bytes(int dtype, int J, int n, int64_t L, int64_t* bytes);
+int mm_expert_fuse_gate_bwd(int dtype, int mode, const void* X, const void* dout, const float* gate, const int* idx, int J, int E,
+                            int n, int64_t L, float* dgate, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- optimizer: AdamW (config_alignment.yaml:38-59 -> torch.optim.AdamW semantics) + grad-norm clip ----------------
  * sumsq partial: out[blk] = sum g^2 over a slice; mm_gradnorm_finish: total[0] = sqrt(sum) ; clip coef in total[1]
  * Contract (tests/test_optim_contract_gpu.py):

@@ -724,6 +724,78 @@ __global__ void expert_fuse_kernel(const T* X, const float* gate, MoeIdx idx, in
   }
 }
 
+// d(loss) / d(gate) of the fusion: d[j] = dout . X[idx[j]] per image.  Workgroup (split, image) owns a run of 16-byte vectors of L and
+// writes its J partial dot products (lanes, then waves, summed in a fixed order); one thread per image then adds the splits in order,
+// applies the softmax's backward (mode 1) and writes the whole dgate row.
+constexpr int MOE_GB_VECS = 256;       // vectors of L per workgroup at least
+constexpr int MOE_GB_MAXSPLIT = 64;
+
+static inline int moe_gb_nsplit(int64_t per) {
+  const int64_t s = (per + MOE_GB_VECS - 1) / MOE_GB_VECS;
+  return (int)(s < 1 ? 1 : s > MOE_GB_MAXSPLIT ? MOE_GB_MAXSPLIT : s);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void expert_fuse_gate_bwd_kernel(const T* __restrict__ X, const T* __restrict__ dout, MoeIdx idx, int J,
+                                                                   int n, int64_t L, int mode, float* __restrict__ partial) {
+  constexpr int VN = Vec16<T>::N;
+  __shared__ float red[4][MOE_MAXJ];
+  const int b = blockIdx.y, nsplit = gridDim.x;
+  const int64_t per = L / VN, chunk = (per + nsplit - 1) / nsplit;
+  const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < per ? lo + chunk : per;
+  float d[MOE_MAXJ];
+#pragma unroll
+  for (int j = 0; j < MOE_MAXJ; ++j) d[j] = 0.f;
+  for (int64_t v = lo + threadIdx.x; v < hi; v += 256) {
+    Vec16<T> g;
+    if (mode == 0) g = *(const Vec16<T>*)(dout + (int64_t)b * L + v * VN);
+#pragma unroll
+    for (int j = 0; j < MOE_MAXJ; ++j) {
+      if (j < J) {
+        if (mode == 1) g = *(const Vec16<T>*)(dout + ((int64_t)b * J + j) * L + v * VN);
+        const Vec16<T> x = *(const Vec16<T>*)(X + ((int64_t)idx.v[j] * n + b) * L + v * VN);
+#pragma unroll
+        for (int k = 0; k < VN; ++k) d[j] = __builtin_fmaf(g.get(k), x.get(k), d[j]);
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < MOE_MAXJ; ++j) {
+    if (j < J) {
+      const float s = wave_sum(d[j]);
+      if (lane == 0) red[wave][j] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < J)
+    partial[((int64_t)b * nsplit + blockIdx.x) * J + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+__global__ void expert_fuse_gate_bwd_finish_kernel(const float* __restrict__ partial, const float* __restrict__ gate, MoeIdx idx, int J,
+                                                   int E, int n, int nsplit, int mode, float* __restrict__ dgate) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  float d[MOE_MAXJ], w[MOE_MAXJ];
+  float mx = -INFINITY, sm = 0.f, dot = 0.f;
+  for (int j = 0; j < J; ++j) {
+    float s = 0.f;
+    for (int p = 0; p < nsplit; ++p) s += partial[((int64_t)b * nsplit + p) * J + j];
+    d[j] = s;
+    w[j] = gate[(int64_t)b * E + idx.v[j]];
+    mx = fmaxf(mx, w[j]);
+  }
+  if (mode == 1) {                                                  // the forward's softmax over the listed weights, then its backward
+    for (int j = 0; j < J; ++j) { w[j] = expf(w[j] - mx); sm += w[j]; }
+    for (int j = 0; j < J; ++j) { w[j] /= sm; dot += w[j] * d[j]; }
+    for (int j = 0; j < J; ++j) d[j] = w[j] * (d[j] - dot);
+  }
+  float* row = dgate + (int64_t)b * E;
+  for (int e = 0; e < E; ++e) row[e] = 0.f;
+  for (int j = 0; j < J; ++j) row[idx.v[j]] += d[j];
+}
+
 // ---------------------------------------------------------------- cast
 template <typename S, typename D>
 __global__ void cast_kernel(const S* s, D* d, int64_t n) {
@@ -1076,6 +1148,45 @@ extern "C" int mm_expert_fuse(int dtype, int backward, int mode, const void* X, 
   } else {
     return MM_ERR_UNSUPPORTED;
   }
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+extern "C" int mm_expert_fuse_gate_bwd_ws_bytes(int dtype, int J, int n, int64_t L, int64_t* bytes) {
+  if (!bytes || J <= 0 || J > MOE_MAXJ || n < 0 || L <= 0) return MM_ERR_ARG;
+  if (dtype != MM_BF16 && dtype != MM_F32) return MM_ERR_UNSUPPORTED;
+  const int vn = dtype == MM_BF16 ? 8 : 4;
+  if (L % vn) return MM_ERR_ALIGN;
+  *bytes = ((int64_t)(n > 0 ? n : 1) * moe_gb_nsplit(L / vn) * J * 4 + 15) / 16 * 16;
+  return MM_OK;
+}
+
+extern "C" int mm_expert_fuse_gate_bwd(int dtype, int mode, const void* X, const void* dout, const float* gate, const int* idx, int J,
+                                       int E, int n, int64_t L, float* dgate, void* ws, int64_t ws_bytes, void* stream) {
+  if (!X || !dout || !gate || !idx || !dgate || !ws || J <= 0 || J > MOE_MAXJ || E <= 0 || n < 0 || n > 65535 || L <= 0 || mode < 0 ||
+      mode > 1)
+    return MM_ERR_ARG;
+  if (dtype != MM_BF16 && dtype != MM_F32) return MM_ERR_UNSUPPORTED;
+  const int vn = dtype == MM_BF16 ? 8 : 4;
+  if ((L % vn) || !mm_aligned16(X) || !mm_aligned16(dout) || !mm_aligned16(dgate) || !mm_aligned16(ws)) return MM_ERR_ALIGN;
+  MoeIdx ix{};
+  for (int j = 0; j < J; ++j) {
+    if (idx[j] < 0 || idx[j] >= E) return MM_ERR_ARG;
+    ix.v[j] = idx[j];
+  }
+  const int nsplit = moe_gb_nsplit(L / vn);
+  if (ws_bytes < (int64_t)n * nsplit * J * 4) return MM_ERR_ARG;
+  if (n == 0) return MM_OK;
+  float* partial = (float*)ws;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)nsplit, (unsigned)n), block(256);
+  if (dtype == MM_BF16)
+    hipLaunchKernelGGL(expert_fuse_gate_bwd_kernel<bf16>, grid, block, 0, s, (const bf16*)X, (const bf16*)dout, ix, J, n, L, mode, partial);
+  else
+    hipLaunchKernelGGL(expert_fuse_gate_bwd_kernel<float>, grid, block, 0, s, (const float*)X, (const float*)dout, ix, J, n, L, mode,
+                       partial);
+  hipLaunchKernelGGL(expert_fuse_gate_bwd_finish_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, partial, gate, ix, J, E, n, nsplit,
+                     mode, dgate);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }

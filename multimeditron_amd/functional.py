@@ -538,24 +538,30 @@ def dropout(x, p, training=True):
 
 class ExpertFuseFn(torch.autograd.Function):
     """Gating-weighted fusion of stacked expert features x [E, n, P, C] (image_modality_moe.py:163-205); `gate` [n, E] fp32 is
-    the gating network's output and receives no gradient here (the gate is not part of this build)."""
+    the gating network's output.  It receives a gradient (mm_expert_fuse_gate_bwd, fp32) only when it requires one: the experts'
+    features are kept for the backward in that case alone."""
 
     @staticmethod
     def forward(ctx, x, gate, idx, mode):
         E, n, P, C = x.shape
         ctx.meta = (tuple(idx), mode, E, P, C)
-        ctx.save_for_backward(gate)
-        out = K.expert_fuse(x.reshape(E, n, P * C), gate, idx, mode)
+        xf = x.reshape(E, n, P * C)
+        if gate.requires_grad:
+            ctx.save_for_backward(gate, xf if xf.is_contiguous() else xf.contiguous())
+        else:
+            ctx.save_for_backward(gate)
+        out = K.expert_fuse(xf, gate, idx, mode)
         return out.view(n, P, C) if mode == 0 else out.view(n, len(idx) * P, C)
 
     @staticmethod
     def backward(ctx, dout):
-        (gate,) = ctx.saved_tensors
+        gate, *kept = ctx.saved_tensors
         idx, mode, E, P, C = ctx.meta
         n = dout.shape[0]
         d = dout.contiguous().view(n, P * C) if mode == 0 else dout.contiguous().view(n, len(idx), P * C)
-        dx = K.expert_fuse(d, gate, idx, mode, backward=True, E=E)
-        return dx.view(E, n, P, C), None, None, None
+        dx = K.expert_fuse(d, gate, idx, mode, backward=True, E=E) if ctx.needs_input_grad[0] else None
+        dgate = K.expert_fuse_gate_bwd(kept[0], d, gate, idx, mode) if kept and ctx.needs_input_grad[1] else None
+        return (dx.view(E, n, P, C) if dx is not None else None), dgate, None, None
 
 
 def expert_fuse(x, gate, idx, mode):

@@ -799,3 +799,129 @@ def gate_head(x: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, top_k: in
     topk = torch.empty((n, top_k), dtype=torch.int64, device=x.device)
     call("mm_gate_head", dt(x), _p(x), n, HW, C, _p(fc_w), _p(fc_b), E, top_k, _p(logits), _p(weights), _p(topk), _stream())
     return logits, topk, weights
+
+
+# ------------------------------------------------------------------------------------------------ gating network, training pieces
+def bn_train_ws(M: int, C: int, device) -> torch.Tensor:
+    """the fp32 workspace of bn_train_fwd / bn_train_bwd for z [M, C]."""
+    import ctypes
+    b = ctypes.c_int64(0)
+    call("mm_bn_train_ws_bytes", int(M), int(C), ctypes.byref(b))
+    return torch.empty(b.value // 4, dtype=torch.float32, device=device)
+
+
+def bn_train_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                 eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                 running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, invstd: Optional[torch.Tensor] = None,
+                 ws: Optional[torch.Tensor] = None):
+    """BatchNorm with batch statistics on z [..., C] (rows = every leading dimension): -> (y, mean fp32 [C], invstd fp32 [C]);
+    the running statistics, when given, are updated in place (see mm_bn_train_fwd)."""
+    assert z.is_contiguous() and gamma.dtype == z.dtype and beta.dtype == z.dtype and gamma.is_contiguous() and beta.is_contiguous()
+    C = z.shape[-1]
+    M = z.numel() // C
+    if out is None:
+        out = torch.empty_like(z)
+    if mean is None:
+        mean = torch.empty(C, dtype=torch.float32, device=z.device)
+    if invstd is None:
+        invstd = torch.empty(C, dtype=torch.float32, device=z.device)
+    if ws is None:
+        ws = bn_train_ws(M, C, z.device)
+    if residual is not None:
+        assert residual.shape == z.shape and residual.is_contiguous() and residual.dtype == z.dtype
+    if running_mean is not None:
+        assert running_mean.dtype == z.dtype and running_var.dtype == z.dtype and num_batches_tracked.dtype == torch.int64
+    call("mm_bn_train_fwd", dt(z), _p(z), M, C, _p(gamma), _p(beta), _p(residual), int(relu), float(eps), float(momentum), _p(out),
+         _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel() * 4, _stream())
+    return out, mean, invstd
+
+
+def bn_train_bwd(dy: torch.Tensor, y: Optional[torch.Tensor], z: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                 gamma: torch.Tensor, relu: bool, want_dres: bool = False, dz: Optional[torch.Tensor] = None,
+                 dres: Optional[torch.Tensor] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
+                 ws: Optional[torch.Tensor] = None):
+    """-> (dz, dres or None, dgamma, dbeta) of bn_train_fwd (see mm_bn_train_bwd); y is the forward's output (the ReLU mask)."""
+    assert dy.is_contiguous() and z.is_contiguous() and dy.shape == z.shape and dy.dtype == z.dtype and gamma.dtype == z.dtype
+    assert mean.dtype == torch.float32 and invstd.dtype == torch.float32 and (not relu or (y is not None and y.is_contiguous()))
+    C = z.shape[-1]
+    M = z.numel() // C
+    if dz is None:
+        dz = torch.empty_like(z)
+    if dres is None and want_dres:
+        dres = torch.empty_like(z)
+    if dgamma is None:
+        dgamma = torch.empty(C, dtype=z.dtype, device=z.device)
+    if dbeta is None:
+        dbeta = torch.empty(C, dtype=z.dtype, device=z.device)
+    if ws is None:
+        ws = bn_train_ws(M, C, z.device)
+    call("mm_bn_train_bwd", dt(z), _p(dy), _p(y), _p(z), M, C, _p(mean), _p(invstd), _p(gamma), int(relu), _p(dz), _p(dres), _p(dgamma),
+         _p(dbeta), _p(ws), ws.numel() * 4, _stream())
+    return dz, dres, dgamma, dbeta
+
+
+def maxpool2d_nhwc_bwd(x: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx of the 3x3 / stride 2 / pad 1 max pool: x [n, H, W, C] is the forward's input, dy [n, Ho, Wo, C]."""
+    assert x.dim() == 4 and x.is_contiguous() and dy.is_contiguous() and dy.dtype == x.dtype
+    n, H, W, C = x.shape
+    assert dy.shape == (n, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C)
+    if out is None:
+        out = torch.empty_like(x)
+    call("mm_maxpool2d_nhwc_bwd", dt(x), _p(x), _p(dy), n, H, W, C, _p(out), _stream())
+    return out
+
+
+def expert_fuse_gate_bwd(x, dout, gate, idx, mode, out=None):
+    """d(loss) / d(gate) of expert_fuse: x [E, n, L], dout [n, L] (mode 0) / [n, J, L] (mode 1), gate [n, E] fp32 -> fp32 [n, E]."""
+    import ctypes
+    J = len(idx)
+    E_, n, L = x.shape
+    assert x.is_contiguous() and dout.is_contiguous() and dout.dtype == x.dtype and gate.dtype == torch.float32 and gate.is_contiguous()
+    assert dout.shape == ((n, L) if mode == 0 else (n, J, L)) and gate.shape == (n, E_)
+    ix = (ctypes.c_int * J)(*[int(i) for i in idx])
+    b = ctypes.c_int64(0)
+    call("mm_expert_fuse_gate_bwd_ws_bytes", dt(x), J, n, L, ctypes.byref(b))
+    ws = torch.empty(b.value // 4, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((n, E_), dtype=torch.float32, device=x.device)
+    call("mm_expert_fuse_gate_bwd", dt(x), int(mode), _p(x), _p(dout), _p(gate), ix, J, E_, n, L, _p(out), _p(ws), b.value, _stream())
+    return out
+
+
+def conv2d_nhwc_dgrad(dz: torch.Tensor, wp: torch.Tensor, H: int, W: int, stride: int, pad: int, addend: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx [n, H, W, Cin] of conv2d_nhwc from dz [n, Ho, Wo, Cout] and the filter packed [Cin, R, R, Cout] (+ addend, in fp32)."""
+    assert dz.dim() == 4 and wp.dim() == 4 and dz.is_contiguous() and wp.is_contiguous() and wp.dtype == dz.dtype
+    n, Ho, Wo, Cout = dz.shape
+    Cin, R = wp.shape[0], wp.shape[1]
+    assert wp.shape[2] == R and wp.shape[3] == Cout
+    assert (Ho, Wo) == (conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad))
+    if out is None:
+        out = torch.empty((n, H, W, Cin), dtype=dz.dtype, device=dz.device)
+    if addend is not None:
+        assert addend.shape == out.shape and addend.is_contiguous() and addend.dtype == dz.dtype
+    call("mm_conv2d_nhwc_dgrad", dt(dz), _p(dz), n, H, W, Cin, _p(wp), Cout, R, stride, pad, _p(addend), _p(out), _stream())
+    return out
+
+
+def conv2d_nhwc_wgrad_ws_bytes(n: int, H: int, W: int, Cin: int, Cout: int, R: int, stride: int, pad: int) -> int:
+    import ctypes
+    b = ctypes.c_int64(0)
+    call("mm_conv2d_nhwc_wgrad_ws_bytes", n, H, W, Cin, Cout, R, stride, pad, ctypes.byref(b))
+    return b.value
+
+
+def conv2d_nhwc_wgrad(dz: torch.Tensor, x: torch.Tensor, R: int, stride: int, pad: int, out: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dw [Cout, R, R, Cin] (the forward's packed order) of conv2d_nhwc from dz [n, Ho, Wo, Cout] and the input x [n, H, W, Cin]."""
+    assert dz.dim() == 4 and x.dim() == 4 and dz.is_contiguous() and x.is_contiguous() and x.dtype == dz.dtype
+    n, H, W, Cin = x.shape
+    Cout = dz.shape[3]
+    assert dz.shape == (n, conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad), Cout)
+    if out is None:
+        out = torch.empty((Cout, R, R, Cin), dtype=x.dtype, device=x.device)
+    if ws is None:
+        ws = torch.empty(conv2d_nhwc_wgrad_ws_bytes(n, H, W, Cin, Cout, R, stride, pad) // 4, dtype=torch.float32, device=x.device)
+    call("mm_conv2d_nhwc_wgrad", dt(x), _p(dz), _p(x), n, H, W, Cin, Cout, R, stride, pad, _p(out), _p(ws), ws.numel() * 4, _stream())
+    return out

@@ -13,9 +13,13 @@ shift, ReLU and the bottleneck's residual add fused; one rounding per convolutio
 shift = beta - running_mean * scale are computed in fp32 from the stored tensors, and the filters are repacked to
 [Cout, R, S, Cin], once per weight load (`_packed`: rebuilt when a parameter or buffer has been written or moved), never per forward.
 
-The gate is FROZEN: eval mode always (`train()` does not change it), no parameter requires a gradient.  Training it (the
-reference's FULL mode, image_modality_moe.py:233-241) would need train-mode BatchNorm statistics and a ResNet backward; neither is
-built."""
+By default the gate is FROZEN: eval mode always (`train()` does not change it), no parameter requires a gradient.  Training it
+(the reference's FULL mode, image_modality_moe.py:233-241) is opt-in: after `set_trainable(True)`, `train(mode)` takes effect and
+the training-mode forward runs as one autograd node (`_GateTrainFn`, csrc/mm_conv_bwd.hip): convolution -> BatchNorm with batch
+statistics per unit, and in reverse BatchNorm backward, convolution weight and data gradients and the max-pool's backward; the
+parameter gradients come back in torchvision's shapes.  In eval mode, and always while not trainable, the fused scale / shift
+forward above runs unchanged, bit for bit.  The MoE modalities switch this on from their `train_gate` config field (DESIGN.md
+section 7)."""
 from __future__ import annotations
 
 import json
@@ -112,15 +116,20 @@ class _ResNet50(_Pretrained):
             setattr(self, f"layer{i + 1}", seq)
         self.fc = _Linear(cin, num_classes)
 
+    def units(self):
+        """[(key, conv, bn)] in launch order; key is the module path of the convolution"""
+        out = [("conv1", self.conv1, self.bn1)]
+        for i in range(4):
+            for b, blk in enumerate(getattr(self, f"layer{i + 1}")):
+                pre = f"layer{i + 1}.{b}."
+                out += [(pre + "conv1", blk.conv1, blk.bn1), (pre + "conv2", blk.conv2, blk.bn2), (pre + "conv3", blk.conv3, blk.bn3)]
+                if blk.downsample is not None:
+                    out.append((pre + "downsample.0", blk.downsample[0], blk.downsample[1]))
+        return out
+
     def conv_bn_pairs(self):
         """[(conv, bn)] in launch order."""
-        out = [(self.conv1, self.bn1)]
-        for i in range(4):
-            for blk in getattr(self, f"layer{i + 1}"):
-                out += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
-                if blk.downsample is not None:
-                    out.append((blk.downsample[0], blk.downsample[1]))
-        return out
+        return [(c, bn) for _key, c, bn in self.units()]
 
 
 class GatingNetwork(_Pretrained):
@@ -133,13 +142,25 @@ class GatingNetwork(_Pretrained):
         self.resnet = _ResNet50(config.num_classes)
         self._packed = None
         self._packed_key = None
+        self._trainable = False
         if dtype is not None or device is not None:
             self.to(device=device, dtype=dtype)
         super().train(False)
 
-    # ---- frozen, eval only
+    # ---- frozen and eval only, unless made trainable
+    def set_trainable(self, flag: bool):
+        """Switch `requires_grad` of all 161 parameters and let `train(mode)` take effect; switching off returns to eval mode."""
+        self._trainable = bool(flag)
+        for p in self.parameters():
+            p.requires_grad = self._trainable
+        if not self._trainable:
+            super().train(False)
+        return self
+
     def train(self, mode: bool = True):
-        return super().train(False)
+        if self._trainable:
+            self._packed = None        # a trainer writes the parameters behind their version counters: repack on the next eval forward
+        return super().train(bool(mode) and self._trainable)
 
     @property
     def dtype(self):
@@ -185,9 +206,20 @@ class GatingNetwork(_Pretrained):
         return out
 
     # ---- forward
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor):
-        """pixels [n, 3, H, W] -> (logits [n, E], topk_indices [n, top_k] int64, weights [n, E]) (reference gating.py:73-89)."""
+    def forward(self, pixel_values: torch.Tensor, stages: Optional[Dict[str, Any]] = None):
+        """pixels [n, 3, H, W] -> (logits [n, E], topk_indices [n, top_k] int64, weights [n, E]) (reference gating.py:73-89).
+        Trainable and in training mode: batch statistics, `logits` and `weights` carry a grad_fn (`_GateTrainFn`); `stages`, when
+        given, receives the operands and results of every launch of that path.  Otherwise the frozen eval forward below."""
+        if self._trainable and self.training:
+            params = [p for _, p in self.resnet.named_parameters()]
+            px = pixel_values.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            logits, weights, topk = _GateTrainFn.apply(self, stages, px, *params)
+            self._packed = None                          # the running statistics were written behind autograd's back
+            return logits, topk, weights
+        with torch.no_grad():
+            return self._forward_eval(pixel_values)
+
+    def _forward_eval(self, pixel_values: torch.Tensor):
         from ... import kernels as K
         r = self.resnet
         pk = self.packed()
@@ -205,6 +237,9 @@ class GatingNetwork(_Pretrained):
                 x = conv(conv(conv(x, blk.conv1), blk.conv2), blk.conv3, residual=identity)
         n, H, W, C = x.shape
         return K.gate_head(x.view(n, H * W, C), r.fc.weight, r.fc.bias, self.top_k)
+
+    def units(self):
+        return self.resnet.units()
 
     # ---- HF layout: config.json + model.safetensors (keys resnet.*)
     def save_pretrained(self, path: str):
@@ -236,3 +271,142 @@ class GatingNetwork(_Pretrained):
 
 def is_gate_dir(path) -> bool:
     return isinstance(path, str) and bool(path) and os.path.isdir(path) and os.path.isfile(os.path.join(path, "config.json"))
+
+
+def _pack_filter(weight):
+    """[Cout, Cin, R, S] -> a packed COPY [Cout, R, S, Cin] (the stem's Cin 3 -> 8 with zeros)"""
+    w = weight.detach().permute(0, 2, 3, 1)
+    if w.shape[3] % 8:
+        return torch.nn.functional.pad(w, (0, 8 - w.shape[3] % 8)).contiguous()
+    return w.clone(memory_format=torch.contiguous_format)
+
+
+class _GateTrainFn(torch.autograd.Function):
+    """The gate in training mode as ONE autograd node.  Forward, per convolution unit: z = mm_conv2d_nhwc_fwd (scale 1, shift 0: the
+    raw convolution, one rounding) -> mm_bn_train_fwd (batch statistics, residual and ReLU fused; running statistics updated in
+    place), then the max-pool after the stem and mm_gate_head.  Backward walks the units in reverse: the head in torch on [n, E] and
+    [n, 2048] tensors (it differentiates weights = T(softmax_fp32(float(T(logits)))) with the pooled mean in fp32, the roundings
+    taken as identities), then per unit mm_bn_train_bwd -> mm_conv2d_nhwc_wgrad and mm_conv2d_nhwc_dgrad, whose addend joins a
+    bottleneck's residual branch with its identity path in one rounding, and mm_maxpool2d_nhwc_bwd in front of the stem.
+    The backward reads COPIES of the filters, gamma and the fc weight taken by the forward (a trainer may update the parameters in
+    between), and writes the parameter gradients, in torchvision's shapes, where every Function of this package writes them
+    (functional.grad_target: the trainer's flat gradient buffer, overwrite or accumulate)."""
+
+    @staticmethod
+    def forward(ctx, gate, stages, px, *params):
+        from ... import kernels as K
+        r = gate.resnet
+        T, dev = gate.dtype, px.device
+        saved = {}
+        affine = {}
+
+        def unit(key, x, c, bn, residual=None, relu=True):
+            w = _pack_filter(c.weight)
+            cout = w.shape[0]
+            if cout not in affine:
+                affine[cout] = (torch.ones(cout, dtype=torch.float32, device=dev), torch.zeros(cout, dtype=torch.float32, device=dev))
+            z = K.conv2d_nhwc(x, w, affine[cout][0], affine[cout][1], c.stride, c.pad)
+            gamma = bn.weight.detach().clone()
+            y, mean, invstd = K.bn_train_fwd(z, gamma, bn.bias.detach(), residual, relu, eps=BN_EPS, running_mean=bn.running_mean,
+                                             running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked)
+            saved[key] = dict(x=x, w=w, gamma=gamma, z=z, y=y, mean=mean, invstd=invstd, relu=relu, k=c.k, stride=c.stride, pad=c.pad,
+                              cin=c.weight.shape[1])
+            return y
+
+        x0 = K.nchw_to_nhwc(px, 8, T)
+        stem = unit("conv1", x0, r.conv1, r.bn1)
+        x = K.maxpool2d_nhwc(stem)
+        for i in range(4):
+            for b, blk in enumerate(getattr(r, f"layer{i + 1}")):
+                pre = f"layer{i + 1}.{b}."
+                identity = x if blk.downsample is None else unit(pre + "downsample.0", x, blk.downsample[0], blk.downsample[1], relu=False)
+                y = unit(pre + "conv1", x, blk.conv1, blk.bn1)
+                y = unit(pre + "conv2", y, blk.conv2, blk.bn2)
+                x = unit(pre + "conv3", y, blk.conv3, blk.bn3, residual=identity)
+        n, H, W, C = x.shape
+        fc_w = r.fc.weight.detach().clone()
+        logits, topk, weights = K.gate_head(x.view(n, H * W, C), fc_w, r.fc.bias.detach(), gate.top_k)
+        ctx.stages, ctx.saved, ctx.last, ctx.T = stages, saved, x, T
+        ctx.blocks = [(f"layer{i + 1}.{b}.", blk.downsample is not None) for i in range(4) for b, blk in enumerate(getattr(r, f"layer{i + 1}"))]
+        ctx.params = dict(zip([nm for nm, _ in r.named_parameters()], params))
+        ctx.head = (logits, fc_w)
+        if stages is not None:
+            for key, u in saved.items():
+                for f in ("x", "z", "y", "mean", "invstd"):
+                    stages[f"{key}.{f}"] = u[f]
+            stages["pool.x"], stages["head.x"], stages["logits"], stages["weights"] = stem, x, logits, weights
+        ctx.mark_non_differentiable(topk)
+        return logits, weights, topk
+
+    @staticmethod
+    def backward(ctx, dlogits, dweights, _dtopk):
+        from ... import functional as Fm
+        from ... import kernels as K
+        stages, saved, last, T = ctx.stages, ctx.saved, ctx.last, ctx.T
+        if saved is None:
+            raise RuntimeError("the gate's training backward ran twice: its saved activations are released after the first pass "
+                               "(retain_graph is not supported)")
+
+        def rec(key, **kw):
+            if stages is not None:
+                for f, v in kw.items():
+                    stages[f"{key}.{f}"] = v
+
+        def emit(name, g):
+            """the gradient of parameter `name` is complete: into its buffer (overwrite or accumulate), then the trainer's hook"""
+            p = ctx.params[name]
+            if not p.requires_grad:
+                return
+            buf, acc = Fm.grad_target(p)
+            if acc:
+                buf.add_(g.view(buf.shape))
+            else:
+                buf.copy_(g.view(buf.shape))
+            Fm._ready(p)
+
+        # ---- head: logits = T(pooled . W^T + b), weights = T(softmax_fp32(float(logits)))
+        logits, fc_w = ctx.head
+        n, H, W, C = last.shape
+        p = torch.softmax(logits.float(), dim=-1)
+        dl = dlogits.float() if dlogits is not None else torch.zeros_like(p)
+        if dweights is not None:
+            dw32 = dweights.float()
+            dl = dl + p * (dw32 - (p * dw32).sum(-1, keepdim=True))
+        pooled = last.view(n, H * W, C).float().mean(1)
+        emit("fc.weight", (dl.t() @ pooled).to(T))
+        emit("fc.bias", dl.sum(0).to(T))
+        dpooled = dl @ fc_w.float()
+        dy = (dpooled / (H * W)).to(T).view(n, 1, 1, C).expand(n, H, W, C).contiguous()
+        rec("head", dl=dl, dx=dy)
+
+        def bn_bwd(key, dy, want_dres=False):
+            u = saved[key]
+            dz, dres, dgamma, dbeta = K.bn_train_bwd(dy, u["y"], u["z"], u["mean"], u["invstd"], u["gamma"], u["relu"], want_dres=want_dres)
+            dw = K.conv2d_nhwc_wgrad(dz, u["x"], u["k"], u["stride"], u["pad"])
+            name = key[:-len("conv1")] + "bn" + key[-1] if not key.endswith("downsample.0") else key[:-1] + "1"
+            emit(key + ".weight", dw[..., :u["cin"]].permute(0, 3, 1, 2).contiguous())
+            emit(name + ".weight", dgamma)
+            emit(name + ".bias", dbeta)
+            rec(key, dy=dy, dz=dz, dres=dres, dw=dw, dgamma=dgamma, dbeta=dbeta)
+            return dz, dres
+
+        def dgrad(key, dz, addend=None):
+            u = saved[key]
+            wp = u["w"].permute(3, 1, 2, 0).contiguous()                         # the forward's filter as [Cin, R, S, Cout]
+            dx = K.conv2d_nhwc_dgrad(dz, wp, u["x"].shape[1], u["x"].shape[2], u["stride"], u["pad"], addend=addend)
+            rec(key, dx=dx)
+            return dx
+
+        for pre, has_down in reversed(ctx.blocks):
+            dz3, dres = bn_bwd(pre + "conv3", dy, want_dres=True)
+            dz2, _ = bn_bwd(pre + "conv2", dgrad(pre + "conv3", dz3))
+            dz1, _ = bn_bwd(pre + "conv1", dgrad(pre + "conv2", dz2))
+            if has_down:
+                dzd, _ = bn_bwd(pre + "downsample.0", dres)
+                dres = dgrad(pre + "downsample.0", dzd)
+            dy = dgrad(pre + "conv1", dz1, addend=dres)                          # the join of the two paths: one rounding
+        dy = K.maxpool2d_nhwc_bwd(saved["conv1"]["y"], dy)
+        rec("pool", dx=dy)
+        bn_bwd("conv1", dy)
+        ctx.saved = ctx.last = None
+        return (None,) * (3 + len(ctx.params))

@@ -20,10 +20,10 @@ width; both run on the one-pass cross-attention kernel `mm_xattn_*` (csrc/mm_xat
 
 The gate (reference moe/gating.py:37-89, a torchvision ResNet-50 with an E-way fc) is `modalities/gating.py`: the same key set
 on libmmhip's NHWC convolution kernels, built from `config.gating_path` when that is a directory holding a `config.json`
-(`GatingNetwork.from_pretrained`), as the submodule `gating_network`: frozen, eval mode always, outside the optimiser.  A
+(`GatingNetwork.from_pretrained`), as the submodule `gating_network`: by default frozen, eval mode always, outside the optimiser.  A
 `gating_network=` argument wins over the path, and may be any callable with the reference's output contract
-`pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  NOT built: training the gate in FULL mode
-(train-mode BatchNorm, a ResNet backward).  The experts run side by side, each on its own HIP
+`pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  Training the gate in FULL mode (train-mode BatchNorm, a ResNet
+backward, a gradient through the fusion weights) is opt-in through the config field `train_gate`.  The experts run side by side, each on its own HIP
 stream (`_run_experts`); a grouped multi-expert GEMM launch would be the step after that.  `CrossAttention`'s two dropouts
 (p = 0.1 on the attention probabilities and on the output projection, active in the reference whenever the module trains) are
 Philox-based: eval mode equals the reference, train mode equals it in distribution (torch's generator cannot be reproduced)."""
@@ -51,8 +51,9 @@ class MOEImageConfig(BaseModalityConfig):
     def __init__(self, hidden_size: int = 1024, use_bias_proj: bool = True, expert_clip_names: Optional[List[str]] = None,
                  image_processor: str = "openai/clip-vit-large-patch14", gating_path: str = "", top_k_experts: int = 1,
                  projection_type: str = "mlp", generalist_idx: int = -1, fusion_method: str = "weighted_average",
-                 cross_attn_heads: int = 8, **kwargs):
+                 cross_attn_heads: int = 8, train_gate: bool = False, **kwargs):
         super().__init__(modality_type="image", hidden_size=hidden_size)
+        self.train_gate = bool(train_gate)       # opt-in: unfreezing the modality also trains the gating network (the reference's FULL mode)
         self.use_bias_proj = use_bias_proj
         self.expert_clip_names = list(expert_clip_names or [])
         self.top_k_experts = top_k_experts
@@ -62,6 +63,12 @@ class MOEImageConfig(BaseModalityConfig):
         self.generalist_idx = generalist_idx
         self.fusion_method = fusion_method
         self.cross_attn_heads = cross_attn_heads
+
+    def to_dict(self) -> Dict[str, Any]:
+        d = super().to_dict()
+        if not d.get("train_gate"):              # written only when set: configs saved without it stay byte-identical
+            d.pop("train_gate", None)
+        return d
 
 
 class MOEImageProcessor(BaseModalityProcessor):
@@ -426,13 +433,23 @@ _NO_GATE = ("{cls} needs a gating network: set `gating_path` to a directory writ
 
 
 class _FrozenGate:
-    """The gate stays frozen and in eval mode whatever the training mode (the reference trains it in FULL mode,
-    image_modality_moe.py:233-241: a stated deviation)."""
+    """By default the gate stays frozen and in eval mode whatever the training mode.  The reference trains it in FULL mode
+    (image_modality_moe.py:233-241); here that is opt-in: with `config.train_gate`, unfreezing the modality's embedder makes a
+    `GatingNetwork` trainable (train-mode BatchNorm, gradients through the fusion weights) and freezing it reverses that
+    (DESIGN.md section 7).  A callable plug is left alone."""
     _warned_frozen_gate = False
 
+    def _gate_trains(self):
+        return bool(getattr(self.config, "train_gate", False)) and isinstance(getattr(self, "gating_network", None), GatingNetwork)
+
+    def _set_gate_trainable(self, flag: bool):
+        self.gating_network.set_trainable(flag)
+        self.gating_network.train(flag)
+
     def _keep_gate_frozen(self, warn=False):
+        """the default: eval mode, no gradient; a `train_gate` modality's gate is left as its last freeze / unfreeze set it"""
         g = getattr(self, "gating_network", None)
-        if not isinstance(g, nn.Module):
+        if not isinstance(g, nn.Module) or self._gate_trains():
             return
         g.eval()
         for p in g.parameters():
@@ -442,6 +459,19 @@ class _FrozenGate:
             _FrozenGate._warned_frozen_gate = True
             warnings.warn("the MoE gating network stays frozen (eval-mode BatchNorm, no gradient): training the gate is not built")
 
+    def _on_unfreeze(self):
+        """the embedder was unfrozen: with `train_gate` the gate joins it, otherwise it stays frozen (and says so once)"""
+        if self._gate_trains():
+            self._set_gate_trainable(True)
+        else:
+            self._keep_gate_frozen(warn=True)
+
+    def _on_freeze(self):
+        if self._gate_trains():
+            self._set_gate_trainable(False)
+        else:
+            self._keep_gate_frozen()
+
     def train(self, mode: bool = True):
         super().train(mode)
         self._keep_gate_frozen()
@@ -449,7 +479,10 @@ class _FrozenGate:
 
     def unfreeze_all(self):
         super().unfreeze_all()
-        self._keep_gate_frozen()
+        if self._gate_trains():
+            self._on_unfreeze()
+        else:
+            self._keep_gate_frozen()
 
 
 @AutoModality.register("moe_meditron_clip")             # applied last: the config class keeps the reference's model_type
@@ -535,14 +568,14 @@ class MOEImageModality(_FrozenGate, BaseModality):      # which the reference it
             for p in e.parameters():
                 p.requires_grad = False
         self.modality_frozen = True
-        self._keep_gate_frozen()
+        self._on_freeze()
 
     def unfreeze_modality_embedder(self):
         for e in self.experts:
             for p in e.parameters():
                 p.requires_grad = True
         self.modality_frozen = False
-        self._keep_gate_frozen(warn=True)
+        self._on_unfreeze()
 
     def unfreeze_projection(self):
         for p in self.projector.parameters():
@@ -649,14 +682,14 @@ class MOEImageModalityPEP(_FrozenGate, BaseModality):
             for p in e.parameters():
                 p.requires_grad = False
         self.modality_frozen = True
-        self._keep_gate_frozen()
+        self._on_freeze()
 
     def unfreeze_modality_embedder(self):
         for e in self.experts:
             for p in e.parameters():
                 p.requires_grad = True
         self.modality_frozen = False
-        self._keep_gate_frozen(warn=True)
+        self._on_unfreeze()
 
     def unfreeze_projection(self):
         for p in self.projectors.parameters():

@@ -177,11 +177,17 @@ class MultiModalModelForCausalLM(nn.Module):
                 seen.add(id(p))
                 out.append(("model." + n, p, "llm", hf_decays("model." + n, owner.get(id(p)))))
         for i, m in enumerate(self.modalities_with_projection):
+            # `train_gate` modalities: the gate is a component of its own.  HF's decay rule (hf_decays) decays BatchNorm weights
+            # (`bn1.weight`, `downsample.1.weight`: neither nn.LayerNorm nor a name it excludes) and not the biases, as it
+            # would for the reference's torchvision ResNet
+            train_gate = bool(getattr(getattr(m, "config", None), "train_gate", False)) and isinstance(
+                getattr(m, "gating_network", None), nn.Module)
             for n, p in m.named_parameters():
-                if id(p) in seen or n.startswith("gating_network."):     # the MoE gate is frozen: outside the flat buffer,
-                    continue                                              # the gradient buckets and the optimiser
+                gate = n.startswith("gating_network.")
+                if id(p) in seen or (gate and not train_gate):           # the MoE gate is frozen by default: outside the flat
+                    continue                                              # buffer, the gradient buckets and the optimiser
                 seen.add(id(p))
-                comp = f"projector{i}" if n.startswith("projector.") else f"encoder{i}"
+                comp = f"gate{i}" if gate else (f"projector{i}" if n.startswith("projector.") else f"encoder{i}")
                 full = f"modalities_with_projection.{i}.{n}"
                 out.append((full, p, comp, hf_decays(full, owner.get(id(p)))))
         return out

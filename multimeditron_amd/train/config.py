@@ -11,7 +11,9 @@ cookbook/sft/*/config.yaml files have this layout):
     attachment_token    placeholder token of an attachment in the text (train.py:101, data_loader.py:26)
     loaders[]           {loader_type, modality_type, **kwargs} -> AutoModalityLoader.from_name (train.py:113-118)
     modalities[]        {model_type, ...} -> AutoModality.config_from_dict (train.py:109-111); the alternate embedder / LLM of
-                        BASELINE config 5 plug in HERE (model_type: meditron_siglip, base_llm: Qwen/Qwen2-7B-Instruct)
+                        BASELINE config 5 plug in HERE (model_type: meditron_siglip, base_llm: Qwen/Qwen2-7B-Instruct).  An MoE
+                        modality's `train_gate: true` (this project's key, default false) makes FULL mode train the gating
+                        network with the experts, as the reference's FULL mode does
     training_mode       ALIGNMENT | END2END | LM_ONLY | FULL (trainer.py:16-23)
     truncation, max_sequence_length, use_2d_position_ids
     training_args{}     the HF TrainingArguments keys that act on this path: learning_rate, weight_decay, max_grad_norm,

@@ -349,6 +349,9 @@ class MultimodalTrainer:
             raise KeyError(start)
 
         def block_key(name):
+            g = name.find(".gating_network.")
+            if g >= 0:             # the MoE gate reads all its parameters inside GatingNetwork.forward: one block, hooked there
+                return name[:g + len(".gating_network")]
             m = re.match(r"(.*?layers\.\d+)\.", name)
             return m.group(1) if m else name.rsplit(".", 1)[0]
 
@@ -360,6 +363,8 @@ class MultimodalTrainer:
             llm = key.startswith("model.")
             m = re.search(r"layers\.(\d+)$", key)
             li = int(m.group(1)) if m else -1
+            if key.endswith(".gating_network"):
+                return (-1, -1, key)                          # the gate runs first in its modality's forward
             if not llm:
                 rank = 3 if ".projector" in key else (2 if li >= 0 else (0 if "embeddings" in key else 1))
             else:
@@ -408,6 +413,9 @@ class MultimodalTrainer:
         self._opt_stream = torch.cuda.Stream(priority=0) if torch.cuda.is_available() and self.flat.device.type == "cuda" else None
 
         def block_key(name):
+            g = name.find(".gating_network.")
+            if g >= 0:             # the MoE gate reads all its parameters inside GatingNetwork.forward: one block, hooked there
+                return name[:g + len(".gating_network")]
             m = re.match(r"(.*?layers\.\d+)\.", name)
             return m.group(1) if m else name.rsplit(".", 1)[0]
 

@@ -2,7 +2,9 @@
 """The MoE gating network (ResNet-50 on the NHWC convolution kernels) in time: the gate alone at n images of 224x224 in bf16, its
 largest kernels, and the forward of tools/moe_bench.py's modality (E ViT-L/14 experts, frozen towers, graph replay) with the real
 gate against the same forward with a constant-callable gate -- both in this process, interleaved round by round.
-   python tools/gating_bench.py [E] [n] [rounds]"""
+   python tools/gating_bench.py [E] [n] [rounds]
+   python tools/gating_bench.py --train [E] [n] [rounds]     the trainable gate's training forward + backward beside its eval forward
+                                                             (timed, not judged: no threshold)"""
 import json
 import os
 import statistics
@@ -15,6 +17,8 @@ from multimeditron_amd import kernels as K
 from multimeditron_amd.nn import FlatParams
 from multimeditron_amd.model.modalities import GatingNetwork, GatingNetworkConfig, MOEImageConfig, MOEImageModality
 
+TRAIN = "--train" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--train"]
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
@@ -39,6 +43,26 @@ px = torch.randn(n, 3, 224, 224, device="cuda")
 for _ in range(3):
     gate(px)
 alone = [timed(lambda: gate(px), 10) for _ in range(rounds)]
+
+if TRAIN:
+    gate.set_trainable(True).train()
+    dw = torch.randn(n, E, device="cuda").to(torch.bfloat16)
+
+    def fwd_bwd():
+        gate(px)[2].backward(dw)
+
+    def fwd_only():
+        with torch.no_grad():          # the training forward's launches without the autograd node's bookkeeping being used
+            gate(px)
+
+    for _ in range(3):
+        fwd_bwd()
+    both = [timed(fwd_bwd, 10) for _ in range(rounds)]
+    fwd = [timed(fwd_only, 10) for _ in range(rounds)]
+    print(json.dumps({"E": E, "n": n, "gate_eval_forward_ms": {"median": statistics.median(alone), "min": min(alone)},
+                      "gate_train_forward_ms": {"median": statistics.median(fwd), "min": min(fwd)},
+                      "gate_train_forward_backward_ms": {"median": statistics.median(both), "min": min(both)}}))
+    sys.exit(0)
 
 # per-convolution times (each shape once, 20 launches), largest first
 per = {}
