@@ -297,6 +297,25 @@ int mm_attn_decode(int dtype, const void* q, const void* k, const void* v, int B
  * multiply by up, as HF's act_fn(gate_proj(x)) * up_proj(x) in the storage dtype.  The backward rounds each output once.        */
 int mm_swiglu_fwd(int dtype, const void* gu, int M, int I, void* out, void* stream);
 int mm_swiglu_bwd(int dtype, const void* gu, const void* dout, int M, int I, void* dgu, void* stream);
+/* xIELU (Apertus MLP: down_proj(xIELU(up_proj(h))); HF 5.15 activations.py XIELUActivation._xielu_python).  x = the pre-activation,
+ * n elements, T = the storage type, all arithmetic fp32:
+ *   sp(a) = a > 20 ? a : log1p(exp(a));   ap = sp(*alpha_p_raw),  an = beta + sp(*alpha_n_raw)
+ *   y  = x > 0 ? ap x^2 + beta x : an (expm1(min(x, eps)) - x) + beta x
+ *   dx = dy * (x > 0 ? 2 ap x + beta : an (m(x) exp(x) - 1) + beta),  m = 1 below eps, 1/2 at eps, 0 above (torch.min's tie rule)
+ *   dalpha_p_raw = sp'(*alpha_p_raw) * sum_{x > 0} dy x^2,   dalpha_n_raw = sp'(*alpha_n_raw) * sum_{x <= 0} dy (expm1(min(x, eps)) - x)
+ * alpha_*_raw: one element of T each in device memory (no host sync).  beta / eps: the values of the model's buffers (in a bf16
+ * model the bf16-rounded ones).  y and dx are rounded once to T.  x, y, dy, dx 16-byte aligned (MM_ERR_ALIGN); any n >= 0.
+ * mm_xielu_bwd: partials = f32 [mm_xielu_bwd_blocks(n), 2] (8-byte aligned), the workgroups' sums of the two scalar gradients' terms;
+ *   NULL = the scalars are frozen: dx only.  mm_xielu_bwd_blocks depends on n alone (never on the device).
+ * mm_xielu_reduce: adds the nblk partials in a fixed order in fp32, applies sp', and writes -- or, where accumulate_* is set, adds
+ *   in fp32 to the existing T value -- the two gradients, rounded once.  No atomics anywhere: equal inputs give equal bits.          */
+int mm_xielu_fwd(int dtype, const void* x, int64_t n, const void* alpha_p_raw, const void* alpha_n_raw, float beta, float eps, void* y,
+                 void* stream);
+int mm_xielu_bwd_blocks(int64_t n);
+int mm_xielu_bwd(int dtype, const void* x, const void* dy, int64_t n, const void* alpha_p_raw, const void* alpha_n_raw, float beta,
+                 float eps, void* dx, float* partials, void* stream);
+int mm_xielu_reduce(int dtype, const float* partials, int nblk, const void* alpha_p_raw, const void* alpha_n_raw, void* dalpha_p_raw,
+                    void* dalpha_n_raw, int accumulate_p, int accumulate_n, void* stream);
 /* kind: 0 = erf GELU (mlp.py:35,37), 1 = quick GELU (HF:clip fc1).  x is the pre-activation.                       */
 /* kind: 0 = erf GELU, 1 = quick GELU, 2 = tanh GELU */
 int mm_gelu_fwd(int dtype, int kind, const void* x, int64_t n, void* y, void* stream);

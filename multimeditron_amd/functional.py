@@ -628,6 +628,53 @@ def swiglu_mlp(x, wgu, wd, I, residual=None, dummy=None):
     return SwiGLUMLPFn.apply(x, residual, dummy, as_group(wgu), as_group(wd), I)
 
 
+class XIELUMLPFn(torch.autograd.Function):
+    """y = down_proj(xIELU(up_proj(x))) + residual as ONE autograd node (HF 5.15 models/apertus ApertusMLP + the layer's residual
+    add).  `act` holds the activation's two raw scalars (`alpha_p`, `alpha_n`, Parameters of shape [1]) and `consts()` -> (beta, eps)
+    as floats.  Backward: down_proj's wgrad and dgrad, mm_xielu_bwd (dx and the scalar gradients' partial sums in one pass),
+    mm_xielu_reduce into the scalars' gradients (overwrite on the first write of a step, accumulate afterwards), up_proj's wgrad and
+    dgrad."""
+
+    @staticmethod
+    def forward(ctx, x, residual, dummy, wu: ParamGroup, wd: ParamGroup, act):
+        beta, eps = act.consts()
+        u = K.linear_fwd(x, wu.tensor())
+        a = K.xielu_fwd(u, act.alpha_p.data, act.alpha_n.data, beta, eps)
+        y = K.linear_fwd(a, wd.tensor(), residual=residual)
+        ctx.wu, ctx.wd, ctx.act, ctx.consts = wu, wd, act, (beta, eps)
+        ctx.has_res = residual is not None
+        ctx.save_for_backward(x, u, a)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, u, a = ctx.saved_tensors
+        wu, wd, act = ctx.wu, ctx.wd, ctx.act
+        beta, eps = ctx.consts
+        if dy.stride(-1) != 1 or (dy.stride(0) % 8):
+            dy = dy.contiguous()
+        dres = dy if ctx.has_res else None
+        _wgrad(dy, a, wd)
+        da = K.linear_dgrad(dy, wd.tensor())
+        ap, an = act.alpha_p, act.alpha_n
+        train = ap.requires_grad or an.requires_grad
+        du, partials = K.xielu_bwd(u, da, ap.data, an.data, beta, eps, want_dalpha=train)
+        if train:
+            if not (ap.requires_grad and an.requires_grad):
+                raise NotImplementedError("xIELU: alpha_p and alpha_n are trained or frozen together")
+            (gp, accp), (gn, accn) = grad_target(ap), grad_target(an)
+            K.xielu_reduce(partials, ap.data, an.data, gp, gn, accp, accn)
+            _ready(ap)
+            _ready(an)
+        _wgrad(du, x, wu)
+        dx = K.linear_dgrad(du, wu.tensor()) if ctx.needs_input_grad[0] else None
+        return dx, dres, None, None, None, None
+
+
+def xielu_mlp(h, w_up, w_down, act, residual=None, dummy=None):
+    return XIELUMLPFn.apply(h, residual, dummy, as_group(w_up), as_group(w_down), act)
+
+
 class AddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -647,7 +694,8 @@ class EmbedSpliceFn(torch.autograd.Function):
     """model.py:433-444 in one pass: token embedding gather with modality rows spliced in."""
 
     @staticmethod
-    def forward(ctx, proj, dummy, emb, ids, batch_idx, token_range, B, S):
+    def forward(ctx, proj, dummy, emb, ids, batch_idx, token_range, B, S, padding_idx=None):
+        ctx.padding_idx = padding_idx
         T = B * S
         ids = ids.reshape(-1).contiguous()
         src_map = None
@@ -690,12 +738,14 @@ class EmbedSpliceFn(torch.autograd.Function):
                 demb.zero_()           # rows no token touched must read 0 (the flat gradient buffer is never memset)
         K.embed_splice_bwd(dE, ids, src_map, batch_idx, token_range, ctx.S, dproj, demb, order, skey, accumulate=acc)
         if emb.requires_grad:
+            if ctx.padding_idx is not None:      # nn.Embedding(padding_idx=...): that row never receives a gradient
+                demb[ctx.padding_idx].zero_()
             _ready(emb)
-        return dproj, None, None, None, None, None, None, None
+        return dproj, None, None, None, None, None, None, None, None
 
 
-def embed_splice(emb, ids, proj, batch_idx, token_range, B, S, dummy=None):
-    return EmbedSpliceFn.apply(proj, dummy, emb, ids, batch_idx, token_range, B, S)
+def embed_splice(emb, ids, proj, batch_idx, token_range, B, S, dummy=None, padding_idx=None):
+    return EmbedSpliceFn.apply(proj, dummy, emb, ids, batch_idx, token_range, B, S, padding_idx)
 
 
 # --------------------------------------------------------------------------------------------------- ViT glue

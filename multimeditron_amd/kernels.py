@@ -582,6 +582,35 @@ def swiglu_bwd(gu, dout, I):
     return dgu
 
 
+def xielu_fwd(x, alpha_p, alpha_n, beta, eps):
+    """Apertus xIELU of the pre-activation x (any shape, contiguous).  alpha_p / alpha_n: the RAW one-element parameters (device
+    memory, x's dtype); beta / eps: the values of the module's buffers as Python floats."""
+    assert x.is_contiguous() and alpha_p.dtype == x.dtype and alpha_n.dtype == x.dtype
+    y = torch.empty_like(x)
+    call("mm_xielu_fwd", dt(x), _p(x), x.numel(), _p(alpha_p), _p(alpha_n), float(beta), float(eps), _p(y), _stream())
+    return y
+
+
+def xielu_bwd_blocks(n):
+    return _lib.lib().mm_xielu_bwd_blocks(n)
+
+
+def xielu_bwd(x, dy, alpha_p, alpha_n, beta, eps, want_dalpha=True):
+    """-> (dx, partials): partials f32 [mm_xielu_bwd_blocks(n), 2] (the workgroups' sums for `xielu_reduce`), None when frozen."""
+    assert x.is_contiguous() and dy.is_contiguous() and dy.dtype == x.dtype and dy.numel() == x.numel()
+    dx = torch.empty_like(x)
+    partials = torch.empty((xielu_bwd_blocks(x.numel()), 2), dtype=torch.float32, device=x.device) if want_dalpha else None
+    call("mm_xielu_bwd", dt(x), _p(x), _p(dy), x.numel(), _p(alpha_p), _p(alpha_n), float(beta), float(eps), _p(dx), _p(partials), _stream())
+    return dx, partials
+
+
+def xielu_reduce(partials, alpha_p, alpha_n, dalpha_p, dalpha_n, accumulate_p, accumulate_n):
+    """dalpha_*_raw (+)= softplus'(alpha_*_raw) * sum of the partials, fixed order, one rounding."""
+    assert partials.is_contiguous() and dalpha_p.dtype == alpha_p.dtype and dalpha_n.dtype == alpha_n.dtype
+    call("mm_xielu_reduce", dt(alpha_p), _p(partials), partials.shape[0], _p(alpha_p), _p(alpha_n), _p(dalpha_p), _p(dalpha_n),
+         int(accumulate_p), int(accumulate_n), _stream())
+
+
 def gelu_fwd(x, kind):
     y = torch.empty_like(x)
     call("mm_gelu_fwd", dt(x), kind, _p(x), x.numel(), _p(y), _stream())

@@ -1,12 +1,14 @@
-"""Llama / Qwen2 / Qwen3 decoder on libmmhip kernels: the MI355X replacement for the HF `AutoModelForCausalLM` the
+"""Llama / Qwen2 / Qwen3 / Apertus decoder on libmmhip kernels: the MI355X replacement for the HF `AutoModelForCausalLM` the
 reference constructs at model.py:253-260 and calls at model.py:517-526 (forward) and :595-602 (decode).
 
 Semantics follow HF transformers 5.15.0 (models/llama/modeling_llama.py): RMSNorm :53-70, RoPE :113-160 (+ llama3
 inv_freq scaling modeling_rope_utils.py:641-662), GQA softmax attention :191-281, SwiGLU MLP :163-176, pre-norm
 residual layer :284-325, final norm + lm_head :413,480, shifted CE loss/loss_utils.py:36-71.  Qwen2 = same graph with
 biased q/k/v projections.  Qwen3 = Llama with a per-head RMSNorm of q and k (`q_norm` / `k_norm`, weights [head_dim]) between
-the projection and RoPE (HF 5.15 models/qwen3/modeling_qwen3.py:50-64,237-257).  Parameter names equal HF's so reference
-checkpoints interchange.
+the projection and RoPE (HF 5.15 models/qwen3/modeling_qwen3.py:50-64,237-257).  Apertus (HF 5.15 models/apertus/modeling_apertus.py) =
+Llama with that q/k norm, llama3 RoPE, the layer norms named `attention_layernorm` / `feedforward_layernorm`, and an ungated MLP
+`down_proj(xIELU(up_proj(x)))` whose activation carries two trainable scalars per layer (csrc/mm_xielu.hip).  Parameter names equal
+HF's so reference checkpoints interchange.
 
 Data layout: activations are [B*S, features] row-major in HBM; q/k/v come out of ONE fused GEMM as a
 [B*S, (Hq+2Hkv)*D] buffer that RoPE rewrites in place and the attention kernel reads through strides; gate/up come
@@ -38,7 +40,9 @@ class LLMConfig:
     rms_norm_eps: float = 1e-5
     tie_word_embeddings: bool = False
     attention_bias: bool = False
-    qk_norm: bool = False              # Qwen3: RMSNorm over every q and k head before RoPE
+    qk_norm: bool = False              # Qwen3, Apertus: RMSNorm over every q and k head before RoPE
+    hidden_act: str = "silu"           # "silu": gated SwiGLU MLP; "xielu" (Apertus): down_proj(xIELU(up_proj(x)))
+    pad_token_id: Optional[int] = None # Apertus (ApertusConfig's default 3): embed_tokens' padding_idx, whose row gets no gradient
     max_position_embeddings: int = 131072
     rope_parameters: Dict[str, Any] = field(default_factory=lambda: {"rope_type": "default", "rope_theta": 10000.0})
 
@@ -62,12 +66,31 @@ class LLMConfig:
             if "sliding_attention" in (d.get("layer_types") or ()):
                 raise NotImplementedError("Qwen3 sliding-window attention layers are not supported")
             kw["qk_norm"] = True                 # Qwen3: q_norm / k_norm per head (HF:models/qwen3:237-257)
+        if mt == "apertus":                      # HF 5.15 models/apertus: q/k norm as Qwen3, an ungated xIELU MLP, its own norm names
+            act = d.get("hidden_act", "xielu")
+            if act != "xielu":
+                raise NotImplementedError(f"Apertus with hidden_act {act!r}: only the xIELU MLP is supported")
+            kw["qk_norm"] = True
+            kw["hidden_act"] = "xielu"
+            kw["pad_token_id"] = d.get("pad_token_id", 3)
+        else:
+            kw["hidden_act"] = "silu"            # every other family here is the gated SiLU MLP, whatever the field says
+            kw["pad_token_id"] = None            # ... and keeps its embedding without a padding row, as before
         if not kw.get("head_dim"):
             kw["head_dim"] = kw.get("hidden_size", 4096) // kw.get("num_attention_heads", 32)
         return cls(**kw)
 
     def to_dict(self):
-        return {k: getattr(self, k) for k in self.__dataclass_fields__}
+        d = {k: getattr(self, k) for k in self.__dataclass_fields__}
+        if d["hidden_act"] == "silu":            # written only when it says something: Llama / Qwen configs stay byte-identical
+            del d["hidden_act"]
+        if d["pad_token_id"] is None:
+            del d["pad_token_id"]
+        return d
+
+    @property
+    def apertus(self) -> bool:
+        return self.model_type == "apertus"
 
 
 def rope_inv_freq(cfg: LLMConfig) -> torch.Tensor:
@@ -118,13 +141,59 @@ class MLP(nn.Module):
         self._wgu = Fm.ParamGroup([self.gate_proj.weight, self.up_proj.weight])
 
 
+class XIELU(nn.Module):
+    """Holder of HF's XIELUActivation state (activations.py, transformers 5.15): the raw scalars `alpha_p`, `alpha_n` (Parameters of
+    shape [1], model dtype; the kernels apply the softplus) and the persistent 0-dim buffers `beta`, `eps` (model dtype, so a bf16
+    model carries eps = bf16(-1e-6), which is what its arithmetic uses)."""
+
+    def __init__(self, dtype, device, alpha_p_init=0.8, alpha_n_init=0.8, beta=0.5, eps=-1e-6):
+        super().__init__()
+        self.alpha_p = nn.Parameter(torch.log(torch.expm1(torch.tensor(alpha_p_init, dtype=dtype))).unsqueeze(0).to(device))
+        self.alpha_n = nn.Parameter(torch.log(torch.expm1(torch.tensor(alpha_n_init - beta, dtype=dtype))).unsqueeze(0).to(device))
+        self.register_buffer("beta", torch.tensor(beta, dtype=dtype, device=device))
+        self.register_buffer("eps", torch.tensor(eps, dtype=dtype, device=device))
+        self._consts = None
+
+    def consts(self):
+        """(beta, eps) as floats for the kernels' arguments: read from the buffers once per value (a host read), not per call."""
+        key = (self.beta._version, self.eps._version, self.beta.data_ptr(), self.eps.data_ptr())
+        if self._consts is None or self._consts[0] != key:
+            self._consts = (key, (float(self.beta), float(self.eps)))
+        return self._consts[1]
+
+
+class XIELUMLP(nn.Module):
+    """Apertus: down_proj(xIELU(up_proj(x))), no gate (HF 5.15 models/apertus/modeling_apertus.py ApertusMLP)."""
+
+    def __init__(self, cfg: LLMConfig, dtype, device):
+        super().__init__()
+        H, I = cfg.hidden_size, cfg.intermediate_size
+        self.I = I
+        self.up_proj = Linear(H, I, bias=False, dtype=dtype, device=device)
+        self.down_proj = Linear(I, H, bias=False, dtype=dtype, device=device)
+        self.act_fn = XIELU(dtype, device)
+        self._wgu = Fm.ParamGroup([self.up_proj.weight])      # the MLP's first GEMM operand, under the name the gated MLP uses
+
+    def act(self, u):
+        """xIELU of the pre-activation (no autograd: prefill and decode)."""
+        f = self.act_fn
+        return K.xielu_fwd(u, f.alpha_p.data, f.alpha_n.data, *f.consts())
+
+
 class DecoderLayer(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
         self.self_attn = Attention(cfg, dtype, device)
-        self.mlp = MLP(cfg, dtype, device)
-        self.input_layernorm = Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device)
-        self.post_attention_layernorm = Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device)
+        self.xielu = cfg.hidden_act == "xielu"
+        self.mlp = XIELUMLP(cfg, dtype, device) if self.xielu else MLP(cfg, dtype, device)
+        n1, n2 = ("attention_layernorm", "feedforward_layernorm") if cfg.apertus else ("input_layernorm", "post_attention_layernorm")
+        setattr(self, n1, Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device))
+        setattr(self, n2, Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device))
+        self._norm_names = (n1, n2)
+
+    def norms(self):
+        """(the norm in front of attention, the norm in front of the MLP): HF names them differently for Apertus."""
+        return getattr(self, self._norm_names[0]), getattr(self, self._norm_names[1])
 
     @torch.no_grad()
     def decode_step(self, x, cos, sin, key_mask, B, cache):
@@ -135,7 +204,8 @@ class DecoderLayer(nn.Module):
         and 57 vs 25 us per launch, so they stay separate launches.)"""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        h, _ = K.rmsnorm_fwd(x, self.input_layernorm.weight, self.input_layernorm.eps)
+        n1, n2 = self.norms()
+        h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
         qkv = K.linear_fwd(h, a._wqkv.tensor(), bias=a._bqkv.tensor() if a._bqkv is not None else None)
         if a.q_norm is not None:
             K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, cache.k, cache.v, cache.len)
@@ -144,8 +214,9 @@ class DecoderLayer(nn.Module):
         cache.len += 1
         o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
         x = K.linear_fwd(o.view(B, Hq * D), a.o_proj.weight, residual=x)
-        h, _ = K.rmsnorm_fwd(x, self.post_attention_layernorm.weight, self.post_attention_layernorm.eps)
-        act = K.swiglu_fwd(K.linear_fwd(h, m._wgu.tensor()), m.I)
+        h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
+        u = K.linear_fwd(h, m._wgu.tensor())
+        act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
         return K.linear_fwd(act, m.down_proj.weight, residual=x)
 
     @torch.no_grad()
@@ -156,7 +227,7 @@ class DecoderLayer(nn.Module):
         and out.  Same bits as decode_step."""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        n1, n2 = self.input_layernorm, self.post_attention_layernorm
+        n1, n2 = self.norms()
         qkv = K.decode_qkv_rope_append(x, a._wqkv.tensor(), a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
                                        cache.k, cache.v, cache.len, norm_w=n1.weight, eps=n1.eps)
         cache.len += 1
@@ -174,7 +245,7 @@ class DecoderLayer(nn.Module):
         a = self.self_attn
         return (self.can_decode_step(x, B, S, cache) and a.D == 128 and a.q_norm is None and K.decode_fusions() and x.shape[-1] <= 8192 and self.mlp.I % 4 == 0
                 and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
-                and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.input_layernorm.bias is None)
+                and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
 
     def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None):
         """rows (functional.LossRows, LAST layer of a training forward only): nothing after this layer's attention reads the
@@ -184,7 +255,8 @@ class DecoderLayer(nn.Module):
         if self.can_decode_step(x, B, S, cache):
             return self.decode_step(x, cos, sin, key_mask, B, cache)
         a = self.self_attn
-        h, x = self.input_layernorm(x)
+        n1, n2 = self.norms()
+        h, x = n1(x)
         if cache is None:      # projection (+ RoPE in its epilogue) + attention as one autograd node
             o = Fm.qkv_rope_attention(h, a._wqkv, a._bqkv, cos, sin, key_mask, B, S, a.Hq, a.Hkv, a.D, True, a.D ** -0.5,
                                       dummy=grad_dummy(a.q_proj.weight), qkn=a.qkn())
@@ -194,7 +266,10 @@ class DecoderLayer(nn.Module):
         if rows is not None:
             o, x = Fm.rows_select(o, rows), Fm.rows_select(x, rows)
         x = a.o_proj(o, residual=x)
-        h, x = self.post_attention_layernorm(x)
+        h, x = n2(x)
+        if self.xielu:
+            m = self.mlp
+            return Fm.xielu_mlp(h, m._wgu, m.down_proj.weight, m.act_fn, residual=x, dummy=grad_dummy(m.up_proj.weight))
         return Fm.swiglu_mlp(h, self.mlp._wgu, self.mlp.down_proj.weight, self.mlp.I, residual=x,
                              dummy=grad_dummy(self.mlp.gate_proj.weight))
 
@@ -231,7 +306,7 @@ class LayerKVCache:
 class DecoderModel(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
-        self.embed_tokens = Embedding(cfg.vocab_size, cfg.hidden_size, dtype=dtype, device=device)
+        self.embed_tokens = Embedding(cfg.vocab_size, cfg.hidden_size, dtype=dtype, device=device, padding_idx=cfg.pad_token_id)
         self.layers = nn.ModuleList([DecoderLayer(cfg, dtype, device) for _ in range(cfg.num_hidden_layers)])
         self.norm = Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device)
 

@@ -23,7 +23,7 @@ from .. import functional as Fm
 from .. import kernels as K
 from ..nn import FlatParams, grad_dummy
 from ..utils import get_torch_dtype, trace_range
-from .llm import CausalLM, CausalLMOutput, LLMConfig
+from .llm import XIELU, CausalLM, CausalLMOutput, LLMConfig
 from .modalities import AutoModality, BaseModality, BaseModalityConfig, BaseModalityProcessor
 from .presets import resolve_llm_config
 
@@ -159,6 +159,8 @@ class MultiModalModelForCausalLM(nn.Module):
                     module.bias.zero_()
             elif getattr(module, "_mm_pretrained", False):
                 pass                                                  # the MoE gate: built by its own from_pretrained, never re-initialised
+            elif isinstance(module, XIELU):
+                pass                                                  # Apertus: the activation's scalars keep HF's constructor values
             else:
                 for n, p in module.named_parameters(recurse=False):   # class/position embeddings, patch conv
                     p.normal_(mean=0.0, std=std)

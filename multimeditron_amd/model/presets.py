@@ -26,10 +26,22 @@ LLM_PRESETS: Dict[str, Dict[str, Any]] = {
                                          num_attention_heads=32, num_key_value_heads=8, head_dim=128, vocab_size=151936,
                                          rms_norm_eps=1e-6, tie_word_embeddings=True, max_position_embeddings=262144,
                                          rope_parameters={"rope_type": "default", "rope_theta": 5000000.0}),
+    # Apertus-8B (HF 5.15 models/apertus).  vocab, hidden, layers, heads, rms_norm_eps, max positions, untied embeddings and the
+    # rope block are ApertusConfig's own defaults in the installed transformers; intermediate_size 21504 and 8 key/value heads
+    # are from the public model card's config.json and could not be verified without hub access: a local checkpoint
+    # directory's config.json takes precedence (resolve_llm_config).
+    "swiss-ai/Apertus-8B-Instruct-2509": dict(model_type="apertus", hidden_size=4096, intermediate_size=21504, num_hidden_layers=32,
+                                               num_attention_heads=32, num_key_value_heads=8, head_dim=128, vocab_size=131072,
+                                               rms_norm_eps=1e-5, tie_word_embeddings=False, max_position_embeddings=65536,
+                                               hidden_act="xielu", pad_token_id=3,
+                                               rope_parameters={"rope_type": "llama3", "rope_theta": 12000000.0, "factor": 8.0,
+                                                                "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                                                                "original_max_position_embeddings": 8192}),
 }
 for _alias, _name in (("meta-llama/Llama-3.1-8B", "meta-llama/Llama-3.1-8B-Instruct"),
                       ("meta-llama/Llama-3.2-1B", "meta-llama/Llama-3.2-1B-Instruct"),
-                      ("Qwen/Qwen2-7B", "Qwen/Qwen2-7B-Instruct")):
+                      ("Qwen/Qwen2-7B", "Qwen/Qwen2-7B-Instruct"),
+                      ("swiss-ai/Apertus-8B-2509", "swiss-ai/Apertus-8B-Instruct-2509")):
     LLM_PRESETS[_alias] = LLM_PRESETS[_name]
 
 VISION_PRESETS: Dict[str, Dict[str, Any]] = {

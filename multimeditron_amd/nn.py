@@ -31,9 +31,10 @@ class Linear(nn.Module):
 
 
 class Embedding(nn.Module):
-    def __init__(self, num, dim, dtype=None, device=None):
+    def __init__(self, num, dim, dtype=None, device=None, padding_idx=None):
         super().__init__()
         self.num_embeddings, self.embedding_dim = num, dim
+        self.padding_idx = padding_idx      # as nn.Embedding: the row's gradient stays zero (HF builds embed_tokens with pad_token_id)
         self.weight = nn.Parameter(torch.empty(num, dim, dtype=dtype, device=device))
 
     def forward(self, ids, proj=None, batch_idx=None, token_range=None):
@@ -42,7 +43,8 @@ class Embedding(nn.Module):
         __call__ on purpose: forward pre-hooks (the trainer's wait for this table's in-flight AdamW update) fire for it."""
         B = ids.shape[0] if ids.dim() > 1 else 1
         S = ids.numel() // B
-        out = Fm.embed_splice(self.weight, ids, proj, batch_idx, token_range, B, S, dummy=grad_dummy(self.weight))
+        out = Fm.embed_splice(self.weight, ids, proj, batch_idx, token_range, B, S, dummy=grad_dummy(self.weight),
+                              padding_idx=self.padding_idx)
         return out.view(*ids.shape, self.embedding_dim)
 
 

@@ -4,10 +4,12 @@
 `from_training_config(cfg, tokenizer)` consumes the dict a recipe YAML parses to (config/config_alignment.yaml:1-59 and the
 cookbook/sft/*/config.yaml files have this layout):
 
-    base_llm            hub name or local directory of the LLM (-> MultimodalConfig.llm_path; shapes from model/presets.py)
+    base_llm            hub name or local directory of the LLM (-> MultimodalConfig.llm_path; shapes from model/presets.py:
+                        Llama 3.x, Qwen2, Qwen3, Apertus -- `model_type: apertus` builds the q/k-norm + xIELU decoder)
     base_model          None: bootstrap a fresh model (model.py:643-671) | a checkpoint directory: from_pretrained (train.py:131-137)
     token_size          LLM hidden size (-> MultimodalConfig.hidden_size)
-    tokenizer_type      ChatTemplate name: llama | apertus | qwen3 (train.py:97)
+    tokenizer_type      ChatTemplate name: llama | apertus | qwen3 (train.py:97); `apertus` goes with an Apertus base_llm
+                        (swiss-ai/Apertus-8B-Instruct-2509)
     attachment_token    placeholder token of an attachment in the text (train.py:101, data_loader.py:26)
     loaders[]           {loader_type, modality_type, **kwargs} -> AutoModalityLoader.from_name (train.py:113-118)
     modalities[]        {model_type, ...} -> AutoModality.config_from_dict (train.py:109-111); the alternate embedder / LLM of

@@ -134,6 +134,7 @@ class MultimodalTrainer:
             Fm.set_wgrad_deferral(None, ())
             return
         ids = []                                     # the first parameter of every trainable GEMM group of layers 0..n-1
+                                                     # (`_wgu`: the fused gate|up weight, or Apertus's up_proj alone)
         for layer in list(layers)[:n]:
             a, m = layer.self_attn, layer.mlp
             for group in (a._wqkv, Fm.as_group(a.o_proj.weight), m._wgu, Fm.as_group(m.down_proj.weight)):

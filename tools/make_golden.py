@@ -10,7 +10,7 @@ init), inputs, per-stage activations, logits, loss, selected grads, greedy token
 collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 
 Import recipe = SURVEY.md Appendix A (three harness-side shims, none edits the reference).
-The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 modules as called
+The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 / Apertus modules as called
 by the reference at model.py:433-444,517-526,595-640 and image_modality.py:130-137.
 """
 import io
@@ -119,6 +119,35 @@ def qwen3_cfg():
     return Qwen3Config(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=1,
                        head_dim=128, vocab_size=128, rms_norm_eps=1e-6, tie_word_embeddings=True,
                        rope_parameters={"rope_type": "default", "rope_theta": 1000000.0})
+
+
+def apertus_cfg():
+    """Apertus (q/k norm as Qwen3, `attention_layernorm` / `feedforward_layernorm`, the ungated xIELU MLP) at qwen3_cfg()'s shape;
+    untied embeddings and ApertusConfig's default RoPE (llama3, theta 12e6)."""
+    from transformers import ApertusConfig
+    return ApertusConfig(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=1,
+                         head_dim=128, vocab_size=128, tie_word_embeddings=False)
+
+
+# the raw xIELU scalars of each layer: bf16-representable, softplus images (1.313, 0.974) and (0.474, 1.701) against the
+# constructor's (0.8, 0.3)
+APERTUS_ALPHAS = ((1.0, 0.5), (-0.5, 1.5))
+
+
+def apertus_prepare_(model):
+    """After randomize_: distinct xIELU scalars per layer, and the `eps` buffers at their bf16-rounded value, so that the bf16
+    weights written below are exactly what this fp32 run used (`beta` = 0.5 is exact)."""
+    with torch.no_grad():
+        for layer, (ap, an) in zip(model.model.model.layers, APERTUS_ALPHAS):
+            f = layer.mlp.act_fn
+            f.alpha_p.fill_(ap)
+            f.alpha_n.fill_(an)
+            bf16_round_(f.alpha_p)
+            bf16_round_(f.alpha_n)
+            assert float(f.alpha_p) == ap and float(f.alpha_n) == an
+            bf16_round_(f.eps)
+            bf16_round_(f.beta)
+            assert float(f.beta) == 0.5
 
 
 SHARD_BYTES = 960 * 1024     # every committed file stays below 1 MiB
@@ -286,9 +315,11 @@ def run_case(model, batch, tag, out, do_grads=True, do_generate=False):
             out[f"{tag}.greedy_T{T}"] = ids.clone()
 
 
-def model_fixture(name, llm_cfg, seed, long_seq=False, sharded=False):
+def model_fixture(name, llm_cfg, seed, long_seq=False, sharded=False, prepare=None):
     with tempfile.TemporaryDirectory() as tmp:
         model = build_model(llm_cfg, seed, tmp)
+        if prepare is not None:
+            prepare(model)
         out = {}
         if long_seq:    # sequences that cross the D = 128 kernels' 64-key tiles and 256-row query blocks
             run_case(model, make_batch(seed + 1, 300, [[3], [2, 150]], "right"), "right", out)
@@ -822,7 +853,7 @@ def collator_fixture():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["llama", "trunc", "qwen2", "llama_d128", "qwen3", "siglip", "moe", "moe_pep", "collator", "ckpt"]
+    which = sys.argv[1:] or ["llama", "trunc", "qwen2", "llama_d128", "qwen3", "apertus", "siglip", "moe", "moe_pep", "collator", "ckpt"]
     if "llama" in which:
         model_fixture("tiny_clip_llama", llama_cfg(), 100)
     if "trunc" in which:
@@ -834,6 +865,9 @@ if __name__ == "__main__":
     if "qwen3" in which:    # sharded: every file below 1 MiB
         model_fixture("tiny_clip_qwen3", qwen3_cfg(), 900, sharded=True)
         model_fixture("tiny_clip_qwen3_long", qwen3_cfg(), 910, long_seq=True, sharded=True)
+    if "apertus" in which:
+        model_fixture("tiny_clip_apertus", apertus_cfg(), 1100, sharded=True, prepare=apertus_prepare_)
+        model_fixture("tiny_clip_apertus_long", apertus_cfg(), 1110, long_seq=True, sharded=True, prepare=apertus_prepare_)
     if "siglip" in which:
         siglip_fixture()
     if "moe" in which:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Small HBM-bound kernels in isolation at the shapes of the 8B step (decoder rows 8192 x 4096, ViT-L rows 1028 x 1024/4096):
 time per launch and the bytes each must move, so that an in-step duration (rocprofv3, other streams sharing the chip) can be
-told from the kernel's own speed.  Also Qwen3's fused per-head q/k RMSNorm + RoPE at the Qwen3-4B step's shape."""
+told from the kernel's own speed.  Also Qwen3's fused per-head q/k RMSNorm + RoPE at the Qwen3-4B step's shape, and the two MLP
+activations at Apertus-8B width (M = 8192, I = 21504): SwiGLU and xIELU, forward and backward."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -67,6 +68,24 @@ def main():
     out = torch.zeros(D, device=dev, dtype=bf)
     timeit(f"reduce_partials {dwq.shape[0]}x{D} (x2 per layer)", lambda: K.reduce_partials(dwq, out, True), dwq.numel() * 4)
     timeit(f"rope_apply {T}x{nh}x{D} (Llama path)", lambda: K.rope_apply_(qkv, T, nh, D, W, cos, sin), 2 * T * nh * D * 2 + tab)
+    # the MLP activations at Apertus-8B width: SwiGLU reads gate | up (2 I) and writes I; xIELU reads and writes I (its backward
+    # also leaves the two scalar gradients' partial sums, finished by xielu_reduce)
+    M, I = 8192, 21504
+    gu = torch.randn(M, 2 * I, device=dev).to(bf)
+    d = torch.randn(M, I, device=dev).to(bf)
+    timeit(f"swiglu_fwd {M}x{I}", lambda: K.swiglu_fwd(gu, I), 3 * M * I * 2, it=20)
+    timeit(f"swiglu_bwd {M}x{I}", lambda: K.swiglu_bwd(gu, d, I), 5 * M * I * 2, it=20)
+    del gu
+    u = torch.randn(M, I, device=dev).to(bf)
+    ap_, an_ = torch.full((1,), 0.2041, device=dev, dtype=bf), torch.full((1,), -1.0469, device=dev, dtype=bf)
+    beta, eps = 0.5, float(torch.tensor(-1e-6, dtype=bf))
+    timeit(f"xielu_fwd {M}x{I}", lambda: K.xielu_fwd(u, ap_, an_, beta, eps), 2 * M * I * 2, it=20)
+    timeit(f"xielu_bwd {M}x{I} (+ partial sums)", lambda: K.xielu_bwd(u, d, ap_, an_, beta, eps), 3 * M * I * 2, it=20)
+    timeit(f"xielu_bwd {M}x{I} (frozen scalars)", lambda: K.xielu_bwd(u, d, ap_, an_, beta, eps, want_dalpha=False), 3 * M * I * 2, it=20)
+    _, part = K.xielu_bwd(u, d, ap_, an_, beta, eps)
+    gp, gn = torch.zeros(1, device=dev, dtype=bf), torch.zeros(1, device=dev, dtype=bf)
+    timeit(f"xielu_reduce {part.shape[0]}x2", lambda: K.xielu_reduce(part, ap_, an_, gp, gn, False, False), part.numel() * 4)
+    del u, d
     x = torch.empty(1 << 28, device=dev, dtype=bf)
     timeit("torch zero_ 512 MB", lambda: x.zero_(), x.numel() * 2, it=10)
 
