@@ -43,6 +43,9 @@ enum {
   MM_EPI_GELU_TANH = 32  /* tanh GELU (HF:activations.py gelu_pytorch_tanh; SigLIP MLP) */
 };
 
+/* most problems in one grouped launch (the *_batched entry points below) */
+enum { MM_GROUP_MAX = 16 };
+
 int mm_version(void);
 const char* mm_error_string(int code);
 /* tuning / A-B switches (benchmarks and the trainer): "gemm_persist" 0|1 (persistent one-workgroup-per-CU grid; the
@@ -99,6 +102,29 @@ int mm_gemm_swiglu_bwd(int dtype, int M, int I, int H, const void* dY, int lddy,
 
 /* column sums: out[N] (+)= sum_m X[m,n]   (bias gradients)                                           */
 int mm_colsum(int dtype, const void* X, int M, int N, int ldx, void* out, int accumulate, void* stream);
+
+/* ---- grouped launches: the expert as a batch dimension (MoE image modality: E CLIP towers of equal shape on every image;
+ * reference modalities/image_modality_moe.py:150-161 loops the experts) ------------------------------------------------------
+ * `groups` problems of EQUAL shape in one launch, 1 <= groups <= MM_GROUP_MAX (MM_ERR_ARG otherwise).  Per-problem pointers arrive as
+ * HOST arrays of `groups` device pointers; the entry point copies them by value into the kernel's arguments: no device table, no
+ * copy, no allocation, no synchronisation (capturable like the rest of the ABI).  Entries may repeat (the patch-embedding GEMM
+ * reads the same patches for every expert) and need not be evenly spaced.  A NULL array or a NULL entry of a required operand is
+ * MM_ERR_ARG.  All checks come before any launch.  Problem g's result has the bits the stand-alone entry point gives for it alone.
+ * mm_gemm_batched: mm_gemm on every problem (alignment rules, epilogue order and the single rounding as there).  MM_F32, and for
+ *   MM_BF16 the problems that take the 128x128, 64x128 or 64x64 tiles (chosen from the tile count of the WHOLE batch; every bf16
+ *   kernel adds the products of a K-step in the same order, so the tile does not change the bits).  MM_ERR_UNSUPPORTED, before any
+ *   launch, where mm_gemm would take a 256-wide tile, the M <= 16 weight-streaming kernels or an activation outside NT: those
+ *   problems fill the chip on their own, so the caller loops mm_gemm (kernels.gemm_batched does).
+ * mm_gemm_act_fwd_batched: mm_gemm_act_fwd (PRE and ACT per problem) under the same rules.
+ * mm_colsum_batched: mm_colsum per problem (the same row partition: same bits).                                                    */
+int mm_gemm_batched(int dtype, int layout, int groups, int M, int N, int K, const void* const* A, int lda, const void* const* B,
+                    int ldb, void* const* C, int ldc, const void* const* bias, const void* const* residual, int ldr, int epilogue,
+                    void* stream);
+int mm_gemm_act_fwd_batched(int dtype, int groups, int M, int N, int K, const void* const* X, int ldx, const void* const* W, int ldw,
+                            const void* const* bias, void* const* PRE, int ldpre, void* const* ACT, int ldact,
+                            const void* const* residual, int ldr, int epilogue, void* stream);
+int mm_colsum_batched(int dtype, const void* const* X, int groups, int M, int N, int ldx, void* const* out, int accumulate,
+                      void* stream);
 
 /* ids outside [0, vocab): *flag (device int, sticky) = 1.  nn.Embedding raises for them (model.py:433 embeds every id of the
  * batch before the splice); mm_embed_splice_fwd reads row 0 instead of out of bounds, so the caller checks this flag (the
@@ -200,6 +226,18 @@ int mm_reduce_partials(int dtype, const float* partial, int nblk, int H, void* o
 /* the same for two (partials, output) pairs in one launch: LayerNorm's dw and db */
 int mm_reduce_partials2(int dtype, const float* partial0, const float* partial1, int nblk, int H, void* out0, void* out1, int accumulate0,
                         int accumulate1, void* stream);
+/* Grouped LayerNorm (conventions of mm_gemm_batched): x, y, dy, dx, dres are ONE expert-major buffer [groups * R, H], mean / rstd
+ * [groups * R]; w[] / b[] are per expert.  A backward workgroup never spans two experts: expert g owns the partial blocks
+ * [g * nb, (g + 1) * nb), nb = mm_norm_bwd_blocks(R), partitioned as a stand-alone call with M = R partitions them (dw_partial /
+ * db_partial: f32 [groups * nb, H]).  mm_reduce_partials2_batched reduces expert g's nblk blocks into out0[g] / out1[g] in the
+ * order of mm_reduce_partials2.  Every output has the bits of `groups` stand-alone calls.                                       */
+int mm_layernorm_fwd_batched(int dtype, const void* x, const void* const* w, const void* const* b, int groups, int R, int H, float eps,
+                             void* y, float* mean, float* rstd, void* stream);
+int mm_layernorm_bwd_batched(int dtype, const void* dy, const void* x, const void* const* w, int groups, const float* mean,
+                             const float* rstd, int R, int H, void* dx, float* dw_partial, float* db_partial, const void* dres,
+                             void* stream);
+int mm_reduce_partials2_batched(int dtype, const float* partial0, const float* partial1, int groups, int nblk, int H, void* const* out0,
+                                void* const* out1, int accumulate0, int accumulate1, void* stream);
 
 /* ---- RoPE: HF:llama:113-160 (rotate_half form) --------------------------------------------------------
  * cos/sin tables [T, D/2] f32 from position_ids and inv_freq (HF:llama:113-127; llama3 scaling is applied by

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("MM_HIP_LIBRARY") or os.path.join(_PKG, "libmmhip.so")
 MM_BF16, MM_F32 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS, EPI_GELU_ERF, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_ACCUMULATE, EPI_GELU_TANH = 1, 2, 4, 8, 16, 32
+ERR_UNSUPPORTED = -3
+GROUP_MAX = 16            # MM_GROUP_MAX: most problems in one grouped launch
 GELU_KIND = {EPI_GELU_ERF: 0, EPI_QUICK_GELU: 1, EPI_GELU_TANH: 2}      # mm_gelu_fwd/bwd `kind` of each epilogue flag
 
 
@@ -70,7 +72,9 @@ def call(name: str, *args):
     rc = getattr(L, name)(*args)
     if rc != 0:
         msg = L.mm_error_string(rc)
-        raise MMHipError(f"{name} failed: {rc} ({msg.decode() if msg else '?'})")
+        err = MMHipError(f"{name} failed: {rc} ({msg.decode() if msg else '?'})")
+        err.code = rc              # MM_ERR_*: callers with a fallback for MM_ERR_UNSUPPORTED (the grouped GEMMs) look at it
+        raise err
 
 
 def get_option(name: str) -> int:

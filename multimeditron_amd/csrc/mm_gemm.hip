@@ -604,6 +604,37 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
   gemm_epilogue<4, 4>(g, acc, m0 + wm * 64, n0 + wn * 64);
 }
 
+// ---- grouped launches (mm_gemm_batched, mm_gemm_act_fwd_batched): `groups` problems of equal shape in ONE grid.  blockIdx.y is the
+// problem; its operand pointers come out of a table passed BY VALUE in the kernel-argument segment (no device table, no copy), so
+// the selection is a scalar load at a uniform offset and the buffer descriptors stay in SGPRs.  A problem's workgroups walk its
+// tiles exactly as a stand-alone launch of the same tile would (blockIdx.x / gridDim.x are per problem): same bits.
+constexpr int GEMM_GROUP_MAX = MM_GROUP_MAX;
+struct GemmBatch {
+  const void* A[GEMM_GROUP_MAX];
+  const void* B[GEMM_GROUP_MAX];
+  void* C[GEMM_GROUP_MAX];
+  const void* bias[GEMM_GROUP_MAX];
+  const void* residual[GEMM_GROUP_MAX];
+  void* C2[GEMM_GROUP_MAX];            // mm_gemm_act_fwd_batched: the pre-activations
+};
+template <typename P>
+__device__ __forceinline__ P uniform_ptr(P p) {      // provably wave-uniform: both halves through readfirstlane
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (P)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ GemmArgs batch_problem(const GemmArgs& g, const GemmBatch& t) {
+  const int p = blockIdx.y;
+  GemmArgs h = g;
+  h.A = uniform_ptr(t.A[p]);
+  h.B = uniform_ptr(t.B[p]);
+  h.C = uniform_ptr(t.C[p]);
+  h.bias = uniform_ptr(t.bias[p]);
+  h.residual = uniform_ptr(t.residual[p]);
+  h.C2 = uniform_ptr(t.C2[p]);
+  return h;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // v2 main kernel: 256x128x64 tile, 8 waves (4 along M x 2 along N, 64x64 each), operands streamed HBM -> LDS by
 // LDS-DMA (buffer_load_dwordx4 ... lds: no staging registers, no ds_write, hardware bounds check) into a 3-deep
@@ -903,7 +934,7 @@ __device__ __forceinline__ bf16x8 frag_load2(const char* tile, int xb, int ks) {
 // BMxBN block tile, 8 waves as WGM x WGN, STAGES-deep LDS ring (3: counted vmcnt keeps one tile in flight across the
 // barrier; 2: the next tile's DMA is issued right after the barrier and has one whole compute phase to land).
 template <bool A_KC, bool B_KC, int BM_, int BN_, int WGM, int STAGES, int ISSUE_WAVES, int EK = 0>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel(GemmArgs g) {
+__device__ __forceinline__ void gemm_bf16_dma_body(const GemmArgs& g) {
   constexpr int WGN = 8 / WGM;
   constexpr int MREP = BM_ / WGM / 16, NREP = BN_ / WGN / 16;
   constexpr int A_BYTES = BM_ * G_BK * 2, B_BYTES = BN_ * G_BK * 2, STAGE_BYTES = A_BYTES + B_BYTES;
@@ -1107,6 +1138,19 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel(GemmArgs g) {
       else gemm_epilogue_plain<MREP, NREPH, false, EK == 1>(g, acch, hm0 + wm * (BM_ / WGM), hn0 + wn * (BNH / WGN));
     }
   }
+}
+
+template <bool A_KC, bool B_KC, int BM_, int BN_, int WGM, int STAGES, int ISSUE_WAVES, int EK = 0>
+__global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel(GemmArgs g) {
+  gemm_bf16_dma_body<A_KC, B_KC, BM_, BN_, WGM, STAGES, ISSUE_WAVES, EK>(g);
+}
+
+// the small tiles (128x128, 64x128, 64x64) on a grid of (workgroups per problem, problems): see batch_problem
+template <bool A_KC, bool B_KC, int BM_, int BN_, int WGM, int STAGES, int ISSUE_WAVES, int EK = 0>
+__global__ __launch_bounds__(512, 2) void gemm_bf16_dma_kernel_batched(GemmArgs g, GemmBatch t) {
+  static_assert(BM_ * BN_ <= 128 * 128, "grouped launches exist for the small tiles only");
+  const GemmArgs h = batch_problem(g, t);
+  gemm_bf16_dma_body<A_KC, B_KC, BM_, BN_, WGM, STAGES, ISSUE_WAVES, EK>(h);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2157,11 +2201,93 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   }
 }
 
+// gemm_f32_kernel's body once more, for the grouped launch below.  A copy on purpose: with the body in a shared inline function the
+// stand-alone kernel's register allocation shifts (42 -> 40 SGPRs), and existing kernels must compile to what they compiled to.
+template <int LAYOUT>
+__device__ __forceinline__ void gemm_f32_body(const GemmArgs& g) {
+  constexpr int TM = 64, TN = 64, TK = 16, LD = 80;  // LD = 80: rows k, k+1 land on disjoint bank halves
+  __shared__ float As[TK * LD];
+  __shared__ float Bs[TK * LD];
+  const int pm = blockIdx.x % g.nbm, pn = blockIdx.x / g.nbm;
+  const int m0 = pm * TM, n0 = pn * TN;
+  const float* A = (const float*)g.A;
+  const float* B = (const float*)g.B;
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wm = w >> 1, wn = w & 1;
+  f32x4 acc[2][2];
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int k0 = 0; k0 < g.K; k0 += TK) {
+    // each thread loads 4 elements of A-tile and 4 of B-tile
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int idx = threadIdx.x + e * 256;  // 0..1023 over [TK][64]
+      int k, x;
+      // A: NT/NN are [M][K] (k fastest), TN is [K][M] (m fastest)
+      if (LAYOUT == MM_GEMM_TN) { x = idx & 63; k = idx >> 6; } else { k = idx & 15; x = idx >> 4; }
+      float va = 0.f;
+      if (m0 + x < g.M && k0 + k < g.K)
+        va = (LAYOUT == MM_GEMM_TN) ? A[(int64_t)(k0 + k) * g.lda + m0 + x] : A[(int64_t)(m0 + x) * g.lda + k0 + k];
+      As[k * LD + x] = va;
+      // B: NT is [N][K] (k fastest), NN/TN are [K][N] (n fastest)
+      if (LAYOUT == MM_GEMM_NT) { k = idx & 15; x = idx >> 4; } else { x = idx & 63; k = idx >> 6; }
+      float vb = 0.f;
+      if (n0 + x < g.N && k0 + k < g.K)
+        vb = (LAYOUT == MM_GEMM_NT) ? B[(int64_t)(n0 + x) * g.ldb + k0 + k] : B[(int64_t)(k0 + k) * g.ldb + n0 + x];
+      Bs[k * LD + x] = vb;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < TK; kk += 4) {
+      float fa[2], fb[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[i] = As[(kk + (l >> 4)) * LD + wm * 32 + i * 16 + (l & 15)];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fb[j] = Bs[(kk + (l >> 4)) * LD + wn * 32 + j * 16 + (l & 15)];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j], fa[i], acc[i][j], 0, 0, 0);  // swapped: D^T
+    }
+    __syncthreads();
+  }
+  float* C = (float*)g.C;
+  const float* bias = (const float*)g.bias;
+  const float* R = (const float*)g.residual;
+  for (int i = 0; i < 2; ++i) {
+    const int m = m0 + wm * 32 + i * 16 + (l & 15);
+    if (m >= g.M) continue;
+    for (int j = 0; j < 2; ++j) {
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn * 32 + j * 16 + 4 * (l >> 4) + r;
+        if (n >= g.N) continue;
+        float v = acc[i][j][r];
+        if (g.epi & MM_EPI_BIAS) v += bias[n];
+        if (g.epi & MM_EPI_GELU_ERF) v = act_gelu_erf(v);
+        else if (g.epi & MM_EPI_QUICK_GELU) v = act_quick_gelu(v);
+        else if (g.epi & MM_EPI_GELU_TANH) v = act_gelu_tanh(v);
+        if (g.epi & MM_EPI_RESIDUAL) v += R[(int64_t)m * g.ldr + n];
+        float* cp = C + (int64_t)m * g.ldc + n;
+        if (g.epi & MM_EPI_ACCUMULATE) v += *cp;
+        *cp = v;
+      }
+    }
+  }
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void gemm_f32_kernel_batched(GemmArgs g, GemmBatch t) {
+  const GemmArgs h = batch_problem(g, t);
+  gemm_f32_body<LAYOUT>(h);
+}
+
 // column sums (bias gradients): block = 256 threads = 32 column groups (16 bytes each) x 8 row lanes; the grid also
 // splits the rows (gridDim.y) and finishes with float atomics into an f32 scratch only when needed -- here rows are
 // few enough (<= 8192) that one block per 32 column groups sweeping all rows with 8 row lanes is HBM-efficient.
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* X, int M, int N, int ldx, T* out, int accumulate) {
+__device__ __forceinline__ void colsum_body(const T* X, int M, int N, int ldx, T* out, int accumulate) {
   // one block = 8 column chunks of 16 B (one 128-B line per row) x 32 row lanes: the bias-gradient inputs are short
   // (ViT: 1028 rows) and narrow, so parallelism comes from many small blocks and 4 independent loads per lane in flight
   constexpr int VN = Vec16<T>::N, CG = 8, RL = 32;
@@ -2203,6 +2329,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* X, int M, int N, i
       out[n] = from_f32<T>(t);
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel(const T* X, int M, int N, int ldx, T* out, int accumulate) {
+  colsum_body<T>(X, M, N, ldx, out, accumulate);
+}
+
+// mm_colsum_batched: blockIdx.y = the problem; each problem's rows are partitioned as a stand-alone launch partitions them
+struct ColsumBatch { const void* X[GEMM_GROUP_MAX]; void* out[GEMM_GROUP_MAX]; };
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel_batched(ColsumBatch t, int M, int N, int ldx, int accumulate) {
+  colsum_body<T>((const T*)uniform_ptr(t.X[blockIdx.y]), M, N, ldx, (T*)uniform_ptr(t.out[blockIdx.y]), accumulate);
 }
 
 }  // namespace
@@ -2668,6 +2806,176 @@ static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
   } else {
     return MM_ERR_UNSUPPORTED;
   }
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+// ---- grouped launches: `groups` equal-shaped problems in one grid (the MoE image modality's E expert towers) -----------------
+// The tile is chosen as gemm_launch chooses it among the small LDS-DMA tiles, but from the tile count of the whole batch (every
+// bf16 kernel adds a K-step's products in the same order, so the tile does not change the bits).  Problems that gemm_launch sends to a 256-wide tile, the
+// M <= 16 weight-streaming kernels or a fused form are MM_ERR_UNSUPPORTED: those fill the chip on their own.
+static int gemm_launch_batched(GemmArgs g, const GemmBatch& t, int groups, int dtype, int layout, hipStream_t s) {
+  g.pipe = g_opt_epi_pipe;
+  const int M = g.M, N = g.N, K = g.K, lda = g.lda, ldb = g.ldb, ldc = g.ldc, ldr = g.ldr, epilogue = g.epi;
+  const bool acts = (epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH)) != 0;
+  if (dtype == MM_F32) {
+    g.nbm = (M + 63) / 64;
+    g.nbn = (N + 63) / 64;
+    if ((int64_t)g.nbm * g.nbn > 0x7FFFFFFF) return MM_ERR_ARG;
+    dim3 grid((unsigned)(g.nbm * g.nbn), (unsigned)groups), block(256);
+    switch (layout) {
+      case MM_GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_NT>), grid, block, 0, s, g, t); break;
+      case MM_GEMM_NN: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_NN>), grid, block, 0, s, g, t); break;
+      default: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_TN>), grid, block, 0, s, g, t); break;
+    }
+    MM_CHECK_LAUNCH();
+    g_last_kernel = 30;
+    return MM_OK;
+  }
+  if (dtype != MM_BF16) return MM_ERR_UNSUPPORTED;
+  if ((lda & 7) || (ldb & 7) || (ldc & 3) || ((epilogue & MM_EPI_RESIDUAL) && (ldr & 3))) return MM_ERR_ALIGN;
+  for (int p = 0; p < groups; ++p)
+    if (!mm_aligned16(t.A[p]) || !mm_aligned16(t.B[p]) || (((uintptr_t)t.C[p]) & 7)) return MM_ERR_ALIGN;
+  static const int forced_env = [] {
+    const char* e = getenv("MM_GEMM_KERNEL");
+    return !e ? 0 : (e[0] == 'v' ? 1 : (e[0] == 'b' ? 3 : 2));
+  }();
+  const int forced = g_opt_kernel ? g_opt_kernel : forced_env;
+  if (forced == 0 && g_opt_skinny && layout == MM_GEMM_NT && M <= 16) return MM_ERR_UNSUPPORTED;   // the weight-streaming kernels
+  if (acts && layout != MM_GEMM_NT) return MM_ERR_UNSUPPORTED;
+  const int64_t ldmax = (int64_t)ldc > ldr ? ldc : ldr;
+  const bool fits32 = ldmax * 128 * 2 + (int64_t)N * 2 < 0x7FFFFFFFll &&
+                      ((layout == MM_GEMM_NT) || ((int64_t)K * ldb * 2 < 0xFFFFFFFFll && (layout != MM_GEMM_TN || (int64_t)K * lda * 2 < 0xFFFFFFFFll)));
+  const int64_t tiles_128 = (int64_t)((M + 255) / 256) * ((N + 127) / 128);
+  const int64_t tiles_256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
+  // the batch's tile: small_variant's thresholds on the tiles of all the problems together
+  const int64_t tb = (int64_t)groups * ((M + 127) / 128) * ((N + 127) / 128);
+  const int small = g_opt_small >= 0 ? g_opt_small : (tb <= 96 ? 4 : (tb <= 320 ? 3 : 0));
+  const bool keep_pre = g.C2 != nullptr;
+  int variant = 0;
+  if (keep_pre) {
+    if (!fits32 || forced == 1) return MM_ERR_UNSUPPORTED;
+    variant = (forced >= 4 && forced <= 6) ? forced - 1 : small;
+    if (variant < 3) variant = 3;
+  } else if (fits32) {
+    if (forced >= 2 && forced <= 6) variant = forced - 1;
+    else if (forced == 0 && tiles_128 >= 192) variant = MM_DEFAULT_DMA_VARIANT(tiles_256);
+    else if (forced == 0) variant = small;
+  }
+  if (variant == 1 || variant == 2) return MM_ERR_UNSUPPORTED;       // the 256-wide tiles (8- and 4-wave kernels)
+  // more than 320 tiles in the batch: mm_gemm's register-staged 128x128 kernel has no grouped form; the LDS-DMA kernel of the same
+  // tile runs instead (same bits), except past the 32-bit offsets and where that kernel was asked for by name
+  if (variant == 0 && fits32 && forced != 1) variant = 3;
+  if (variant == 0) return MM_ERR_UNSUPPORTED;
+  {
+    static const int TBM[6] = {0, 256, 256, 128, 64, 64}, TBN[6] = {0, 128, 256, 128, 128, 64};
+    const int bm = TBM[variant], bn = TBN[variant];
+    g.nbm = (M + bm - 1) / bm;
+    g.nbn = (N + bn - 1) / bn;
+    const int64_t nwg = (int64_t)g.nbm * g.nbn;
+    if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
+    const size_t lds = 2 * (bm + bn) * G_BK * 2;
+    static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
+    const int64_t nblk = g_opt_persist ? (nwg < (int64_t)ncu ? nwg : (int64_t)ncu) : nwg;      // per problem, as a stand-alone launch
+    dim3 grid((unsigned)nblk, (unsigned)groups), block(512);
+#define MM_LAUNCH_ONE_B(...)                                                                                             \
+  do {                                                                                                                   \
+    auto kfn = gemm_bf16_dma_kernel_batched<__VA_ARGS__>;                                                                \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
+    hipLaunchKernelGGL(kfn, grid, block, lds, s, g, t);                                                                  \
+  } while (0)
+#define MM_LAUNCH_DMA_B(AKC, BKC, EK)                                                                                    \
+  do {                                                                                                                   \
+    if (variant == 3) MM_LAUNCH_ONE_B(AKC, BKC, 128, 128, 2, 2, 4, EK);                                                  \
+    else if (variant == 4) MM_LAUNCH_ONE_B(AKC, BKC, 64, 128, 2, 2, 4, EK);                                              \
+    else MM_LAUNCH_ONE_B(AKC, BKC, 64, 64, 2, 2, 4, EK);                                                                 \
+  } while (0)
+    if (acts) {
+      MM_LAUNCH_DMA_B(true, true, 1);
+    } else {
+      switch (layout) {
+        case MM_GEMM_NT: MM_LAUNCH_DMA_B(true, true, 0); break;
+        case MM_GEMM_NN: MM_LAUNCH_DMA_B(true, false, 0); break;
+        default: MM_LAUNCH_DMA_B(false, false, 0); break;
+      }
+    }
+#undef MM_LAUNCH_ONE_B
+#undef MM_LAUNCH_DMA_B
+  }
+  MM_CHECK_LAUNCH();
+  g_last_kernel = variant;
+  return MM_OK;
+}
+
+static int batch_table(GemmBatch& t, int groups, const void* const* A, const void* const* B, void* const* C, const void* const* bias,
+                       const void* const* residual, void* const* C2, int epilogue) {
+  if (groups < 1 || groups > MM_GROUP_MAX || !A || !B || !C) return MM_ERR_ARG;
+  if ((epilogue & MM_EPI_BIAS) && !bias) return MM_ERR_ARG;
+  if ((epilogue & MM_EPI_RESIDUAL) && !residual) return MM_ERR_ARG;
+  memset(&t, 0, sizeof(t));
+  for (int p = 0; p < groups; ++p) {
+    if (!A[p] || !B[p] || !C[p] || (C2 && !C2[p])) return MM_ERR_ARG;
+    if ((epilogue & MM_EPI_BIAS) && !bias[p]) return MM_ERR_ARG;
+    if ((epilogue & MM_EPI_RESIDUAL) && !residual[p]) return MM_ERR_ARG;
+    t.A[p] = A[p];
+    t.B[p] = B[p];
+    t.C[p] = C[p];
+    t.bias[p] = (epilogue & MM_EPI_BIAS) ? bias[p] : nullptr;
+    t.residual[p] = (epilogue & MM_EPI_RESIDUAL) ? residual[p] : nullptr;
+    t.C2[p] = C2 ? C2[p] : nullptr;
+  }
+  return MM_OK;
+}
+
+extern "C" int mm_gemm_batched(int dtype, int layout, int groups, int M, int N, int K, const void* const* A, int lda,
+                               const void* const* B, int ldb, void* const* C, int ldc, const void* const* bias,
+                               const void* const* residual, int ldr, int epilogue, void* stream) {
+  if (M < 0 || N < 0 || K < 0 || layout < 0 || layout > 2 || (epilogue & ~63)) return MM_ERR_ARG;
+  GemmBatch t;
+  const int rc = batch_table(t, groups, A, B, C, bias, residual, nullptr, epilogue);
+  if (rc != MM_OK) return rc;
+  if (M == 0 || N == 0) return MM_OK;
+  GemmArgs g{M, N, K, t.A[0], lda, t.B[0], ldb, t.C[0], ldc, t.bias[0], t.residual[0], ldr, epilogue, 0, 0, 0, 0, nullptr, 0, nullptr, 0};
+  return gemm_launch_batched(g, t, groups, dtype, layout, (hipStream_t)stream);
+}
+
+extern "C" int mm_gemm_act_fwd_batched(int dtype, int groups, int M, int N, int K, const void* const* X, int ldx, const void* const* W,
+                                       int ldw, const void* const* bias, void* const* PRE, int ldpre, void* const* ACT, int ldact,
+                                       const void* const* residual, int ldr, int epilogue, void* stream) {
+  if (M < 0 || N <= 0 || K <= 0 || !PRE) return MM_ERR_ARG;
+  const int acts = epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH);
+  if (!acts || (acts & (acts - 1)) || (epilogue & ~(acts | MM_EPI_BIAS | MM_EPI_RESIDUAL))) return MM_ERR_ARG;
+  GemmBatch t;
+  const int rc = batch_table(t, groups, X, W, ACT, bias, residual, PRE, epilogue);
+  if (rc != MM_OK) return rc;
+  if (M == 0) return MM_OK;
+  if (dtype != MM_BF16 || M <= 16) return MM_ERR_UNSUPPORTED;
+  if (ldpre & 3) return MM_ERR_ALIGN;
+  for (int p = 0; p < groups; ++p)
+    if (((uintptr_t)t.C2[p]) & 7) return MM_ERR_ALIGN;
+  GemmArgs g{M, N, K, t.A[0], ldx, t.B[0], ldw, t.C[0], ldact, t.bias[0], t.residual[0], ldr, epilogue, 0, 0, 0, 0, t.C2[0], ldpre, nullptr, 0};
+  return gemm_launch_batched(g, t, groups, dtype, MM_GEMM_NT, (hipStream_t)stream);
+}
+
+extern "C" int mm_colsum_batched(int dtype, const void* const* X, int groups, int M, int N, int ldx, void* const* out, int accumulate,
+                                 void* stream) {
+  if (groups < 1 || groups > MM_GROUP_MAX || !X || !out || M < 0 || N <= 0) return MM_ERR_ARG;
+  const int vn = dtype == MM_BF16 ? 8 : 4;
+  ColsumBatch t;
+  memset(&t, 0, sizeof(t));
+  for (int p = 0; p < groups; ++p) {
+    if (!X[p] || !out[p]) return MM_ERR_ARG;
+    t.X[p] = X[p];
+    t.out[p] = out[p];
+  }
+  if (ldx % vn) return MM_ERR_ALIGN;
+  for (int p = 0; p < groups; ++p)
+    if (!mm_aligned16(t.X[p])) return MM_ERR_ALIGN;
+  dim3 grid((N + 8 * vn - 1) / (8 * vn), groups), block(256);
+  if (dtype == MM_BF16)
+    hipLaunchKernelGGL(colsum_kernel_batched<bf16>, grid, block, 0, (hipStream_t)stream, t, M, N, ldx, accumulate);
+  else
+    hipLaunchKernelGGL(colsum_kernel_batched<float>, grid, block, 0, (hipStream_t)stream, t, M, N, ldx, accumulate);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }

@@ -2,6 +2,8 @@
 // RMSNorm, LayerNorm, RoPE, SwiGLU, GELU, residual add, cross-entropy, arg-max.
 // All: 16-byte vector accesses, fp32 math, wave-shuffle + small LDS reductions, one pass over HBM
 // where the algorithm allows (rows up to 8K elements are kept in registers between the two sweeps).
+#include <string.h>
+
 #include "mm_common.h"
 
 namespace {
@@ -110,8 +112,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* dy, const T* 
 
 // ---------------------------------------------------------------- LayerNorm
 template <typename T, int CH>
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* x, const T* w, const T* b, int M, int H, float eps, T* y,
-                                                            float* mean, float* rstd) {
+__device__ __forceinline__ void layernorm_fwd_body(const T* x, const T* w, const T* b, int M, int H, float eps, T* y,
+                                                   float* mean, float* rstd) {
   __shared__ float red[8];
   constexpr int VN = Vec16<T>::N;
   const int row = blockIdx.x;
@@ -148,6 +150,32 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* x, const T*
       *(Vec16<T>*)(y + (int64_t)row * H + e) = o;
     }
   }
+}
+
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* x, const T* w, const T* b, int M, int H, float eps, T* y,
+                                                            float* mean, float* rstd) {
+  layernorm_fwd_body<T, CH>(x, w, b, M, H, eps, y, mean, rstd);
+}
+
+// ---- grouped forms (mm_layernorm_*_batched, mm_reduce_partials2_batched): E experts' rows in one expert-major buffer [E * R, H],
+// weights per expert from a pointer table passed by value in the kernel arguments.  The grid's second (third) dimension is the
+// expert; inside it a workgroup does what the stand-alone kernel does on that expert's R rows: same partition, same bits.
+struct NormBatch { const void* w[MM_GROUP_MAX]; const void* b[MM_GROUP_MAX]; };
+template <typename P>
+__device__ __forceinline__ P uniform_ptr(P p) {
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (P)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void layernorm_fwd_kernel_batched(const T* x, NormBatch t, int R, int H, float eps, T* y,
+                                                                    float* mean, float* rstd) {
+  const int g = blockIdx.y;
+  const int64_t r0 = (int64_t)g * R;
+  layernorm_fwd_body<T, CH>(x + r0 * H, (const T*)uniform_ptr(t.w[g]), (const T*)uniform_ptr(t.b[g]), R, H, eps, y + r0 * H, mean + r0,
+                            rstd + r0);
 }
 
 template <typename T, int CH>
@@ -217,6 +245,87 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* dy, const T
   }
 }
 
+// layernorm_bwd_kernel's body once more, for the grouped launch below.  A copy on purpose: with the body in a shared inline function
+// the stand-alone kernel's register allocation shifts (188 -> 186 VGPRs), and existing kernels must compile to what they compiled to.
+template <typename T, int CH>
+__device__ __forceinline__ void layernorm_bwd_body(const T* dy, const T* x, const T* w, const float* mean,
+                                                   const float* rstd, int M, int H, T* dx, float* dwp, float* dbp, const T* dres) {
+  __shared__ float red[8];
+  constexpr int VN = Vec16<T>::N;
+  float dw[CH][VN], db[CH][VN];
+  Vec16<T> wv[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (c * 256 + threadIdx.x) * VN;
+    if (e < H) wv[c] = *(const Vec16<T>*)(w + e);
+#pragma unroll
+    for (int i = 0; i < VN; ++i) { dw[c][i] = 0.f; db[c][i] = 0.f; }
+  }
+  const int r0 = blockIdx.x * NORM_BWD_ROWS_PER_BLOCK;
+  const int r1 = min(M, r0 + NORM_BWD_ROWS_PER_BLOCK);
+  for (int row = r0; row < r1; ++row) {
+    const float rs = rstd[row], mu = mean[row];
+    Vec16<T> xv[CH], gv[CH];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (c * 256 + threadIdx.x) * VN;
+      if (e < H) {
+        xv[c] = *(const Vec16<T>*)(x + (int64_t)row * H + e);
+        gv[c] = *(const Vec16<T>*)(dy + (int64_t)row * H + e);
+#pragma unroll
+        for (int i = 0; i < VN; ++i) {
+          const float xh = (xv[c].get(i) - mu) * rs;
+          const float g = gv[c].get(i);
+          dw[c][i] += g * xh;
+          db[c][i] += g;
+          const float gw = g * wv[c].get(i);
+          s1 += gw;
+          s2 += gw * xh;
+        }
+      }
+    }
+    s1 = block_sum_256(s1, red) / (float)H;
+    s2 = block_sum_256(s2, red) / (float)H;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int e = (c * 256 + threadIdx.x) * VN;
+      if (e < H) {
+        Vec16<T> o, rv;
+        if (dres) rv = *(const Vec16<T>*)(dres + (int64_t)row * H + e);
+#pragma unroll
+        for (int i = 0; i < VN; ++i) {
+          const float xh = (xv[c].get(i) - mu) * rs;
+          o.set(i, rs * (gv[c].get(i) * wv[c].get(i) - s1 - xh * s2) + (dres ? rv.get(i) : 0.f));
+        }
+        *(Vec16<T>*)(dx + (int64_t)row * H + e) = o;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int e = (c * 256 + threadIdx.x) * VN;
+    if (e < H)
+#pragma unroll
+      for (int i = 0; i < VN; ++i) {
+        dwp[(int64_t)blockIdx.x * H + e + i] = dw[c][i];
+        dbp[(int64_t)blockIdx.x * H + e + i] = db[c][i];
+      }
+  }
+}
+
+// expert g = blockIdx.y owns rows [g R, (g + 1) R) and the partial blocks [g nb, (g + 1) nb), nb = gridDim.x = mm_norm_bwd_blocks(R):
+// no workgroup spans two experts
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel_batched(const T* dy, const T* x, NormBatch t, const float* mean,
+                                                                    const float* rstd, int R, int H, T* dx, float* dwp, float* dbp,
+                                                                    const T* dres) {
+  const int g = blockIdx.y;
+  const int64_t r0 = (int64_t)g * R, p0 = (int64_t)g * gridDim.x * H;
+  layernorm_bwd_body<T, CH>(dy + r0 * H, x + r0 * H, (const T*)uniform_ptr(t.w[g]), mean + r0, rstd + r0, R, H, dx + r0 * H, dwp + p0,
+                            dbp + p0, dres ? dres + r0 * H : nullptr);
+}
+
 // out[h] (+)= sum_b partial[b][h].  16 columns per workgroup (H/16 workgroups: 256 for H = 4096, one per CU) x 64 row
 // lanes, every lane's 16-byte loads of its rows all in flight at once, then a fixed-order tree through LDS (deterministic).
 // The old shape (64 columns x 4 row lanes, 64 workgroups, 4-byte loads: 128 dependent rounds per thread) took 44 us on the
@@ -224,8 +333,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* dy, const T
 // blockIdx.y selects one of two (partials, output) pairs: LayerNorm's dw and db leave backward in ONE launch (each launch of the
 // ViT's backward chain costs ~90 us while the deferred weight-gradient GEMMs hold the CUs, whatever its own work is)
 template <typename T>
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* p, int nblk, int H, T* out, int accumulate, const float* p1 = nullptr,
-                                                              T* out1 = nullptr, int accumulate1 = 0) {
+__device__ __forceinline__ void reduce_partials_body(const float* p, int nblk, int H, T* out, int accumulate, const float* p1, T* out1,
+                                                     int accumulate1) {
   __shared__ f32x4 red[64][4];
   if (blockIdx.y == 1) { p = p1; out = out1; accumulate = accumulate1; }
   const int c4 = threadIdx.x & 3, rl = threadIdx.x >> 2;
@@ -258,6 +367,22 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* p, in
       out[h + i] = from_f32<T>(v);
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* p, int nblk, int H, T* out, int accumulate, const float* p1 = nullptr,
+                                                              T* out1 = nullptr, int accumulate1 = 0) {
+  reduce_partials_body<T>(p, nblk, H, out, accumulate, p1, out1, accumulate1);
+}
+
+// mm_reduce_partials2_batched: blockIdx.z = the expert; its nblk partial blocks follow those of the expert before it
+struct ReduceBatch { void* out0[MM_GROUP_MAX]; void* out1[MM_GROUP_MAX]; };
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_partials_kernel_batched(const float* p, const float* p1, int nblk, int H, ReduceBatch t,
+                                                                      int accumulate, int accumulate1) {
+  const int g = blockIdx.z;
+  const int64_t p0 = (int64_t)g * nblk * H;
+  reduce_partials_body<T>(p + p0, nblk, H, (T*)uniform_ptr(t.out0[g]), accumulate, p1 + p0, (T*)uniform_ptr(t.out1[g]), accumulate1);
 }
 
 // ---------------------------------------------------------------- RoPE
@@ -894,6 +1019,78 @@ extern "C" int mm_reduce_partials2(int dtype, const float* partial0, const float
     hipLaunchKernelGGL(reduce_partials_kernel<bf16>, grid, block, 0, s, partial0, nblk, H, (bf16*)out0, accumulate0, partial1, (bf16*)out1, accumulate1);
   else
     hipLaunchKernelGGL(reduce_partials_kernel<float>, grid, block, 0, s, partial0, nblk, H, (float*)out0, accumulate0, partial1, (float*)out1, accumulate1);
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+static int norm_table(NormBatch& t, int groups, const void* const* w, const void* const* b) {
+  if (groups < 1 || groups > MM_GROUP_MAX || !w) return MM_ERR_ARG;
+  memset(&t, 0, sizeof(t));
+  for (int g = 0; g < groups; ++g) {
+    if (!w[g] || (b && !b[g])) return MM_ERR_ARG;
+    t.w[g] = w[g];
+    t.b[g] = b ? b[g] : nullptr;
+  }
+  return MM_OK;
+}
+
+extern "C" int mm_layernorm_fwd_batched(int dtype, const void* x, const void* const* w, const void* const* b, int groups, int R, int H,
+                                        float eps, void* y, float* mean, float* rstd, void* stream) {
+  if (!x || !b || !y || !mean || !rstd || R < 0 || H <= 0) return MM_ERR_ARG;
+  NormBatch t;
+  const int rc = norm_table(t, groups, w, b);
+  if (rc != MM_OK) return rc;
+  if (R == 0) return MM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(R, groups);
+  if (dtype == MM_BF16) {
+    if (H % 8) return MM_ERR_ALIGN;
+    DISPATCH_CH(bf16, norm_ch<bf16>(H), hipLaunchKernelGGL((layernorm_fwd_kernel_batched<bf16, CH>), grid, dim3(256), 0, s, (const bf16*)x, t, R, H, eps, (bf16*)y, mean, rstd));
+  } else {
+    if (H % 4) return MM_ERR_ALIGN;
+    DISPATCH_CH(float, norm_ch<float>(H), hipLaunchKernelGGL((layernorm_fwd_kernel_batched<float, CH>), grid, dim3(256), 0, s, (const float*)x, t, R, H, eps, (float*)y, mean, rstd));
+  }
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+extern "C" int mm_layernorm_bwd_batched(int dtype, const void* dy, const void* x, const void* const* w, int groups, const float* mean,
+                                        const float* rstd, int R, int H, void* dx, float* dwp, float* dbp, const void* dres, void* stream) {
+  if (!dy || !x || !mean || !rstd || !dx || !dwp || !dbp || R < 0 || H <= 0) return MM_ERR_ARG;
+  NormBatch t;
+  const int rc = norm_table(t, groups, w, nullptr);
+  if (rc != MM_OK) return rc;
+  if (R == 0) return MM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(mm_norm_bwd_blocks(R), groups);
+  if (dtype == MM_BF16) {
+    if (H % 8) return MM_ERR_ALIGN;
+    DISPATCH_CH(bf16, norm_ch<bf16>(H), hipLaunchKernelGGL((layernorm_bwd_kernel_batched<bf16, CH>), grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, t, mean, rstd, R, H, (bf16*)dx, dwp, dbp, (const bf16*)dres));
+  } else {
+    if (H % 4) return MM_ERR_ALIGN;
+    DISPATCH_CH(float, norm_ch<float>(H), hipLaunchKernelGGL((layernorm_bwd_kernel_batched<float, CH>), grid, dim3(256), 0, s, (const float*)dy, (const float*)x, t, mean, rstd, R, H, (float*)dx, dwp, dbp, (const float*)dres));
+  }
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+extern "C" int mm_reduce_partials2_batched(int dtype, const float* partial0, const float* partial1, int groups, int nblk, int H,
+                                           void* const* out0, void* const* out1, int accumulate0, int accumulate1, void* stream) {
+  if (groups < 1 || groups > MM_GROUP_MAX || !partial0 || !partial1 || !out0 || !out1 || nblk < 0 || H <= 0) return MM_ERR_ARG;
+  ReduceBatch t;
+  memset(&t, 0, sizeof(t));
+  for (int g = 0; g < groups; ++g) {
+    if (!out0[g] || !out1[g]) return MM_ERR_ARG;
+    t.out0[g] = out0[g];
+    t.out1[g] = out1[g];
+  }
+  if ((H & 3) || !mm_aligned16(partial0) || !mm_aligned16(partial1)) return MM_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((H + 15) / 16, 2, groups), block(256);
+  if (dtype == MM_BF16)
+    hipLaunchKernelGGL(reduce_partials_kernel_batched<bf16>, grid, block, 0, s, partial0, partial1, nblk, H, t, accumulate0, accumulate1);
+  else
+    hipLaunchKernelGGL(reduce_partials_kernel_batched<float>, grid, block, 0, s, partial0, partial1, nblk, H, t, accumulate0, accumulate1);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }

@@ -274,6 +274,141 @@ def layernorm(x, w, b, eps, dummy=None):
     return LayerNormFn.apply(x, dummy, w, b, eps)
 
 
+# --------------------------------------------------------------------------------------------------- grouped (expert-major)
+# The MoE image modality's E expert towers as ONE chain: activations are expert-major [E * R, C] (expert e owns rows
+# [e R, (e + 1) R)), every op whose operands differ per expert takes the experts' parameters as lists and runs one grouped
+# launch (kernels.*_batched).  Gradients go where LinearFn / LayerNormFn put them: through grad_target, then _ready.
+def _grouped_targets(groups):
+    """grad_target of every expert's group -> (buffers, accumulate?) when they agree on overwrite / accumulate, else
+    (buffers, list of flags): the caller then loops per expert."""
+    tg = [g.grad_target() if isinstance(g, ParamGroup) else grad_target(g) for g in groups]
+    accs = [a for _, a in tg]
+    return [t for t, _ in tg], (accs[0] if all(a == accs[0] for a in accs) else accs)
+
+
+def _all_ready(groups):
+    for g in groups:
+        if isinstance(g, ParamGroup):
+            g.ready()
+        else:
+            _ready(g)
+
+
+class GroupedLinearFn(torch.autograd.Function):
+    """LinearFn for E experts at once: x [E*R, K] expert-major, wgs / bgs = one ParamGroup per expert."""
+
+    @staticmethod
+    def forward(ctx, x, residual, dummy, wgs, bgs, act: int):
+        ws = [wg.tensor() for wg in wgs]
+        bs = [bg.tensor() for bg in bgs] if bgs is not None else None
+        pre = None
+        if act and (x.requires_grad or any(wg.requires_grad for wg in wgs)):
+            fused = K.linear_act_fwd_batched(x, ws, bs, act, residual)
+            if fused is not None:
+                pre, y = fused
+            else:
+                pre = K.linear_fwd_batched(x, ws, biases=bs)
+                y = K.gelu_fwd(pre, GELU_KIND[act])
+                if residual is not None:
+                    y = K.add(y, residual)
+        else:
+            y = K.linear_fwd_batched(x, ws, biases=bs, residual=residual, act=act)
+        ctx.wgs, ctx.bgs, ctx.act = wgs, bgs, act
+        ctx.has_res = residual is not None
+        ctx.save_for_backward(x, pre)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, pre = ctx.saved_tensors
+        wgs, bgs = ctx.wgs, ctx.bgs
+        E = len(wgs)
+        dy = dy.contiguous()
+        dres = dy if ctx.has_res else None
+        if ctx.act:
+            dy = K.gelu_bwd(pre, dy, GELU_KIND[ctx.act])
+        R = dy.shape[0] // E
+        if bgs is not None:
+            live = [e for e in range(E) if bgs[e].requires_grad]
+            if len(live) == E:
+                gs, acc = _grouped_targets(bgs)
+                if isinstance(acc, list):            # the experts disagree on overwrite / accumulate: per expert
+                    for e in range(E):
+                        K.colsum(dy[e * R:(e + 1) * R], gs[e], acc[e])
+                else:
+                    K.colsum_batched(dy, gs, acc)
+                _all_ready(bgs)
+            else:
+                for e in live:
+                    g, acc = bgs[e].grad_target()
+                    K.colsum(dy[e * R:(e + 1) * R], g, acc)
+                    bgs[e].ready()
+        live = [e for e in range(E) if wgs[e].requires_grad]
+        if len(live) == E:
+            gs, acc = _grouped_targets(wgs)
+            if isinstance(acc, list):
+                for e in range(E):
+                    K.linear_wgrad(dy[e * R:(e + 1) * R], x[e * R:(e + 1) * R], gs[e], acc[e])
+            else:
+                K.linear_wgrad_batched(dy, x, gs, acc)
+            _all_ready(wgs)
+        else:
+            for e in live:
+                _wgrad(dy[e * R:(e + 1) * R], x[e * R:(e + 1) * R], wgs[e])
+        dx = K.linear_dgrad_batched(dy, [wg.tensor() for wg in wgs]) if ctx.needs_input_grad[0] else None
+        return dx, dres, None, None, None, None
+
+
+def grouped_linear(x, wgs, bgs=None, residual=None, act=0, dummy=None):
+    return GroupedLinearFn.apply(x, residual, dummy, [as_group(w) for w in wgs], [as_group(b) for b in bgs] if bgs is not None else None, act)
+
+
+class GroupedLayerNormFn(torch.autograd.Function):
+    """LayerNormFn for E experts at once: x [E*R, H] expert-major, ws / bs = one weight / bias Parameter per expert."""
+
+    @staticmethod
+    def forward(ctx, x, dummy, ws, bs, eps):
+        y, mean, rstd = K.layernorm_fwd_batched(x, [w.data for w in ws], [b.data for b in bs], eps)
+        ctx.ws, ctx.bs = ws, bs
+        ctx.save_for_backward(x, mean, rstd)
+        return y, x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dy, dres):
+        x, mean, rstd = ctx.saved_tensors
+        ws, bs = ctx.ws, ctx.bs
+        E = len(ws)
+        if dy is None:
+            return dres, None, None, None, None
+        dx, dwp, dbp = K.layernorm_bwd_batched(dy.contiguous(), x, [w.data for w in ws], mean, rstd,
+                                               dres.contiguous() if dres is not None else None)
+        nb = dwp.shape[0] // E
+        if all(w.requires_grad for w in ws) and all(b.requires_grad for b in bs):
+            gw, aw = _grouped_targets(ws)
+            gb, ab = _grouped_targets(bs)
+            if isinstance(aw, list) or isinstance(ab, list):
+                for e in range(E):
+                    K.reduce_partials2(dwp[e * nb:(e + 1) * nb], dbp[e * nb:(e + 1) * nb], gw[e], gb[e],
+                                       aw[e] if isinstance(aw, list) else aw, ab[e] if isinstance(ab, list) else ab)
+            else:
+                K.reduce_partials2_batched(dwp, dbp, gw, gb, aw, ab)
+            for w, b in zip(ws, bs):
+                _ready(w)
+                _ready(b)
+            return dx, None, None, None, None
+        for e in range(E):                               # partly frozen norms: what LayerNormFn does, per expert
+            for p, part in ((ws[e], dwp), (bs[e], dbp)):
+                if p.requires_grad:
+                    g, acc = grad_target(p)
+                    K.reduce_partials(part[e * nb:(e + 1) * nb], g, acc)
+                    _ready(p)
+        return dx, None, None, None, None
+
+
+def grouped_layernorm(x, ws, bs, eps, dummy=None):
+    return GroupedLayerNormFn.apply(x, dummy, ws, bs, eps)
+
+
 # --------------------------------------------------------------------------------------------------- attention
 class RopeAttentionFn(torch.autograd.Function):
     """qkv [T, (Hq+2Hkv)*D] (fused projection output, consumed in place) -> out [T, Hq*D].

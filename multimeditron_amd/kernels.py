@@ -196,6 +196,143 @@ def colsum(x2d, out, accumulate):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ grouped launches
+# `groups` equal-shaped problems in ONE launch (the MoE image modality's expert towers): per-problem operands are lists of 2-D
+# tensors with equal strides; the pointers travel as host arrays (include/mm_hip.h, "grouped launches").
+def _pa(ts):
+    """host array of device pointers (None for an absent operand)"""
+    import ctypes
+    if ts is None:
+        return None
+    return (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])
+
+
+def _same_stride(ts):
+    ld = ts[0].stride(0)
+    assert all(t.dim() == 2 and t.stride(1) == 1 and t.stride(0) == ld and t.dtype == ts[0].dtype for t in ts)
+    return ld
+
+
+def _unsupported(err):
+    return getattr(err, "code", None) == _lib.ERR_UNSUPPORTED
+
+
+def gemm_batched(layout, As, Bs, M, N, K, outs, biases=None, residuals=None, act=0, accumulate=False):
+    """mm_gemm on every (As[g], Bs[g]) -> outs[g] in one launch; problems the grouped kernels do not cover (those that fill the
+    chip on their own: 256-wide tiles, M <= 16) are looped through mm_gemm -- same bits either way."""
+    epi = act | (EPI_BIAS if biases is not None else 0) | (EPI_RESIDUAL if residuals is not None else 0) | (EPI_ACCUMULATE if accumulate else 0)
+    lda, ldb, ldc = _same_stride(As), _same_stride(Bs), _same_stride(outs)
+    ldr = _same_stride(residuals) if residuals is not None else 0
+    try:
+        call("mm_gemm_batched", dt(As[0]), layout, len(As), M, N, K, _pa(As), lda, _pa(Bs), ldb, _pa(outs), ldc, _pa(biases), _pa(residuals),
+             ldr, epi, _stream())
+    except _lib.MMHipError as err:
+        if not _unsupported(err):
+            raise
+        for g in range(len(As)):
+            call("mm_gemm", dt(As[g]), layout, M, N, K, _p(As[g]), lda, _p(Bs[g]), ldb, _p(outs[g]), ldc,
+                 _p(biases[g]) if biases is not None else None, _p(residuals[g]) if residuals is not None else None, ldr, epi, _stream())
+    return outs
+
+
+def _rows(t, groups):
+    """the `groups` equal row blocks of an expert-major 2-D tensor"""
+    R = t.shape[0] // groups
+    return [t[g * R:(g + 1) * R] for g in range(groups)]
+
+
+def linear_fwd_batched(x, ws, biases=None, residual=None, act=0):
+    """x [G*R, K] expert-major, ws[g] [N, K] -> y [G*R, N]: y_g = x_g @ ws[g]^T (+ bias_g) (act) (+ residual_g)."""
+    G = len(ws)
+    R, Kd = x.shape[0] // G, x.shape[1]
+    N = ws[0].shape[0]
+    y = torch.empty((G * R, N), dtype=x.dtype, device=x.device)
+    gemm_batched(GEMM_NT, _rows(x, G), ws, R, N, Kd, _rows(y, G), biases=biases, residuals=_rows(residual, G) if residual is not None else None,
+                 act=act)
+    return y
+
+
+def linear_act_fwd_batched(x, ws, biases, act, residual=None):
+    """linear_act_fwd on every expert's rows in one launch -> (pre, y) [G*R, N], or None where the separate launches must run."""
+    G = len(ws)
+    R, Kd = x.shape[0] // G, x.shape[1]
+    N = ws[0].shape[0]
+    if x.dtype != torch.bfloat16 or R <= 16 or _os.environ.get("MM_FUSED_GELU", "1") == "0":
+        return None
+    pre = torch.empty((G * R, N), dtype=x.dtype, device=x.device)
+    y = torch.empty((G * R, N), dtype=x.dtype, device=x.device)
+    xs, pres, ys = _rows(x, G), _rows(pre, G), _rows(y, G)
+    res = _rows(residual, G) if residual is not None else None
+    epi = act | (EPI_BIAS if biases is not None else 0) | (EPI_RESIDUAL if residual is not None else 0)
+    ldx, ldw = _same_stride(xs), _same_stride(ws)
+    ldr = residual.stride(0) if residual is not None else 0
+    try:
+        call("mm_gemm_act_fwd_batched", dt(x), G, R, N, Kd, _pa(xs), ldx, _pa(ws), ldw, _pa(biases), _pa(pres), pre.stride(0), _pa(ys),
+             y.stride(0), _pa(res), ldr, epi, _stream())
+    except _lib.MMHipError as err:
+        if not _unsupported(err):
+            raise
+        for g in range(G):
+            call("mm_gemm_act_fwd", dt(x), R, N, Kd, _p(xs[g]), ldx, _p(ws[g]), ldw, _p(biases[g]) if biases is not None else None,
+                 _p(pres[g]), pre.stride(0), _p(ys[g]), y.stride(0), _p(res[g]) if res is not None else None, ldr, epi, _stream())
+    return pre, y
+
+
+def linear_dgrad_batched(dy, ws):
+    """dx [G*R, K] = dy_g [R, N] @ ws[g] [N, K] per expert."""
+    G = len(ws)
+    R = dy.shape[0] // G
+    N, Kd = ws[0].shape
+    dx = torch.empty((G * R, Kd), dtype=dy.dtype, device=dy.device)
+    gemm_batched(GEMM_NN, _rows(dy, G), ws, R, Kd, N, _rows(dx, G))
+    return dx
+
+
+def linear_wgrad_batched(dy, x, outs, accumulate):
+    """outs[g] [N, K] (+)= dy_g^T @ x_g per expert."""
+    G = len(outs)
+    R, N = dy.shape[0] // G, dy.shape[1]
+    gemm_batched(GEMM_TN, _rows(dy, G), _rows(x, G), N, x.shape[1], R, outs, accumulate=accumulate)
+
+
+def colsum_batched(x, outs, accumulate):
+    """outs[g] [N] (+)= the column sums of expert g's rows of x [G*R, N]."""
+    G = len(outs)
+    xs = _rows(x, G)
+    call("mm_colsum_batched", dt(x), _pa(xs), G, xs[0].shape[0], x.shape[1], x.stride(0), _pa(outs), int(accumulate), _stream())
+
+
+def layernorm_fwd_batched(x2d, ws, bs, eps):
+    G = len(ws)
+    M, H = x2d.shape
+    y = torch.empty_like(x2d)
+    mean = torch.empty(M, dtype=torch.float32, device=x2d.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x2d.device)
+    call("mm_layernorm_fwd_batched", dt(x2d), _p(x2d), _pa(ws), _pa(bs), G, M // G, H, float(eps), _p(y), _p(mean), _p(rstd), _stream())
+    return y, mean, rstd
+
+
+def layernorm_bwd_batched(dy2d, x2d, ws, mean, rstd, dres=None):
+    """-> (dx, dw partials, db partials); expert g's partial blocks are rows [g*nb, (g+1)*nb), nb = norm_bwd_blocks(R)."""
+    G = len(ws)
+    M, H = x2d.shape
+    R = M // G
+    dx = torch.empty_like(x2d)
+    nb = norm_bwd_blocks(R)
+    dwp = torch.empty((G * nb, H), dtype=torch.float32, device=x2d.device)
+    dbp = torch.empty((G * nb, H), dtype=torch.float32, device=x2d.device)
+    call("mm_layernorm_bwd_batched", dt(x2d), _p(dy2d), _p(x2d), _pa(ws), G, _p(mean), _p(rstd), R, H, _p(dx), _p(dwp), _p(dbp), _p(dres),
+         _stream())
+    return dx, dwp, dbp
+
+
+def reduce_partials2_batched(partial0, partial1, outs0, outs1, accumulate0, accumulate1):
+    G = len(outs0)
+    assert partial0.shape == partial1.shape and partial0.shape[0] % G == 0
+    call("mm_reduce_partials2_batched", dt(outs0[0]), _p(partial0), _p(partial1), G, partial0.shape[0] // G, partial0.shape[1], _pa(outs0),
+         _pa(outs1), int(accumulate0), int(accumulate1), _stream())
+
+
 # ------------------------------------------------------------------------------------------------ splice
 def splice_build_map(batch_idx, token_range, S, T):
     m = torch.empty(T, dtype=torch.int32, device=batch_idx.device if batch_idx is not None else "cuda")

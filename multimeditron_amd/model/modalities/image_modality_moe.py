@@ -24,7 +24,8 @@ on libmmhip's NHWC convolution kernels, built from `config.gating_path` when tha
 `gating_network=` argument wins over the path, and may be any callable with the reference's output contract
 `pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  Training the gate in FULL mode (train-mode BatchNorm, a ResNet
 backward, a gradient through the fusion weights) is opt-in through the config field `train_gate`.  The experts run side by side, each on its own HIP
-stream (`_run_experts`); a grouped multi-expert GEMM launch would be the step after that.  `CrossAttention`'s two dropouts
+stream (`_run_experts`), or -- opt-in through the config field `grouped_towers` / MM_MOE_GROUPED=1 -- as ONE chain of grouped
+launches with the expert as a batch dimension (model/vision_grouped.py: no graph capture, no side streams).  `CrossAttention`'s two dropouts
 (p = 0.1 on the attention probabilities and on the output projection, active in the reference whenever the module trains) are
 Philox-based: eval mode equals the reference, train mode equals it in distribution (torch's generator cannot be reproduced)."""
 from __future__ import annotations
@@ -51,8 +52,9 @@ class MOEImageConfig(BaseModalityConfig):
     def __init__(self, hidden_size: int = 1024, use_bias_proj: bool = True, expert_clip_names: Optional[List[str]] = None,
                  image_processor: str = "openai/clip-vit-large-patch14", gating_path: str = "", top_k_experts: int = 1,
                  projection_type: str = "mlp", generalist_idx: int = -1, fusion_method: str = "weighted_average",
-                 cross_attn_heads: int = 8, train_gate: bool = False, **kwargs):
+                 cross_attn_heads: int = 8, train_gate: bool = False, grouped_towers: bool = False, **kwargs):
         super().__init__(modality_type="image", hidden_size=hidden_size)
+        self.grouped_towers = bool(grouped_towers)       # opt-in: the expert towers as one chain of grouped launches (vision_grouped.py)
         self.train_gate = bool(train_gate)       # opt-in: unfreezing the modality also trains the gating network (the reference's FULL mode)
         self.use_bias_proj = use_bias_proj
         self.expert_clip_names = list(expert_clip_names or [])
@@ -66,8 +68,9 @@ class MOEImageConfig(BaseModalityConfig):
 
     def to_dict(self) -> Dict[str, Any]:
         d = super().to_dict()
-        if not d.get("train_gate"):              # written only when set: configs saved without it stay byte-identical
-            d.pop("train_gate", None)
+        for key in ("train_gate", "grouped_towers"):     # written only when set: configs saved without them stay byte-identical
+            if not d.get(key):
+                d.pop(key, None)
         return d
 
 
@@ -144,7 +147,17 @@ class CrossAttention(nn.Module):
         return Fm.dropout(o, self.proj_drop_p, self.training).view(n, Nq, C)
 
 
-def _run_experts(experts, pixels, post=None):
+def _grouped_on(grouped) -> bool:
+    """the `grouped_towers` switch: the config field, overridden by MM_MOE_GROUPED=0|1"""
+    import os
+    env = os.environ.get("MM_MOE_GROUPED")
+    return bool(grouped) if env in (None, "") else env != "0"
+
+
+_warned_ineligible = False
+
+
+def _run_experts(experts, pixels, post=None, grouped=False):
     """Every expert tower on the same pixels (reference image_modality_moe.py:156-160), off the host-bound path two ways:
       * FROZEN towers (the shipped alignment / end2end recipes freeze them; also any no-grad call) are one captured hipGraph per
         image count: the ~210 launches per ViT-B/32 tower cost the host nothing at replay, and the towers sit on parallel branches
@@ -153,9 +166,24 @@ def _run_experts(experts, pixels, post=None):
         chains of short kernels, so E of them side by side take little more than one.  Autograd replays each tower's backward on
         the stream its forward ran on.  `post(e, tokens)` is applied on the expert's stream.  MM_MOE_STREAMS=0: one after the
         other on the current stream.
+    With `grouped` (config `grouped_towers`, MM_MOE_GROUPED) and eligible experts -- one VisionConfig, one dtype, all on the device, at
+    most MM_GROUP_MAX of them -- trainable, frozen and no-grad calls alike take ONE chain of grouped launches instead
+    (vision_grouped.grouped_towers): ordinary autograd, no graph, no side stream, no state between calls.  Ineligible experts take
+    the paths above, with one warning.
     Same kernels either way, same results bit for bit."""
     import os
     n = pixels.shape[0]
+    if _grouped_on(grouped):
+        from .. import vision_grouped
+        why = vision_grouped.ineligible(experts) if pixels.is_cuda else "the pixels are not on the device"
+        if why is None:
+            outs = vision_grouped.grouped_towers(experts, pixels)
+            return [post(e, o) if post is not None else o for e, o in enumerate(outs)]
+        global _warned_ineligible
+        if not _warned_ineligible:
+            import warnings
+            _warned_ineligible = True
+            warnings.warn(f"grouped_towers: {why}; the expert towers run one by one")
 
     def tower(e, expert, px=None):
         hs = expert(pixels if px is None else px).last_hidden_state                             # [n, 1+P, C]
@@ -543,7 +571,7 @@ class MOEImageModality(_FrozenGate, BaseModality):      # which the reference it
         pixels = pixels.to(self.device, non_blocking=True)
         n, E = pixels.shape[0], len(self.experts)
         w = self.gate_weights(pixels)                                     # [n, E] fp32, expert order
-        feats = _run_experts(self.experts, pixels)                        # every expert on every image (reference :156-160)
+        feats = _run_experts(self.experts, pixels, grouped=getattr(self.config, "grouped_towers", False))      # every expert on every image (reference :156-160)
         stacked = torch.stack(feats, dim=0)                               # [E, n, P, C] (device copy; autograd unbinds it)
         P, C = stacked.shape[2], stacked.shape[3]
         if self.fusion_method == "sequence_append":
@@ -656,7 +684,8 @@ class MOEImageModalityPEP(_FrozenGate, BaseModality):
             raise NotImplementedError(_NO_GATE.format(cls="MOEImageModalityPEP"))
         _logits, _topk, weights = self.gating_network(pixels)
         w_raw = weights.to(device=self.device, dtype=torch.float32).contiguous()          # gate order, as weighted_average uses it (:214)
-        outs = _run_experts(self.experts, pixels, post=lambda e, tok: self.projectors[e](tok))      # [n, P, H] each
+        outs = _run_experts(self.experts, pixels, post=lambda e, tok: self.projectors[e](tok),
+                            grouped=getattr(self.config, "grouped_towers", False))                  # [n, P, H] each
         stacked = torch.stack(outs, dim=0)                                # [E, n, P, H]
         P, H = stacked.shape[2], stacked.shape[3]
         if self.fusion_method == "sequence_append":

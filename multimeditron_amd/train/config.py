@@ -15,7 +15,9 @@ cookbook/sft/*/config.yaml files have this layout):
     modalities[]        {model_type, ...} -> AutoModality.config_from_dict (train.py:109-111); the alternate embedder / LLM of
                         BASELINE config 5 plug in HERE (model_type: meditron_siglip, base_llm: Qwen/Qwen2-7B-Instruct).  An MoE
                         modality's `train_gate: true` (this project's key, default false) makes FULL mode train the gating
-                        network with the experts, as the reference's FULL mode does
+                        network with the experts, as the reference's FULL mode does; `grouped_towers: true` (this project's
+                        key, default false; MM_MOE_GROUPED=0|1 overrides) runs the expert towers as one chain of grouped
+                        launches instead of captured graphs / side streams
     training_mode       ALIGNMENT | END2END | LM_ONLY | FULL (trainer.py:16-23)
     truncation, max_sequence_length, use_2d_position_ids
     training_args{}     the HF TrainingArguments keys that act on this path: learning_rate, weight_decay, max_grad_norm,

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""MoE image modality at ViT-L/14 size: E experts on n images, forward + backward, experts on one stream vs one stream each.
+"""MoE image modality at ViT-L/14 size: E experts on n images, forward + backward: experts on one stream, one stream each, replayed
+from captured graphs, and as one chain of grouped launches (MM_MOE_GROUPED=1: the expert as a batch dimension).  Every row is
+printed twice (the spread between the two printings is the noise a difference has to exceed).
    python tools/moe_bench.py [E] [n]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,9 +28,10 @@ for fusion in ("weighted_average", "cross_attn"):
         p.requires_grad_(True)
     px = torch.randn(n, 3, 224, 224, device="cuda")
     ref = None
-    for streams, graph in (("0", "0"), ("1", "0"), ("1", "1"), ("0", "0"), ("1", "0"), ("1", "1")):
+    for streams, graph, grouped in (("0", "0", "0"), ("1", "0", "0"), ("1", "1", "0"), ("1", "1", "1")) * 2:
         os.environ["MM_MOE_STREAMS"] = streams
         os.environ["MM_MOE_TRAIN_GRAPH"] = graph        # trainable towers replayed from captured forward / backward graphs
+        os.environ["MM_MOE_GROUPED"] = grouped          # one chain of grouped launches (wins over the two switches above)
         for it in range(6):
             if it == 3:
                 torch.cuda.synchronize()
@@ -39,11 +42,14 @@ for fusion in ("weighted_average", "cross_attn"):
         ms = (time.perf_counter() - t0) / 3 * 1e3
         same = "" if ref is None else f"  output identical to the sequential run: {bool(torch.equal(ref, y))}"
         ref = y.detach().clone() if ref is None else ref
-        print(f"{fusion}: E={E} experts (ViT-L/14), n={n} images, MM_MOE_STREAMS={streams} MM_MOE_TRAIN_GRAPH={graph}: {ms:.2f} ms fwd+bwd{same}", flush=True)
+        how = "MM_MOE_GROUPED=1" if grouped == "1" else f"MM_MOE_STREAMS={streams} MM_MOE_TRAIN_GRAPH={graph}"
+        print(f"{fusion}: E={E} experts (ViT-L/14), n={n} images, {how}: {ms:.2f} ms fwd+bwd{same}", flush=True)
     # the shipped alignment / end2end recipes: towers frozen, projector (and cross-attention) trainable
     m.freeze_modality_embedder()
-    for graph in ("0", "1", "0", "1"):
+    ref = None
+    for graph, grouped in (("0", "0"), ("1", "0"), ("1", "1")) * 2:
         os.environ["MM_MOE_GRAPH"] = graph
+        os.environ["MM_MOE_GROUPED"] = grouped
         for it in range(4):
             if it == 2:
                 torch.cuda.synchronize()
@@ -52,6 +58,10 @@ for fusion in ("weighted_average", "cross_attn"):
             y.backward(torch.ones_like(y))
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) / 2 * 1e3
-        print(f"{fusion}: frozen towers, MM_MOE_GRAPH={graph}: {ms:.2f} ms fwd (+ projector / fusion bwd)", flush=True)
+        same = "" if ref is None else f"  output identical to the eager run: {bool(torch.equal(ref, y))}"
+        ref = y.detach().clone() if ref is None else ref
+        how = "MM_MOE_GROUPED=1" if grouped == "1" else f"MM_MOE_GRAPH={graph}"
+        print(f"{fusion}: frozen towers, {how}: {ms:.2f} ms fwd (+ projector / fusion bwd){same}", flush=True)
+    os.environ["MM_MOE_GROUPED"] = "0"
     del m
     torch.cuda.empty_cache()
