@@ -278,20 +278,36 @@ def layernorm(x, w, b, eps, dummy=None):
 # The MoE image modality's E expert towers as ONE chain: activations are expert-major [E * R, C] (expert e owns rows
 # [e R, (e + 1) R)), every op whose operands differ per expert takes the experts' parameters as lists and runs one grouped
 # launch (kernels.*_batched).  Gradients go where LinearFn / LayerNormFn put them: through grad_target, then _ready.
-def _grouped_targets(groups):
-    """grad_target of every expert's group -> (buffers, accumulate?) when they agree on overwrite / accumulate, else
-    (buffers, list of flags): the caller then loops per expert."""
-    tg = [g.grad_target() if isinstance(g, ParamGroup) else grad_target(g) for g in groups]
-    accs = [a for _, a in tg]
-    return [t for t, _ in tg], (accs[0] if all(a == accs[0] for a in accs) else accs)
+def _grouped_grad_write(slots, batched, single, partly=None):
+    """One gradient write for E experts.  slots[k][e]: expert e's k-th parameter of the write (a ParamGroup or a Parameter; a
+    LayerNorm's write has two slots, weight and bias).
+      * all train, and each slot's experts agree on overwrite / accumulate: batched(bufs..., accs...), one launch;
+      * all train, but the experts disagree: single(e, bufs..., accs...) per expert; either way the ready hooks follow, by expert;
+      * some are frozen: partly(e) for every expert -- by default `single` and the hooks for an expert whose slots all train."""
+    slots = [[as_group(g) for g in s] for s in slots]
+    E = len(slots[0])
 
+    def single_if_live(e):
+        if all(s[e].requires_grad for s in slots):
+            tg = [s[e].grad_target() for s in slots]
+            single(e, *[t for t, _ in tg], *[a for _, a in tg])
+            for s in slots:
+                s[e].ready()
 
-def _all_ready(groups):
-    for g in groups:
-        if isinstance(g, ParamGroup):
-            g.ready()
-        else:
-            _ready(g)
+    if not all(g.requires_grad for s in slots for g in s):
+        for e in range(E):
+            (partly or single_if_live)(e)
+        return
+    tg = [[g.grad_target() for g in s] for s in slots]
+    bufs, accs = [[t for t, _ in s] for s in tg], [[a for _, a in s] for s in tg]
+    if all(a == s[0] for s in accs for a in s):
+        batched(*bufs, *[s[0] for s in accs])
+    else:
+        for e in range(E):
+            single(e, *[b[e] for b in bufs], *[a[e] for a in accs])
+    for e in range(E):
+        for s in slots:
+            s[e].ready()
 
 
 class GroupedLinearFn(torch.autograd.Function):
@@ -328,33 +344,12 @@ class GroupedLinearFn(torch.autograd.Function):
         if ctx.act:
             dy = K.gelu_bwd(pre, dy, GELU_KIND[ctx.act])
         R = dy.shape[0] // E
+        rows = [slice(e * R, (e + 1) * R) for e in range(E)]
         if bgs is not None:
-            live = [e for e in range(E) if bgs[e].requires_grad]
-            if len(live) == E:
-                gs, acc = _grouped_targets(bgs)
-                if isinstance(acc, list):            # the experts disagree on overwrite / accumulate: per expert
-                    for e in range(E):
-                        K.colsum(dy[e * R:(e + 1) * R], gs[e], acc[e])
-                else:
-                    K.colsum_batched(dy, gs, acc)
-                _all_ready(bgs)
-            else:
-                for e in live:
-                    g, acc = bgs[e].grad_target()
-                    K.colsum(dy[e * R:(e + 1) * R], g, acc)
-                    bgs[e].ready()
-        live = [e for e in range(E) if wgs[e].requires_grad]
-        if len(live) == E:
-            gs, acc = _grouped_targets(wgs)
-            if isinstance(acc, list):
-                for e in range(E):
-                    K.linear_wgrad(dy[e * R:(e + 1) * R], x[e * R:(e + 1) * R], gs[e], acc[e])
-            else:
-                K.linear_wgrad_batched(dy, x, gs, acc)
-            _all_ready(wgs)
-        else:
-            for e in live:
-                _wgrad(dy[e * R:(e + 1) * R], x[e * R:(e + 1) * R], wgs[e])
+            _grouped_grad_write([bgs], lambda gs, acc: K.colsum_batched(dy, gs, acc), lambda e, g, acc: K.colsum(dy[rows[e]], g, acc))
+        _grouped_grad_write([wgs], lambda gs, acc: K.linear_wgrad_batched(dy, x, gs, acc),
+                            lambda e, g, acc: K.linear_wgrad(dy[rows[e]], x[rows[e]], g, acc),
+                            partly=lambda e: _wgrad(dy[rows[e]], x[rows[e]], wgs[e]))       # _wgrad: skips a frozen group, honours deferral
         dx = K.linear_dgrad_batched(dy, [wg.tensor() for wg in wgs]) if ctx.needs_input_grad[0] else None
         return dx, dres, None, None, None, None
 
@@ -383,25 +378,17 @@ class GroupedLayerNormFn(torch.autograd.Function):
         dx, dwp, dbp = K.layernorm_bwd_batched(dy.contiguous(), x, [w.data for w in ws], mean, rstd,
                                                dres.contiguous() if dres is not None else None)
         nb = dwp.shape[0] // E
-        if all(w.requires_grad for w in ws) and all(b.requires_grad for b in bs):
-            gw, aw = _grouped_targets(ws)
-            gb, ab = _grouped_targets(bs)
-            if isinstance(aw, list) or isinstance(ab, list):
-                for e in range(E):
-                    K.reduce_partials2(dwp[e * nb:(e + 1) * nb], dbp[e * nb:(e + 1) * nb], gw[e], gb[e],
-                                       aw[e] if isinstance(aw, list) else aw, ab[e] if isinstance(ab, list) else ab)
-            else:
-                K.reduce_partials2_batched(dwp, dbp, gw, gb, aw, ab)
-            for w, b in zip(ws, bs):
-                _ready(w)
-                _ready(b)
-            return dx, None, None, None, None
-        for e in range(E):                               # partly frozen norms: what LayerNormFn does, per expert
+        blocks = [slice(e * nb, (e + 1) * nb) for e in range(E)]
+
+        def partly(e):                                   # partly frozen norms: what LayerNormFn does, per expert
             for p, part in ((ws[e], dwp), (bs[e], dbp)):
                 if p.requires_grad:
                     g, acc = grad_target(p)
-                    K.reduce_partials(part[e * nb:(e + 1) * nb], g, acc)
+                    K.reduce_partials(part[blocks[e]], g, acc)
                     _ready(p)
+
+        _grouped_grad_write([ws, bs], lambda gw, gb, aw, ab: K.reduce_partials2_batched(dwp, dbp, gw, gb, aw, ab),
+                            lambda e, gw, gb, aw, ab: K.reduce_partials2(dwp[blocks[e]], dbp[blocks[e]], gw, gb, aw, ab), partly)
         return dx, None, None, None, None
 
 

@@ -24,7 +24,7 @@ on libmmhip's NHWC convolution kernels, built from `config.gating_path` when tha
 `gating_network=` argument wins over the path, and may be any callable with the reference's output contract
 `pixels [n,3,H,W] -> (logits [n,E], topk_indices, weights [n,E])`.  Training the gate in FULL mode (train-mode BatchNorm, a ResNet
 backward, a gradient through the fusion weights) is opt-in through the config field `train_gate`.  The experts run side by side, each on its own HIP
-stream (`_run_experts`), or -- opt-in through the config field `grouped_towers` / MM_MOE_GROUPED=1 -- as ONE chain of grouped
+stream or replayed from captured hipGraphs (model/expert_towers.py: `run_experts` picks the path), or -- opt-in through the config field `grouped_towers` / MM_MOE_GROUPED=1 -- as ONE chain of grouped
 launches with the expert as a batch dimension (model/vision_grouped.py: no graph capture, no side streams).  `CrossAttention`'s two dropouts
 (p = 0.1 on the attention probabilities and on the output projection, active in the reference whenever the module trains) are
 Philox-based: eval mode equals the reference, train mode equals it in distribution (torch's generator cannot be reproduced)."""
@@ -38,6 +38,7 @@ import torch.nn as nn
 from ... import functional as Fm
 from ...nn import Linear, grad_dummy
 from ..constants import MODALITY_VALUE_KEY, NUM_EMBEDDINGS_KEY
+from ..expert_towers import run_experts
 from ..presets import resolve_preprocessor_config, resolve_vision_config
 from ..projectors.mlp import MLPProjector
 from ..vision import VisionConfig, VisionTransformer
@@ -147,305 +148,6 @@ class CrossAttention(nn.Module):
         return Fm.dropout(o, self.proj_drop_p, self.training).view(n, Nq, C)
 
 
-def _grouped_on(grouped) -> bool:
-    """the `grouped_towers` switch: the config field, overridden by MM_MOE_GROUPED=0|1"""
-    import os
-    env = os.environ.get("MM_MOE_GROUPED")
-    return bool(grouped) if env in (None, "") else env != "0"
-
-
-_warned_ineligible = False
-
-
-def _run_experts(experts, pixels, post=None, grouped=False):
-    """Every expert tower on the same pixels (reference image_modality_moe.py:156-160), off the host-bound path two ways:
-      * FROZEN towers (the shipped alignment / end2end recipes freeze them; also any no-grad call) are one captured hipGraph per
-        image count: the ~210 launches per ViT-B/32 tower cost the host nothing at replay, and the towers sit on parallel branches
-        of the graph (`_frozen_towers`; MM_MOE_GRAPH=0 disables).  The per-expert projectors (`post`, trainable) stay outside.
-      * trainable towers run side by side, each on ITS OWN HIP stream: at the modality's size the towers are launch-latency-bound
-        chains of short kernels, so E of them side by side take little more than one.  Autograd replays each tower's backward on
-        the stream its forward ran on.  `post(e, tokens)` is applied on the expert's stream.  MM_MOE_STREAMS=0: one after the
-        other on the current stream.
-    With `grouped` (config `grouped_towers`, MM_MOE_GROUPED) and eligible experts -- one VisionConfig, one dtype, all on the device, at
-    most MM_GROUP_MAX of them -- trainable, frozen and no-grad calls alike take ONE chain of grouped launches instead
-    (vision_grouped.grouped_towers): ordinary autograd, no graph, no side stream, no state between calls.  Ineligible experts take
-    the paths above, with one warning.
-    Same kernels either way, same results bit for bit."""
-    import os
-    n = pixels.shape[0]
-    if _grouped_on(grouped):
-        from .. import vision_grouped
-        why = vision_grouped.ineligible(experts) if pixels.is_cuda else "the pixels are not on the device"
-        if why is None:
-            outs = vision_grouped.grouped_towers(experts, pixels)
-            return [post(e, o) if post is not None else o for e, o in enumerate(outs)]
-        global _warned_ineligible
-        if not _warned_ineligible:
-            import warnings
-            _warned_ineligible = True
-            warnings.warn(f"grouped_towers: {why}; the expert towers run one by one")
-
-    def tower(e, expert, px=None):
-        hs = expert(pixels if px is None else px).last_hidden_state                             # [n, 1+P, C]
-        T = hs.shape[1]
-        return Fm.drop_cls(hs.reshape(n * T, -1), n, T)                                          # [n, P, C]
-
-    frozen = not torch.is_grad_enabled() or not any(p.requires_grad for ex in experts for p in ex.parameters())
-    if frozen and pixels.is_cuda and os.environ.get("MM_MOE_GRAPH", "1") != "0":
-        outs = _frozen_towers(experts, pixels, tower)
-        return [post(e, o) if post is not None else o for e, o in enumerate(outs)]
-    if (not frozen and pixels.is_cuda and not pixels.requires_grad and os.environ.get("MM_MOE_GRAPH", "1") != "0"
-            and os.environ.get("MM_MOE_TRAIN_GRAPH", "1") != "0" and _graphable(experts)):
-        outs = _trainable_towers(experts, pixels, tower)
-        if outs is not None:
-            return [post(e, o) if post is not None else o for e, o in enumerate(outs)]
-        # None: a forward of this pixel shape still waits for its backward (two micro-batch losses summed before .backward(), a
-        # grad-enabled evaluation in between): the graphs' saved activations are shared buffers, so THIS call takes the eager launches
-    if len(experts) == 1 or not pixels.is_cuda or os.environ.get("MM_MOE_STREAMS", "1") == "0":
-        return [post(e, tower(e, ex)) if post is not None else tower(e, ex) for e, ex in enumerate(experts)]
-    main = torch.cuda.current_stream()
-    outs = []
-    for e, ex in enumerate(experts):
-        st = _expert_stream(pixels.device, e)
-        st.wait_stream(main)                                              # pixels (and the previous step's work) are ready
-        with torch.cuda.stream(st):
-            o = tower(e, ex)
-            if post is not None:
-                o = post(e, o)
-        o.record_stream(main)                                             # produced on `st`, consumed on the compute stream
-        outs.append((o, st))
-    for _, st in outs:
-        main.wait_stream(st)
-    return [o for o, _ in outs]
-
-
-def _frozen_towers(experts, pixels, tower):
-    """Captured-graph forward of frozen expert towers: -> list of [n, P, C] token tensors (no autograd history).  One graph per
-    (image count, image size, parameter storage); the pixels are copied into the graph's input buffer, the outputs out of its pool."""
-    key = (tuple(pixels.shape), pixels.dtype, experts[0].embeddings.position_embedding.weight.data_ptr())
-    cache = getattr(experts, "_mm_graphs", None)
-    if cache is None:
-        cache = experts._mm_graphs = {}
-    ent = cache.get(key)
-    if ent is None:
-        with torch.no_grad():
-            static_px = pixels.clone()
-            cur = torch.cuda.current_stream()
-            warm = torch.cuda.Stream()
-            warm.wait_stream(cur)
-            with torch.cuda.stream(warm):                                 # lazy initialisation (kernel attributes, id checks) outside capture
-                for _ in range(2):
-                    for e, ex in enumerate(experts):
-                        tower(e, ex, static_px)
-            cur.wait_stream(warm)
-            graph = torch.cuda.CUDAGraph()
-            with _no_gc(), torch.cuda.graph(graph):
-                main = torch.cuda.current_stream()
-                res = []
-                for e, ex in enumerate(experts):                          # fork: every tower on its own branch of the graph
-                    st = _expert_stream(pixels.device, e)
-                    st.wait_stream(main)
-                    with torch.cuda.stream(st):
-                        res.append(tower(e, ex, static_px))
-                for e in range(len(experts)):
-                    main.wait_stream(_expert_stream(pixels.device, e))    # join
-        ent = cache[key] = (graph, static_px, res)
-        if len(cache) > 8:                                                # a handful of image counts at most: drop the oldest
-            cache.pop(next(iter(cache)))
-    graph, static_px, res = ent
-    static_px.copy_(pixels)
-    graph.replay()
-    return [o.clone() for o in res]
-
-
-class _no_gc:
-    """No automatic garbage collection while a hipGraph is being captured: a collection that happens to run mid-capture can destroy
-    an OLDER graph (an earlier model's towers) -- releasing a graph's memory pool is not a capturable operation and aborts the
-    process.  (torch.cuda.graph collects once on entry; this keeps the interpreter from collecting again before the capture ends.)"""
-
-    def __enter__(self):
-        import gc
-        self.was = gc.isenabled()
-        gc.disable()
-
-    def __exit__(self, *exc):
-        import gc
-        if self.was:
-            gc.enable()
-
-
-def _graphable(experts):
-    """Trainable towers can be replayed from captured graphs when every parameter's gradient lives in a flat buffer (the wgrad
-    kernels write `param.grad` in place: a gradient tensor allocated during capture would belong to the graph's pool)."""
-    return all(getattr(p, "_mm_flat", None) is not None for ex in experts for p in ex.parameters() if p.requires_grad)
-
-
-class _TowerGraphs:
-    """Forward and backward hipGraphs of E TRAINABLE expert towers for one pixel shape.  The forward graph is captured with
-    autograd recording, on E parallel branches; the autograd graph of that capture is kept, and the backward graphs are captured
-    by running it (per expert, on the expert's branch) -- one graph for `first gradient of the step` (the wgrad kernels overwrite)
-    and one for `accumulate`.  A replay costs the host two calls instead of ~1,200 launches per ViT-L/14 tower, which is what
-    bounds E trainable towers otherwise (E host-bound chains)."""
-
-    def __init__(self, experts, pixels, tower):
-        from ... import functional as F_
-        import gc
-        torch.cuda.synchronize()            # garbage (older graphs, their pools) goes now, at a quiet point, not in the middle of the
-        gc.collect()                        # warm-up / capture / first replay below
-        self.experts = experts
-        self.params = [p for ex in experts for p in ex.parameters() if p.requires_grad]
-        dev = pixels.device
-        self.streams = [_expert_stream(dev, e) for e in range(len(experts))]
-        self.static_px = pixels.detach().clone()
-        cur = torch.cuda.current_stream()
-        warm = torch.cuda.Stream()
-        warm.wait_stream(cur)
-        with torch.cuda.stream(warm), torch.no_grad():                      # lazy initialisation outside capture
-            for e, ex in enumerate(experts):
-                tower(e, ex, self.static_px)
-        cur.wait_stream(warm)
-        self.fwd = torch.cuda.CUDAGraph()
-        with _no_gc(), torch.enable_grad(), torch.cuda.graph(self.fwd):
-            main = torch.cuda.current_stream()
-            self.res = []
-            for e, ex in enumerate(experts):
-                st = self.streams[e]
-                st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    self.res.append(tower(e, ex, self.static_px))
-            for st in self.streams:
-                main.wait_stream(st)
-        self.pool = self.fwd.pool()
-        self.static_g = [torch.zeros_like(o) for o in self.res]
-        self.bwd = {}
-        self.warmed = False
-        self._F = F_
-        # The saved activations of the capture are SHARED buffers: a second forward before the first one's backward would overwrite
-        # what that backward reads, and a second backward of one forward would re-read buffers a later forward has refilled.
-        # `generation` counts forwards; `pending` = the generation whose backward has not run yet (None: the buffers are free).
-        self.generation = 0
-        self.pending = None
-
-    def _flags(self, fresh):
-        for p in self.params:
-            p._mm_flat.ensure_grad()
-            p.grad = p._mm_grad_view
-            p._mm_fresh = fresh
-
-    def _run_autograd(self):
-        main = torch.cuda.current_stream()
-        for e, st in enumerate(self.streams):
-            st.wait_stream(main)
-            with torch.cuda.stream(st):
-                torch.autograd.backward([self.res[e]], [self.static_g[e]], retain_graph=True)
-        for st in self.streams:
-            main.wait_stream(st)
-
-    def forward(self, pixels):
-        mods = [m for ex in self.experts for m in ex.modules() if m._forward_pre_hooks]      # looked up per call: a Trainer may come later
-        for m in mods:                                                       # parameter-read hooks (the Trainer's per-block wait for
-            kw = getattr(m, "_forward_pre_hooks_with_kwargs", {})            # the overlapped optimiser): the replay calls no module
-            for hid, hook in list(m._forward_pre_hooks.items()):
-                if hid in kw:
-                    hook(m, (), {})
-                else:
-                    hook(m, ())
-        self.static_px.copy_(pixels)
-        self.fwd.replay()
-        self.generation += 1
-        self.pending = self.generation
-        return [o.detach().clone() for o in self.res]
-
-    def backward(self, grads, generation=None):
-        if generation is not None and generation != self.pending:
-            raise RuntimeError("MoE expert towers (graph replay): backward of a forward whose saved activations are gone -- it ran "
-                               "twice, or another forward of the same pixel shape ran in between (MM_MOE_TRAIN_GRAPH=0 = eager towers)")
-        self.pending = None
-        F_ = self._F
-        p0 = self.params[0]
-        fresh = p0.grad is None or bool(getattr(p0, "_mm_fresh", False))
-        for sg, g in zip(self.static_g, grads):
-            if g is None:
-                sg.zero_()
-            else:
-                sg.copy_(g)
-        if not self.warmed:                 # first backward: eager, through the autograd graph of the capture (its saved tensors are
-            self.warmed = True              # the graph's buffers, which the forward replay has just filled) -- a real backward
-            self._flags(fresh)
-            hook, order = F_._grad_ready_hook, []
-
-            def spy(p):                     # which parameters report a finished gradient, and in which order: replays repeat it
-                order.append(p)
-                if hook is not None:
-                    hook(p)
-
-            F_.set_grad_ready_hook(spy)
-            try:
-                self._run_autograd()
-            finally:
-                F_.set_grad_ready_hook(hook)
-            self.ready_order = order
-            return
-        g = self.bwd.get(fresh)
-        if g is None:
-            hook = F_._grad_ready_hook
-            F_.set_grad_ready_hook(None)    # python side effects do not replay: the hooks are called after every replay instead
-            try:
-                self._flags(fresh)
-                g = torch.cuda.CUDAGraph()
-                with _no_gc(), torch.cuda.graph(g, pool=self.pool):
-                    self._run_autograd()
-            finally:
-                F_.set_grad_ready_hook(hook)
-            self.bwd[fresh] = g
-        self._flags(False)                  # what grad_target leaves behind: .grad attached, the next write accumulates
-        g.replay()
-        for p in self.ready_order:
-            F_._ready(p)
-
-
-class _TrainableTowersFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, dummy, pixels, graphs):
-        ctx.graphs = graphs
-        out = tuple(graphs.forward(pixels))
-        ctx.generation = graphs.generation
-        return out
-
-    @staticmethod
-    def backward(ctx, *grads):
-        ctx.graphs.backward(grads, ctx.generation)
-        return None, None, None
-
-
-def _trainable_towers(experts, pixels, tower):
-    """Graph-replayed forward + backward of trainable expert towers (see _TowerGraphs); same kernels as the eager path."""
-    key = ("train", tuple(pixels.shape), pixels.dtype, experts[0].embeddings.position_embedding.weight.data_ptr(),
-           tuple(p.requires_grad for ex in experts for p in ex.parameters()))
-    cache = getattr(experts, "_mm_graphs", None)
-    if cache is None:
-        cache = experts._mm_graphs = {}
-    ent = cache.get(key)
-    if ent is None:
-        ent = cache[key] = _TowerGraphs(experts, pixels, tower)
-        if len(cache) > 8:
-            cache.pop(next(iter(cache)))
-    if ent.pending is not None:
-        return None                          # its buffers hold a forward that still waits for its backward: this call runs eagerly
-    p0 = ent.params[0]
-    return list(_TrainableTowersFn.apply(grad_dummy(p0), pixels, ent))
-
-
-_EXPERT_STREAMS = {}
-
-
-def _expert_stream(device, e):
-    key = (device.index or 0, e)
-    if key not in _EXPERT_STREAMS:
-        _EXPERT_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _EXPERT_STREAMS[key]
-
-
 def _resolve_gate(config, gating_network, dtype, device):
     """The `gating_network=` argument wins; otherwise a `gating_path` that is a directory with a config.json is the reference's
     `GatingNetwork.from_pretrained(config.gating_path)` (image_modality_moe.py:123), in the modality's dtype and device; anything
@@ -513,27 +215,25 @@ class _FrozenGate:
             self._keep_gate_frozen()
 
 
-@AutoModality.register("moe_meditron_clip")             # applied last: the config class keeps the reference's model_type
-@AutoModality.register("moe_meditron_clip_shared")      # alias: the name the shipped recipes use (cookbook/sft/moe/*/*/shared/config.yaml),
-class MOEImageModality(_FrozenGate, BaseModality):      # which the reference itself does not register (image_modality_moe.py:89)
-    config_class = MOEImageConfig
-    preprocessor_class = MOEImageProcessor
+class _MOEImageBase(_FrozenGate, BaseModality):
+    """What the two MoE image modalities share: the experts, the gate and its class-order -> expert-order permutation, freezing,
+    and the three-way fusion.  A subclass states which VisionConfig fields the experts must share (`_same`, `_mismatch`), where its
+    projector(s) sit (`_add_expert` / `_build_projection`, `_post`, `_project`), which order of the gate's weights
+    `weighted_average` takes (`_fusion_weights`), and the texts of its errors (`_mismatch`, `_no_experts`)."""
+    _post = None                    # post(e, tokens): applied to every expert's tokens before the fusion
 
-    def __init__(self, config: MOEImageConfig, dtype: torch.dtype = torch.bfloat16, device=None,
-                 gating_network: Optional[Callable] = None):
+    def __init__(self, config: MOEImageConfig, dtype: torch.dtype = torch.bfloat16, device=None, gating_network: Optional[Callable] = None):
         super().__init__(config, dtype=dtype)
         self.expert_names: List[str] = list(config.expert_clip_names)
-        assert len(self.expert_names) > 0, "config.expert_clip_names must be non-empty"
+        assert len(self.expert_names) > 0, self._no_experts
         self.experts = nn.ModuleList()
         vis0 = None
         for name in self.expert_names:
             vis = VisionConfig.from_dict(resolve_vision_config(name))
-            if vis0 is None:
-                vis0 = vis
-            elif (vis.hidden_size, vis.num_patches) != (vis0.hidden_size, vis0.num_patches):
-                raise ValueError("every expert must produce the same [patches, width] token grid")      # reference :166 comment
-            self.experts.append(VisionTransformer(vis, dtype, device))       # = the reference's `expert_model.vision_model`
-        self.embedding_size = vis0.hidden_size
+            vis0 = vis0 or vis
+            if any(getattr(vis, k) != getattr(vis0, k) for k in self._same):
+                raise ValueError(self._mismatch)
+            self._add_expert(vis, config, dtype, device)
         self._num_patches_per_entry = vis0.num_patches
         self.generalist_idx = config.generalist_idx
         self.fusion_method = config.fusion_method.replace("-", "_")
@@ -549,61 +249,93 @@ class MOEImageModality(_FrozenGate, BaseModality):      # which the reference it
         else:
             perm = list(range(len(self.experts)))
         self.register_buffer("_gating_to_expert_perm", torch.tensor(perm, dtype=torch.long), persistent=False)
-        self.projector = MLPProjector(self.embedding_size, config.hidden_size, dtype=dtype, device=device)
+        self._build_projection(vis0, config, dtype, device)              # sets `embedding_size`, the width the LLM sees
         if self.fusion_method == "cross_attn":
-            self.cross_attn = CrossAttention(self.embedding_size, num_heads=config.cross_attn_heads, qkv_bias=True, dtype=dtype,
-                                             device=device)
+            self.cross_attn = CrossAttention(self.embedding_size, num_heads=config.cross_attn_heads, qkv_bias=True, dtype=dtype, device=device)
         self.modality_frozen = not self.training
+
+    def _add_expert(self, vis, config, dtype, device):
+        self.experts.append(VisionTransformer(vis, dtype, device))       # = the reference's `expert_model.vision_model`
 
     @property
     def device(self):
         return self.experts[0].embeddings.patch_embedding.weight.device
 
-    def gate_weights(self, pixels: torch.Tensor) -> torch.Tensor:
+    def _gate(self, pixels: torch.Tensor) -> torch.Tensor:
+        """-> the gate's weights [n, E], fp32 on the device, in the gate's own class order"""
         if self.gating_network is None:
-            raise NotImplementedError(_NO_GATE.format(cls="MOEImageModality"))
+            raise NotImplementedError(_NO_GATE.format(cls=type(self).__name__))
         _logits, _topk, weights = self.gating_network(pixels)
-        w = weights.to(device=self.device, dtype=torch.float32)
-        return w.index_select(-1, self._gating_to_expert_perm.to(w.device)).contiguous()      # reference :171-173, :185-186
+        return weights.to(device=self.device, dtype=torch.float32)
+
+    def _expert_order(self, w: torch.Tensor) -> torch.Tensor:
+        return w.index_select(-1, self._gating_to_expert_perm.to(w.device)).contiguous()
+
+    def gate_weights(self, pixels: torch.Tensor) -> torch.Tensor:
+        return self._expert_order(self._gate(pixels))                    # reference :171-173, :185-186
 
     def forward(self, inputs, stages=None) -> torch.Tensor:
         pixels = torch.stack(list(inputs), dim=0) if not torch.is_tensor(inputs) else inputs
         pixels = pixels.to(self.device, non_blocking=True)
         n, E = pixels.shape[0], len(self.experts)
-        w = self.gate_weights(pixels)                                     # [n, E] fp32, expert order
-        feats = _run_experts(self.experts, pixels, grouped=getattr(self.config, "grouped_towers", False))      # every expert on every image (reference :156-160)
+        w_avg, w_expert = self._fusion_weights(pixels)                    # [n, E] fp32; the gate runs before the towers
+        # every expert on every image (reference :156-160)
+        feats = run_experts(self.experts, pixels, post=self._post, grouped=getattr(self.config, "grouped_towers", False))
         stacked = torch.stack(feats, dim=0)                               # [E, n, P, C] (device copy; autograd unbinds it)
         P, C = stacked.shape[2], stacked.shape[3]
         if self.fusion_method == "sequence_append":
             fused = stacked.permute(1, 0, 2, 3).reshape(n, E * P, C)
         elif self.fusion_method == "weighted_average":
-            fused = Fm.expert_fuse(stacked, w, list(range(E)), 0)
+            fused = Fm.expert_fuse(stacked, w_avg, list(range(E)), 0)
         elif self.fusion_method == "cross_attn":
             gi = self.generalist_idx % E
             spec = [i for i in range(E) if i != gi]
-            ctx = Fm.expert_fuse(stacked, w, spec, 1)                     # [n, (E-1)*P, C], each specialist scaled by its weight
+            ctx = Fm.expert_fuse(stacked, w_expert(), spec, 1)            # [n, (E-1)*P, C], each specialist scaled by its weight
             fused = self.cross_attn(stacked[gi], ctx)
         else:
             raise ValueError(f"Unsupported fusion_method: {self.fusion_method}")
-        out = self.projector(fused.contiguous())
+        fused = fused.contiguous()
+        out = self._project(fused)
         if stages is not None:
             stages["moe_fused"] = fused
             stages["projector_out"] = out
         return out
 
-    def freeze_modality_embedder(self):
+    def _set_experts_trainable(self, flag: bool):
         for e in self.experts:
             for p in e.parameters():
-                p.requires_grad = False
-        self.modality_frozen = True
+                p.requires_grad = flag
+        self.modality_frozen = not flag
+
+    def freeze_modality_embedder(self):
+        self._set_experts_trainable(False)
         self._on_freeze()
 
     def unfreeze_modality_embedder(self):
-        for e in self.experts:
-            for p in e.parameters():
-                p.requires_grad = True
-        self.modality_frozen = False
+        self._set_experts_trainable(True)
         self._on_unfreeze()
+
+
+@AutoModality.register("moe_meditron_clip")             # applied last: the config class keeps the reference's model_type
+@AutoModality.register("moe_meditron_clip_shared")      # alias: the name the shipped recipes use (cookbook/sft/moe/*/*/shared/config.yaml),
+class MOEImageModality(_MOEImageBase):                  # which the reference itself does not register (image_modality_moe.py:89)
+    """experts -> fusion in the towers' width -> ONE projector"""
+    config_class = MOEImageConfig
+    preprocessor_class = MOEImageProcessor
+    _same = ("hidden_size", "num_patches")
+    _mismatch = "every expert must produce the same [patches, width] token grid"      # reference :166 comment
+    _no_experts = "config.expert_clip_names must be non-empty"
+
+    def _build_projection(self, vis0, config, dtype, device):
+        self.embedding_size = vis0.hidden_size
+        self.projector = MLPProjector(self.embedding_size, config.hidden_size, dtype=dtype, device=device)
+
+    def _fusion_weights(self, pixels):
+        w = self.gate_weights(pixels)                                     # expert order for both fusions, permuted on every forward
+        return w, lambda: w
+
+    def _project(self, fused):
+        return self.projector(fused)
 
     def unfreeze_projection(self):
         for p in self.projector.parameters():
@@ -628,97 +360,34 @@ class MOEImageProcessorPEP(MOEImageProcessor):
 
 
 @AutoModality.register("moe_meditron_clip_pep")
-class MOEImageModalityPEP(_FrozenGate, BaseModality):
+class MOEImageModalityPEP(_MOEImageBase):
     """reference image_modality_moe_pep.py:91-288: experts -> one projector PER expert -> fusion in the projected space."""
     config_class = MOEImageConfigPEP
     preprocessor_class = MOEImageProcessorPEP
+    _same = ("image_size", "patch_size")                                 # reference :131-137
+    _mismatch = "sequence_append requires identical (image_size, patch_size) across experts."
+    _no_experts = "No experts provided in config.expert_clip_names."
 
-    def __init__(self, config: MOEImageConfigPEP, dtype: torch.dtype = torch.bfloat16, device=None,
-                 gating_network: Optional[Callable] = None):
-        super().__init__(config, dtype=dtype)
-        self.expert_names: List[str] = list(config.expert_clip_names)
-        assert len(self.expert_names) > 0, "No experts provided in config.expert_clip_names."
-        self.experts = nn.ModuleList()
-        self.projectors = nn.ModuleList()
-        vis0 = None
-        for name in self.expert_names:
-            vis = VisionConfig.from_dict(resolve_vision_config(name))
-            if vis0 is None:
-                vis0 = vis
-            elif (vis.image_size, vis.patch_size) != (vis0.image_size, vis0.patch_size):      # reference :131-137
-                raise ValueError("sequence_append requires identical (image_size, patch_size) across experts.")
-            self.experts.append(VisionTransformer(vis, dtype, device))
-            if config.projection_type != "mlp":
-                raise ValueError(f"Unsupported projection_type: {config.projection_type}")
-            self.projectors.append(MLPProjector(vis.hidden_size, config.hidden_size, dtype=dtype, device=device))
+    def _add_expert(self, vis, config, dtype, device):
+        super()._add_expert(vis, config, dtype, device)
+        if config.projection_type != "mlp":
+            raise ValueError(f"Unsupported projection_type: {config.projection_type}")
+        if "projectors" not in self._modules:
+            self.projectors = nn.ModuleList()
+        self.projectors.append(MLPProjector(vis.hidden_size, config.hidden_size, dtype=dtype, device=device))
+
+    def _build_projection(self, vis0, config, dtype, device):
         self.embedding_size = config.hidden_size                         # post-projection width seen by the LLM (:252-254)
-        self._num_patches_per_entry = vis0.num_patches
-        self.generalist_idx = config.generalist_idx
-        self.fusion_method = config.fusion_method.replace("-", "_")
-        gating_network = _resolve_gate(config, gating_network, dtype, device)
-        self.gating_network = gating_network
-        names = list(getattr(getattr(gating_network, "config", None), "class_names", []) or [])
-        if names:
-            lookup = {nm: i for i, nm in enumerate(self.expert_names)}
-            try:
-                perm = [lookup[nm] for nm in names]
-            except KeyError as e:
-                raise ValueError(f"Gating class name {e} not found in expert_clip_names: {self.expert_names}")
-        else:
-            perm = list(range(len(self.experts)))
-        self.register_buffer("_gating_to_expert_perm", torch.tensor(perm, dtype=torch.long), persistent=False)
-        if self.fusion_method == "cross_attn":
-            self.cross_attn = CrossAttention(config.hidden_size, num_heads=config.cross_attn_heads, qkv_bias=True, dtype=dtype,
-                                             device=device)
-        self.modality_frozen = not self.training
 
-    @property
-    def device(self):
-        return self.experts[0].embeddings.patch_embedding.weight.device
+    def _post(self, e, tok):
+        return self.projectors[e](tok)                                    # [n, P, H]
 
-    def forward(self, inputs, stages=None) -> torch.Tensor:
-        pixels = torch.stack(list(inputs), dim=0) if not torch.is_tensor(inputs) else inputs
-        pixels = pixels.to(self.device, non_blocking=True)
-        n, E = pixels.shape[0], len(self.experts)
-        if self.gating_network is None:
-            raise NotImplementedError(_NO_GATE.format(cls="MOEImageModalityPEP"))
-        _logits, _topk, weights = self.gating_network(pixels)
-        w_raw = weights.to(device=self.device, dtype=torch.float32).contiguous()          # gate order, as weighted_average uses it (:214)
-        outs = _run_experts(self.experts, pixels, post=lambda e, tok: self.projectors[e](tok),
-                            grouped=getattr(self.config, "grouped_towers", False))                  # [n, P, H] each
-        stacked = torch.stack(outs, dim=0)                                # [E, n, P, H]
-        P, H = stacked.shape[2], stacked.shape[3]
-        if self.fusion_method == "sequence_append":
-            fused = stacked.permute(1, 0, 2, 3).reshape(n, E * P, H)
-        elif self.fusion_method == "weighted_average":
-            fused = Fm.expert_fuse(stacked, w_raw, list(range(E)), 0)
-        elif self.fusion_method == "cross_attn":
-            gi = self.generalist_idx % E
-            spec = [i for i in range(E) if i != gi]
-            w_exp = w_raw.index_select(-1, self._gating_to_expert_perm.to(w_raw.device)).contiguous()     # expert order (:229-230)
-            ctx = Fm.expert_fuse(stacked, w_exp, spec, 1)
-            fused = self.cross_attn(stacked[gi], ctx)
-        else:
-            raise ValueError(f"Unsupported fusion_method: {self.fusion_method}")
-        fused = fused.contiguous()
-        if stages is not None:
-            stages["moe_fused"] = fused
-            stages["projector_out"] = fused
+    def _fusion_weights(self, pixels):
+        w_raw = self._gate(pixels).contiguous()                           # gate order, as weighted_average uses it (:214)
+        return w_raw, lambda: self._expert_order(w_raw)                   # expert order for cross_attn only, after the towers (:229-230)
+
+    def _project(self, fused):
         return fused
-
-    def freeze_modality_embedder(self):
-        for e in self.experts:
-            for p in e.parameters():
-                p.requires_grad = False
-        self.modality_frozen = True
-        self._on_freeze()
-
-    def unfreeze_modality_embedder(self):
-        for e in self.experts:
-            for p in e.parameters():
-                p.requires_grad = True
-        self.modality_frozen = False
-        self._on_unfreeze()
 
     def unfreeze_projection(self):
         for p in self.projectors.parameters():

@@ -45,6 +45,11 @@ class VisionConfig:
     def num_patches(self):
         return (self.image_size // self.patch_size) ** 2
 
+    @property
+    def num_tokens(self):
+        """tokens per image in the tower: the patches, and CLIP's CLS token"""
+        return self.num_patches + (0 if self.kind == "siglip" else 1)
+
 
 class _PatchConv(nn.Module):
     _mm_param_holder = True      # never __call__ed: VisionEmbeddings.forward reads .weight/.bias (hooks belong on the parent)
@@ -73,7 +78,7 @@ class VisionEmbeddings(nn.Module):
         has_cls = cfg.kind != "siglip"
         self.class_embedding = nn.Parameter(torch.empty(cfg.hidden_size, dtype=dtype, device=device)) if has_cls else None
         self.patch_embedding = _PatchConv(cfg, dtype, device)
-        self.position_embedding = _PosEmb(cfg.num_patches + (1 if has_cls else 0), cfg.hidden_size, dtype, device)
+        self.position_embedding = _PosEmb(cfg.num_tokens, cfg.hidden_size, dtype, device)
 
     def forward(self, pixels):
         c = self.cfg
@@ -109,6 +114,18 @@ class VisionMLP(nn.Module):
         self.act = _ACT[cfg.hidden_act]
 
 
+def attention_core(qkv, B, T, heads, hd):
+    """Non-causal attention of B images of T tokens on the fused projection output qkv [B*T, 3*heads*hd] -> [B*T, heads*hd]; a
+    head width the flash kernels do not have runs zero-padded (e.g. SigLIP-so400m: 16 heads x 72 as 16 x 128, exact)."""
+    hw = Fm.attention_head_width(hd, qkv.dtype)
+    if hw != hd:
+        qkv = Fm.head_pad(qkv, 3 * heads, hd, hw)
+    o = Fm.rope_attention(qkv, None, None, None, B, T, heads, heads, hw, False, hd ** -0.5)
+    if hw != hd:
+        o = Fm.head_strip(o, heads, hd, hw)
+    return o
+
+
 class VisionLayer(nn.Module):
     def __init__(self, cfg, dtype, device):
         super().__init__()
@@ -121,13 +138,7 @@ class VisionLayer(nn.Module):
         a = self.self_attn
         h, x = self.layer_norm1(x)
         qkv = Fm.linear(h, a._wqkv, a._bqkv, dummy=grad_dummy(a.q_proj.weight))
-        hw = Fm.attention_head_width(a.hd, qkv.dtype)
-        if hw != a.hd:      # e.g. SigLIP-so400m: 16 heads x 72 run as 16 x 128 with zero columns (exact)
-            qkv = Fm.head_pad(qkv, 3 * a.heads, a.hd, hw)
-        o = Fm.rope_attention(qkv, None, None, None, n, T, a.heads, a.heads, hw, False, a.hd ** -0.5)
-        if hw != a.hd:
-            o = Fm.head_strip(o, a.heads, a.hd, hw)
-        x = a.out_proj(o, residual=x)
+        x = a.out_proj(attention_core(qkv, n, T, a.heads, a.hd), residual=x)
         h, x = self.layer_norm2(x)
         h = self.mlp.fc1(h, act=self.mlp.act)
         return self.mlp.fc2(h, residual=x)
@@ -156,7 +167,7 @@ class VisionTransformer(nn.Module):
 
     def forward(self, pixel_values, stages=None) -> VisionOutput:
         n = pixel_values.shape[0]
-        T = self.config.num_patches + (0 if self.config.kind == "siglip" else 1)
+        T = self.config.num_tokens
         x = self.embeddings(pixel_values)
         if stages is not None:
             stages["vit_embeddings"] = x.view(n, T, -1)

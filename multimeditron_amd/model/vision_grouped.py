@@ -16,7 +16,8 @@ import torch
 
 from .. import functional as Fm
 from .._lib import GROUP_MAX
-from ..nn import grad_dummy
+from ..nn import fire_forward_pre_hooks, grad_dummy
+from .vision import attention_core
 
 
 def ineligible(experts) -> Optional[str]:
@@ -37,20 +38,6 @@ def ineligible(experts) -> Optional[str]:
     return None
 
 
-def _fire_pre_hooks(mod, recurse=True):
-    """The grouped chain reads parameters without calling their modules: run the forward pre-hooks by hand (the Trainer's waits
-    for the overlapped / sharded optimiser hang there)."""
-    for m in (mod.modules() if recurse else (mod,)):
-        if not m._forward_pre_hooks:
-            continue
-        kw = getattr(m, "_forward_pre_hooks_with_kwargs", {})
-        for hid, hook in list(m._forward_pre_hooks.items()):
-            if hid in kw:
-                hook(m, (), {})
-            else:
-                hook(m, ())
-
-
 def _norm(norms, x):
     return Fm.grouped_layernorm(x, [m.weight for m in norms], [m.bias for m in norms], norms[0].eps, dummy=grad_dummy(norms[0].weight))
 
@@ -63,18 +50,12 @@ def _linear(lins, x, residual=None, act=0):
 def _layer(layers, x, B, T):
     """VisionLayer.forward for E experts at once; B = E * n images."""
     for l in layers:
-        _fire_pre_hooks(l)
+        fire_forward_pre_hooks(l)
     a0 = layers[0].self_attn
     h, x = _norm([l.layer_norm1 for l in layers], x)
     qkv = Fm.grouped_linear(h, [l.self_attn._wqkv for l in layers], [l.self_attn._bqkv for l in layers],
                             dummy=grad_dummy(a0.q_proj.weight))
-    hw = Fm.attention_head_width(a0.hd, qkv.dtype)
-    if hw != a0.hd:
-        qkv = Fm.head_pad(qkv, 3 * a0.heads, a0.hd, hw)
-    o = Fm.rope_attention(qkv, None, None, None, B, T, a0.heads, a0.heads, hw, False, a0.hd ** -0.5)
-    if hw != a0.hd:
-        o = Fm.head_strip(o, a0.heads, a0.hd, hw)
-    x = _linear([l.self_attn.out_proj for l in layers], o, residual=x)
+    x = _linear([l.self_attn.out_proj for l in layers], attention_core(qkv, B, T, a0.heads, a0.hd), residual=x)
     h, x = _norm([l.layer_norm2 for l in layers], x)
     h = _linear([l.mlp.fc1 for l in layers], h, act=layers[0].mlp.act)
     return _linear([l.mlp.fc2 for l in layers], h, residual=x)
@@ -86,24 +67,24 @@ def grouped_towers(experts, pixels) -> List[torch.Tensor]:
     experts = list(experts)
     E, n = len(experts), pixels.shape[0]
     cfg = experts[0].config
-    T = cfg.num_patches + (0 if cfg.kind == "siglip" else 1)
+    T = cfg.num_tokens
     for ex in experts:
-        _fire_pre_hooks(ex, recurse=False)
+        fire_forward_pre_hooks(ex, recurse=False)
     xs = [ex.embeddings(pixels) for ex in experts]             # once per tower; __call__: the embeddings' own hooks fire
     x = torch.cat(xs, dim=0)                                   # expert-major [E * n * T, C]
     if experts[0].pre_layrnorm is not None:
         norms = [ex.pre_layrnorm for ex in experts]
         for m in norms:
-            _fire_pre_hooks(m)
+            fire_forward_pre_hooks(m)
         x, _ = _norm(norms, x)
     for i in range(cfg.num_hidden_layers):
         x = _layer([ex.encoder.layers[i] for ex in experts], x, E * n, T)
     if experts[0].post_layernorm is not None:
         norms = [ex.post_layernorm for ex in experts]
         for m in norms:
-            _fire_pre_hooks(m)
+            fire_forward_pre_hooks(m)
         x, _ = _norm(norms, x)
     C = x.shape[-1]
-    x = Fm.drop_cls(x, E * n, T)                               # [E * n, T - 1, C], as _run_experts' per-expert tower does
+    x = Fm.drop_cls(x, E * n, T)                               # [E * n, T - 1, C], as expert_towers.run_experts' per-expert tower does
     P = x.shape[1]
     return list(x.view(E, n, P, C).unbind(0))

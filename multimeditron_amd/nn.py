@@ -66,6 +66,20 @@ class Norm(nn.Module):
         return Fm.layernorm(x2d, self.weight, self.bias, self.eps, dummy=d)
 
 
+def fire_forward_pre_hooks(module: nn.Module, recurse: bool = True):
+    """Run the forward pre-hooks of `module` (and of its submodules) by hand, for code that reads parameters without calling their
+    modules: the grouped expert chain, a graph replay (the Trainer's waits for the overlapped / sharded optimiser hang there)."""
+    for m in (module.modules() if recurse else (module,)):
+        if not m._forward_pre_hooks:
+            continue
+        kw = getattr(m, "_forward_pre_hooks_with_kwargs", {})
+        for hid, hook in list(m._forward_pre_hooks.items()):
+            if hid in kw:
+                hook(m, (), {})
+            else:
+                hook(m, ())
+
+
 _HF_NO_DECAY = None
 
 

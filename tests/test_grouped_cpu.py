@@ -81,7 +81,7 @@ def test_grouped_towers_config_field(pep):
 
 
 def test_environment_overrides_the_config_field(monkeypatch):
-    from multimeditron_amd.model.modalities.image_modality_moe import _grouped_on
+    from multimeditron_amd.model.expert_towers import _grouped_on
     monkeypatch.delenv("MM_MOE_GROUPED", raising=False)
     assert _grouped_on(True) and not _grouped_on(False)
     monkeypatch.setenv("MM_MOE_GROUPED", "1")

@@ -275,7 +275,7 @@ def test_the_expert_is_a_batch_dimension(moe, tmp_path, monkeypatch):
     """Library calls of forward + backward: the grouped E = 3 towers make no more calls than ONE tower, but for the embedding stage,
     which runs once per tower (not once per layer) and stays E calls."""
     from multimeditron_amd import functional as Fm
-    from multimeditron_amd.model.modalities.image_modality_moe import _run_experts
+    from multimeditron_amd.model.expert_towers import run_experts as _run_experts
     meta, w, v = moe
     m = _build(meta, w, v, "weighted_average", torch.bfloat16, tmp_path)
     _mode(monkeypatch, m, True)
@@ -310,7 +310,7 @@ def test_the_expert_is_a_batch_dimension(moe, tmp_path, monkeypatch):
 def test_ineligible_experts_take_the_old_paths_with_one_warning(moe, tmp_path, monkeypatch):
     """one expert with a different layer count: the switch changes nothing but for ONE warning"""
     import dataclasses
-    from multimeditron_amd.model.modalities import image_modality_moe as mod
+    from multimeditron_amd.model import expert_towers as mod
     from multimeditron_amd.model.vision import VisionTransformer
     from multimeditron_amd.nn import FlatParams
     meta, w, v = moe
