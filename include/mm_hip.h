@@ -56,14 +56,33 @@ const char* mm_error_string(int code);
  * hand-scheduled kernel gemm_bf16_w4_kernel: 0 = the 8-wave kernel, 1 = the shipped schedule, n = another schedule of
  * csrc/gen_gemm_w4.py: 4 / 5 split barriers, 6 / 7 = 1 / 4 with an L2 prefetch), "gemm_w4_big" 4|1 (schedule 4 where N or K >= 14336: default), "gemm_w4_rowmajor" 0|1 (its row-major, LDS-transposed epilogues), "gemm_w4_stream" 0|1 (wait-free plain
  * epilogue in the accumulator layout), "gemm_w4_shuffle" (0; 1 = the plain epilogue by register lane exchange instead of the LDS round trip: bit-identical, measured equal),
- * "gemm_w4_group_m", "gemm_w4_stagger" / "gemm_w4_stagger_slots" (experiments).  Unknown names return MM_ERR_ARG.   */
+ * "gemm_w4_group_m", "gemm_w4_stagger" / "gemm_w4_stagger_slots" (experiments), "gemm_epi_pipe" 0|1, "gemv_stream" 0|1, "gemv_nt" 0|1,
+ * "gemv_wgs", "gemm_w4_diag_epi" (diagnostic builds), "adamw_blocks" (mm_adamw_step), and the "attn_*" switches of the attention
+ * kernels.  A 0|1 switch stores value != 0; a value outside a switch's range returns MM_ERR_ARG and leaves the switch as it was;
+ * unknown names return MM_ERR_ARG.                                                                                       */
 int mm_set_option(const char* name, int value);
-/* current value of a "gemm_*" switch (so that a caller that flips one temporarily can restore what it found); also
- * "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged kernel (also the
- * fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10 the 4-wave
- * 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the decode
- * fusions), 30 the fp32 kernel */
+/* current value of a switch: every name mm_set_option answers except "attn_*" (one table serves both), so a caller that flips
+ * one temporarily can restore what it found.  MM_GEMM_KERNEL (environment, used while "gemm_kernel" is 0) does not show here.
+ * Also the read-only "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged
+ * kernel (also the fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10
+ * the 4-wave 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the
+ * decode fusions), 30 the fp32 kernel */
 int mm_get_option(const char* name, int* value);
+/* What a GEMM call with these facts would do, under the current switches: host only, launches nothing, needs no device when ncu
+ * is given, and leaves "gemm_last_kernel" alone.  It is the function the launcher itself runs (csrc/mm_gemm_plan.h).
+ * kind: 0 mm_gemm(_batched), 1 mm_gemm_act_fwd(_batched), 2 mm_gemm_swiglu_fwd (N = 2 swi_I), 3 mm_gemm_rope_fwd, 4 mm_gemm_swiglu_bwd
+ * (N = I, K = H, ldaux = ldgu), after the entry point's own argument checks; groups: 0 = a stand-alone call; ptr_bits: the low four
+ * address bits of A, B, C, bias, residual, aux (GU of swiglu_bwd), C2 (PRE / ACT) in nibbles 0..6 (a grouped call: OR-ed over its
+ * problems); ncu: compute units, 0 = those of the current device.
+ * plan[MM_GEMM_PLAN_INTS] receives: [0] the return code the call would give before launching, [1] "gemm_last_kernel" after the call
+ * (-2: unchanged), [2] the kernel family (-1 none, 0 register-staged 128x128, 1 LDS-DMA, 2 4-wave, 3 gemm_skinny, 4 gemv_stream, 5
+ * fp32), [3..10] its template arguments (register-staged {A_KC, B_KC}; LDS-DMA {A_KC, B_KC, BM, BN, WGM, STAGES, ISSUE_WAVES, EK};
+ * 4-wave {A_KC, B_KC, EK, SCHED}; gemv_stream {MODE, NORM, NT}; fp32 {LAYOUT}; the rest 0), [11..14] grid x, grid y, block, dynamic
+ * LDS bytes, [15..25] the kernel arguments nbm, nbn, tail, pipe, stagger, stagger_slots, diag_epi, shuffle, group_m, stream_epi,
+ * rowmajor.  MM_ERR_ARG for a NULL plan or facts no entry point passes on (M, N <= 0, unknown layout / kind / epilogue bits).   */
+enum { MM_GEMM_PLAN_INTS = 26 };
+int mm_gemm_plan(int dtype, int layout, int kind, int groups, int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldaux,
+                 int epilogue, int swi_I, int ptr_bits, int ncu, int* plan);
 
 /* ---- GEMM: every nn.Linear / Conv2d(k=s) on the path -------------------------------------
  * replaces F.linear in mlp.py:33-39, HF:clip:280-384 (q/k/v/out/fc1/fc2), HF:clip:152-158 (patch conv as

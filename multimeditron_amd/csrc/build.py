@@ -30,7 +30,7 @@ def build(force=False, verbose=True):
     gen, inc = os.path.join(HERE, "gen_gemm_w4.py"), os.path.join(HERE, "mm_gemm_w4.inc")
     if force or _stale(inc, [gen]):                     # the 4-wave GEMM's main loop (asm text) is generated
         subprocess.run([sys.executable, gen], check=True, stdout=subprocess.DEVNULL)
-    headers = [os.path.join(HERE, "mm_common.h"), os.path.join(PKG, "..", "include", "mm_hip.h"), inc]
+    headers = [os.path.join(HERE, "mm_common.h"), os.path.join(HERE, "mm_gemm_plan.h"), os.path.join(PKG, "..", "include", "mm_hip.h"), inc]
     jobs = []
     for src in SOURCES:
         s = os.path.join(HERE, src)

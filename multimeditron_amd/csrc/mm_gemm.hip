@@ -18,16 +18,17 @@
 // padding and K only has to be a multiple of 8 for K-contiguous operands.
 //
 // f32 path (parity only): 64x64x16 tiles on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain).
+//
+// The file's last part is the host half.  Which kernel a call runs on, its grid, schedule and kernel-argument switches are decided
+// by gemm_plan (mm_gemm_plan.h, plain C++): one launcher serves the stand-alone and the grouped entry points, fills GemmArgs from
+// the plan and picks the instantiation from one template table; mm_gemm_plan reports the same plan without launching.
+#include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
 #include <string.h>
 
 #include "mm_common.h"
-
-// default DMA variant when both fit: 1 = 256x128 (3-stage ring), 2 = 256x256 (2 stages)
-#ifndef MM_DEFAULT_DMA_VARIANT
-#define MM_DEFAULT_DMA_VARIANT(tiles256) ((tiles256) >= 192 ? 2 : 1)
-#endif
+#include "mm_gemm_plan.h"      // which kernel runs, on what grid and with which schedule: the host half below launches its plan
 
 namespace {
 
@@ -62,7 +63,6 @@ struct GemmArgs {
                                 // path is what a round's epilogue burst queues at) -- spreads the bursts inside every XCD
   int rowmajor;                 // 4-wave kernel: the plain epilogue in its row-major form (16-byte accesses; set by the host when alignment allows)
 };
-constexpr int MM_EPI_SWIGLU_BWD = 1 << 20;   // internal epilogue flag (mm_gemm_swiglu_bwd), not part of the ABI enum
 
 __device__ __forceinline__ float act_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float act_quick_gelu(float x) { return x / (1.0f + __expf(-1.702f * x)); }
@@ -2345,41 +2345,14 @@ __global__ __launch_bounds__(256) void colsum_kernel_batched(ColsumBatch t, int 
 
 }  // namespace
 
-static int g_opt_persist = 1;   // walk tiles with resident workgroups
-static int g_opt_kernel = 0;    // 0 auto, 1 v1 (128x128 register staged), 2..6 LDS-DMA tiles 256x128, 256x256, 128x128, 64x128, 64x64
-static int g_opt_tail = 1;      // cut the tiles of a less-than-half-full last round into 256x128 halves (persistent 256x256 grid)
-static int g_opt_skinny = 1;    // M <= 16 NT problems (decode) on the weight-streaming kernel
-static int g_opt_gemv_stream = 1;   // ... in its ring-buffered form (gemv_stream_kernel); 0 = gemm_skinny_kernel (A/B)
-static int g_opt_gemv_nt = 0;       // non-temporal policy on the decode kernels' weight loads (A/B: tools/gemv_bench.py)
-static int g_opt_gemv_wgs = 0;      // persistent workgroups per CU of gemv_stream_kernel (0 = what fits: 2, or 1 with a large x)
-static int g_opt_small = -1;    // experiments: force the DMA variant for problems that do not fill the chip (-1 = heuristic)
-// problems too small for the 256-wide tiles (ViT-L/14 on 4 images = 1028 rows, projector): these are latency-bound, so
-// the tile is chosen by how many workgroups it yields (tools/gemm_bench.py --small: 64x128 wins up to ~96 tiles of
-// 128x128, the 128x128 LDS-DMA kernel up to ~320, beyond that the register-staged 128x128 kernel at 2 workgroups/CU)
-static int small_variant(int M, int N, int K) {
-  (void)K;
-  if (g_opt_small >= 0) return g_opt_small;
-  const int64_t t = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  return t <= 96 ? 4 : (t <= 320 ? 3 : 0);
-}
-static int g_opt_epi_pipe = 1;      // pipelined, branch-free epilogue of the plain / SwiGLU-backward LDS-DMA kernels
-static int g_opt_issue_waves = 4;   // waves that issue the 256x256 kernel's DMA (4 staggers the two waves of each SIMD)
-static int g_opt_w4_big = 4;        // 4 = the split-barrier schedule 4 for operands that stream from HBM (N or K >= 14336), 1 = schedule 1 everywhere.  Step A/B, three series on three boxes: 354.2 / 348.6 / 353.9 vs 355.6 / 352.2 / 355.4 ms (medians)
-                                    // SwiGLU GEMMs alone, 348.6 vs 352.2 ms at step level, tools/step_ab.py: off)
-static int g_opt_w4_group_m = 8;    // experiment: GROUP_M of the 4-wave kernel's tile order
-static int g_opt_w4_stream = 1;     // 4-wave kernel: wait-free plain epilogue (0 = gemm_epilogue_plain_pipe, A/B)
-static int g_opt_w4_shuffle = 0;    // GemmArgs::shuffle (measured equal to the LDS form within +-0.5 %: DESIGN.md section 4, the round-4 list, item 8)
-static int g_opt_w4_diag_epi = 0;   // MM_W4_DIAG builds: GemmArgs::diag_epi
-// which kernel the last mm_gemm* / mm_decode_* call launched (mm_get_option "gemm_last_kernel"; -1 before the first):
-//   0 gemm_bf16_kernel (v1, 128x128 register staged; also the fallback when a K-strided operand or C passes the 32-bit offsets)
-//   1..5 gemm_bf16_dma_kernel tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64
-//   10 gemm_bf16_w4_kernel (4-wave 256x256)     20 gemm_skinny_kernel     21 gemv_stream_kernel (M <= 16 NT, decode fusions)
-//   30 gemm_f32_kernel
-static int g_last_kernel = -1;
-static int g_opt_w4_stagger_slots = 4;
-static int g_opt_w4_stagger = 0;    // experiment: see GemmArgs::stagger
-static int g_opt_w4_rowmajor = 1;   // 4-wave kernel: row-major (LDS-transposed, 16-byte) plain epilogue; 0 = the accumulator-layout epilogue (A/B)
-static int g_opt_w4 = [] { const char* e = getenv("MM_GEMM_W4"); return e ? atoi(e) : 1; }();            // (MM_GEMM_W4=0: A/B at step level) NT / NN 256x256 tiles on the 4-wave hand-scheduled kernel (gemm_bf16_w4_kernel); 0 = the 8-wave kernel (A/B)
+// ---- host half: options, entry points, and one launcher that runs what gemm_plan (mm_gemm_plan.h) decides ------------------------
+static GemmOptions g_opt = [] {
+  GemmOptions o;
+  if (const char* e = getenv("MM_GEMM_W4")) o.w4 = atoi(e);                                   // A/B at step level
+  if (const char* e = getenv("MM_GEMM_KERNEL")) o.kernel_env = e[0] == 'v' ? 1 : (e[0] == 'b' ? 3 : 2);      // v1 | dma (256x128) | big (256x256)
+  return o;
+}();
+static int g_last_kernel = -1;      // which kernel the last mm_gemm* / mm_decode_* call launched ("gemm_last_kernel": ids in mm_hip.h)
 
 int mm_attn_option(const char* name, int value);
 
@@ -2404,52 +2377,74 @@ extern "C" int mm_w4_diag_read(unsigned* out, int reset) {      // diag builds o
 }
 #endif
 
+// every switch mm_set_option and mm_get_option answer (the attn_* names are forwarded to mm_attn.hip).  kind: 'b' any value, stored
+// as value != 0; 'r' lo <= value <= hi; 'e' lo or hi
+struct OptionRow { const char* name; int* value; int lo, hi; char kind; };
+static const OptionRow g_options[] = {
+    {"adamw_blocks", &g_adamw_blocks, 0, INT_MAX, 'r'},
+    {"gemm_tail", &g_opt.tail, 0, 1, 'b'},
+    {"gemm_skinny", &g_opt.skinny, 0, 1, 'b'},
+    {"gemv_stream", &g_opt.gemv_stream, 0, 1, 'b'},
+    {"gemv_nt", &g_opt.gemv_nt, 0, 1, 'b'},
+    {"gemv_wgs", &g_opt.gemv_wgs, INT_MIN, INT_MAX, 'r'},
+    {"gemm_small", &g_opt.small, -1, 5, 'r'},
+    {"gemm_persist", &g_opt.persist, 0, 1, 'b'},
+    {"gemm_epi_pipe", &g_opt.epi_pipe, 0, 1, 'b'},
+    {"gemm_issue_waves", &g_opt.issue_waves, 4, 8, 'e'},
+    {"gemm_w4_rowmajor", &g_opt.w4_rowmajor, 0, 1, 'b'},
+    {"gemm_w4_big", &g_opt.w4_big, 1, 4, 'e'},
+    {"gemm_w4_group_m", &g_opt.w4_group_m, 1, INT_MAX, 'r'},
+    {"gemm_w4_stream", &g_opt.w4_stream, 0, 1, 'b'},
+    {"gemm_w4_shuffle", &g_opt.w4_shuffle, 0, 1, 'b'},
+    {"gemm_w4_diag_epi", &g_opt.w4_diag_epi, INT_MIN, INT_MAX, 'r'},
+    {"gemm_w4_stagger_slots", &g_opt.w4_stagger_slots, 1, 32, 'r'},
+    {"gemm_w4_stagger", &g_opt.w4_stagger, 0, INT_MAX, 'r'},
+    {"gemm_w4", &g_opt.w4, 0, INT_MAX, 'r'},
+    {"gemm_kernel", &g_opt.kernel, 0, 6, 'r'},
+};
+static const OptionRow* find_option(const char* name) {
+  for (const OptionRow& r : g_options)
+    if (!strcmp(name, r.name)) return &r;
+  return nullptr;
+}
+
 extern "C" int mm_set_option(const char* name, int value) {
   if (!name) return MM_ERR_ARG;
   if (!strncmp(name, "attn_", 5)) return mm_attn_option(name, value);
-  if (!strcmp(name, "adamw_blocks")) { if (value < 0) return MM_ERR_ARG; g_adamw_blocks = value; return MM_OK; }
-  if (!strcmp(name, "gemm_tail")) { g_opt_tail = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_skinny")) { g_opt_skinny = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemv_stream")) { g_opt_gemv_stream = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemv_nt")) { g_opt_gemv_nt = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemv_wgs")) { g_opt_gemv_wgs = value; return MM_OK; }
-  if (!strcmp(name, "gemm_small")) { if (value < -1 || value > 5) return MM_ERR_ARG; g_opt_small = value; return MM_OK; }
-  if (!strcmp(name, "gemm_persist")) { g_opt_persist = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_epi_pipe")) { g_opt_epi_pipe = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_issue_waves")) { if (value != 4 && value != 8) return MM_ERR_ARG; g_opt_issue_waves = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_rowmajor")) { g_opt_w4_rowmajor = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_big")) { if (value != 1 && value != 4) return MM_ERR_ARG; g_opt_w4_big = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_group_m")) { if (value < 1) return MM_ERR_ARG; g_opt_w4_group_m = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_stream")) { g_opt_w4_stream = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_shuffle")) { g_opt_w4_shuffle = value != 0; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_diag_epi")) { g_opt_w4_diag_epi = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_stagger_slots")) { if (value < 1 || value > 32) return MM_ERR_ARG; g_opt_w4_stagger_slots = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_stagger")) { if (value < 0) return MM_ERR_ARG; g_opt_w4_stagger = value; return MM_OK; }
-  if (!strcmp(name, "gemm_w4")) { if (value < 0) return MM_ERR_ARG; g_opt_w4 = value; return MM_OK; }      // 0 off, 1 the shipped schedule, n > 1: gen_gemm_w4.py SCHEDS
-  if (!strcmp(name, "gemm_kernel")) { if (value < 0 || value > 6) return MM_ERR_ARG; g_opt_kernel = value; return MM_OK; }
-  return MM_ERR_ARG;
+  const OptionRow* r = find_option(name);
+  if (!r) return MM_ERR_ARG;
+  if (r->kind == 'b') value = value != 0;
+  else if (r->kind == 'e' ? (value != r->lo && value != r->hi) : (value < r->lo || value > r->hi)) return MM_ERR_ARG;
+  *r->value = value;
+  return MM_OK;
 }
 
 extern "C" int mm_get_option(const char* name, int* value) {
   if (!name || !value) return MM_ERR_ARG;
-  if (!strcmp(name, "gemm_tail")) { *value = g_opt_tail; return MM_OK; }
-  if (!strcmp(name, "gemm_skinny")) { *value = g_opt_skinny; return MM_OK; }
-  if (!strcmp(name, "gemv_stream")) { *value = g_opt_gemv_stream; return MM_OK; }
-  if (!strcmp(name, "gemv_nt")) { *value = g_opt_gemv_nt; return MM_OK; }
-  if (!strcmp(name, "gemv_wgs")) { *value = g_opt_gemv_wgs; return MM_OK; }
-  if (!strcmp(name, "gemm_small")) { *value = g_opt_small; return MM_OK; }
-  if (!strcmp(name, "gemm_persist")) { *value = g_opt_persist; return MM_OK; }
-  if (!strcmp(name, "gemm_epi_pipe")) { *value = g_opt_epi_pipe; return MM_OK; }
-  if (!strcmp(name, "gemm_issue_waves")) { *value = g_opt_issue_waves; return MM_OK; }
-  if (!strcmp(name, "gemm_w4")) { *value = g_opt_w4; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_rowmajor")) { *value = g_opt_w4_rowmajor; return MM_OK; }
-  if (!strcmp(name, "gemm_w4_shuffle")) { *value = g_opt_w4_shuffle; return MM_OK; }
-  if (!strcmp(name, "gemm_last_kernel")) { *value = g_last_kernel; return MM_OK; }       // (bench.py: which launches the roofline's kernel took)
-  if (!strcmp(name, "gemm_kernel")) { *value = g_opt_kernel; return MM_OK; }
-  return MM_ERR_ARG;
+  const OptionRow* r = find_option(name);
+  if (r) *value = *r->value;
+  else if (!strcmp(name, "gemm_last_kernel")) *value = g_last_kernel;       // read-only (bench.py: which launches the roofline's kernel took)
+  else return MM_ERR_ARG;
+  return MM_OK;
 }
 
-static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s);
+static int device_cus() {                     // of the device current at the first call; 256 where there is none
+  static const int n = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
+  return n;
+}
+
+extern "C" int mm_gemm_plan(int dtype, int layout, int kind, int groups, int M, int N, int K, int lda, int ldb, int ldc, int ldr, int ldaux,
+                            int epilogue, int swi_I, int ptr_bits, int ncu, int* plan) {
+  if (!plan || layout < 0 || layout > 2 || kind < GEMM_PLAIN || kind > GEMM_SWIGLU_BWD || groups < 0 || groups > MM_GROUP_MAX) return MM_ERR_ARG;
+  if (M <= 0 || N <= 0 || K < 0 || (epilogue & ~63) || ncu < 0) return MM_ERR_ARG;
+  const GemmProblem p{dtype, layout, kind, groups, M, N, K, lda, ldb, ldc, ldr, ldaux, epilogue | (kind == GEMM_SWIGLU_BWD ? MM_EPI_SWIGLU_BWD : 0),
+                      swi_I, (unsigned)ptr_bits};
+  const GemmPlan pl = gemm_plan(p, g_opt, ncu ? ncu : device_cus());
+  memcpy(plan, &pl, sizeof(pl));
+  return MM_OK;
+}
+
+static int gemm_launch(GemmArgs g, const GemmBatch* t, int groups, int kind, int dtype, int layout, hipStream_t s);
 
 extern "C" int mm_gemm(int dtype, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
                        int ldc, const void* bias, const void* residual, int ldr, int epilogue, void* stream) {
@@ -2460,7 +2455,7 @@ extern "C" int mm_gemm(int dtype, int layout, int M, int N, int K, const void* A
   if ((epilogue & MM_EPI_RESIDUAL) && !residual) return MM_ERR_ARG;
   if (epilogue & ~63) return MM_ERR_ARG;
   GemmArgs g{M, N, K, A, lda, B, ldb, C, ldc, bias, residual, ldr, epilogue, 0, 0, 0, 0, nullptr, 0, nullptr, 0};
-  return gemm_launch(g, dtype, layout, (hipStream_t)stream);
+  return gemm_launch(g, nullptr, 0, GEMM_PLAIN, dtype, layout, (hipStream_t)stream);
 }
 
 // y = silu(x Wg^T) * (x Wu^T) with ONE GEMM over the fused [2I, K] gate|up weight (HF:models/llama/modeling_llama.py:163-176
@@ -2474,7 +2469,7 @@ extern "C" int mm_gemm_swiglu_fwd(int dtype, int M, int I, int K, const void* X,
   if (dtype != MM_BF16 || (I & 127) || (K & 63) || M < 256) return MM_ERR_UNSUPPORTED;
   if ((ldgu & 3) || (ldact & 3) || (((uintptr_t)ACT) & 7) || (int64_t)2 * I * ldw * 2 >= 0xFFFFFFFFll) return MM_ERR_ALIGN;
   GemmArgs g{M, 2 * I, K, X, ldx, Wgu, ldw, GU, ldgu, nullptr, nullptr, 0, 0, 0, 0, 0, I, ACT, ldact, nullptr, 0};
-  return gemm_launch(g, dtype, MM_GEMM_NT, (hipStream_t)stream);
+  return gemm_launch(g, nullptr, 0, GEMM_SWIGLU_FWD, dtype, MM_GEMM_NT, (hipStream_t)stream);
 }
 
 // qkv = x W^T (+ b) for the fused [q | k | v] projection with RoPE applied to the q and k heads in the GEMM's epilogue
@@ -2494,8 +2489,8 @@ extern "C" int mm_gemm_rope_fwd(int dtype, int M, int N, int K, const void* X, i
   GemmArgs g{M, N, K, X, ldx, W, ldw, QKV, ldqkv, bias, nullptr, 0, bias ? MM_EPI_BIAS : 0, 0, 0, 0, 0, nullptr, 0, nullptr, 0};
   g.rope_cos = cos_t;
   g.rope_sin = sin_t;
-  g.rope_cols = rope_cols ? rope_cols : -1;          // -1: the fused kernel with nothing to rotate (keeps the dispatch below simple)
-  return gemm_launch(g, dtype, MM_GEMM_NT, (hipStream_t)stream);
+  g.rope_cols = rope_cols ? rope_cols : -1;          // -1: the fused kernel with nothing to rotate
+  return gemm_launch(g, nullptr, 0, GEMM_ROPE_FWD, dtype, MM_GEMM_NT, (hipStream_t)stream);
 }
 
 // y = act(x W^T + b) (+ residual) with the bf16 pre-activation kept in PRE for backward: the forward of a Linear + GELU in ONE
@@ -2507,12 +2502,12 @@ extern "C" int mm_gemm_act_fwd(int dtype, int M, int N, int K, const void* X, in
   if (!X || !W || !PRE || !ACT) return MM_ERR_ARG;
   if ((epilogue & MM_EPI_BIAS) && !bias) return MM_ERR_ARG;
   if ((epilogue & MM_EPI_RESIDUAL) && !residual) return MM_ERR_ARG;
-  const int acts = epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH);
+  const int acts = epilogue & MM_EPI_ACTS;
   if (!acts || (acts & (acts - 1)) || (epilogue & ~(acts | MM_EPI_BIAS | MM_EPI_RESIDUAL))) return MM_ERR_ARG;
   if (dtype != MM_BF16 || M <= 16) return MM_ERR_UNSUPPORTED;       // the fp32 path and the decode GEMM keep the separate passes
   if ((ldpre & 3) || (((uintptr_t)PRE) & 7)) return MM_ERR_ALIGN;
   GemmArgs g{M, N, K, X, ldx, W, ldw, ACT, ldact, bias, residual, ldr, epilogue, 0, 0, 0, 0, PRE, ldpre, nullptr, 0};
-  return gemm_launch(g, dtype, MM_GEMM_NT, (hipStream_t)stream);
+  return gemm_launch(g, nullptr, 0, GEMM_ACT_FWD, dtype, MM_GEMM_NT, (hipStream_t)stream);
 }
 
 // d(gate|up) [M, 2I] = swiglu'(GU) applied to d(act) = dY [M, H] . Wd [H, I], in the dgrad GEMM's epilogue: the backward of
@@ -2525,7 +2520,7 @@ extern "C" int mm_gemm_swiglu_bwd(int dtype, int M, int I, int H, const void* dY
   if (dtype != MM_BF16 || (I & 3)) return MM_ERR_UNSUPPORTED;
   if ((ldgu & 3) || (lddgu & 3) || (((uintptr_t)GU) & 7) || (((uintptr_t)dGU) & 7)) return MM_ERR_ALIGN;
   GemmArgs g{M, I, H, dY, lddy, Wd, ldw, dGU, lddgu, nullptr, nullptr, 0, MM_EPI_SWIGLU_BWD, 0, 0, 0, 0, nullptr, 0, GU, ldgu};
-  return gemm_launch(g, dtype, MM_GEMM_NN, (hipStream_t)stream);
+  return gemm_launch(g, nullptr, 0, GEMM_SWIGLU_BWD, dtype, MM_GEMM_NN, (hipStream_t)stream);
 }
 
 // ---- decode-step entry points (KV-cache decode of generate, reference model.py:595-602: M = batch <= 16 rows) ------------------
@@ -2537,25 +2532,11 @@ static int skinny_common(int dtype, int M, int K, const void* X, int ldx, const 
   return MM_OK;
 }
 
-// x rows staged in LDS beside gemv_stream_kernel's STATIC arrays (red: 2 x 8 x 4 x 64 floats = 16 384 B, nred: 128 B) in the 160 KB of a
-// CU: 143 KB leaves 896 B of slack.  kernels.decode_fits mirrors the number; a launch that still cannot get its LDS reports
-// MM_ERR_UNSUPPORTED (the caller then takes the tiled decode step).
-constexpr int64_t GEMV_X_LDS_MAX = 143 * 1024;
-static_assert(GEMV_X_LDS_MAX + 2 * 8 * 4 * 64 * 4 + 8 * 4 * 4 <= 160 * 1024, "x + static reduction scratch must fit the CU's LDS");
-
-static bool gemv_stream_fits(int M, int K) { return (K & 7) == 0 && (int64_t)M * K * 2 <= GEMV_X_LDS_MAX; }
-
+// gemv_stream_kernel on `grid` persistent workgroups with the x rows in `lds` bytes (gemv_grid); a launch that cannot get its LDS
+// reports MM_ERR_UNSUPPORTED (the caller then takes the tiled decode step)
 template <int MODE>
-static int gemv_stream_launch(const SkinnyArgs& g, unsigned nblk, hipStream_t s) {
-  if (!gemv_stream_fits(g.M, g.K)) return MM_ERR_UNSUPPORTED;
-  if (g.norm_w && (g.K > 8192 || !mm_aligned16(g.norm_w))) return MM_ERR_UNSUPPORTED;
+static int gemv_stream_go(const SkinnyArgs& g, unsigned nblk, unsigned grid, size_t lds, hipStream_t s) {
   g_last_kernel = 21;
-  const size_t lds = (size_t)g.M * g.K * 2;
-  // persistent grid: as many workgroups as the chip holds at once (2 per CU by registers, fewer when x takes most of the LDS)
-  static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
-  const int per_cu = g_opt_gemv_wgs > 0 ? g_opt_gemv_wgs : ((lds + 17 * 1024) * 2 <= 160 * 1024 ? 2 : 1);
-  const unsigned cap = (unsigned)(ncu * per_cu);
-  const unsigned grid = nblk < cap ? nblk : cap;
 #define MM_GEMV_LAUNCH(NORM, NT)                                                                              \
   do {                                                                                                        \
     auto kfn = gemv_stream_kernel<MODE, NORM, NT>;                                                            \
@@ -2565,11 +2546,19 @@ static int gemv_stream_launch(const SkinnyArgs& g, unsigned nblk, hipStream_t s)
     }                                                                                                         \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, s, g, (int)nblk);                                     \
   } while (0)
-  if (g.norm_w) { if (g_opt_gemv_nt) MM_GEMV_LAUNCH(true, true); else MM_GEMV_LAUNCH(true, false); }
-  else { if (g_opt_gemv_nt) MM_GEMV_LAUNCH(false, true); else MM_GEMV_LAUNCH(false, false); }
+  if (g.norm_w) { if (g_opt.gemv_nt) MM_GEMV_LAUNCH(true, true); else MM_GEMV_LAUNCH(true, false); }
+  else { if (g_opt.gemv_nt) MM_GEMV_LAUNCH(false, true); else MM_GEMV_LAUNCH(false, false); }
 #undef MM_GEMV_LAUNCH
   MM_CHECK_LAUNCH();
   return MM_OK;
+}
+
+template <int MODE>
+static int gemv_stream_launch(const SkinnyArgs& g, unsigned nblk, hipStream_t s) {
+  if (!gemv_stream_fits(g.M, g.K)) return MM_ERR_UNSUPPORTED;
+  if (g.norm_w && (g.K > 8192 || !mm_aligned16(g.norm_w))) return MM_ERR_UNSUPPORTED;
+  const GemvGrid gg = gemv_grid(g.M, g.K, nblk, g_opt, device_cus());
+  return gemv_stream_go<MODE>(g, nblk, gg.grid, (size_t)gg.lds, s);
 }
 
 extern "C" int mm_decode_gateup_swiglu(int dtype, int M, int I, int K, const void* X, int ldx, const void* Wgu, int ldw, void* ACT, int ldact,
@@ -2615,298 +2604,117 @@ extern "C" int mm_decode_linear(int dtype, int M, int N, int K, const void* X, i
   return gemv_stream_launch<0>(g, (unsigned)((N + 15) / 16), (hipStream_t)stream);
 }
 
-static int gemm_launch(GemmArgs g, int dtype, int layout, hipStream_t s) {
-  g.pipe = g_opt_epi_pipe;
-  const int M = g.M, N = g.N, K = g.K, lda = g.lda, ldb = g.ldb, ldc = g.ldc, ldr = g.ldr, epilogue = g.epi;
-  const void *A = g.A, *B = g.B;
-  void* C = g.C;
-  if (dtype == MM_BF16) {
-    g_last_kernel = 0;
-    if ((lda & 7) || (ldb & 7) || (ldc & 3) || ((epilogue & MM_EPI_RESIDUAL) && (ldr & 3))) return MM_ERR_ALIGN;
-    if (!mm_aligned16(A) || !mm_aligned16(B) || (((uintptr_t)C) & 7)) return MM_ERR_ALIGN;
-    // kernel choice: the LDS-DMA 256x128 kernel when its grid fills the chip, else the 128x128 register-staged one.
-    // MM_GEMM_KERNEL=v1|dma forces one (A/B benchmarking).
-    static const int forced_env = [] {
-      const char* e = getenv("MM_GEMM_KERNEL");      // v1 | dma (256x128) | big (256x256)
-      return !e ? 0 : (e[0] == 'v' ? 1 : (e[0] == 'b' ? 3 : 2));
-    }();
-    const int forced = g_opt_kernel ? g_opt_kernel : forced_env;
-    if (forced == 0 && g_opt_skinny && layout == MM_GEMM_NT && M <= 16 && !g.swi_I && !g.rope_cols &&
-        (int64_t)16 * lda * 2 < 0xFFFFFFFFll && (int64_t)16 * ldb * 2 < 0xFFFFFFFFll) {   // decode: stream W once
-      if (g_opt_gemv_stream && gemv_stream_fits(M, K) && (int64_t)N * ldb * 2 < 0xFFFFFFFFll) {   // the ring-buffered form (same bits)
-        SkinnyArgs q{};
-        q.M = M; q.N = N; q.K = K; q.A = (const bf16*)A; q.lda = lda; q.B = (const bf16*)B; q.ldb = ldb; q.C = (bf16*)C; q.ldc = ldc;
-        q.bias = (epilogue & MM_EPI_BIAS) ? (const bf16*)g.bias : nullptr;
-        q.residual = (epilogue & MM_EPI_RESIDUAL) ? (const bf16*)g.residual : nullptr;
-        q.ldr = ldr; q.epi = epilogue;
-        return gemv_stream_launch<0>(q, (unsigned)((N + 15) / 16), s);
-      }
-      g_last_kernel = 20;
-      dim3 grid((unsigned)((N + 15) / 16)), block(512);
-      hipLaunchKernelGGL(gemm_skinny_kernel, grid, block, 0, s, g);
-      MM_CHECK_LAUNCH();
-      return MM_OK;
-    }
-    // the DMA kernels address a K-strided operand with 32-bit byte offsets over the whole matrix
-    // ... and (pipelined epilogues) one wave tile of C / residual / aux with 32-bit byte offsets: 128 rows of the largest leading dimension
-    const int64_t ldmax = (int64_t)ldc > ldr ? (ldc > g.ldaux ? ldc : g.ldaux) : (ldr > g.ldaux ? ldr : g.ldaux);
-    const bool fits32 = ldmax * 128 * 2 + (int64_t)N * 2 < 0x7FFFFFFFll &&
-                        ((layout == MM_GEMM_NT) || ((int64_t)K * ldb * 2 < 0xFFFFFFFFll && (layout != MM_GEMM_TN || (int64_t)K * lda * 2 < 0xFFFFFFFFll)));
-    const int64_t tiles_128 = (int64_t)((M + 255) / 256) * ((N + 127) / 128);
-    const int64_t tiles_256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-    int variant = 0;   // 0 = v1 (128x128 register staged); DMA tiles: 1 = 256x128, 2 = 256x256, 3 = 128x128, 4 = 64x128, 5 = 64x64
-    const bool keep_pre = g.C2 != nullptr && !g.swi_I;      // mm_gemm_act_fwd: compiled into the small-tile DMA kernels only
-    if (g.swi_I || g.rope_cols) {             // the fused gate|up / RoPE tiles are defined on the 256x256 kernel only
-      if (!fits32) return MM_ERR_UNSUPPORTED;
-      variant = 2;
-    } else if (keep_pre) {
-      if (!fits32 || forced == 1) return MM_ERR_UNSUPPORTED;
-      variant = (forced >= 4 && forced <= 6) ? forced - 1 : small_variant(M, N, K);
-      if (variant < 3) variant = 3;           // a problem that would take a 256-wide tile: 128x128 (the caller may prefer the separate launches)
-    } else if (fits32) {
-      if (forced >= 2 && forced <= 6) variant = forced - 1;
-      else if (forced == 0 && tiles_128 >= 192) variant = MM_DEFAULT_DMA_VARIANT(tiles_256);
-      else if (forced == 0) variant = small_variant(M, N, K);
-    }
-    if (variant) {
-      static const int TBM[6] = {0, 256, 256, 128, 64, 64}, TBN[6] = {0, 128, 256, 128, 128, 64};
-      const int bm = TBM[variant], bn = TBN[variant];
-      g.nbm = (M + bm - 1) / bm;
-      g.nbn = g.swi_I ? g.swi_I / 128 : (N + bn - 1) / bn;
-      const int64_t nwg = (int64_t)g.nbm * g.nbn;
-      if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-      const size_t lds = 2 * (bm + bn) * G_BK * 2;
-      static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
-      // persistent: one resident workgroup per CU walks the tiles; otherwise one tile each
-      int64_t nblk = g_opt_persist ? (nwg < (int64_t)ncu ? nwg : (int64_t)ncu) : nwg;
-      // NT / NN 256x256 tiles: the 4-wave kernel (A K-contiguous, whole K-steps, the epilogue kinds it instantiates)
-      const bool acts = (epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH)) != 0;
-      // (a last round at most half full: its tiles are cut into 256 x 128 halves, g.tail -- plain epilogue kinds only)
-      const int64_t rem4 = g_opt_persist ? nwg % ncu : 0;
-      const bool tail4 = g_opt_tail && !g.swi_I && !g.rope_cols && !(epilogue & MM_EPI_SWIGLU_BWD) && rem4 > 0 && 2 * rem4 <= ncu;
-      g_last_kernel = variant;
-      if (g_opt_w4 && variant == 2 && K >= 192 && !acts) {
-        g_last_kernel = 10;
-        int64_t nb4 = g_opt_persist ? (nwg < (int64_t)ncu ? nwg : (int64_t)ncu) : nwg;
-        if (tail4) {
-          g.tail = (int)rem4;
-          nb4 = nwg >= ncu ? ncu : 2 * rem4;
-        }
-        dim3 grid4((unsigned)nb4), block4(256);
-        const size_t lds = 160 * 1024;                  // the ring (128 KB) + 8 KB per wave for the row-major epilogue's transposition
-        g.stagger = g_opt_w4_stagger;
-        g.stagger_slots = g_opt_w4_stagger_slots;
-        g.diag_epi = g_opt_w4_diag_epi;
-        g.shuffle = g_opt_w4_shuffle;
-        g.group_m = g_opt_w4_group_m;
-        g.stream_epi = g_opt_w4_stream;
-        g.rowmajor = g_opt_w4_rowmajor && (N & 7) == 0 && (ldc & 7) == 0 && mm_aligned16(C) &&
-                     (!(epilogue & MM_EPI_RESIDUAL) || ((ldr & 7) == 0 && mm_aligned16(g.residual))) &&
-                     (!(epilogue & MM_EPI_BIAS) || mm_aligned16(g.bias)) &&
-                     (!(epilogue & MM_EPI_SWIGLU_BWD) || ((g.ldaux & 7) == 0 && mm_aligned16(g.aux)));
-        if (g.swi_I) g.rowmajor = g_opt_w4_rowmajor;       // mm_gemm_swiglu_fwd: 8-byte accesses, alignment checked at the entry point
-#define MM_LAUNCH_W4(AKC, BKC, EK, SCHED)                                                                                    \
+// ---- the launcher: a stand-alone call (t == nullptr, groups == 0) or `groups` equal-shaped problems in one grid (the MoE image
+// modality's E expert towers), whose per-problem pointers are in *t and whose g carries problem 0's ----------------------------------
+static unsigned ptr_nibbles(const void* A, const void* B, const void* C, const void* bias, const void* residual, const void* aux, const void* C2) {
+  const auto low = [](const void* p, int at) { return (unsigned)((uintptr_t)p & 15) << at; };
+  return low(A, GEMM_PTR_A) | low(B, GEMM_PTR_B) | low(C, GEMM_PTR_C) | low(bias, GEMM_PTR_BIAS) | low(residual, GEMM_PTR_RESIDUAL) |
+         low(aux, GEMM_PTR_AUX) | low(C2, GEMM_PTR_C2);
+}
+
+static int gemm_launch(GemmArgs g, const GemmBatch* t, int groups, int kind, int dtype, int layout, hipStream_t s) {
+  unsigned bits = ptr_nibbles(g.A, g.B, g.C, g.bias, g.residual, g.aux, g.C2);
+  for (int p = 1; p < groups; ++p) bits |= ptr_nibbles(t->A[p], t->B[p], t->C[p], t->bias[p], t->residual[p], nullptr, t->C2[p]);
+  const GemmProblem prob{dtype, layout, kind, groups, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.ldr, g.ldaux, g.epi, g.swi_I, bits};
+  const GemmPlan pl = gemm_plan(prob, g_opt, device_cus());
+  if (pl.last_kernel != GEMM_LAST_UNCHANGED) g_last_kernel = pl.last_kernel;
+  if (pl.rc != MM_OK) return pl.rc;
+  g.nbm = pl.nbm; g.nbn = pl.nbn; g.tail = pl.tail; g.pipe = pl.pipe; g.stagger = pl.stagger; g.stagger_slots = pl.stagger_slots;
+  g.diag_epi = pl.diag_epi; g.shuffle = pl.shuffle; g.group_m = pl.group_m; g.stream_epi = pl.stream_epi; g.rowmajor = pl.rowmajor;
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block((unsigned)pl.block);
+  const size_t lds = (size_t)pl.lds;
+  const int ek = pl.family == GEMM_FAM_W4 ? pl.t[2] : pl.t[7];
+
+  // the template table: every instantiation the library holds.  ARGS is the kernel's argument list in parentheses.
+#define MM_UNPAREN(...) __VA_ARGS__
+#define MM_LAUNCH_ONE(KERNEL, ARGS, ...)                                                                                 \
   do {                                                                                                                   \
-    auto kfn = gemm_bf16_w4_kernel<AKC, BKC, EK, SCHED>;                                                                     \
+    auto kfn = KERNEL<__VA_ARGS__>;                                                                                      \
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-    hipLaunchKernelGGL(kfn, grid4, block4, lds, s, g);                                                                   \
+    hipLaunchKernelGGL(kfn, grid, block, lds, s, MM_UNPAREN ARGS);                                                       \
   } while (0)
-#define MM_W4_CASE(AKC, BKC, SCHED) case SCHED: MM_LAUNCH_W4(AKC, BKC, 0, SCHED); break;
-#ifdef MM_W4_DIAG
-#define MM_W4_CASES(AKC, BKC) MM_W4_CASE(AKC, BKC, 2) MM_W4_CASE(AKC, BKC, 3) MM_W4_CASE(AKC, BKC, 4) MM_W4_CASE(AKC, BKC, 5) MM_W4_CASE(AKC, BKC, 6) MM_W4_CASE(AKC, BKC, 7) MM_W4_CASE(AKC, BKC, 104) MM_W4_CASE(AKC, BKC, 105) MM_W4_CASE(AKC, BKC, 111) MM_W4_CASE(AKC, BKC, 112) MM_W4_CASE(AKC, BKC, 113) MM_W4_CASE(AKC, BKC, 114) MM_W4_CASE(AKC, BKC, 115) MM_W4_CASE(AKC, BKC, 117) MM_W4_CASE(AKC, BKC, 121)
-#else
-#define MM_W4_CASES(AKC, BKC) MM_W4_CASE(AKC, BKC, 4) MM_W4_CASE(AKC, BKC, 6) MM_W4_CASE(AKC, BKC, 7)
-#endif
-        // schedule: 1 everywhere (one barrier per K-step), except -- "gemm_w4_big" = 4 -- on operands that stream from beyond the
-        // Infinity Cache (a wide N or a long K): there the split-barrier schedule 4 (a DMA piece gets 105-168 MFMAs to land instead of
-        // 68-128) measured +3...+9 % (tools/w4_check.py --scheds), while on MALL-resident 4096-sized operands it costs 3 %
-        const bool big = g_opt_w4_big == 4 && g_opt_w4 == 1 && ((int64_t)N >= 14336 || (int64_t)K >= 14336);
-        if (g.rope_cols) { if (layout != MM_GEMM_NT) return MM_ERR_ARG; MM_LAUNCH_W4(true, true, 4, 1); }
-        else if (g.swi_I) { if (layout != MM_GEMM_NT) return MM_ERR_ARG; if (big) MM_LAUNCH_W4(true, true, 3, 4); else MM_LAUNCH_W4(true, true, 3, 1); }
-        else if (epilogue & MM_EPI_SWIGLU_BWD) { if (layout != MM_GEMM_NN) return MM_ERR_ARG; if (big) MM_LAUNCH_W4(true, false, 2, 4); else MM_LAUNCH_W4(true, false, 2, 1); }
-        else if (layout == MM_GEMM_NT) { switch (big ? 4 : g_opt_w4) { MM_W4_CASES(true, true) default: MM_LAUNCH_W4(true, true, 0, 1); } }
-        else if (layout == MM_GEMM_NN) { switch (big ? 4 : g_opt_w4) { MM_W4_CASES(true, false) default: MM_LAUNCH_W4(true, false, 0, 1); } }
-        else { switch (g_opt_w4) { MM_W4_CASES(false, false) default: MM_LAUNCH_W4(false, false, 0, 1); } }
-#undef MM_W4_CASES
+#define MM_LAUNCH_SMALL(KERNEL, ARGS, AKC, BKC, EK)                /* the tiles that also have a grouped form */            \
+  do {                                                                                                                   \
+    if (pl.t[2] == 128) MM_LAUNCH_ONE(KERNEL, ARGS, AKC, BKC, 128, 128, 2, 2, 4, EK);                                    \
+    else if (pl.t[3] == 128) MM_LAUNCH_ONE(KERNEL, ARGS, AKC, BKC, 64, 128, 2, 2, 4, EK);                                \
+    else MM_LAUNCH_ONE(KERNEL, ARGS, AKC, BKC, 64, 64, 2, 2, 4, EK);                                                     \
+  } while (0)
+#define MM_LAUNCH_256(AKC, BKC, EK)                                /* 256x256, 8 waves */                                  \
+  do {                                                                                                                   \
+    if (pl.t[6] == 4) MM_LAUNCH_ONE(gemm_bf16_dma_kernel, (g), AKC, BKC, 256, 256, 2, 2, 4, EK);                         \
+    else MM_LAUNCH_ONE(gemm_bf16_dma_kernel, (g), AKC, BKC, 256, 256, 2, 2, 8, EK);                                      \
+  } while (0)
+#define MM_LAUNCH_DMA(AKC, BKC, EK)                                /* a stand-alone call: every tile */                    \
+  do {                                                                                                                   \
+    if (pl.t[2] != 256) MM_LAUNCH_SMALL(gemm_bf16_dma_kernel, (g), AKC, BKC, EK);                                        \
+    else if (pl.t[3] == 128) MM_LAUNCH_ONE(gemm_bf16_dma_kernel, (g), AKC, BKC, 256, 128, 4, 2, 8, EK);                  \
+    else MM_LAUNCH_256(AKC, BKC, EK);                                                                                    \
+  } while (0)
+#define MM_LAUNCH_ANY(AKC, BKC, EK)                                                                                      \
+  do {                                                                                                                   \
+    if (t) MM_LAUNCH_SMALL(gemm_bf16_dma_kernel_batched, (g, *t), AKC, BKC, EK);                                         \
+    else MM_LAUNCH_DMA(AKC, BKC, EK);                                                                                    \
+  } while (0)
+#define MM_LAUNCH_W4(AKC, BKC, EK, SCHED) MM_LAUNCH_ONE(gemm_bf16_w4_kernel, (g), AKC, BKC, EK, SCHED)
+#define MM_W4_CASE(SCHED, AKC, BKC) case SCHED: MM_LAUNCH_W4(AKC, BKC, 0, SCHED); break;
+#define MM_W4_PLAIN(AKC, BKC) switch (pl.t[3]) { MM_W4_SCHEDS(MM_W4_CASE, AKC, BKC) default: MM_LAUNCH_W4(AKC, BKC, 0, 1); }
+#define MM_LAUNCH_F32(LAYOUT)                                                                                            \
+  do {                                                                                                                   \
+    if (t) hipLaunchKernelGGL((gemm_f32_kernel_batched<LAYOUT>), grid, block, 0, s, g, *t);                              \
+    else hipLaunchKernelGGL((gemm_f32_kernel<LAYOUT>), grid, block, 0, s, g);                                            \
+  } while (0)
+  switch (pl.family) {
+    case GEMM_FAM_GEMV: {
+      SkinnyArgs q{};
+      q.M = g.M; q.N = g.N; q.K = g.K; q.A = (const bf16*)g.A; q.lda = g.lda; q.B = (const bf16*)g.B; q.ldb = g.ldb; q.C = (bf16*)g.C; q.ldc = g.ldc;
+      q.bias = (g.epi & MM_EPI_BIAS) ? (const bf16*)g.bias : nullptr;
+      q.residual = (g.epi & MM_EPI_RESIDUAL) ? (const bf16*)g.residual : nullptr;
+      q.ldr = g.ldr; q.epi = g.epi;
+      return gemv_stream_go<0>(q, (unsigned)((g.N + 15) / 16), grid.x, lds, s);
+    }
+    case GEMM_FAM_SKINNY: hipLaunchKernelGGL(gemm_skinny_kernel, grid, block, 0, s, g); break;
+    case GEMM_FAM_W4:
+      if (ek == 4) MM_LAUNCH_W4(true, true, 4, 1);
+      else if (ek == 3) { if (pl.t[3] == 4) MM_LAUNCH_W4(true, true, 3, 4); else MM_LAUNCH_W4(true, true, 3, 1); }
+      else if (ek == 2) { if (pl.t[3] == 4) MM_LAUNCH_W4(true, false, 2, 4); else MM_LAUNCH_W4(true, false, 2, 1); }
+      else if (layout == MM_GEMM_NT) MM_W4_PLAIN(true, true)
+      else if (layout == MM_GEMM_NN) MM_W4_PLAIN(true, false)
+      else MM_W4_PLAIN(false, false)
+      break;
+    case GEMM_FAM_DMA:
+      if (ek == 4) MM_LAUNCH_256(true, true, 4);                  // mm_gemm_rope_fwd
+      else if (ek == 3) MM_LAUNCH_256(true, true, 3);             // mm_gemm_swiglu_fwd
+      else if (ek == 2) MM_LAUNCH_DMA(true, false, 2);            // mm_gemm_swiglu_bwd
+      else if (ek == 1) MM_LAUNCH_ANY(true, true, 1);             // activation (mm_gemm / mm_gemm_act_fwd and their grouped forms)
+      else if (layout == MM_GEMM_NT) MM_LAUNCH_ANY(true, true, 0);
+      else if (layout == MM_GEMM_NN) MM_LAUNCH_ANY(true, false, 0);
+      else MM_LAUNCH_ANY(false, false, 0);
+      break;
+    case GEMM_FAM_V1:
+      if (layout == MM_GEMM_NT) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, lds, s, g);
+      else if (layout == MM_GEMM_NN) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, lds, s, g);
+      else hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, lds, s, g);
+      break;
+    default:                                   // GEMM_FAM_F32
+      if (layout == MM_GEMM_NT) MM_LAUNCH_F32(MM_GEMM_NT);
+      else if (layout == MM_GEMM_NN) MM_LAUNCH_F32(MM_GEMM_NN);
+      else MM_LAUNCH_F32(MM_GEMM_TN);
+  }
+#undef MM_LAUNCH_F32
+#undef MM_W4_PLAIN
 #undef MM_W4_CASE
 #undef MM_LAUNCH_W4
-        MM_CHECK_LAUNCH();
-        return MM_OK;
-      }
-      if (g_opt_persist && g_opt_tail && variant == 2 && !g.swi_I && !g.rope_cols) {       // wave quantisation: see the kernel
-        const int64_t rem = nwg % ncu;
-        if (rem > 0 && 2 * rem <= ncu) {
-          g.tail = (int)rem;
-          nblk = nwg >= ncu ? ncu : 2 * rem;
-        }
-      }
-      dim3 grid((unsigned)nblk), block(512);
-#define MM_LAUNCH_ONE(...)                                                                                               \
-  do {                                                                                                                   \
-    auto kfn = gemm_bf16_dma_kernel<__VA_ARGS__>;                                                                        \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-    hipLaunchKernelGGL(kfn, grid, block, lds, s, g);                                                                     \
-  } while (0)
-#define MM_LAUNCH_DMA(AKC, BKC, EK)                                                                                      \
-  do {                                                                                                                   \
-    if (variant == 1) MM_LAUNCH_ONE(AKC, BKC, 256, 128, 4, 2, 8, EK);                                                    \
-    else if (variant == 3) MM_LAUNCH_ONE(AKC, BKC, 128, 128, 2, 2, 4, EK);                                               \
-    else if (variant == 4) MM_LAUNCH_ONE(AKC, BKC, 64, 128, 2, 2, 4, EK);                                                \
-    else if (variant == 5) MM_LAUNCH_ONE(AKC, BKC, 64, 64, 2, 2, 4, EK);                                                 \
-    else if (g_opt_issue_waves == 4) MM_LAUNCH_ONE(AKC, BKC, 256, 256, 2, 2, 4, EK);                                     \
-    else MM_LAUNCH_ONE(AKC, BKC, 256, 256, 2, 2, 8, EK);                                                                 \
-  } while (0)
-      // epilogue kind = kernel instantiation: the SwiGLU ones exist for the layout their entry point uses only
-      if (g.rope_cols) {                                           // mm_gemm_rope_fwd: NT, 256x256
-        if (layout != MM_GEMM_NT) return MM_ERR_ARG;
-        if (g_opt_issue_waves == 4) MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 4, 4);
-        else MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 8, 4);
-      } else if (g.swi_I) {                                               // mm_gemm_swiglu_fwd: NT, 256x256 (variant 2 above)
-        if (layout != MM_GEMM_NT) return MM_ERR_ARG;
-        if (g_opt_issue_waves == 4) MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 4, 3);
-        else MM_LAUNCH_ONE(true, true, 256, 256, 2, 2, 8, 3);
-      } else if (epilogue & MM_EPI_SWIGLU_BWD) {                          // mm_gemm_swiglu_bwd: NN
-        if (layout != MM_GEMM_NN) return MM_ERR_ARG;
-        MM_LAUNCH_DMA(true, false, 2);
-      } else if (epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH)) {      // activation: NT (mm_gemm / mm_gemm_act_fwd)
-        if (layout != MM_GEMM_NT) return MM_ERR_UNSUPPORTED;
-        MM_LAUNCH_DMA(true, true, 1);
-      } else {
-        switch (layout) {
-          case MM_GEMM_NT: MM_LAUNCH_DMA(true, true, 0); break;
-          case MM_GEMM_NN: MM_LAUNCH_DMA(true, false, 0); break;
-          default: MM_LAUNCH_DMA(false, false, 0); break;
-        }
-      }
-#undef MM_LAUNCH_ONE
+#undef MM_LAUNCH_ANY
 #undef MM_LAUNCH_DMA
-    } else {
-      g.nbm = (M + BM - 1) / BM;
-      g.nbn = (N + BN - 1) / BN;
-      const int64_t nwg = (int64_t)g.nbm * g.nbn;
-      if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-      const size_t lds = 4 * TILE_BYTES;
-      dim3 grid((unsigned)nwg), block(256);
-      switch (layout) {
-        case MM_GEMM_NT: hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, lds, s, g); break;
-        case MM_GEMM_NN: hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, lds, s, g); break;
-        default: hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, lds, s, g); break;
-      }
-    }
-  } else if (dtype == MM_F32) {
-    g_last_kernel = 30;
-    g.nbm = (M + 63) / 64;
-    g.nbn = (N + 63) / 64;
-    dim3 grid((unsigned)(g.nbm * g.nbn)), block(256);
-    switch (layout) {
-      case MM_GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<MM_GEMM_NT>), grid, block, 0, s, g); break;
-      case MM_GEMM_NN: hipLaunchKernelGGL((gemm_f32_kernel<MM_GEMM_NN>), grid, block, 0, s, g); break;
-      default: hipLaunchKernelGGL((gemm_f32_kernel<MM_GEMM_TN>), grid, block, 0, s, g); break;
-    }
-  } else {
-    return MM_ERR_UNSUPPORTED;
-  }
+#undef MM_LAUNCH_256
+#undef MM_LAUNCH_SMALL
+#undef MM_LAUNCH_ONE
+#undef MM_UNPAREN
   MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
-// ---- grouped launches: `groups` equal-shaped problems in one grid (the MoE image modality's E expert towers) -----------------
-// The tile is chosen as gemm_launch chooses it among the small LDS-DMA tiles, but from the tile count of the whole batch (every
-// bf16 kernel adds a K-step's products in the same order, so the tile does not change the bits).  Problems that gemm_launch sends to a 256-wide tile, the
-// M <= 16 weight-streaming kernels or a fused form are MM_ERR_UNSUPPORTED: those fill the chip on their own.
-static int gemm_launch_batched(GemmArgs g, const GemmBatch& t, int groups, int dtype, int layout, hipStream_t s) {
-  g.pipe = g_opt_epi_pipe;
-  const int M = g.M, N = g.N, K = g.K, lda = g.lda, ldb = g.ldb, ldc = g.ldc, ldr = g.ldr, epilogue = g.epi;
-  const bool acts = (epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH)) != 0;
-  if (dtype == MM_F32) {
-    g.nbm = (M + 63) / 64;
-    g.nbn = (N + 63) / 64;
-    if ((int64_t)g.nbm * g.nbn > 0x7FFFFFFF) return MM_ERR_ARG;
-    dim3 grid((unsigned)(g.nbm * g.nbn), (unsigned)groups), block(256);
-    switch (layout) {
-      case MM_GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_NT>), grid, block, 0, s, g, t); break;
-      case MM_GEMM_NN: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_NN>), grid, block, 0, s, g, t); break;
-      default: hipLaunchKernelGGL((gemm_f32_kernel_batched<MM_GEMM_TN>), grid, block, 0, s, g, t); break;
-    }
-    MM_CHECK_LAUNCH();
-    g_last_kernel = 30;
-    return MM_OK;
-  }
-  if (dtype != MM_BF16) return MM_ERR_UNSUPPORTED;
-  if ((lda & 7) || (ldb & 7) || (ldc & 3) || ((epilogue & MM_EPI_RESIDUAL) && (ldr & 3))) return MM_ERR_ALIGN;
-  for (int p = 0; p < groups; ++p)
-    if (!mm_aligned16(t.A[p]) || !mm_aligned16(t.B[p]) || (((uintptr_t)t.C[p]) & 7)) return MM_ERR_ALIGN;
-  static const int forced_env = [] {
-    const char* e = getenv("MM_GEMM_KERNEL");
-    return !e ? 0 : (e[0] == 'v' ? 1 : (e[0] == 'b' ? 3 : 2));
-  }();
-  const int forced = g_opt_kernel ? g_opt_kernel : forced_env;
-  if (forced == 0 && g_opt_skinny && layout == MM_GEMM_NT && M <= 16) return MM_ERR_UNSUPPORTED;   // the weight-streaming kernels
-  if (acts && layout != MM_GEMM_NT) return MM_ERR_UNSUPPORTED;
-  const int64_t ldmax = (int64_t)ldc > ldr ? ldc : ldr;
-  const bool fits32 = ldmax * 128 * 2 + (int64_t)N * 2 < 0x7FFFFFFFll &&
-                      ((layout == MM_GEMM_NT) || ((int64_t)K * ldb * 2 < 0xFFFFFFFFll && (layout != MM_GEMM_TN || (int64_t)K * lda * 2 < 0xFFFFFFFFll)));
-  const int64_t tiles_128 = (int64_t)((M + 255) / 256) * ((N + 127) / 128);
-  const int64_t tiles_256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-  // the batch's tile: small_variant's thresholds on the tiles of all the problems together
-  const int64_t tb = (int64_t)groups * ((M + 127) / 128) * ((N + 127) / 128);
-  const int small = g_opt_small >= 0 ? g_opt_small : (tb <= 96 ? 4 : (tb <= 320 ? 3 : 0));
-  const bool keep_pre = g.C2 != nullptr;
-  int variant = 0;
-  if (keep_pre) {
-    if (!fits32 || forced == 1) return MM_ERR_UNSUPPORTED;
-    variant = (forced >= 4 && forced <= 6) ? forced - 1 : small;
-    if (variant < 3) variant = 3;
-  } else if (fits32) {
-    if (forced >= 2 && forced <= 6) variant = forced - 1;
-    else if (forced == 0 && tiles_128 >= 192) variant = MM_DEFAULT_DMA_VARIANT(tiles_256);
-    else if (forced == 0) variant = small;
-  }
-  if (variant == 1 || variant == 2) return MM_ERR_UNSUPPORTED;       // the 256-wide tiles (8- and 4-wave kernels)
-  // more than 320 tiles in the batch: mm_gemm's register-staged 128x128 kernel has no grouped form; the LDS-DMA kernel of the same
-  // tile runs instead (same bits), except past the 32-bit offsets and where that kernel was asked for by name
-  if (variant == 0 && fits32 && forced != 1) variant = 3;
-  if (variant == 0) return MM_ERR_UNSUPPORTED;
-  {
-    static const int TBM[6] = {0, 256, 256, 128, 64, 64}, TBN[6] = {0, 128, 256, 128, 128, 64};
-    const int bm = TBM[variant], bn = TBN[variant];
-    g.nbm = (M + bm - 1) / bm;
-    g.nbn = (N + bn - 1) / bn;
-    const int64_t nwg = (int64_t)g.nbm * g.nbn;
-    if (nwg > 0x7FFFFFFF) return MM_ERR_ARG;
-    const size_t lds = 2 * (bm + bn) * G_BK * 2;
-    static const int ncu = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n; }();
-    const int64_t nblk = g_opt_persist ? (nwg < (int64_t)ncu ? nwg : (int64_t)ncu) : nwg;      // per problem, as a stand-alone launch
-    dim3 grid((unsigned)nblk, (unsigned)groups), block(512);
-#define MM_LAUNCH_ONE_B(...)                                                                                             \
-  do {                                                                                                                   \
-    auto kfn = gemm_bf16_dma_kernel_batched<__VA_ARGS__>;                                                                \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-    hipLaunchKernelGGL(kfn, grid, block, lds, s, g, t);                                                                  \
-  } while (0)
-#define MM_LAUNCH_DMA_B(AKC, BKC, EK)                                                                                    \
-  do {                                                                                                                   \
-    if (variant == 3) MM_LAUNCH_ONE_B(AKC, BKC, 128, 128, 2, 2, 4, EK);                                                  \
-    else if (variant == 4) MM_LAUNCH_ONE_B(AKC, BKC, 64, 128, 2, 2, 4, EK);                                              \
-    else MM_LAUNCH_ONE_B(AKC, BKC, 64, 64, 2, 2, 4, EK);                                                                 \
-  } while (0)
-    if (acts) {
-      MM_LAUNCH_DMA_B(true, true, 1);
-    } else {
-      switch (layout) {
-        case MM_GEMM_NT: MM_LAUNCH_DMA_B(true, true, 0); break;
-        case MM_GEMM_NN: MM_LAUNCH_DMA_B(true, false, 0); break;
-        default: MM_LAUNCH_DMA_B(false, false, 0); break;
-      }
-    }
-#undef MM_LAUNCH_ONE_B
-#undef MM_LAUNCH_DMA_B
-  }
-  MM_CHECK_LAUNCH();
-  g_last_kernel = variant;
-  return MM_OK;
-}
-
+// ---- grouped entry points -------------------------------------------------------------------------------------------------------
 static int batch_table(GemmBatch& t, int groups, const void* const* A, const void* const* B, void* const* C, const void* const* bias,
                        const void* const* residual, void* const* C2, int epilogue) {
   if (groups < 1 || groups > MM_GROUP_MAX || !A || !B || !C) return MM_ERR_ARG;
@@ -2936,14 +2744,14 @@ extern "C" int mm_gemm_batched(int dtype, int layout, int groups, int M, int N, 
   if (rc != MM_OK) return rc;
   if (M == 0 || N == 0) return MM_OK;
   GemmArgs g{M, N, K, t.A[0], lda, t.B[0], ldb, t.C[0], ldc, t.bias[0], t.residual[0], ldr, epilogue, 0, 0, 0, 0, nullptr, 0, nullptr, 0};
-  return gemm_launch_batched(g, t, groups, dtype, layout, (hipStream_t)stream);
+  return gemm_launch(g, &t, groups, GEMM_PLAIN, dtype, layout, (hipStream_t)stream);
 }
 
 extern "C" int mm_gemm_act_fwd_batched(int dtype, int groups, int M, int N, int K, const void* const* X, int ldx, const void* const* W,
                                        int ldw, const void* const* bias, void* const* PRE, int ldpre, void* const* ACT, int ldact,
                                        const void* const* residual, int ldr, int epilogue, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !PRE) return MM_ERR_ARG;
-  const int acts = epilogue & (MM_EPI_GELU_ERF | MM_EPI_QUICK_GELU | MM_EPI_GELU_TANH);
+  const int acts = epilogue & MM_EPI_ACTS;
   if (!acts || (acts & (acts - 1)) || (epilogue & ~(acts | MM_EPI_BIAS | MM_EPI_RESIDUAL))) return MM_ERR_ARG;
   GemmBatch t;
   const int rc = batch_table(t, groups, X, W, ACT, bias, residual, PRE, epilogue);
@@ -2954,7 +2762,7 @@ extern "C" int mm_gemm_act_fwd_batched(int dtype, int groups, int M, int N, int 
   for (int p = 0; p < groups; ++p)
     if (((uintptr_t)t.C2[p]) & 7) return MM_ERR_ALIGN;
   GemmArgs g{M, N, K, t.A[0], ldx, t.B[0], ldw, t.C[0], ldact, t.bias[0], t.residual[0], ldr, epilogue, 0, 0, 0, 0, t.C2[0], ldpre, nullptr, 0};
-  return gemm_launch_batched(g, t, groups, dtype, MM_GEMM_NT, (hipStream_t)stream);
+  return gemm_launch(g, &t, groups, GEMM_ACT_FWD, dtype, MM_GEMM_NT, (hipStream_t)stream);
 }
 
 extern "C" int mm_colsum_batched(int dtype, const void* const* X, int groups, int M, int N, int ldx, void* const* out, int accumulate,

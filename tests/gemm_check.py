@@ -309,7 +309,7 @@ def operands(layout, a, b, dtype=BF, lda=None, ldb=None):
 
 
 def expected_kernel(layout, M, N, K, forced=0, acts=False, w4=1, gemv=True, ncu_tiles=192):
-    """The kernel id gemm_launch picks for a plain mm_gemm call (csrc/mm_gemm.hip, with 32-bit offsets that fit): forced =
+    """The kernel id gemm_plan picks for a plain mm_gemm call (csrc/mm_gemm_plan.h, with 32-bit offsets that fit): forced =
     mm_set_option("gemm_kernel"), w4 = "gemm_w4", gemv = "gemv_stream"; every other switch at its default."""
     if forced == 0 and layout == NT and M <= 16:
         return GEMV if gemv and K % 8 == 0 and M * K * 2 <= 143 * 1024 else SKINNY

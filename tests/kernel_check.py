@@ -169,16 +169,12 @@ def rc(name, *args):
     return getattr(lib(), name)(*args, stream())
 
 
-# options without a getter: their library defaults
-_DEFAULTS = {"gemm_w4_big": 4, "gemm_w4_stream": 1, "gemm_small": -1, "gemm_epi_pipe": 1, "adamw_blocks": 0}
-
-
 @contextlib.contextmanager
 def options(**kw):
     """Set mm_set_option switches for the block and restore what was there."""
     old = {}
     for k, v in kw.items():
-        old[k] = _DEFAULTS[k] if k in _DEFAULTS else get_option(k)
+        old[k] = get_option(k)
         assert lib().mm_set_option(k.encode(), int(v)) == 0, (k, v)
     try:
         yield

@@ -9,6 +9,9 @@ Only OUTPUTS are written (tests/golden/*.safetensors / *.json): weights (bf16-ro
 init), inputs, per-stage activations, logits, loss, selected grads, greedy token ids, and the
 collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 
+`python tools/make_golden.py gemm_plan` is a mode apart: it rewrites tests/golden/gemm_plan.jsonl (the GEMM launch decisions) from
+the built library and needs neither the reference nor a GPU (gemm_plan_table below).
+
 Import recipe = SURVEY.md Appendix A (three harness-side shims, none edits the reference).
 The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 / Apertus modules as called
 by the reference at model.py:433-444,517-526,595-640 and image_modality.py:130-137.
@@ -22,6 +25,39 @@ import types
 
 sys.dont_write_bytecode = True
 os.environ.setdefault("HF_HUB_OFFLINE", "1")
+
+
+def gemm_plan_table():
+    """`make_golden.py gemm_plan`: rewrite the `plan` of every row of tests/golden/gemm_plan.jsonl from the library's mm_gemm_plan
+    (the rows' option flip, CU count and problem are the sweep and stay).  Needs the built library only, not the reference: after
+    a change of the GEMM launch policy (csrc/mm_gemm_plan.h) the diff of the table shows exactly which decisions moved."""
+    import ctypes
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    sys.path.insert(0, root)
+    from multimeditron_amd import _lib
+    path = os.path.join(root, "tests", "golden", "gemm_plan.jsonl")
+    with open(path) as f:
+        header, *rows = [json.loads(line) for line in f]
+    L, moved = _lib.lib(), 0
+    for r in rows:
+        old = _lib.get_option(r["opt"][0]) if r["opt"] else None
+        if r["opt"]:
+            _lib.call("mm_set_option", r["opt"][0].encode(), r["opt"][1])
+        out = (ctypes.c_int * len(r["plan"]))()
+        _lib.call("mm_gemm_plan", *r["problem"], r["ncu"], out)
+        if r["opt"]:
+            _lib.call("mm_set_option", r["opt"][0].encode(), old)
+        moved += list(out) != r["plan"]
+        r["plan"] = list(out)
+    with open(path, "w") as f:
+        for r in [header] + rows:
+            f.write(json.dumps(r, separators=(",", ":")) + "\n")
+    print(f"gemm_plan: {len(rows)} rows, {moved} changed")
+
+
+if sys.argv[1:] == ["gemm_plan"]:
+    gemm_plan_table()
+    sys.exit(0)
 
 import numpy as np
 import torch
