@@ -61,8 +61,8 @@ const char* mm_error_string(int code);
  * kernels.  A 0|1 switch stores value != 0; a value outside a switch's range returns MM_ERR_ARG and leaves the switch as it was;
  * unknown names return MM_ERR_ARG.                                                                                       */
 int mm_set_option(const char* name, int value);
-/* current value of a switch: every name mm_set_option answers except "attn_*" (one table serves both), so a caller that flips
- * one temporarily can restore what it found.  MM_GEMM_KERNEL (environment, used while "gemm_kernel" is 0) does not show here.
+/* current value of a switch: every name mm_set_option answers (one table serves both; the "attn_*" names are answered by the
+ * attention kernels' own pair of functions), so a caller that flips one temporarily can restore what it found.  MM_GEMM_KERNEL (environment, used while "gemm_kernel" is 0) does not show here.
  * Also the read-only "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged
  * kernel (also the fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10
  * the 4-wave 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the
@@ -341,7 +341,12 @@ int mm_decode_linear(int dtype, int M, int N, int K, const void* X, int ldx, con
  * in mm_attn_fwd, key_mask [B,Skv] or NULL, out [B,Hq,D] contiguous.  MM_BF16, D in {64,128}, Hq/Hkv in {1,2,4,7,8}.
  * workspace: f32 [B*Hq*nsplit*(D+2)] with nsplit = mm_attn_decode_splits(B,Hkv,Skv) (slices of the keys, merged in a
  * fixed order).  sync: int [B*Hkv], zero on entry and left zero -- the slice that arrives last does the merge inside
- * the same launch; NULL = merge in a second launch.  Rows with no visible key give 0.                              */
+ * the same launch; NULL = merge in a second launch.  Rows with no visible key give 0.
+ * Any nsplit >= 1 is accepted (the workspace is sized by the nsplit passed): slice s holds keys [s*chunk, min(Skv, (s+1)*chunk))
+ * with chunk = ceil(Skv / nsplit), and a slice with no key or with masked keys only adds nothing.  Masked keys (key_mask = 0
+ * inside [0, Skv)) must hold finite values: the MFMA slice kernel forms 0 * v for them; rows from Skv on are never read.
+ * MM_ERR_ARG: Hq % Hkv != 0, nsplit < 1, Skv <= 0, a NULL operand; MM_ERR_UNSUPPORTED: another dtype, D or Hq/Hkv;
+ * MM_ERR_ALIGN: a stride that is not a multiple of 8 elements, q / k / v not 16-byte aligned; B = 0: MM_OK, nothing written.  */
 int mm_attn_decode_splits(int B, int Hkv, int Skv);
 int mm_attn_decode(int dtype, const void* q, const void* k, const void* v, int B, int Skv, int Hq, int Hkv, int D,
                    int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
@@ -425,7 +430,8 @@ int mm_sample(int dtype, const void* logits, int rows, int V, int ld, float temp
               int64_t seed, int64_t offset, int64_t* out, float* thresh, void* ws, int64_t ws_bytes, void* stream);
 int mm_sample_uniforms(int64_t seed, int64_t offset, int rows, float* u, void* stream);
 /* generate()'s per-token bookkeeping ON the device (the reference syncs per token: model.py:618-625,637-638): id = finished[b]
- * ? eos : tok[b]; finished[b] |= id == eos; out[b, col] = id; next_ids[b] = id (the next step's embedding lookup).       */
+ * ? eos : tok[b]; finished[b] |= id == eos; out[b, col] = id; next_ids[b] = id (the next step's embedding lookup).  Nothing
+ * else is written (out [B, ld_out]: column col only).  MM_ERR_ARG: a NULL pointer, B < 0, col outside [0, ld_out); B = 0: MM_OK. */
 int mm_decode_select(const int64_t* tok, unsigned char* finished, int64_t eos, int B, int64_t* out, int ld_out, int col,
                      int64_t* next_ids, void* stream);
 
@@ -433,7 +439,11 @@ int mm_decode_select(const int64_t* tok, unsigned char* finished, int64_t eos, i
  * X [E, n, L] (L = P*C, expert-major), gate [n, E] fp32 (the gating network's softmax weights, expert order), idx[J] = the
  * experts taking part (host array).  mode 0: out[n, L] = sum_j gate[n, idx[j]] * X[idx[j], n]  (`weighted_average`, :170-176);
  * mode 1: out[n, J, L] = softmax_j(gate[n, idx[.]])[j] * X[idx[j], n]  (the specialists' scaled contexts of `cross_attn`,
- * :186-199).  backward = 1: X is d(out), out is dX [E, n, L] (only the listed experts' slices are written).                */
+ * :186-199).  backward = 1: X is d(out), out is dX [E, n, L]: dX[idx[j], n] = w_j * dout[n] (mode 0) / w'_j * dout[n, j] (mode 1);
+ * only the listed experts' slices are written, the unlisted slices are not touched (the caller zeroes them).
+ * Rounding: the weights, the J-way softmax and the sum are fp32 arithmetic; each output element is rounded ONCE to the dtype.
+ * MM_ERR_ARG: J outside 1 .. 16, an index outside [0, E), mode outside {0, 1}, a NULL pointer; MM_ERR_ALIGN: L not a multiple of
+ * the 16-byte vector (8 bf16 / 4 f32), X or out not 16-byte aligned; n = 0: MM_OK, nothing written.                        */
 int mm_expert_fuse(int dtype, int backward, int mode, const void* X, const float* gate, const int* idx, int J, int E, int n,
                    int64_t L, void* out, void* stream);
 

@@ -1972,6 +1972,15 @@ int mm_attn_option(const char* name, int value) {   // reached through mm_set_op
   return MM_ERR_ARG;
 }
 
+int mm_attn_get_option(const char* name, int* value) {   // reached through mm_get_option (mm_gemm.hip)
+  if (!strcmp(name, "attn_decode_mfma")) *value = g_attn_decode_mfma;
+  else if (!strcmp(name, "attn_decode_wgs")) *value = g_attn_decode_wgs;
+  else if (!strcmp(name, "attn_q_prio")) *value = g_attn_q_prio;
+  else if (!strcmp(name, "attn_diag")) *value = g_attn_diag;
+  else return MM_ERR_ARG;
+  return MM_OK;
+}
+
 static int check_common(int dtype, int B, int Sq, int Skv, int Hq, int Hkv, int D) {
   if (B < 0 || Sq < 0 || Skv < 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || D <= 0) return MM_ERR_ARG;
   if (dtype == MM_BF16 && D != 64 && D != 128) return MM_ERR_UNSUPPORTED;

@@ -2355,6 +2355,7 @@ static GemmOptions g_opt = [] {
 static int g_last_kernel = -1;      // which kernel the last mm_gemm* / mm_decode_* call launched ("gemm_last_kernel": ids in mm_hip.h)
 
 int mm_attn_option(const char* name, int value);
+int mm_attn_get_option(const char* name, int* value);
 
 extern int g_adamw_blocks;    // mm_optim.hip
 
@@ -2421,6 +2422,7 @@ extern "C" int mm_set_option(const char* name, int value) {
 
 extern "C" int mm_get_option(const char* name, int* value) {
   if (!name || !value) return MM_ERR_ARG;
+  if (!strncmp(name, "attn_", 5)) return mm_attn_get_option(name, value);
   const OptionRow* r = find_option(name);
   if (r) *value = *r->value;
   else if (!strcmp(name, "gemm_last_kernel")) *value = g_last_kernel;       // read-only (bench.py: which launches the roofline's kernel took)

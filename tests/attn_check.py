@@ -39,6 +39,12 @@ C = {
     "bf16-d128-long": {"out": 4.0, "lse": 1.0, "dq": 1.0, "dk": 1.0, "dv": 4.0},
     "bf16-d64": {"out": 4.0, "lse": 1.0, "dq": 1.0, "dk": 2.0, "dv": 4.0},         # measured 1.58, 0.38, 0.43, 0.59, 1.79
     "f32": {"out": 2.0, "lse": 2.0, "dq": 0.25, "dk": 0.25, "dv": 2.0},            # measured 0.59, 0.75, 0.10, 0.09, 0.62
+    # mm_attn_decode.  DERIVED, not measured: the decode kernels keep P in fp32, so their one bf16 rounding is out = bf16(o / l)
+    # with |o / l| <= P.|V| = E_out, err / (u E) <= 1; the fp32 score, exp2 and accumulation errors sit in E through the kappa
+    # terms.  c = 1 (the rounding) x 2 (margin).  The measured ratios are beside each path for the record only.
+    "bf16-decode-valu": {"out": 2.0},      # attn_decode_partial_kernel + attn_decode_merge_kernel: measured 0.855
+    "bf16-decode-mfma": {"out": 2.0},      # attn_decode_partial128_mfma_kernel + merge: measured 0.855
+    "bf16-decode-fused": {"out": 2.0},     # attn_decode_partial_kernel, merged by the last slice (sync): measured 0.855
 }
 
 # worst err / (u E) seen per (path, quantity) in this process; MM_ATTN_RATIO_LOG=<file> writes them out at exit
@@ -226,3 +232,191 @@ def run_bwd(q, k, v, out, dout, lse, key_mask, causal, scale, stream=None):
     call("mm_attn_bwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), B, Sq, Skv, Hq, Hkv, D, *_s3(q),
          *_s3(k), *_s3(v), ptr(key_mask), int(causal), float(scale), ptr(dq), ptr(dk), ptr(dv), ptr(delta), st.cuda_stream)
     return dq, dk, dv, [(f"dq/dk/dv storage {i}", g) for i, g in enumerate(stores)]
+
+
+# ---- mm_attn_decode: one query token over a KV cache, split over slices of the keys --------------------------------------------
+# The reference is `reference(..., backward=False)` with Sq = 1.  What is below: the launch path names, the split count mirrored
+# from mm_attn_decode_splits, the problems of tests/test_attention_contract_gpu.py (shared with the emulation of
+# tests/test_attn_check_cpu.py) and the guarded launch.
+BF16 = torch.bfloat16
+SYNC_SPARE = 5                       # counters behind B * Hkv that no launch may touch
+DECODE_WGS = 768                     # g_attn_decode_wgs, the library's default for option attn_decode_wgs
+
+
+def decode_path(D, G, fused=False, mfma=True):
+    """the kernel mm_attn_decode launches: MFMA scores for D = 128, G <= 4 in the two-launch form unless attn_decode_mfma = 0"""
+    if fused:
+        return "bf16-decode-fused"
+    return "bf16-decode-mfma" if mfma and D == 128 and G <= 4 else "bf16-decode-valu"
+
+
+def decode_splits(B, Hkv, Skv, wgs=DECODE_WGS):
+    """mm_attn_decode_splits: ceil(wgs / (B Hkv)) slices, at least 64 keys each, at least one."""
+    return max(1, min(-(-wgs // (B * Hkv)), -(-Skv // 64)))
+
+
+def decode_chunk(Skv, nsplit):
+    """keys per slice: slice s holds [s chunk, min(Skv, (s + 1) chunk)), which is empty once s chunk >= Skv"""
+    return -(-Skv // nsplit)
+
+
+def decode_case(B, Skv, Hq, Hkv, D, mask=None, ns="lib"):
+    """ns: "lib" / "lib8" = the library's split count under attn_decode_wgs = 768 / 8, or an explicit nsplit"""
+    return dict(B=B, Skv=Skv, Hq=Hq, Hkv=Hkv, D=D, mask=mask, ns=ns)
+
+
+def decode_case_id(c):
+    return f"B{c['B']}-k{c['Skv']}-h{c['Hq']}x{c['Hkv']}-d{c['D']}-{c['mask'] or 'nomask'}-ns{c['ns']}"
+
+
+def decode_nsplit(c):
+    if c["ns"] in ("lib", "lib8"):
+        return decode_splits(c["B"], c["Hkv"], c["Skv"], 8 if c["ns"] == "lib8" else DECODE_WGS)
+    return int(c["ns"])
+
+
+def decode_mask(kind, B, Skv, nsplit):
+    """[B, Skv] int64 or None.  leftpad: the first third (one key less per sequence); holes: every fifth key and a run;
+    slice: exactly the keys of one slice (a different one per sequence); dead: every key of sequence 0; single: one visible key."""
+    if kind is None:
+        return None
+    m = torch.ones(B, Skv, dtype=torch.long)
+    chunk = decode_chunk(Skv, nsplit)
+    for b in range(B):
+        if kind == "leftpad":
+            m[b, :max(0, Skv // 3 - b)] = 0
+        elif kind == "holes":
+            m[b, 3 + b::5] = 0
+            m[b, 20:40 + b] = 0
+        elif kind == "slice":
+            assert nsplit > 1, "with one slice this is the dead row"
+            s = (b + 1) % min(nsplit, -(-Skv // chunk))
+            m[b, s * chunk:(s + 1) * chunk] = 0
+        elif kind == "dead":
+            if b == 0:
+                m[b] = 0
+        elif kind == "single":
+            m[b] = 0
+            m[b, (Skv - 1, 0, Skv // 2)[b % 3]] = 1
+        else:
+            raise ValueError(kind)
+    return m
+
+
+def decode_operands(c, mask, seed=1):
+    """q [B, Hq, D], k / v [B, Skv, Hkv, D] in bf16 (CPU).  Masked keys hold finite values about 1e3 times the visible ones: a
+    weight that leaks is loud, and 0 * v stays 0."""
+    B, Skv, Hq, Hkv, D = c["B"], c["Skv"], c["Hq"], c["Hkv"], c["D"]
+    g = torch.Generator().manual_seed(seed + 13 * Skv + D + Hq)
+    q = torch.randn(B, Hq, D, generator=g)
+    k = torch.randn(B, Skv, Hkv, D, generator=g)
+    v = torch.randn(B, Skv, Hkv, D, generator=g)
+    if mask is not None:
+        big = torch.where(mask == 0, 1000.0, 1.0)[:, :, None, None]
+        k, v = k * big, v * big
+    return q.to(BF16), k.to(BF16), v.to(BF16)
+
+
+def decode_one_key(c, nsplit, seed=2):
+    """The exact family `one_key`: one visible key per sequence -- the first key of a slice, the last key of a slice, the key
+    Skv - 1, in turn -- so p = exp2(0) = 1 and l = 1: every head of a group returns that key's V row bit for bit.
+    -> (q, k, v, mask, want [B, Hq, D])"""
+    B, Skv, Hq, Hkv = c["B"], c["Skv"], c["Hq"], c["Hkv"]
+    chunk = decode_chunk(Skv, nsplit)
+    first = chunk if chunk < Skv else 0
+    m = torch.zeros(B, Skv, dtype=torch.long)
+    keys = [(first, chunk - 1, Skv - 1)[b % 3] for b in range(B)]
+    for b, j in enumerate(keys):
+        m[b, j] = 1
+    q, k, v = decode_operands(c, m, seed)
+    want = torch.stack([v[b, j] for b, j in enumerate(keys)]).repeat_interleave(Hq // Hkv, dim=1)
+    return q, k, v, m, want
+
+
+def decode_uniform(c, nvis=128, seed=3):
+    """The exact family `uniform`: q = 0, V small integers in [-2, 2], nvis >> b visible keys in sequence b (powers of two, spread
+    evenly over the keys and so over the slices).  Every p is exactly 1, every partial sum is an integer of at most 2 nvis, and
+    o / l is exact in bf16: one dropped, doubled or leaked key changes bits.  -> (q, k, v, mask, want [B, Hq, D])"""
+    B, Skv, Hq, Hkv, D = c["B"], c["Skv"], c["Hq"], c["Hkv"], c["D"]
+    assert nvis <= 128 and nvis & (nvis - 1) == 0 and nvis <= Skv
+    g = torch.Generator().manual_seed(seed + Skv)
+    m = torch.zeros(B, Skv, dtype=torch.long)
+    for b in range(B):
+        n = max(1, nvis >> b)
+        m[b, (torch.arange(n) * Skv) // n + (b if (n - 1) * Skv // n + b < Skv else 0)] = 1
+    q = torch.zeros(B, Hq, D)
+    k = torch.randn(B, Skv, Hkv, D, generator=g) * torch.where(m == 0, 1000.0, 1.0)[:, :, None, None]
+    v = torch.randint(-2, 3, (B, Skv, Hkv, D), generator=g).double()
+    ref = (v * m[:, :, None, None]).sum(1) / m.sum(1)[:, None, None].double()                 # [B, Hkv, D]
+    want = ref.float().to(BF16)
+    assert bool((want.double() == ref).all()), "uniform family: o / l is not exact in bf16"
+    return q.to(BF16), k.to(BF16), v.to(BF16), m, want.repeat_interleave(Hq // Hkv, dim=1)
+
+
+def decode_place(q, k, v, device="cuda"):
+    """The operands as generate() passes them: q a strided view into a fused [B, (Hq + 2 Hkv) D] projection row, k / v prefix
+    views [:, :Skv] of a longer cache.  The rest of the row and the cache rows from Skv on hold the sentinel NaN, so a read
+    past Skv that reaches the result shows as a non-finite output."""
+    from tests.kernel_check import sentinel_fill
+    B, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    row = sentinel_fill(torch.empty(B, (Hq + 2 * Hkv) * D, dtype=q.dtype))
+    row[:, :Hq * D] = q.reshape(B, Hq * D)
+    kc = sentinel_fill(torch.empty(B, Skv + 11, Hkv, D, dtype=q.dtype))
+    vc = sentinel_fill(torch.empty(B, Skv + 11, Hkv, D, dtype=q.dtype))
+    kc[:, :Skv], vc[:, :Skv] = k, v
+    row, kc, vc = row.to(device), kc.to(device), vc.to(device)
+    return row[:, :Hq * D].view(B, Hq, D), kc[:, :Skv], vc[:, :Skv]
+
+
+def decode_reference(q, k, v, key_mask, scale):
+    """fp64 out [B, Hq, D] with its error scale, and rows [B] (the sequence has a visible key; elsewhere E = 0 and out == 0)."""
+    r = reference(q[:, None], k, v, None, key_mask, False, scale, backward=False)
+    return {"out": r["out"][:, 0], "E_out": r["E_out"][:, 0], "rows": r["rows"][:, 0]}
+
+
+def _where_decode(idx, shape):
+    b, h, d = coords(idx, shape)
+    return f"(b={b}, head={h}, d={d})"
+
+
+def check_decode(out, ref, path, c=None):
+    """The rule on a decode output; recorded in RATIOS[(path, "out")]."""
+    return check_bound("out", out, ref["out"], ref["E_out"], C[path]["out"] if c is None else c, U[BF16],
+                       key=path and (path, "out"), log=RATIOS, where=_where_decode)
+
+
+def decode_args(q, k, v, key_mask, scale, out, ws, nsplit, sync):
+    """mm_attn_decode's arguments up to the stream"""
+    B, Hq, D = q.shape
+    return (dt(q.dtype), ptr(q), ptr(k), ptr(v), B, k.shape[1], Hq, k.shape[2], D, q.stride(0), q.stride(1), *_s3(k), *_s3(v),
+            ptr(key_mask), float(scale), ptr(out), ptr(ws), nsplit, ptr(sync))
+
+
+def decode_buffers(B, Hq, D, nsplit, device):
+    """out [B, Hq, D] and the fp32 workspace [B Hq nsplit (D + 2)] in guarded storages -> (out, ws, [guards]); the workspace is
+    verified with require_written: every slice writes its record, an empty one included."""
+    go = Guarded(B * Hq * D, BF16, device)
+    gw = Guarded(B * Hq * nsplit * (D + 2), torch.float32, device)
+    return (go.view((B, Hq, D), (Hq * D, D, 1)), gw.view((B * Hq * nsplit * (D + 2),), (1,)),
+            [("out", go), ("workspace", gw, True)])
+
+
+def run_decode(q, k, v, key_mask, scale, nsplit=None, fused=False, sync=None):
+    """mm_attn_decode with out and the workspace inside guarded storages.  nsplit=None takes mm_attn_decode_splits.  fused: the
+    single-launch form on `sync`, or on a fresh zeroed tensor with SYNC_SPARE counters behind B * Hkv; after the run the whole
+    tensor must still be zero (`decode_sync_clean`).  -> (out, [guards], sync)"""
+    from multimeditron_amd._lib import call, lib
+    B, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    ns = lib().mm_attn_decode_splits(B, Hkv, Skv) if nsplit is None else nsplit
+    out, ws, guards = decode_buffers(B, Hq, D, ns, q.device)
+    if fused and sync is None:
+        sync = torch.zeros(B * Hkv + SYNC_SPARE, dtype=torch.int32, device=q.device)
+    call("mm_attn_decode", *decode_args(q, k, v, key_mask, scale, out, ws, ns, sync if fused else None),
+         torch.cuda.current_stream().cuda_stream)
+    return out, guards, sync if fused else None
+
+
+def decode_sync_clean(sync):
+    assert not bool(sync.any()), f"the arrival counters are not left at zero: {sync.tolist()}"

@@ -10,7 +10,12 @@ kernel output.  A result passes when |got - ref| <= c u E elementwise, with
       MI355X over that checker's contract tests (the measured ratios are written beside each constant);
   E = 0  means no rounding can occur there: the result must EQUAL the reference (the zeros of masked rows, keys and padding).
 Every other element must be finite.  The bound is a worst case (sum of |terms|), so it is rigorous and loses power as 1/sqrt(n)
-on long sums; each checker's test_*_check_cpu.py shows which kernel mistakes it flags at the sizes the GPU tests use."""
+on long sums; each checker's test_*_check_cpu.py shows which kernel mistakes it flags at the sizes the GPU tests use.
+
+Where c is DERIVED instead of measured (the kernel's only rounding to the output dtype is the store, so err / (u E) <= 1, times 2 of
+margin; the measured ratio is then only recorded beside it): attn_check's bf16-decode-valu / bf16-decode-mfma / bf16-decode-fused
+(mm_attn_decode) and rowwise_check's expert_fuse (mm_expert_fuse, forward and backward = 1).  mm_decode_select is integer
+bookkeeping: tests/test_rowwise_contract_gpu.py compares every buffer whole."""
 import atexit
 import contextlib
 import json

@@ -14,6 +14,8 @@ tests/kernel_check.py (`bound`).  The rounding points, read off mm_rowwise.hip (
   ce_fwd        per-thread online (max, sum) over ce_iters(V) vectors, block max, rescale, block sum, lse = max + logf(sum)
   ce_bwd        T((exp(x - lse) - [v == label]) * gscale / max(count, 1))
   argmax        s = f32(T(x / temp)), p = T(exp(s - max s) / sum), first index of the maximum of p
+  expert_fuse   w = gate[n, idx[j]] (mode 1: their J-way softmax in fp32);  T(sum_j w_j x_j) / T(w'_j x_j): one rounding to T
+                (c derived, not measured: see the section at the end)
 
 Summation depth.  The accumulation term of a reduction is (depth) * u32 * sum|terms| with the kernel's real worst-case depth:
   norm_depth(dtype, H) = CH_body * VN products added by one thread + 6 shuffle levels + 3 adds of the 4 wave sums (block_sum_256),
@@ -64,6 +66,9 @@ C = {
     "ce.loss_row": (0.25, 0.25),       # 0.091, 0.111
     "ce.loss": (0.125, 0.125),         # 0.051, 0.052
     "ce.dlogits": (2.0, 2.0),          # 0.995, 0.855
+    # mm_expert_fuse, forward and backward = 1.  DERIVED, not measured: one output rounding bounds bf16 by 1, the fp32 terms are
+    # counted explicitly in E (expert_fuse_reference), times 2 of margin.  The measured ratios are for the record only.
+    "expert_fuse": (2.0, 2.0),         # 0.995, 0.416
 }
 
 
@@ -510,3 +515,71 @@ def guarded(shape, dtype, ld=None, extra_rows=0, device="cuda"):
     ld = W if ld is None else ld
     g = Guarded((R + extra_rows) * ld, dtype, device)
     return g.view((R, W), (ld, 1)), g
+
+
+# ---- MoE expert fusion (mm_expert_fuse) -------------------------------------------------------------------------------------------
+# expert_fuse_kernel: w_j = gate[n, idx[j]] (mode 1: the J-way softmax of those, expf(w - max) / sum, fp32), then
+#   mode 0  out[n]    = T(sum_j w_j X[idx[j], n])   one fma per expert in fp32, ONE rounding
+#   mode 1  out[n, j] = T(w'_j X[idx[j], n])         one product, ONE rounding
+#   backward = 1: dX[idx[j], n] = T(w_j dout[n]) (mode 0) / T(w'_j dout[n, j]) (mode 1); the unlisted slices are not written.
+# Error scale, kappa = U32 / u:  mode 0: E = |ref| + kappa (J + 2) sum_j |w_j x_j| (J adds, the product, the store);
+#                                mode 1: E = |ref| (1 + kappa (J + 8))  (expf, the J-term sum and the divide of the softmax).
+FUSE_MAXJ = 16                       # MOE_MAXJ
+
+
+def _fuse_weights(gate, idx, mode):
+    w = gate.double()[:, list(idx)]                                        # [n, J]
+    return torch.softmax(w, -1) if mode == 1 else w
+
+
+def expert_fuse_reference(X, gate, idx, mode):
+    """X [E, n, L] (stored), gate [n, E] fp32, idx the listed experts.  -> (ref, E): [n, L] (mode 0) / [n, J, L] (mode 1), fp64."""
+    J, kappa = len(idx), _uscale(X.dtype)
+    w = _fuse_weights(gate, idx, mode)
+    terms = w[:, :, None] * X.double()[list(idx)].permute(1, 0, 2)          # [n, J, L]
+    if mode == 0:
+        ref = terms.sum(1)
+        return ref, ref.abs() + kappa * (J + 2) * terms.abs().sum(1)
+    return terms, terms.abs() * (1.0 + kappa * (J + 8))
+
+
+def expert_fuse_bwd_reference(dout, gate, idx, mode, E_experts):
+    """dout [n, L] (mode 0) / [n, J, L] (mode 1).  -> (dX, E) [E_experts, n, L] in fp64; the slices of experts that are not listed
+    are zero here with E = 0 -- the kernel does not write them, so a caller compares the listed slices only."""
+    J, kappa = len(idx), _uscale(dout.dtype)
+    w = _fuse_weights(gate, idx, mode)
+    d = dout.double()
+    n, L = d.shape[0], d.shape[-1]
+    ref = torch.zeros(E_experts, n, L, dtype=torch.float64, device=d.device)
+    for j, e in enumerate(idx):
+        ref[e] = w[:, j, None] * (d if mode == 0 else d[:, j])
+    return ref, ref.abs() * (1.0 + kappa * ((J + 2) if mode == 0 else (J + 8)))
+
+
+def expert_fuse_problem(E_experts, idx, n, L, dtype, mode, device, seed, exact=False):
+    """X [E, n, L], gate [n, E] fp32 (softmax weights of random logits), dout in the mode's output shape.  With E = 3 and mode 1
+    the first gate row is [90, 50, 10]: without the max subtraction expf overflows, with it the weights are 1, e^-40, e^-80.
+    exact: X and dout small integers and every gate entry 0.25 -- mode 0 is then exact in fp32, and so is mode 1 when J is a
+    power of two (the softmax is exactly 1 / J): the output is ONE rounding of the fp64 result."""
+    g = _gen(device, seed)
+    J = len(idx)
+    oshape = (n, L) if mode == 0 else (n, J, L)
+    if exact:
+        X = torch.randint(-4, 5, (E_experts, n, L), generator=g, device=device).to(dtype)
+        dout = torch.randint(-4, 5, oshape, generator=g, device=device).to(dtype)
+        gate = torch.full((n, E_experts), 0.25, device=device)
+    else:
+        # |x| >= 2^-6: the smallest weight of the range row, e^-80 = 1.8e-35, times x then stays a NORMAL number (>= 2.8e-37) in
+        # bf16 and fp32 alike -- the rule's u is a relative roundoff and does not describe a subnormal result
+        away = lambda t: torch.where(t < 0, -1.0, 1.0) * t.abs().clamp_min(2.0 ** -6)
+        X = away(torch.randn(E_experts, n, L, generator=g, device=device)).to(dtype)
+        dout = away(torch.randn(*oshape, generator=g, device=device)).to(dtype)
+        gate = torch.softmax(2.0 * torch.randn(n, E_experts, generator=g, device=device), -1)
+        if E_experts == 3 and mode == 1:
+            gate[0] = torch.tensor([90.0, 50.0, 10.0], device=device)
+    return X, gate, dout
+
+
+def fuse_listed(t, idx):
+    """the listed experts' slices of a [E, n, L] tensor, in idx order: [J, n, L]"""
+    return t[list(idx)]

@@ -4,11 +4,14 @@ Paths (launch_bf16_fwd / launch_bf16_bwd / mm_attn_bwd): bf16 D = 128 (attn_fwd1
 attn_bwd_dq128p_kernel, attn_bwd_dkv128_pairp_kernel), bf16 D = 64 (attn_fwd_kernel<64>, attn_bwd_dq_kernel<64>,
 attn_bwd_dkv_kernel<64>), fp32 (attn_fwd_f32_kernel, attn_bwd_f32_kernel, both forms of attn_delta_kernel).  Every launch writes
 into guarded storages (tests/kernel_check.py: Guarded) and every case checks the output contract.  Then the exact invariances:
-the work mapping (batch split, KV-head permutation), masked padding keys, and repeat determinism with a GEMM running beside."""
+the work mapping (batch split, KV-head permutation), masked padding keys, and repeat determinism with a GEMM running beside.
+The last section holds mm_attn_decode (the VALU and MFMA slice kernels, the merge kernel and the single-launch merge) to the same
+rule, to two exact families and to its return codes."""
 import pytest
 import torch
 
 from tests import attn_check as AC
+from tests.kernel_check import SENTINEL, check_bits, lib, options, rc
 
 pytestmark = pytest.mark.gpu
 BF, F32 = torch.bfloat16, torch.float32
@@ -261,3 +264,149 @@ def test_attention_masked_padding_keys(K, npad, path):
     if dt == BF:
         assert torch.equal(base["dk"], pad["dk"][:, :Skv]) and torch.equal(base["dv"], pad["dv"][:, :Skv]), \
             f"dk/dv of the original keys change when {npad} masked keys are appended"
+
+
+# ---- mm_attn_decode: one query token over a KV cache ---------------------------------------------------------------------------
+# Kernels: attn_decode_partial_kernel<D, G> (VALU; keys per wave trip / workgroup trip: 16 / 64 at D = 128, 32 / 128 at D = 64),
+# attn_decode_partial128_mfma_kernel<G> (D = 128, G <= 4, two-launch form; 16 / 64), attn_decode_merge_kernel, and the merge by
+# the last slice through the `sync` counters.  Every case runs the three launch forms -- two launches with attn_decode_mfma = 1
+# (MFMA where it applies), two launches with attn_decode_mfma = 0 (VALU), fused (VALU) -- each twice into fresh guards.
+DC = AC.decode_case
+DECODE_CASES = [
+    # D = 128, G <= 4: every Skv through the MFMA and the VALU slice kernels
+    DC(1, 1, 1, 1, 128),
+    DC(3, 15, 4, 2, 128, "leftpad"),
+    DC(1, 17, 4, 1, 128, "holes", ns=1),
+    DC(3, 63, 2, 2, 128, "single"),
+    DC(3, 65, 8, 2, 128, "dead"),
+    DC(3, 129, 2, 1, 128, "slice", ns="lib8"),              # 3 slices of 43 keys
+    DC(1, 200, 1, 1, 128, "holes", ns="lib8"),              # 4 slices of 50
+    DC(3, 200, 8, 2, 128, "leftpad", ns=3),                 # chunk 67: a slice edge that is no multiple of 16
+    DC(1, 10, 2, 1, 128, ns=8),                             # chunk 2: slices 5 .. 7 hold no key
+    DC(3, 10, 4, 1, 128, "slice", ns=8),                    # ... and one more holds only masked keys
+    DC(1, 2051, 4, 1, 128, "holes"),                        # the library's own count: 33 slices of 63
+    # D = 128, G in {7, 8}: VALU in every form
+    DC(1, 65, 7, 1, 128, "leftpad"),
+    DC(3, 200, 16, 2, 128, "dead", ns=3),
+    DC(1, 129, 14, 2, 128, "slice", ns="lib8"),
+    # D = 64: every Skv, every G
+    DC(1, 1, 2, 2, 64),
+    DC(3, 15, 7, 1, 64, "leftpad"),
+    DC(1, 17, 8, 1, 64, "holes", ns=1),
+    DC(3, 63, 1, 1, 64, "single"),
+    DC(3, 65, 4, 1, 64, "dead"),
+    DC(3, 129, 4, 2, 64, "slice", ns="lib8"),
+    DC(1, 200, 14, 2, 64, "holes", ns="lib8"),
+    DC(3, 200, 2, 1, 64, "leftpad", ns=3),
+    DC(1, 10, 8, 2, 64, ns=8),
+    DC(1, 2051, 8, 1, 64, "holes"),
+]
+ONE_KEY_CASES = [DC(3, 200, 8, 2, 128, ns=3), DC(3, 10, 7, 1, 128, ns=8), DC(3, 2051, 4, 1, 128), DC(3, 200, 2, 1, 64, ns=3),
+                 DC(3, 65, 14, 2, 64), DC(3, 17, 1, 1, 128, ns=1)]
+UNIFORM_CASES = [DC(3, 200, 4, 2, 128, ns=3), DC(3, 200, 7, 1, 64, ns="lib8"), DC(3, 2051, 2, 1, 128), DC(3, 2051, 8, 1, 64),
+                 DC(3, 200, 16, 2, 128, ns=8)]
+
+
+def decode_nsplit(c):
+    """the case's split count; the library's own value is asked of mm_attn_decode_splits and must match its mirror"""
+    ns = AC.decode_nsplit(c)
+    if c["ns"] in ("lib", "lib8"):
+        with options(attn_decode_wgs=8 if c["ns"] == "lib8" else AC.DECODE_WGS):
+            assert lib().mm_attn_decode_splits(c["B"], c["Hkv"], c["Skv"]) == ns
+    return ns
+
+
+def decode_forms(q, k, v, mask, scale, ns):
+    """{path: out} of the three launch forms.  Each runs twice into fresh guards (the fused form on the same counters) and must
+    repeat bit for bit; the fused form must equal the two-launch VALU form bit for bit and leave every counter zero."""
+    B, Hq, D = q.shape
+    G = Hq // k.shape[2]
+    res, guards = {}, []
+    for mfma in (1, 0):
+        with options(attn_decode_mfma=mfma):
+            a, g1, _ = AC.run_decode(q, k, v, mask, scale, ns)
+            b, g2, _ = AC.run_decode(q, k, v, mask, scale, ns)
+        path = AC.decode_path(D, G, mfma=bool(mfma))
+        guards += g1 + g2
+        check_bits(f"{path} rerun", b, a)
+        if path in res:                                     # no MFMA kernel for this shape: the switch changes nothing
+            check_bits(f"{path} with attn_decode_mfma = {mfma}", a, res[path])
+        res[path] = a
+    a, g1, sync = AC.run_decode(q, k, v, mask, scale, ns, fused=True)
+    b, g2, _ = AC.run_decode(q, k, v, mask, scale, ns, fused=True, sync=sync)
+    torch.cuda.synchronize()
+    AC.verify_guards(guards + g1 + g2)
+    AC.decode_sync_clean(sync)
+    check_bits("fused rerun on the same counters", b, a)
+    check_bits("fused == two-launch VALU", a, res["bf16-decode-valu"])
+    res["bf16-decode-fused"] = a
+    return res
+
+
+@pytest.mark.parametrize("c", DECODE_CASES, ids=[AC.decode_case_id(c) for c in DECODE_CASES])
+def test_decode_contract(K, c):
+    ns = decode_nsplit(c)
+    mask = AC.decode_mask(c["mask"], c["B"], c["Skv"], ns)
+    q, k, v = AC.decode_place(*AC.decode_operands(c, mask))
+    mg = mask.cuda() if mask is not None else None
+    scale = c["D"] ** -0.5
+    res = decode_forms(q, k, v, mg, scale, ns)
+    if c["D"] == 128 and c["Hq"] // c["Hkv"] <= 4:
+        assert set(res) == {"bf16-decode-mfma", "bf16-decode-valu", "bf16-decode-fused"}
+    ref = AC.decode_reference(q, k, v, mg, scale)
+    for path, out in res.items():
+        AC.check_decode(out, ref, path)
+        dead = out[~ref["rows"]]
+        check_bits(f"{path}: rows with no visible key give 0", dead, torch.zeros_like(dead))
+
+
+@pytest.mark.parametrize("c", ONE_KEY_CASES, ids=[AC.decode_case_id(c) for c in ONE_KEY_CASES])
+def test_decode_one_key_exact(K, c):
+    """One visible key per sequence (first of a slice, last of a slice, Skv - 1): p = 1, l = 1, out == that key's V row."""
+    ns = decode_nsplit(c)
+    q, k, v, mask, want = AC.decode_one_key(c, ns)
+    qd, kd, vd = AC.decode_place(q, k, v)
+    for path, out in decode_forms(qd, kd, vd, mask.cuda(), c["D"] ** -0.5, ns).items():
+        check_bits(f"one_key {path}", out, want)
+
+
+@pytest.mark.parametrize("c", UNIFORM_CASES, ids=[AC.decode_case_id(c) for c in UNIFORM_CASES])
+def test_decode_uniform_exact(K, c):
+    """q = 0, integer V, 128 / 64 / 32 visible keys spread over the slices: every sum is exact, out == mean of the visible V."""
+    ns = decode_nsplit(c)
+    q, k, v, mask, want = AC.decode_uniform(c)
+    qd, kd, vd = AC.decode_place(q, k, v)
+    for path, out in decode_forms(qd, kd, vd, mask.cuda(), c["D"] ** -0.5, ns).items():
+        check_bits(f"uniform {path}", out, want, zero_sign=False)
+
+
+def test_decode_return_codes(K):
+    """Every refusal of mm_attn_decode by code, with out, the workspace and the counters bit-unchanged; B = 0 is MM_OK and
+    writes nothing."""
+    OK, ERR_ARG, ERR_ALIGN, ERR_UNSUPPORTED = 0, -1, -2, -3
+    B, Skv, Hq, Hkv, D, ns = 2, 40, 4, 2, 128, 2
+
+    def attempt(want, B=B, Hq=Hq, Hkv=Hkv, D=D, ns=ns, dtype=BF, dq=0, dsb=0):
+        q = torch.randn(max(B, 1), Hq, D + 8, device="cuda").to(dtype)[..., :D]
+        k = torch.randn(max(B, 1), Skv, Hkv, D, device="cuda").to(dtype)
+        v = torch.randn(max(B, 1), Skv, Hkv, D, device="cuda").to(dtype)
+        out, ws, guards = AC.decode_buffers(max(B, 1), Hq, D, max(ns, 1), "cuda")
+        sync = torch.full((max(B, 1) * Hkv + AC.SYNC_SPARE,), 77, dtype=torch.int32, device="cuda")
+        for s in (None, sync):
+            a = list(AC.decode_args(q, k, v, None, D ** -0.5, out, ws, ns, s))
+            a[0], a[1], a[4], a[9] = (0 if dtype == BF else 1), a[1] + dq, B, a[9] + dsb
+            assert rc("mm_attn_decode", *a) == want, (want, B, Hq, Hkv, D, ns, dtype, dq, dsb)
+        torch.cuda.synchronize()
+        for _, g, *_ in guards:
+            assert bool((g.buf.view(torch.int16 if g.dtype == BF else torch.int32) == SENTINEL[g.dtype]).all()), \
+                "a refused or empty call wrote to out or the workspace"
+        assert bool((sync == 77).all()), "a refused or empty call touched the counters"
+
+    attempt(ERR_UNSUPPORTED, dtype=F32)
+    attempt(ERR_UNSUPPORTED, D=96)
+    attempt(ERR_UNSUPPORTED, Hq=3, Hkv=1)                  # G = 3
+    attempt(ERR_ARG, Hq=5, Hkv=2)                          # Hq % Hkv != 0
+    attempt(ERR_ARG, ns=0)
+    attempt(ERR_ALIGN, dsb=4)                              # q_sb not a multiple of 8 elements
+    attempt(ERR_ALIGN, dq=2)                               # q not 16-byte aligned
+    attempt(OK, B=0)

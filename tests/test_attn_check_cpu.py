@@ -1,13 +1,17 @@
 """The attention checker has power (no GPU): a plain-torch emulation of the bf16 kernels' rounding points passes
 tests/attn_check.py at the bf16 constants, and each of the usual ways these kernels go wrong, applied to that emulation, is
 flagged by at least 4x the constant.  `pytest -s` prints which of them whole-tensor rel-L2 at the GPU tests' tolerance
-(1e-2 for out, 2e-2 for gradients) would have missed."""
+(1e-2 for out, 2e-2 for gradients) would have missed.  The last section does the same for mm_attn_decode: an emulation of the
+split-K arithmetic on the GPU tests' own cases, nine planted mistakes, each flagged by the bound at >= 4x c or by an exact family."""
+import functools
 import math
 
 import pytest
 import torch
 
 from tests import attn_check as AC
+from tests import test_attention_contract_gpu as GPU          # its case lists; nothing in it runs without a GPU
+from tests.kernel_check import check_bits
 
 BF = torch.bfloat16
 LN2 = math.log(2.0)
@@ -215,3 +219,155 @@ def test_mutation_flagged(mutation):
     print(f"\n  [{name}] flagged by {ratio:.1f}x c on {worst_q}; whole-tensor rel-L2 out {rl2['out']:.2e} "
           f"dq {rl2['dq']:.2e} dk {rl2['dk']:.2e} dv {rl2['dv']:.2e} -> "
           f"{'MISSED by rel-L2' if missed else 'seen by rel-L2'}")
+
+
+# ---- mm_attn_decode: the split-K arithmetic, on the shapes of the GPU tests --------------------------------------------------------
+DECODE_C = AC.C["bf16-decode-valu"]["out"]
+
+
+def emulate_decode(q, k, v, mask, scale, nsplit, mut=None):
+    """attn_decode_partial_kernel + the merge in plain torch: per slice an online softmax in fp32 with base-2 exponentials (here
+    the slice's max taken at once), a record (m, l, o) per (sequence, head, slice) -- (-inf, 0, 0) for a slice with no visible key
+    --, the merge in slice order with the max rescale, ONE rounding to bf16; 0 where no key is visible.  `mut` names a deliberate
+    mistake; a mistake inside a slice or in the merge is planted in slice 1 (slice 0 where there is only one) of ONE row, the
+    last head of the last sequence."""
+    B, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    chunk = AC.decode_chunk(Skv, nsplit)
+    st = 1 if chunk < Skv else 0
+    kvh, qsrc = torch.arange(Hq) // G, torch.arange(Hq)
+    if mut == "wrong_kv_head":
+        kvh[-1] = (kvh[-1] + 1) % Hkv
+    if mut == "next_query" and G > 1:
+        qsrc[0] = 1
+    qf = q.float()[:, qsrc] * (scale * AC.LOG2E)
+    kf = k.float().permute(0, 2, 1, 3)[:, kvh]                               # [B, Hq, Skv, D]
+    vf = v.float().permute(0, 2, 1, 3)[:, kvh]
+    vis = torch.ones(B, Skv, dtype=torch.bool) if mask is None else mask != 0
+    s = torch.einsum("bhd,bhkd->bhk", qf, kf)
+    ms, ls, os_ = [], [], []
+    for sl in range(nsplit):
+        k0, k1 = sl * chunk, min(Skv, (sl + 1) * chunk)
+        if k0 >= k1:                                                         # a slice with no key at all
+            empty_l = 1.0 if mut == "empty_l_one" else 0.0
+            ms.append(torch.full((B, Hq), 0.0 if mut == "empty_l_one" else -math.inf))
+            ls.append(torch.full((B, Hq), empty_l))
+            os_.append(torch.zeros(B, Hq, D))
+            continue
+        al = vis[:, k0:k1].clone()
+        mult = torch.ones(k1 - k0)
+        if sl == st:
+            if mut == "drop_last":
+                al[:, -1] = False
+            elif mut == "first_twice":
+                mult[0] = 2.0
+            elif mut == "mask_ignored":
+                al[:] = True
+        ss = s[:, :, k0:k1].masked_fill(~al[:, None], -math.inf)
+        m = ss.amax(-1)
+        p = torch.exp2(ss - torch.where(m == -math.inf, torch.zeros_like(m), m)[..., None]) * mult
+        ms.append(m)
+        ls.append(p.sum(-1))
+        os_.append(torch.einsum("bhk,bhkd->bhd", p, vf[:, :, k0:k1]))
+    if mut == "skip_slice" and len(ms) > 1:
+        del ms[st], ls[st], os_[st]
+    M, L, O = torch.stack(ms), torch.stack(ls), torch.stack(os_)
+    mn = M.amax(0)
+    al = torch.exp2(M - torch.where(mn == -math.inf, torch.zeros_like(mn), mn))
+    if mut == "no_rescale":
+        al = torch.ones_like(al)
+    lt, ot = (L * al).sum(0), (O * al[..., None]).sum(0)
+    out = torch.where(lt[..., None] > 0, ot / torch.where(lt > 0, lt, torch.ones_like(lt))[..., None], torch.zeros_like(ot))
+    if mut == "dead_mean":
+        dead = ~vis.any(-1)
+        out[dead] = vf.mean(2)[dead]
+    if mut in SLICE_MUTATIONS:                        # planted in ONE row: the last head of the last sequence
+        clean = emulate_decode(q, k, v, mask, scale, nsplit).float()
+        clean[B - 1, Hq - 1] = out[B - 1, Hq - 1]
+        out = clean
+    return out.to(BF)
+
+
+SLICE_MUTATIONS = ("drop_last", "first_twice", "skip_slice", "no_rescale", "mask_ignored", "empty_l_one")
+
+
+@functools.lru_cache(maxsize=None)
+def decode_problem(i):
+    """operands, mask, split count and the fp64 reference of GPU.DECODE_CASES[i], computed once"""
+    c = GPU.DECODE_CASES[i]
+    ns = AC.decode_nsplit(c)
+    mask = AC.decode_mask(c["mask"], c["B"], c["Skv"], ns)
+    q, k, v = AC.decode_operands(c, mask)
+    return c, ns, mask, q, k, v, AC.decode_reference(q, k, v, mask, c["D"] ** -0.5)
+
+
+def decode_exact(mut):
+    """the exact families on the GPU tests' shapes -> the names of those whose bits the emulation misses"""
+    bad = []
+    for fam, cases, make in (("one_key", GPU.ONE_KEY_CASES, AC.decode_one_key), ("uniform", GPU.UNIFORM_CASES, None)):
+        for c in cases:
+            ns = AC.decode_nsplit(c)
+            q, k, v, mask, want = make(c, ns) if make else AC.decode_uniform(c)
+            got = emulate_decode(q, k, v, mask, c["D"] ** -0.5, ns, mut)
+            try:
+                check_bits(fam, got, want, zero_sign=False)
+            except AssertionError:
+                bad.append(f"{fam} {AC.decode_case_id(c)}")
+    return bad
+
+
+def test_decode_case_lists_reach_every_edge():
+    cs = GPU.DECODE_CASES
+    for D in (64, 128):
+        assert {c["Hq"] // c["Hkv"] for c in cs if c["D"] == D} == {1, 2, 4, 7, 8}
+        # every length through each kernel: D = 64 is VALU for every G; at D = 128 the G <= 4 cases run MFMA and VALU both
+        assert {1, 15, 17, 63, 65, 129, 200, 2051} <= {c["Skv"] for c in cs if c["D"] == D and (D == 64 or c["Hq"] // c["Hkv"] <= 4)}
+    assert {c["B"] for c in cs} == {1, 3} and {c["Hkv"] for c in cs} == {1, 2}
+    assert {c["mask"] for c in cs} == {None, "leftpad", "holes", "slice", "dead", "single"}
+    assert {"lib", "lib8", 1, 3, 8} <= {c["ns"] for c in cs}
+    assert any(c["ns"] == 3 and c["Skv"] == 200 for c in cs) and any(c["ns"] == 8 and c["Skv"] == 10 for c in cs)
+    assert AC.decode_nsplit(AC.decode_case(1, 2051, 4, 1, 128)) == 33 and AC.decode_nsplit(AC.decode_case(3, 129, 2, 1, 128, ns="lib8")) == 3
+
+
+def test_decode_emulation_passes():
+    worst = 0.0
+    for i in range(len(GPU.DECODE_CASES)):
+        c, ns, mask, q, k, v, ref = decode_problem(i)
+        out = emulate_decode(q, k, v, mask, c["D"] ** -0.5, ns)
+        worst = max(worst, AC.check_decode(out, ref, "bf16-decode-emulation", c=DECODE_C))
+        assert bool((out[~ref["rows"]] == 0).all())
+    assert decode_exact(None) == []
+    assert worst < DECODE_C
+    print(f"\n  [decode emulation] worst err/(u E) = {worst:.3f} (c = {DECODE_C})")
+
+
+DECODE_MUTATIONS = [("the last key of a slice dropped", "drop_last"), ("the first key of a slice counted twice", "first_twice"),
+                    ("one slice skipped by the merge", "skip_slice"), ("the merge without the max rescale", "no_rescale"),
+                    ("the mask ignored inside one slice", "mask_ignored"), ("head g reads head g+1's query", "next_query"),
+                    ("the wrong kv head", "wrong_kv_head"), ("a fully masked row returns the mean of V", "dead_mean"),
+                    ("an empty slice contributes l = 1", "empty_l_one")]
+
+
+@pytest.mark.parametrize("mutation", DECODE_MUTATIONS, ids=[m[1] for m in DECODE_MUTATIONS])
+def test_decode_mutation_flagged(mutation):
+    name, mut = mutation
+    best, where, hit, missed = 0.0, None, 0, []
+    for i in range(len(GPU.DECODE_CASES)):
+        c, ns, mask, q, k, v, ref = decode_problem(i)
+        out = emulate_decode(q, k, v, mask, c["D"] ** -0.5, ns, mut)
+        if torch.equal(out, emulate_decode(q, k, v, mask, c["D"] ** -0.5, ns)):
+            continue                                                         # the mistake has no effect at this shape
+        hit += 1
+        try:
+            ratio = AC.check_decode(out, ref, None, c=math.inf) / DECODE_C
+        except AssertionError:                                               # a non-finite value, or != 0 where E = 0
+            ratio = math.inf
+        if _rel(out.float(), ref["out"]) < TOL_OUT:
+            missed.append(f"{AC.decode_case_id(c)} (bound: {ratio:.1f}x c)")
+        if ratio > best:
+            best, where = ratio, AC.decode_case_id(c)
+    exact = decode_exact(mut)
+    assert best >= 4.0 or exact, f"{name}: worst err/(c u E) = {best:.2f} and no exact family flags it"
+    print(f"\n  [decode: {name}] changes the output of {hit} GPU cases; bound: {best:.1f}x c at {where}; exact-family cases that "
+          f"flag it: {len(exact)}; whole-tensor rel-L2 at {TOL_OUT} MISSES it in {len(missed)} of the {hit}: {missed}")

@@ -21,6 +21,8 @@ OPTIONS = {
     "gemm_issue_waves": (8, 8, 6), "gemm_w4_rowmajor": (3, 1, None), "gemm_w4_big": (1, 1, 2), "gemm_w4_group_m": (4, 4, 0),
     "gemm_w4_stream": (7, 1, None), "gemm_w4_shuffle": (2, 1, None), "gemm_w4_diag_epi": (5, 5, None), "gemm_w4_stagger_slots": (32, 32, 33),
     "gemm_w4_stagger": (100, 100, -1), "gemm_w4": (6, 6, -1), "gemm_kernel": (6, 6, 7),
+    # the attention kernels' switches (mm_attn.hip answers them): tests/kernel_check.options needs them to read back
+    "attn_decode_mfma": (0, 0, None), "attn_decode_wgs": (8, 8, 0), "attn_q_prio": (0, 0, None), "attn_diag": (2, 2, None),
 }
 
 

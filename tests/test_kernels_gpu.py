@@ -543,6 +543,13 @@ def test_attention_decode(K, case):
         assert rel(out.float(), out_valu.float()) < 4e-3 and not (Skv > 64 and torch.equal(out, out_valu) and False)
     else:
         assert torch.equal(out, out_valu)
+    # per element against the fp64 reference, every launch form under its own path; a sequence without a visible key gives 0
+    from tests import attn_check as AC
+    ref64 = AC.decode_reference(qv, kv, vv, mg, scale)
+    G = Hq // Hkv
+    for o, path in ((out, AC.decode_path(D, G)), (out_valu, AC.decode_path(D, G, mfma=False)), (out1, AC.decode_path(D, G, fused=True))):
+        AC.check_decode(o, ref64, path)
+        assert not bool(o[~ref64["rows"]].any())
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])

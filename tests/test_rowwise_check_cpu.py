@@ -2,13 +2,15 @@
 different order from the kernel (torch's own reduction over the columns reversed), passes tests/rowwise_check.py with the final c
 of every path.  (b) Each of the usual ways such a kernel goes wrong, applied to that emulation, is flagged -- by the per-element
 bound, by an exact check, by the count, or by the guard bands.  (c) The case lists of tests/test_rowwise_contract_gpu.py cover
-the launch variants: every norm_ch, both loop bodies of reduce_partials, both arg-max kernels."""
+the launch variants: every norm_ch, both loop bodies of reduce_partials, both arg-max kernels.  The MoE expert fusion
+(mm_expert_fuse, forward and backward = 1) has its emulation and its six planted mistakes in a section of its own."""
 import pytest
 import torch
 
 from tests import gemm_check as GC
 from tests import rowwise_check as RC
 from tests import test_rowwise_contract_gpu as GPU
+from tests.kernel_check import check_bits
 from tests.rowwise_check import BF, F32, U32
 
 DTYPES = [BF, F32]
@@ -331,6 +333,83 @@ def test_guard_bands_see_a_write_past_the_row():
         v2, g2 = RC.guarded((4, H), dtype, extra_rows=1, device="cpu")
         v2[:3].fill_(1.0)
         fails(lambda: g2.verify("last row never written"))
+
+
+# ---- MoE expert fusion ---------------------------------------------------------------------------------------------------------------
+def fuse_weights(gate, idx, mode, mut=None):
+    cols = list(range(len(idx))) if mut == "gate_j" else list(idx)
+    w = gate.float()[:, cols]
+    if mode == 1:
+        if mut == "softmax_all":                                # over all E experts in place of the listed J
+            a = gate.float()
+            e = torch.exp(a - a.max(-1, keepdim=True).values)
+            return (e / e.sum(-1, keepdim=True))[:, cols]
+        e = torch.exp(w - w.max(-1, keepdim=True).values)
+        w = e / e.sum(-1, keepdim=True)
+    return w
+
+
+def fuse_fwd(X, gate, idx, mode, mut=None):
+    """expert_fuse_kernel's forward: fp32 arithmetic (mode 0 adds the experts in idx order), one rounding"""
+    n, J, L = X.shape[1], len(idx), X.shape[2]
+    t = fuse_weights(gate, idx, mode, mut)[:, :, None] * X.float()[list(idx)].permute(1, 0, 2)       # [n, J, L]
+    if mode == 0:
+        acc = torch.zeros(n, L)
+        for j in range(J - 1 if mut == "drop_last" else J):
+            acc = acc + t[:, j]
+        return acc.to(X.dtype)
+    out = t.to(X.dtype)
+    return out.permute(1, 0, 2).contiguous().view(n, J, L) if mut == "layout_jnl" else out
+
+
+def fuse_bwd(dout, gate, idx, mode, E, mut=None):
+    """the backward = 1 form into a NaN-filled [E, n, L]: only the listed slices are written"""
+    w, d = fuse_weights(gate, idx, mode), dout.float()
+    dX = torch.full((E, d.shape[0], d.shape[-1]), float("nan")).to(dout.dtype)
+    for j, e in enumerate(idx):
+        dj = d if mode == 0 else d[:, 0 if mut == "bwd_dout0" else j]
+        dX[j if mut == "bwd_slice_j" else e] = (w[:, j, None] * dj).to(dout.dtype)
+    return dX
+
+
+FUSE_MUTATIONS = [  # (what, mutation, backward, mode)
+    ("gate[:, j] read in place of gate[:, idx[j]]", "gate_j", False, 0), ("softmax over all E experts", "softmax_all", False, 1),
+    ("the mode-1 output laid out [J, n, L]", "layout_jnl", False, 1), ("the backward reads dout[n, 0] for every j", "bwd_dout0", True, 1),
+    ("the backward writes slice j in place of idx[j]", "bwd_slice_j", True, 0), ("mode 0 without the last expert", "drop_last", False, 0)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+def test_expert_fuse_emulation_passes_and_mutations_fail(dtype):
+    c = RC.c_of("expert_fuse", dtype)
+    cases = [(E, idx, n, L) for (E, idx) in GPU.FUSE_EXPERTS for n in GPU.FUSE_N for L in GPU.fuse_L(dtype)[:2]]
+
+    def ratio(E, idx, n, L, mode, backward, mut=None, exact=False):
+        """worst err / (u E) of the emulation (inf: a non-finite value, or a miss where E = 0); exact: the bits of the exact family"""
+        X, gate, dout = RC.expert_fuse_problem(E, idx, n, L, dtype, mode, "cpu", E + n + L, exact=exact)
+        if backward:
+            got = RC.fuse_listed(fuse_bwd(dout, gate, idx, mode, E, mut), idx)
+            ref, Er = (RC.fuse_listed(t, idx) for t in RC.expert_fuse_bwd_reference(dout, gate, idx, mode, E))
+        else:
+            got = fuse_fwd(X, gate, idx, mode, mut)
+            ref, Er = RC.expert_fuse_reference(X, gate, idx, mode)
+        try:
+            if exact:
+                check_bits("exact family", got, RC.rne(ref, dtype), zero_sign=False)
+                return 0.0
+            return RC.check_bound("expert_fuse", got, ref, Er, float("inf"), RC.U[dtype])
+        except AssertionError:
+            return float("inf")
+
+    worst = max(ratio(*cs, mode, backward) for cs in cases for mode in (0, 1) for backward in (False, True))
+    print(f"\n  [expert_fuse emulation {RC.NAME[dtype]}] worst err/(u E) = {worst:.3f} (c = {c})")
+    assert worst < c
+    assert all(ratio(*cs, mode, backward, exact=True) == 0.0 for cs in cases for mode in (0, 1) for backward in (False, True)
+               if mode == 0 or len(cs[1]) in (1, 2, 16))
+    for what, mut, backward, mode in FUSE_MUTATIONS:
+        by_bound = max(ratio(*cs, mode, backward, mut) for cs in cases)
+        by_bits = any(ratio(*cs, mode, backward, mut, exact=True) for cs in cases if mode == 0 or len(cs[1]) in (1, 2, 16))
+        print(f"  [expert_fuse {RC.NAME[dtype]}: {what}] bound: {by_bound / c:.1f}x c; exact family flags it: {by_bits}")
+        assert by_bound >= 4.0 * c or by_bits, what
 
 
 # ---- (c) the case lists cover the edge matrix --------------------------------------------------------------------------------------

@@ -2,15 +2,17 @@
 |got - ref| <= c u E per element against fp64 elsewhere (tests/rowwise_check.py), every output in a NaN-sentinel storage
 (Guarded) with spare rows and, where the entry takes one, a padded leading dimension; inputs the contract says are not read hold
 NaN sentinels.  Refusals are asserted by return code with the outputs untouched; no call passes a pointer or a size an entry
-does not check."""
+does not check.  The last two sections hold the MoE expert fusion (mm_expert_fuse, forward and backward = 1) and generate()'s eos
+bookkeeping (mm_decode_select) the same way."""
 import ctypes
+import itertools
 
 import pytest
 import torch
 
 from tests import gemm_check as GC
 from tests import rowwise_check as RC
-from tests.kernel_check import SENTINEL, dt, lib, rc
+from tests.kernel_check import SENTINEL, Guarded, check_bits, dt, lib, rc
 from tests.kernel_check import ptr as p_
 from tests.rowwise_check import BF, F32, U32, VN, check_exact, guarded
 
@@ -593,3 +595,129 @@ def test_refusals_return_before_any_launch(dtype):
     sync()
     untouched(gx, go, g1, g2, gd, gy)
     assert out.tolist() == [-7] * 4
+
+
+# ---- MoE expert fusion (mm_expert_fuse, forward and backward = 1) ---------------------------------------------------------------------
+FUSE_EXPERTS = [(3, (0, 1, 2)), (3, (2, 0)), (4, (3,)), (16, (5, 12, 0, 9, 15, 3, 7, 1, 14, 10, 2, 8, 13, 6, 11, 4))]
+FUSE_N = [1, 3]
+
+
+def fuse_L(dtype):
+    """one 16-byte vector; 136; 257 vectors of bf16 -- with n = 3 the n x 257 threads end in a partial 256-thread block"""
+    return [VN[dtype], 136, 257 * 8]
+
+
+def cints(idx):
+    return (ctypes.c_int * len(idx))(*idx)
+
+
+def fuse_launch(dtype, mode, E, idx, n, L, X, gate, dout):
+    """forward into a guarded out, backward into a guarded [E, n, L] storage whose views are the listed experts' slices.  The
+    slices of X and the columns of gate that belong to unlisted experts hold NaN: they are not read.
+    -> (out, dX listed [J, n, L], tag)"""
+    J = len(idx)
+    tag = f"expert_fuse {RC.NAME[dtype]} mode={mode} E={E} idx={list(idx)} n={n} L={L}"
+    unlisted = [e for e in range(E) if e not in idx]
+    X, gate = X.clone(), gate.clone()
+    X[unlisted] = float("nan")
+    gate[:, unlisted] = float("nan")
+    oshape = (n, L) if mode == 0 else (n, J, L)
+    go = Guarded(n * L * (1 if mode == 0 else J), dtype, DEV)
+    out = go.view(oshape, (L, 1) if mode == 0 else (J * L, L, 1))
+    assert rc("mm_expert_fuse", dt(dtype), 0, mode, p_(X), p_(gate), cints(idx), J, E, n, L, p_(out)) == RC.OK
+    gd = Guarded(E * n * L, dtype, DEV)
+    dX = [gd.view((n, L), (L, 1), e * n * L) for e in idx]
+    assert rc("mm_expert_fuse", dt(dtype), 1, mode, p_(dout), p_(gate), cints(idx), J, E, n, L, p_(gd.buf[gd.pad:])) == RC.OK
+    sync()
+    go.verify(tag + " out")
+    gd.verify(tag + " dX: the listed slices are written whole, the unlisted ones keep the sentinel")
+    return out, torch.stack(dX), tag
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+def test_expert_fuse_contract(dtype, mode):
+    for (E, idx), n, L in itertools.product(FUSE_EXPERTS, FUSE_N, fuse_L(dtype)):
+        X, gate, dout = RC.expert_fuse_problem(E, idx, n, L, dtype, mode, DEV, E + n + L)
+        out, dX, tag = fuse_launch(dtype, mode, E, idx, n, L, X, gate, dout)
+        ref, Eo = RC.expert_fuse_reference(X, gate, idx, mode)
+        RC.bound(tag + " out", "expert_fuse", dtype, out, ref, Eo)
+        ref, Ed = RC.expert_fuse_bwd_reference(dout, gate, idx, mode, E)
+        RC.bound(tag + " dX", "expert_fuse", dtype, dX, RC.fuse_listed(ref, idx), RC.fuse_listed(Ed, idx))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+def test_expert_fuse_exact(dtype, mode):
+    """integer X / dout, every gate entry 0.25: mode 0, and mode 1 with J in {1, 2, 16} (softmax exactly 1 / J), have no fp32
+    rounding, so every output is the one rounding of the fp64 result, bit for bit."""
+    for (E, idx), n, L in itertools.product(FUSE_EXPERTS, FUSE_N, fuse_L(dtype)):
+        if mode == 1 and len(idx) not in (1, 2, 16):
+            continue
+        X, gate, dout = RC.expert_fuse_problem(E, idx, n, L, dtype, mode, DEV, E + n + L, exact=True)
+        out, dX, tag = fuse_launch(dtype, mode, E, idx, n, L, X, gate, dout)
+        check_bits(tag + " out (exact family)", out, RC.rne(RC.expert_fuse_reference(X, gate, idx, mode)[0], dtype), zero_sign=False)
+        ref = RC.expert_fuse_bwd_reference(dout, gate, idx, mode, E)[0]
+        check_bits(tag + " dX (exact family)", dX, RC.rne(RC.fuse_listed(ref, idx), dtype), zero_sign=False)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+def test_expert_fuse_return_codes(dtype):
+    """every refusal by code with nothing written; n = 0 is MM_OK and writes nothing"""
+    vn, E, n, L = VN[dtype], 20, 2, 16 * VN[dtype]
+    X = torch.randn(E, n, L + vn, device=DEV).to(dtype)
+    gate = torch.rand(n, E, device=DEV)
+    out, go = guarded((E * n, L + vn), dtype)
+
+    def attempt(want, idx=(0, 1), mode=0, n=n, L=L):
+        for backward in (0, 1):
+            assert rc("mm_expert_fuse", dt(dtype), backward, mode, p_(X), p_(gate), cints(idx), len(idx), E, n, L, p_(out)) == want, \
+                (want, idx, mode, n, L, backward)
+
+    attempt(RC.ERR_ARG, idx=tuple(range(17)))                # J = 17 > 16
+    attempt(RC.ERR_ARG, idx=(0, E))                          # an index >= E
+    attempt(RC.ERR_ARG, idx=(0, -1))
+    attempt(RC.ERR_ARG, mode=2)
+    attempt(RC.ERR_ALIGN, L=L + 1)
+    attempt(RC.OK, n=0)
+    sync()
+    untouched(go)
+
+
+# ---- generate()'s eos bookkeeping (mm_decode_select) ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 64, 65, 130])
+def test_decode_select(B):
+    """Three chained steps (columns 0, 3, 6 of out [B, 7]) on the same `finished`, rows a mix of already finished, emitting eos
+    now and live: every buffer, whole -- the other columns of out and the spare elements behind B of finished / next_ids
+    included --, equals a torch rendering of the header's four assignments; a finished row keeps emitting eos."""
+    EOS, LD, MARK, SPARE = 2, 7, -99, 5
+    r = torch.arange(B, device=DEV)
+    fin = torch.full((B + SPARE,), 0xAB, dtype=torch.uint8, device=DEV)
+    fin[:B] = (r % 3 == 0).to(torch.uint8)
+    out = torch.full((B + 2, LD), MARK, dtype=torch.int64, device=DEV)
+    nxt = torch.full((B + SPARE,), MARK, dtype=torch.int64, device=DEV)
+    fin_ref, out_ref, nxt_ref = fin.clone(), out.clone(), nxt.clone()
+    g = RC._gen(DEV, B)
+    for step, col in enumerate((0, 3, 6)):
+        tok = torch.randint(3, 1000, (B + SPARE,), generator=g, device=DEV)
+        tok[:B][(r + step) % 4 == 1] = EOS
+        assert rc("mm_decode_select", p_(tok), p_(fin), EOS, B, p_(out), LD, col, p_(nxt)) == RC.OK
+        was = fin_ref[:B] != 0
+        chosen = torch.where(was, torch.full_like(tok[:B], EOS), tok[:B])
+        fin_ref[:B] |= (chosen == EOS).to(torch.uint8)
+        out_ref[:B, col] = chosen
+        nxt_ref[:B] = chosen
+        sync()
+        assert torch.equal(fin, fin_ref), f"finished after step {step}"
+        assert torch.equal(out, out_ref), f"out after step {step} (column {col})"
+        assert torch.equal(nxt, nxt_ref), f"next_ids after step {step}"
+        assert bool((chosen[was] == EOS).all())
+    assert B < 3 or bool(((out[:B, 6] == EOS) >= (out[:B, 0] == EOS)).all())     # eos sticks
+    # refusals change nothing; B = 0 is MM_OK and writes nothing
+    args = lambda **kw: [kw.get("tok", p_(tok)), kw.get("fin", p_(fin)), EOS, kw.get("B", B), kw.get("out", p_(out)), LD, kw.get("col", 1),
+                         kw.get("nxt", p_(nxt))]
+    for bad in (dict(col=LD), dict(col=-1), dict(tok=None), dict(fin=None), dict(out=None), dict(nxt=None)):
+        assert rc("mm_decode_select", *args(**bad)) == RC.ERR_ARG, bad
+    assert rc("mm_decode_select", *args(B=0)) == RC.OK
+    sync()
+    assert torch.equal(fin, fin_ref) and torch.equal(out, out_ref) and torch.equal(nxt, nxt_ref)
