@@ -134,8 +134,17 @@ int mm_colsum(int dtype, const void* X, int M, int N, int ldx, void* out, int ac
  *   kernel adds the products of a K-step in the same order, so the tile does not change the bits).  MM_ERR_UNSUPPORTED, before any
  *   launch, where mm_gemm would take a 256-wide tile, the M <= 16 weight-streaming kernels or an activation outside NT: those
  *   problems fill the chip on their own, so the caller loops mm_gemm (kernels.gemm_batched does).
- * mm_gemm_act_fwd_batched: mm_gemm_act_fwd (PRE and ACT per problem) under the same rules.
- * mm_colsum_batched: mm_colsum per problem (the same row partition: same bits).                                                    */
+ * mm_gemm_act_fwd_batched: mm_gemm_act_fwd (PRE and ACT per problem) under the same rules.  MM_ERR_UNSUPPORTED for MM_F32, for
+ *   M <= 16 and under "gemm_kernel" = 1; ldpre a multiple of 4 and every PRE[g] 8-byte aligned (MM_ERR_ALIGN); N, K <= 0, a NULL PRE
+ *   table or entry, no activation or more than one: MM_ERR_ARG.
+ * mm_colsum_batched: mm_colsum per problem (the same row partition: same bits).
+ * Alignment is that of the stand-alone entry point for EVERY problem: the low address bits are OR-ed over the problems, so one
+ *   misaligned pointer in any problem is MM_ERR_ALIGN for the launch.  M == 0 or N == 0 (mm_gemm_batched), M == 0
+ *   (mm_gemm_act_fwd_batched): MM_OK after the argument checks, nothing is launched or written.
+ * "gemm_last_kernel": a grouped GEMM that launches sets it to the id of the tile the WHOLE batch ran on (3, 4, 5, or 30 for MM_F32);
+ *   one that returns before launching -- any error code, or MM_OK for an empty problem -- leaves it as it was.
+ * tests/test_grouped_contract_gpu.py holds these entry points to fp64 references, to the stand-alone bits and to these codes at
+ *   the sizes where a workgroup walks several tiles and where the batch's tile differs from the stand-alone call's.          */
 int mm_gemm_batched(int dtype, int layout, int groups, int M, int N, int K, const void* const* A, int lda, const void* const* B,
                     int ldb, void* const* C, int ldc, const void* const* bias, const void* const* residual, int ldr, int epilogue,
                     void* stream);
@@ -249,7 +258,9 @@ int mm_reduce_partials2(int dtype, const float* partial0, const float* partial1,
  * [groups * R]; w[] / b[] are per expert.  A backward workgroup never spans two experts: expert g owns the partial blocks
  * [g * nb, (g + 1) * nb), nb = mm_norm_bwd_blocks(R), partitioned as a stand-alone call with M = R partitions them (dw_partial /
  * db_partial: f32 [groups * nb, H]).  mm_reduce_partials2_batched reduces expert g's nblk blocks into out0[g] / out1[g] in the
- * order of mm_reduce_partials2.  Every output has the bits of `groups` stand-alone calls.                                       */
+ * order of mm_reduce_partials2.  Every output has the bits of `groups` stand-alone calls.  Widths as for the stand-alone norms
+ * (MM_ERR_ALIGN / MM_ERR_UNSUPPORTED), checked before any launch; R == 0: MM_OK, nothing is launched or written; nblk == 0: out0[g] /
+ * out1[g] = 0, or stay under their `accumulate`.  groups outside 1..MM_GROUP_MAX, a NULL table or a NULL entry: MM_ERR_ARG.          */
 int mm_layernorm_fwd_batched(int dtype, const void* x, const void* const* w, const void* const* b, int groups, int R, int H, float eps,
                              void* y, float* mean, float* rstd, void* stream);
 int mm_layernorm_bwd_batched(int dtype, const void* dy, const void* x, const void* const* w, int groups, const float* mean,

@@ -28,6 +28,7 @@ padding columns and in rows past K, bias and residual NaN past N (`kc_storage`, 
 contract that reaches a stored element then fails the exact check; a write outside the output fails Guarded.verify.
 
 `last_kernel()` is mm_get_option("gemm_last_kernel"): every case states the kernel id it expects (see mm_hip.h)."""
+import ctypes
 import math
 
 import torch
@@ -47,8 +48,10 @@ V1, DMA256x128, DMA256x256, DMA128, DMA64x128, DMA64, W4, SKINNY, GEMV, F32 = 0,
 # c per random-family path: the smallest power of two >= 2x the worst err / (u E) measured on the MI355X over the cases of
 # tests/test_gemm_contract_gpu.py and the existing GEMM tests (the PR description lists the measured ratios)
 C = {
-    "linear": 2.0,         # every bf16 linear path of the random family (v1, DMA tiles, 4-wave, skinny, gemv_stream): measured 0.994
-    "act": 2.0,            # GELU epilogues (erf, quick, tanh), with and without the kept pre-activation: measured 0.996
+    "linear": 2.0,         # every bf16 linear path of the random family (v1, DMA tiles, 4-wave, skinny, gemv_stream): measured 0.994;
+                           # the grouped launches (paths grouped-linear, grouped-linear-f32): 0.993, 0.075
+    "act": 2.0,            # GELU epilogues (erf, quick, tanh), with and without the kept pre-activation: measured 0.996;
+                           # mm_gemm_act_fwd_batched (path grouped-act): 0.995
     "swiglu": 2.0,         # SwiGLU forward (GEMM epilogue and decode fusion) and backward: measured 0.995
     "rope": 2.0,           # RoPE epilogue (GEMM and decode fusion): measured 0.996
     "norm": 0.5,           # decode fusions with the RMSNorm prologue: measured 0.160
@@ -69,7 +72,8 @@ def pad64(n):
 # ---- exact family --------------------------------------------------------------------------------------------------------
 def exact_problem(M, N, K, device, seed, span=3, amp=8, c_amp=None):
     """Logical fp64 operands of C[M, N] = A[M, K] . B[N, K]^T + bias + res + c0 (B always as [N, K]; the layout only decides
-    how it is stored).  Returns a dict with A, B, bias [N], res, c0 [M, N] and q [M, N] (the quantum of every element)."""
+    how it is stored).  Returns a dict with A, B, bias [N], res, c0 [M, N], q [M, N] (the quantum of every element) and the
+    row / column exponents re [M], ce [N] behind it (q = 2^(re + ce))."""
     g = torch.Generator(device=device).manual_seed(seed)
     ri = lambda lo, hi, shape: torch.randint(lo, hi + 1, shape, generator=g, device=device).double()
     re, ce = ri(-span, span, (M,)), ri(-span, span, (N,))
@@ -80,7 +84,7 @@ def exact_problem(M, N, K, device, seed, span=3, amp=8, c_amp=None):
     bias = ri(-ca, ca, (N,)) * torch.exp2(re.max() + ce)
     res = ri(-ca, ca, (M, N)) * q
     c0 = ri(-ca, ca, (M, N)) * q
-    return {"A": a, "B": b, "bias": bias, "res": res, "c0": c0, "q": q}
+    return {"A": a, "B": b, "bias": bias, "res": res, "c0": c0, "q": q, "re": re, "ce": ce}
 
 
 def exact_reference(p, epi=0, a=None, b=None):
@@ -333,3 +337,194 @@ def check_random(name, got, a, b, epi=0, bias=None, res=None, c0=None, path="lin
     """Random-family check of a bf16 linear result: a [M, K], b [N, K] the logical operands (any layout they were stored in)."""
     ref, E = bound_reference(a, b, epi, bias=bias, res=res, c0=c0)
     return check_bound(name, got, ref, E, C[path], path)
+
+
+# ---- grouped launches (mm_gemm_batched, mm_gemm_act_fwd_batched, mm_colsum_batched) ------------------------------------------------
+# A grouped launch is held to the SAME references as the stand-alone call, problem by problem: every problem of a launch has
+# its own seed (operands, bias, residual and accumulated C differ from problem to problem, so a pointer-table entry taken from
+# another problem lands on foreign data), the exact family is compared bitwise and the random family under C["linear"] /
+# C["act"] -- the arithmetic is mm_gemm's, so there is no constant of its own; the worst ratios are recorded under the path
+# keys grouped-linear (measured 0.993 against c = 2), grouped-linear-f32 (0.075; the fp32 E counts one rounding per fma) and
+# grouped-act (0.995 against c = 2) over tests/test_grouped_contract_gpu.py.  Outputs sit expert-major in ONE Guarded storage (problem p + 1's
+# rows follow problem p's at a padded ld, as kernels._rows hands them over: a tile that overhangs M lands in the next problem)
+# or in one Guarded storage per problem between sentinel rows.  `plan` is mm_gemm_plan: every case asserts the path it claims.
+FP32 = torch.float32                             # the dtype; F32 above is the fp32 kernel's id
+GROUP_MAX = 16                                   # MM_GROUP_MAX
+KIND_PLAIN, KIND_ACT_FWD = 0, 1                  # mm_gemm_plan's `kind`
+FAM_NONE, FAM_V1, FAM_DMA, FAM_F32 = -1, 0, 1, 5   # ... and the kernel families it reports
+OK, ERR_ARG, ERR_ALIGN, ERR_UNSUPPORTED = 0, -1, -2, -3
+PLAN_INTS = 26
+GROUPED_PLACEMENTS = ("expert_major", "separate")
+
+
+def pa(ts):
+    """host array of device pointers for a grouped entry point: tensors, raw addresses or None (a NULL entry); None -> a NULL table"""
+    if ts is None:
+        return None
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() if isinstance(t, torch.Tensor) else t for t in ts])
+
+
+def out_ld(N):
+    """the padded leading dimension of a grouped output"""
+    return pad8(N) + 8
+
+
+def grouped_lds(layout, M, N, K):
+    """(lda, ldb, ldc, ldr) of `operands`, `grouped_out` and `rows_storage` at their defaults"""
+    return (pad8(M) + 8 if layout == TN else pad8(K) + 16, pad8(K) + 16 if layout == NT else pad8(N) + 8, out_ld(N), pad8(N) + 8)
+
+
+def plan(dtype, layout, kind, groups, M, N, K, epi=0, ncu=0, lds=None, ptr_bits=0):
+    """mm_gemm_plan under the current switches (groups = 0: the stand-alone call; ncu = 0: the current device's CUs) -> dict with
+    rc, last (the kernel id, -2 = unchanged), family, tile (BM, BN of an LDS-DMA plan), grid_x, grid_y, tiles (per problem)."""
+    lda, ldb, ldc, ldr = lds or grouped_lds(layout, M, N, K)
+    out = (ctypes.c_int * PLAN_INTS)()
+    rc = KC.lib().mm_gemm_plan(KC.dt(dtype), layout, kind, groups, M, N, K, lda, ldb, ldc, ldr if epi & EPI_RESIDUAL else 0, 0, epi, 0,
+                               ptr_bits, ncu, out)
+    assert rc == 0, (rc, dtype, layout, kind, groups, M, N, K)
+    v = list(out)
+    return dict(rc=v[0], last=v[1], family=v[2], tile=(v[5], v[6]), grid_x=v[11], grid_y=v[12], tiles=v[15] * v[16])
+
+
+def grouped_problems(family, groups, M, N, K, device, seed, dtype=BF, same_a=False):
+    """`groups` problems of one shape, each under its own seed -> a list of exact_problem-style dicts (fp64 values that the
+    storage dtype holds exactly).  family "random": normal operands (sigma 0.5), bias / residual / C of sigma 1.  same_a: every
+    problem reads problem 0's A (the patch embedding's form); an exact problem then keeps only what a plain epilogue needs."""
+    out = []
+    for p in range(groups):
+        s = seed + 7919 * p
+        if family == "exact":
+            d = exact_problem(M, N, K, device, s)
+            if same_a and p:
+                d = {"A": out[0]["A"], "B": d["B"], "re": out[0]["re"], "ce": d["ce"], "q": torch.exp2(out[0]["re"][:, None] + d["ce"][None, :])}
+        else:
+            g = torch.Generator(device=device).manual_seed(s)
+            r = lambda *sh: (torch.randn(*sh, generator=g, device=device) * 0.5).to(dtype).double()
+            d = {"A": r(M, K), "B": r(N, K), "bias": r(N) * 2.0, "res": r(M, N) * 2.0, "c0": r(M, N) * 2.0}
+            if same_a and p:
+                d["A"] = out[0]["A"]
+        out.append(d)
+    return out
+
+
+def grouped_operands(layout, probs, epi, dtype=BF, same_a=False):
+    """stored operands of every problem (NaN beyond the contract: `operands`, `vec_storage`, `rows_storage`) ->
+    (As, Bs, biases or None, residuals or None)"""
+    As, Bs = [], []
+    for p, d in enumerate(probs):
+        A, B = operands(layout, d["A"], d["B"], dtype)
+        As.append(As[0] if same_a and p else A)
+        Bs.append(B)
+    biases = [vec_storage(d["bias"], dtype) for d in probs] if epi & EPI_BIAS else None
+    res = [rows_storage(d["res"], dtype) for d in probs] if epi & EPI_RESIDUAL else None
+    return As, Bs, biases, res
+
+
+def grouped_out(groups, M, N, place, dtype=BF, device="cuda", extra_rows=8, gap_rows=3):
+    """`groups` outputs [M, N] at ld = out_ld(N).  'expert_major': ONE Guarded storage [groups * M + extra_rows, ld], problem p at
+    row p * M;  'separate': one Guarded storage per problem with gap_rows sentinel rows above and below.  -> (views, guards)"""
+    ld = out_ld(N)
+    if place == "expert_major":
+        g = Guarded((groups * M + extra_rows) * ld, dtype, device)
+        return [g.view((M, N), (ld, 1), p * M * ld) for p in range(groups)], [g]
+    guards = [Guarded((M + 2 * gap_rows) * ld, dtype, device) for _ in range(groups)]
+    return [g.view((M, N), (ld, 1), gap_rows * ld) for g in guards], guards
+
+
+def fill_c0(outs, probs, dtype=BF):
+    """what C holds before an accumulating launch"""
+    for c, d in zip(outs, probs):
+        c.copy_(d["c0"].to(dtype))
+
+
+def verify_all(name, guards, require_written=True):
+    for i, g in enumerate(guards):
+        g.verify(f"{name} [{i}]", require_written)
+
+
+def untouched(guards):
+    """a refused or empty call wrote nothing: every element of every storage is still the sentinel"""
+    for g in guards:
+        assert bool((KC._ints(g.buf) == KC.SENTINEL[g.dtype]).all()), "a refused or empty call wrote to its output"
+
+
+def batched_args(layout, M, N, K, As, Bs, Cs, biases=None, res=None, epi=0, dtype=BF, pres=None):
+    """the arguments of one mm_gemm_batched call (pres given: mm_gemm_act_fwd_batched, Cs = ACT) by name, so that a refusal
+    test can replace one of them; the pointer lists take tensors, raw addresses or None."""
+    return dict(dtype=KC.dt(dtype), layout=layout, groups=len(Cs), M=M, N=N, K=K, A=list(As), lda=As[0].stride(0), B=list(Bs),
+                ldb=Bs[0].stride(0), C=list(Cs), ldc=Cs[0].stride(0), bias=list(biases) if biases is not None else None,
+                res=list(res) if res is not None else None, ldr=res[0].stride(0) if res is not None else 0, epi=epi,
+                PRE=list(pres) if pres is not None else None, ldpre=pres[0].stride(0) if pres is not None else 0, act_fwd=pres is not None)
+
+
+def launch_batched(a):
+    """-> the raw return code of the grouped entry point `a` (batched_args) describes"""
+    if a["act_fwd"]:
+        return KC.rc("mm_gemm_act_fwd_batched", a["dtype"], a["groups"], a["M"], a["N"], a["K"], pa(a["A"]), a["lda"], pa(a["B"]), a["ldb"],
+                     pa(a["bias"]), pa(a["PRE"]), a["ldpre"], pa(a["C"]), a["ldc"], pa(a["res"]), a["ldr"], a["epi"])
+    return KC.rc("mm_gemm_batched", a["dtype"], a["layout"], a["groups"], a["M"], a["N"], a["K"], pa(a["A"]), a["lda"], pa(a["B"]), a["ldb"],
+                 pa(a["C"]), a["ldc"], pa(a["bias"]), pa(a["res"]), a["ldr"], a["epi"])
+
+
+def grouped_want(family, d, epi, dtype=BF):
+    """what problem `d` must give under the linear epilogue flags `epi`: ('exact', tensor of the output dtype) or
+    ('bound', (ref, E)) with E in units of the output dtype's u (fp32: |ref| + (K + 3) |A|.|B| + ..., one rounding per fma)."""
+    if family == "exact":
+        ref = exact_reference(d, epi)
+        return "exact", (ref.float() if dtype == FP32 else rne_bf16(ref))
+    ref, E = bound_reference(d["A"], d["B"], epi, bias=d.get("bias"), res=d.get("res"), c0=d.get("c0"))
+    if dtype == FP32:
+        E = ref.abs() + (E - ref.abs()) * (U_BF / U32)
+    return "bound", (ref, E)
+
+
+def check_grouped(tag, family, probs, epi, outs, dtype=BF, path="grouped-linear"):
+    """every problem's output against ITS reference: bitwise in the exact family, C["linear"] in the random one (recorded under
+    `path`, `path`-f32 for fp32).  -> the worst ratio (0 in the exact family)."""
+    worst = 0.0
+    for p, (d, c) in enumerate(zip(probs, outs)):
+        kind, want = grouped_want(family, d, epi, dtype)
+        if kind == "exact":
+            check_exact(f"{tag} problem {p}", c, want.to(c.device))
+        else:
+            ref, E = want
+            key = path if dtype == BF else path + "-f32"
+            worst = max(worst, check_bound(f"{tag} problem {p}", c, ref.to(c.device), E.to(c.device), C["linear"], key, u=KC.U[dtype]))
+    return worst
+
+
+def check_grouped_act(tag, family, probs, flags, kind, pres, acts, path="grouped"):
+    """mm_gemm_act_fwd(_batched) per problem: PRE = bf16(X.W^T + bias) (exact family: bitwise; random: C["linear"]), ACT = act(PRE)
+    (rounded to bf16 before a residual add) from the kernel's own PRE under C["act"], recorded under `path`-linear / `path`-act."""
+    worst = 0.0
+    for p, d in enumerate(probs):
+        check_grouped(f"{tag} PRE", family, [d], flags & EPI_BIAS, [pres[p]], path=path + "-linear")
+        res = d["res"].to(pres[p].device) if flags & EPI_RESIDUAL else None
+        ref, E = act_reference(pres[p].double(), kind, res, round_act=True)
+        worst = max(worst, check_bound(f"{tag} ACT problem {p}", acts[p], ref, E, C["act"], path + "-act"))
+    return worst
+
+
+def colsum_problems(groups, R, N, device, seed):
+    """exact-family rows per expert, as test_colsum_exact builds them: d["res"] [R, N] are the rows, d["c0"][0] * 2^6 what `out`
+    holds before an accumulating call."""
+    return [exact_problem(R, N, 8, device, seed + 7919 * p, span=2) for p in range(groups)]
+
+
+def colsum_storage(probs, dtype, extra_rows=4):
+    """the experts' rows expert-major in ONE storage [groups * R + extra_rows, ldx] with a padded ldx: NaN in the padding columns
+    and in the rows past the last expert; expert p + 1's rows follow expert p's.  -> the per-expert [R, N] views"""
+    R, N = probs[0]["res"].shape
+    ldx = pad8(N) + 8
+    buf = sentinel_fill(torch.empty(len(probs) * R + extra_rows, ldx, dtype=dtype, device=probs[0]["res"].device))
+    for p, d in enumerate(probs):
+        buf[p * R:(p + 1) * R, :N] = d["res"].to(dtype)
+    return [buf[p * R:(p + 1) * R, :N] for p in range(len(probs))]
+
+
+def colsum_want(d, accumulate, dtype):
+    """-> (what out holds before, the exact result in the output dtype) after the range assertion of the exact family"""
+    base = d["c0"][0] * 2.0 ** 6 if accumulate else torch.zeros_like(d["c0"][0])
+    ref = d["res"].sum(0) + base
+    assert float(((d["res"].abs().sum(0) + base.abs()) / d["q"].min(0).values).max()) < 2.0 ** 24
+    return base.to(dtype), (ref.float() if dtype == FP32 else rne_bf16(ref))

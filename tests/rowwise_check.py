@@ -583,3 +583,67 @@ def expert_fuse_problem(E_experts, idx, n, L, dtype, mode, device, seed, exact=F
 def fuse_listed(t, idx):
     """the listed experts' slices of a [E, n, L] tensor, in idx order: [J, n, L]"""
     return t[list(idx)]
+
+
+# ---- grouped LayerNorm / reduce (mm_layernorm_*_batched, mm_reduce_partials2_batched) ---------------------------------------------
+# One expert-major buffer [groups * R, H]; expert g's rows are checked against the fp64 LayerNorm of ITS slice with ITS w / b under
+# the stand-alone constants C["layernorm.*"] (the arithmetic is the stand-alone kernel's), recorded under grouped.layernorm.*.
+# Every expert has its own seed and its own w / b ramp (sign and slope change with g), so another expert's weights are far off.
+# Measured over tests/test_grouped_contract_gpu.py (bf16, f32), against the c of C["layernorm.*"]: mean 0.074, 0.204; rstd 0.233,
+# 0.219; y 0.996, 0.240; dx 0.996, 0.387; dw 0.995, 0.139; db 0.995, 0.105.
+def grouped_norm_problem(groups, R, H, dtype, device, seed):
+    """-> dict: x, dy, dres [groups * R, H] expert-major, ws / bs = per-expert [H] (all in the storage dtype)"""
+    ps = [norm_problem(R, H, dtype, device, seed + 7919 * g, layer=True) for g in range(groups)]
+    slope = lambda g: (1.0 + 0.25 * g) * (-1.0 if g % 2 else 1.0)
+    cat = lambda k: torch.cat([p[k] for p in ps]) if groups * R else ps[0][k][:0]
+    return {"x": cat("x"), "dy": cat("dy"), "dres": cat("dres"),
+            "ws": [(p["w"].float() * slope(g)).to(dtype) for g, p in enumerate(ps)],
+            "bs": [(p["b"].float() + 0.5 * g * slope(g)).to(dtype) for g, p in enumerate(ps)]}
+
+
+GROUPED_PREFIX = ["grouped"]         # tests/test_grouped_check_cpu.py records its emulation under "grouped_emulation" instead
+
+
+def _gbound(name, kernel, dtype, got, ref, E, u=None):
+    return check_bound(name, got, ref.to(got.device), E.to(got.device), c_of(kernel, dtype), U[dtype] if u is None else u,
+                       key=f"{GROUPED_PREFIX[0]}.{kernel}.{NAME[dtype]}", log=RATIOS)
+
+
+def check_grouped_layernorm_fwd(tag, x, ws, bs, eps, R, y, mean, rstd):
+    """y, mean, rstd [groups * R (, H)] of mm_layernorm_fwd_batched, expert by expert"""
+    dtype = x.dtype
+    for g in range(len(ws)):
+        sl = slice(g * R, (g + 1) * R)
+        y64, Ey, m64, Em, r64, Er = layernorm_fwd_reference(x[sl], ws[g], bs[g], eps)
+        _gbound(f"{tag} mean, expert {g}", "layernorm.mean", dtype, mean[sl], m64, Em, u=U32)
+        _gbound(f"{tag} rstd, expert {g}", "layernorm.rstd", dtype, rstd[sl], r64, Er, u=U32)
+        _gbound(f"{tag} y, expert {g}", "layernorm.y", dtype, y[sl], y64, Ey)
+
+
+def check_grouped_layernorm_bwd(tag, dy, x, ws, mean, rstd, dres, R, dx, dws, dbs):
+    """dx [groups * R, H] and the reduced per-expert dws[g] / dbs[g] [H] of mm_layernorm_bwd_batched + mm_reduce_partials2_batched
+    (overwrite), from the STORED mean / rstd"""
+    dtype = x.dtype
+    for g in range(len(ws)):
+        sl = slice(g * R, (g + 1) * R)
+        dx64, Edx, dw64, Edw, db64, Edb = layernorm_bwd_reference(dy[sl], x[sl], ws[g], mean[sl], rstd[sl], dres[sl] if dres is not None else None)
+        _gbound(f"{tag} dx, expert {g}", "layernorm.dx", dtype, dx[sl], dx64, Edx)
+        _gbound(f"{tag} dw, expert {g}", "layernorm.dw", dtype, dws[g], dw64, Edw)
+        _gbound(f"{tag} db, expert {g}", "layernorm.db", dtype, dbs[g], db64, Edb)
+
+
+def grouped_partials_problem(groups, nblk, H, device, seed, extra_rows=2):
+    """the exact family of partials_problem per expert: partials [groups * nblk + extra_rows, H] f32 expert-major (expert g + 1's
+    blocks follow expert g's; NaN in the rows past the last expert's) -> (p, [before_g], [q_g])"""
+    ps = [partials_problem(nblk, H, device, seed + 7919 * g) for g in range(groups)]
+    p = torch.full((groups * nblk + extra_rows, H), float("nan"), dtype=F32, device=device)
+    for g, (pg, _, _) in enumerate(ps):
+        p[g * nblk:(g + 1) * nblk] = pg
+    return p, [b for _, b, _ in ps], [q for _, _, q in ps]
+
+
+def check_grouped_partials(tag, p, befores, qs, nblk, accumulate, outs, dtype):
+    """outs[g] == the ONE rounding of the fp64 sum of expert g's nblk blocks (+ what it held), bitwise"""
+    for g, out in enumerate(outs):
+        want = rne(partials_reference(p[g * nblk:(g + 1) * nblk], qs[g], befores[g] if accumulate else None), dtype)
+        check_exact(f"{tag} expert {g}", out, want.to(out.device))
