@@ -66,7 +66,7 @@ int mm_set_option(const char* name, int value);
  * Also the read-only "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged
  * kernel (also the fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10
  * the 4-wave 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the
- * decode fusions), 30 the fp32 kernel */
+ * decode fusions), 22 gemv_stream on MXFP8 weights (the mm_decode_*_w8 entry points), 30 the fp32 kernel */
 int mm_get_option(const char* name, int* value);
 /* What a GEMM call with these facts would do, under the current switches: host only, launches nothing, needs no device when ncu
  * is given, and leaves "gemm_last_kernel" alone.  It is the function the launcher itself runs (csrc/mm_gemm_plan.h).
@@ -346,6 +346,31 @@ int mm_decode_qkv_rope_append(int dtype, int M, int Hq, int Hkv, int D, int K, c
                               int64_t dstride, const void* in_norm_w, float eps, void* stream);
 int mm_decode_linear(int dtype, int M, int N, int K, const void* X, int ldx, const void* W, int ldw, const void* bias,
                      const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream);
+
+/* ---- weight-only MXFP8 for the decode step (opt-in).  A row-major bf16 matrix W[N,K], K % 32 == 0, is stored as OCP e4m3fn elements
+ * with one power-of-two scale byte (E8M0: 2^(byte - 127)) per block of 32 consecutive k of a row: 1 + 1/32 byte per weight.
+ * Per block: amax = largest |w|; e = the SMALLEST integer with amax * 2^-e <= 448, i.e. e0 = floor(log2 amax) - 8, or e0 + 1 when
+ * amax * 2^-e0 > 448 (the OCP "floor" rule would saturate the block's largest element there); scale byte = clamp(e + 127, 27, 254),
+ * 127 for an all-zero block; element = e4m3fn(clamp(w * 2^-e, -448, 448)), round to nearest even, sign of zero kept.  The lower
+ * clamp keeps every dequantised value a normal bf16, and an e4m3 value times a power of two IS a bf16 number: the dequantised matrix W'
+ * is an ordinary bf16 tensor, exactly.  NaN / Inf in W are outside the contract (the result is unspecified).
+ * The layout of the packed buffer is private to the library (csrc/mm_mxfp8.h) and depends on (N, K) only.
+ * mm_mxfp8_bytes:   bytes of the packed buffer of W[N,K] (elements + scales, a multiple of 16); negative (MM_ERR_UNSUPPORTED) if K % 32.
+ * mm_quant_mxfp8:   W (row stride ldw >= K elements, ldw % 8 == 0, 16-byte aligned) -> packed (16-byte aligned, mm_mxfp8_bytes); one pass.
+ * mm_dequant_mxfp8: packed -> Wd = W' (bf16, row stride ldd).
+ * mm_decode_*_w8:   the three decode fusions above with `packed` in place of (W, ldw) -- for mm_decode_gateup_swiglu_w8 the fused
+ *                   [2I,K] gate|up matrix quantised as one matrix.  Bit-identical to the bf16 entry point run on W' (every MFMA sees
+ *                   the same K elements).  MM_ERR_UNSUPPORTED before any launch if K % 32 or x does not fit the LDS stage.         */
+int64_t mm_mxfp8_bytes(int N, int K);
+int mm_quant_mxfp8(const void* W, int ldw, int N, int K, void* packed, void* stream);
+int mm_dequant_mxfp8(const void* packed, int N, int K, void* Wd, int ldd, void* stream);
+int mm_decode_gateup_swiglu_w8(int dtype, int M, int I, int K, const void* X, int ldx, const void* packed, void* ACT, int ldact,
+                               const void* in_norm_w, float eps, void* stream);
+int mm_decode_qkv_rope_append_w8(int dtype, int M, int Hq, int Hkv, int D, int K, const void* X, int ldx, const void* packed,
+                                 const void* bias, void* QKV, int ldqkv, const float* cos_t, const float* sin_t, void* kdst, void* vdst,
+                                 int64_t dstride, const void* in_norm_w, float eps, void* stream);
+int mm_decode_linear_w8(int dtype, int M, int N, int K, const void* X, int ldx, const void* packed, const void* bias,
+                        const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream);
 
 /* KV-cache decode step: ONE query token per sequence over the cached keys (reference model.py:595-602 calling the LLM with
  * past_key_values; HF:llama:217-281 with q_len = 1).  q [B,Hq,D] (strides q_sb,q_sh; D contiguous), k/v [B,Skv,Hkv,D] as

@@ -28,7 +28,7 @@ def parse_header(path: str = HEADER):
     src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
     src = re.sub(r"//[^\n]*", " ", src)
     protos = {}
-    for m in re.finditer(r"\b(int|const\s+char\s*\*)\s+(mm_\w+)\s*\(([^)]*)\)\s*;", src):
+    for m in re.finditer(r"\b(int64_t|int|const\s+char\s*\*)\s+(mm_\w+)\s*\(([^)]*)\)\s*;", src):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         argtypes = []
         if args and args != "void":
@@ -44,7 +44,7 @@ def parse_header(path: str = HEADER):
                     argtypes.append(ctypes.c_int)
                 else:
                     raise ValueError(f"unhandled C type in header: {a!r} ({name})")
-        protos[name] = (ctypes.c_char_p if "char" in ret else ctypes.c_int, argtypes)
+        protos[name] = (ctypes.c_char_p if "char" in ret else ctypes.c_int64 if ret == "int64_t" else ctypes.c_int, argtypes)
     return protos
 
 

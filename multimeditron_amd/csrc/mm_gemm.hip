@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "mm_common.h"
+#include "mm_mxfp8.h"          // the weight-only MXFP8 storage gemv_stream_kernel<.., W8> streams
 #include "mm_gemm_plan.h"      // which kernel runs, on what grid and with which schedule: the host half below launches its plan
 
 namespace {
@@ -1868,6 +1869,7 @@ struct SkinnyArgs {
   bf16* kdst; bf16* vdst; int64_t dstride;      // cache row of this step for sequence 0; elements between sequences
   const bf16* norm_w; float eps;                // NORM: weight / eps of the RMSNorm in front of the projection (nullptr: none)
   int epi;                                      // gemv_stream_kernel MODE 0: MM_EPI_* activation / accumulate flags
+  const unsigned char* Bs; int sper;            // W8: B = the e4m3 elements, Bs = their scales, both in runs of sper step slots (mm_mxfp8.h)
 };
 
 // ------------------------------------------------------------------------------------------------------
@@ -1886,6 +1888,13 @@ struct SkinnyArgs {
 //     a device-scope ticket plus a dependent round trip, ~6 us per launch, twice per layer).
 // MODE 0 plain epilogue (bias, activation, residual, accumulate; any N), 1 gate|up + SwiGLU, 2 q|k|v + RoPE + KV-cache append.
 // NT: non-temporal policy on the W loads (read once).
+// W8: W is the MXFP8 copy of mm_quant_mxfp8 (mm_mxfp8.h) -- only the W stream differs.  The ring is 16 slots of 16 bytes = 32 steps (the
+//     same 16 KiB and 64 registers per wave; the storage interleaves two steps so that a load stays 16 bytes per lane, 64-byte row
+//     segments as in the bf16 kernel) plus 8 dwords of scales (a dword = 4 consecutive steps of the wave's share); a step's 8 bytes become the bf16x8
+//     fragment in registers right in front of its MFMA (4 v_cvt_scalef32_pk_bf16_fp8 with the block's power of two as the scale:
+//     exact), so every MFMA multiplies the very K elements, in the very order, of the bf16 kernel run on the dequantised matrix: same
+//     bits.  (A ring round is 32 steps instead of 16: a block may end with up to 16 more all-zero MFMAs, which add +0 to an accumulator
+//     that is never -0.)
 // ------------------------------------------------------------------------------------------------------
 template <int CH, int R>
 __device__ __forceinline__ void rmsnorm_rows_to_lds(const bf16* x, int ldx, const bf16* w, int H, float eps, char* xs, int nrows, float* red) {
@@ -1947,7 +1956,7 @@ __device__ __forceinline__ void rmsnorm_rows_to_lds(const bf16* x, int ldx, cons
   }
 }
 
-template <int MODE, bool NORM, bool NT>
+template <int MODE, bool NORM, bool NT, bool W8 = false>
 __global__ __launch_bounds__(512, 4) void gemv_stream_kernel(SkinnyArgs g, int nblocks) {      // 4 waves per SIMD (2 workgroups per CU): <= 128 VGPRs
   extern __shared__ __attribute__((aligned(16))) char xs[];          // x, M rows of K bf16 (normalised when NORM)
   __shared__ float red[2][8][4][64];
@@ -1967,40 +1976,61 @@ __global__ __launch_bounds__(512, 4) void gemv_stream_kernel(SkinnyArgs g, int n
       wr = blk * 16 + row;
       if (wr >= g.N) wr = -1;
     }
+    if constexpr (W8) return wr < 0 ? 0xFFFFFFFFu : (unsigned)wr;           // the row itself: wbase_of / sbase_of below
     return wr < 0 ? 0xFFFFFFFFu : (unsigned)wr * (unsigned)g.ldb * 2u;
   };
-  auto rw = make_rsrc(g.B, (int64_t)(MODE == 1 ? 2 * g.I : g.N) * g.ldb * 2);
-  constexpr int U = 16;
+  const int64_t wrows = MODE == 1 ? 2 * g.I : g.N;
+  auto rw = make_rsrc(g.B, W8 ? wrows * 8 * g.sper * 32 : wrows * g.ldb * 2);
+  auto rs = make_rsrc(g.Bs, W8 ? wrows * 8 * g.sper : 0);                   // W8: the scale runs
+  constexpr int U = W8 ? 32 : 16;
   constexpr int WPOL = NT ? 2 : 0;
   const int nks = (g.K + 31) / 32;
   const int per = (nks + 7) / 8;                            // K-steps per wave and row block (the wave's share of K) ...
   const int ipb = (per + U - 1) / U;                        // ... walked in ipb rounds of the U-slot ring (steps beyond `per` load nothing)
   const int ks0 = w * per, ks1 = min(nks, ks0 + per);
-  u32x4 fw[U];
+  // W8: the lane's constant part of its element offsets (the (row, wave) run of step slots, its 16 bytes of a slot pair) and of its scale
+  // run, once per row block -- a step then adds 32 i / i (no multiply in the ring)
+  auto wbase_of = [&](unsigned wr) -> unsigned { return wr == 0xFFFFFFFFu ? wr : (wr * 8u + (unsigned)w) * (unsigned)g.sper * 32u + (unsigned)kc * 16u; };
+  auto sbase_of = [&](unsigned wr) -> unsigned { return wr == 0xFFFFFFFFu ? wr : (wr * 8u + (unsigned)w) * (unsigned)g.sper; };
+  u32x4 fw[W8 ? 1 : U];
+  u32x4 fq[W8 ? U / 2 : 1];                                 // W8: the ring of e4m3 bytes, a slot = the lane's 8 k of TWO steps (mm_mxfp8.h) ...
+  unsigned fs[W8 ? U / 4 : 1];                              // ... and the scales of steps 4 s .. 4 s + 3 of the round
   // PERSISTENT: the workgroup walks row blocks blockIdx.x, + gridDim.x, ...; x is staged (and normalised) once, the ring runs across
   // block boundaries (the slot a step frees is refilled with the same step of the NEXT block when this block has no further round)
-  auto issue = [&](int u, unsigned wrow, int i) {            // i = step inside the block
+  auto issue = [&](int u, unsigned wrow, int i, unsigned srow = 0u) {      // i = step inside the block; W8: wrow = wbase_of, srow = sbase_of
     const int ks = ks0 + i;
     const int k = ks * 32 + kc * 8;
-    const bool ok = i < per && ks < ks1 && k < g.K && wrow != 0xFFFFFFFFu;
-    fw[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? wrow + (unsigned)k * 2u : 0xFFFFFFFFu, 0, WPOL);
+    if constexpr (W8) {
+      if (u & 1) {                                           // the 2nd step of a slot has been consumed (or: first fill): steps i-1, i
+        const bool ok = i - 1 < per && ks - 1 < ks1 && wrow != 0xFFFFFFFFu;  // (a pair's 2nd step past the wave's share: zero padding, like its x)
+        fq[u >> 1] = __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? wrow + (unsigned)(i - 1) * 32u : 0xFFFFFFFFu, 0, WPOL);
+      }
+      if ((u & 3) == 3) {                                    // the 4th step of a scale dword has been consumed (or: first fill): steps i-3 .. i
+        const bool oks = i - 3 < per && ks - 3 < ks1 && wrow != 0xFFFFFFFFu;     // i % 4 == 3: an aligned dword of the wave's run (bytes past `per`: padding)
+        fs[u >> 2] = __builtin_amdgcn_raw_buffer_load_b32(rs, oks ? srow + (unsigned)(i - 3) : 0xFFFFFFFFu, 0, 0);
+      }
+    } else {
+      const bool ok = i < per && ks < ks1 && k < g.K && wrow != 0xFFFFFFFFu;
+      fw[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? wrow + (unsigned)k * 2u : 0xFFFFFFFFu, 0, WPOL);
+    }
   };
   int blk = blockIdx.x;
-  unsigned wrow = wrow_of(blk);
+  unsigned wrow = wrow_of(blk), srow = 0u;
+  if constexpr (W8) { srow = sbase_of(wrow); wrow = wbase_of(wrow); }
   // ---- x -> LDS.  Plain: requested first (L2 hits), stored once the W ring has been requested behind it.  NORM: the rows pass
   // through registers (sum of squares); half of the ring is requested before, the other half after (the norm's own registers and
   // the whole ring together would not leave room for two workgroups per CU).
   const int xchunks = g.M * (g.K / 8);                      // 16-byte chunks of x (K % 8 == 0: host)
   if constexpr (NORM) {
 #pragma unroll
-    for (int u = 0; u < U / 2; ++u) issue(u, wrow, u);
+    for (int u = 0; u < U / 2; ++u) issue(u, wrow, u, srow);
     if (g.K <= 2048) rmsnorm_rows_to_lds<1, 4>(g.A, g.lda, g.norm_w, g.K, g.eps, xs, g.M, nred);
     else if (g.K <= 4096) rmsnorm_rows_to_lds<2, 4>(g.A, g.lda, g.norm_w, g.K, g.eps, xs, g.M, nred);
     else rmsnorm_rows_to_lds<4, 2>(g.A, g.lda, g.norm_w, g.K, g.eps, xs, g.M, nred);
 #pragma unroll
-    for (int u = U / 2; u < U; ++u) issue(u, wrow, u);
+    for (int u = U / 2; u < U; ++u) issue(u, wrow, u, srow);
   } else {
-    constexpr int XU = 8;                                   // chunks per thread and pass
+    constexpr int XU = W8 ? 4 : 8;                          // chunks per thread and pass (W8: the ring's scales and the conversion need the room)
     const int cpr = g.K / 8;
     bool first = true;
     for (int base = 0; base < xchunks; base += 512 * XU) {
@@ -2013,7 +2043,7 @@ __global__ __launch_bounds__(512, 4) void gemv_stream_kernel(SkinnyArgs g, int n
       }
       if (first) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) issue(u, wrow, u);
+        for (int u = 0; u < U; ++u) issue(u, wrow, u, srow);
         first = false;
       }
 #pragma unroll
@@ -2026,9 +2056,10 @@ __global__ __launch_bounds__(512, 4) void gemv_stream_kernel(SkinnyArgs g, int n
   __syncthreads();
   const char* xrow = xs + (int64_t)row * g.K * 2 + kc * 16;
   const bool xlane = row < g.M;
-  const int m = l & 15, gq = l >> 4;                        // epilogue (wave 0): m = activation row, local W rows 4 * gq + r
+  const int m_ = l & 15, gq = l >> 4;                       // epilogue (wave 0): m = activation row, local W rows 4 * gq + r
   for (int j = 0; blk < nblocks; ++j, blk += gridDim.x) {
-    const unsigned wnext = wrow_of(blk + gridDim.x);
+    unsigned wnext = wrow_of(blk + gridDim.x), snext = 0u;
+    if constexpr (W8) { snext = sbase_of(wnext); wnext = wbase_of(wnext); }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int it = 0; it < ipb; ++it) {
       const bool more = it + 1 < ipb;                       // another round of this block, or on to the next block
@@ -2037,16 +2068,23 @@ __global__ __launch_bounds__(512, 4) void gemv_stream_kernel(SkinnyArgs g, int n
         const int i = it * U + u, kk = ks0 + i;
         u32x4 fx = {0u, 0u, 0u, 0u};
         if (xlane && i < per && kk < ks1 && kk * 32 + kc * 8 < g.K) fx = *(const u32x4*)(xrow + kk * 64);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fw[u]), __builtin_bit_cast(bf16x8, fx), acc, 0, 0, 0);
-        issue(u, more ? wrow : wnext, more ? i + U : u);
+        bf16x8 wf;
+        if constexpr (W8) wf = mx8_to_bf16x8(u32x2{fq[u >> 1][2 * (u & 1)], fq[u >> 1][2 * (u & 1) + 1]}, mx8_scale((fs[u >> 2] >> (8 * (u & 3))) & 0xFFu));
+        else wf = __builtin_bit_cast(bf16x8, fw[u]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(bf16x8, fx), acc, 0, 0, 0);
+        issue(u, more ? wrow : wnext, more ? i + U : u, more ? srow : snext);
       }
     }
     wrow = wnext;
+    srow = snext;
     float (*rb)[4][64] = red[j & 1];
 #pragma unroll
     for (int r = 0; r < 4; ++r) rb[w][r][l] = acc[r];
     __syncthreads();                 // red[j & 1] is rewritten two blocks later: wave 0 has passed the barrier in between
     if (w != 0) continue;
+    int m = m_;
+    if constexpr (W8) asm volatile("" : "+v"(m));            // the epilogue's row pointers are rebuilt per block: hoisted out of the loop they
+                                                             // would sit beside the ring and its scales and spill (once per block is nothing)
     if constexpr (MODE == 0) {
       if (m >= g.M) continue;
       const int n = blk * 16 + 4 * gq;
@@ -2536,12 +2574,12 @@ static int skinny_common(int dtype, int M, int K, const void* X, int ldx, const 
 
 // gemv_stream_kernel on `grid` persistent workgroups with the x rows in `lds` bytes (gemv_grid); a launch that cannot get its LDS
 // reports MM_ERR_UNSUPPORTED (the caller then takes the tiled decode step)
-template <int MODE>
+template <int MODE, bool W8 = false>
 static int gemv_stream_go(const SkinnyArgs& g, unsigned nblk, unsigned grid, size_t lds, hipStream_t s) {
-  g_last_kernel = 21;
+  g_last_kernel = W8 ? 22 : 21;
 #define MM_GEMV_LAUNCH(NORM, NT)                                                                              \
   do {                                                                                                        \
-    auto kfn = gemv_stream_kernel<MODE, NORM, NT>;                                                            \
+    auto kfn = gemv_stream_kernel<MODE, NORM, NT, W8>;                                                        \
     if (hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
       (void)hipGetLastError();                                                                                \
       return MM_ERR_UNSUPPORTED;                                                                              \
@@ -2555,16 +2593,26 @@ static int gemv_stream_go(const SkinnyArgs& g, unsigned nblk, unsigned grid, siz
   return MM_OK;
 }
 
+// `packed` (the _w8 entry points): W is the MXFP8 copy mm_quant_mxfp8 made of the [wrows, K] matrix, streamed by gemv_stream_kernel<.., W8>
 template <int MODE>
-static int gemv_stream_launch(const SkinnyArgs& g, unsigned nblk, hipStream_t s) {
+static int gemv_stream_launch(SkinnyArgs& g, unsigned nblk, hipStream_t s, bool packed, int64_t wrows) {
   if (!gemv_stream_fits(g.M, g.K)) return MM_ERR_UNSUPPORTED;
   if (g.norm_w && (g.K > 8192 || !mm_aligned16(g.norm_w))) return MM_ERR_UNSUPPORTED;
+  if (packed) {
+    const Mx8Layout L = mx8_layout((int)wrows, g.K);
+    if (wrows * 8 * L.sper * 32 >= 0xFFFFFFFFll) return MM_ERR_UNSUPPORTED;
+    g.Bs = (const unsigned char*)g.B + L.scale_off;
+    g.sper = L.sper;
+  }
   const GemvGrid gg = gemv_grid(g.M, g.K, nblk, g_opt, device_cus());
+  if (packed) return gemv_stream_go<MODE, true>(g, nblk, gg.grid, (size_t)gg.lds, s);
   return gemv_stream_go<MODE>(g, nblk, gg.grid, (size_t)gg.lds, s);
 }
 
-extern "C" int mm_decode_gateup_swiglu(int dtype, int M, int I, int K, const void* X, int ldx, const void* Wgu, int ldw, void* ACT, int ldact,
-                                       const void* in_norm_w, float eps, void* stream) {
+// the three fusions; packed: Wgu / W is an MXFP8 buffer (its rows are K bytes apart)
+static int decode_gateup_swiglu(bool packed, int dtype, int M, int I, int K, const void* X, int ldx, const void* Wgu, int ldw, void* ACT, int ldact,
+                                const void* in_norm_w, float eps, void* stream) {
+  if (packed && (K <= 0 || K % 32)) return MM_ERR_UNSUPPORTED;
   int rc = skinny_common(dtype, M, K, X, ldx, Wgu, ldw, (int64_t)2 * I);
   if (rc != MM_OK) return rc;
   if (I <= 0 || !ACT) return MM_ERR_ARG;
@@ -2572,12 +2620,21 @@ extern "C" int mm_decode_gateup_swiglu(int dtype, int M, int I, int K, const voi
   SkinnyArgs g{};
   g.M = M; g.N = 2 * I; g.K = K; g.A = (const bf16*)X; g.lda = ldx; g.B = (const bf16*)Wgu; g.ldb = ldw; g.C = (bf16*)ACT; g.ldc = ldact; g.I = I;
   g.norm_w = (const bf16*)in_norm_w; g.eps = eps;
-  return gemv_stream_launch<1>(g, (unsigned)((I + 7) / 8), (hipStream_t)stream);
+  return gemv_stream_launch<1>(g, (unsigned)((I + 7) / 8), (hipStream_t)stream, packed, (int64_t)2 * I);
+}
+extern "C" int mm_decode_gateup_swiglu(int dtype, int M, int I, int K, const void* X, int ldx, const void* Wgu, int ldw, void* ACT, int ldact,
+                                       const void* in_norm_w, float eps, void* stream) {
+  return decode_gateup_swiglu(false, dtype, M, I, K, X, ldx, Wgu, ldw, ACT, ldact, in_norm_w, eps, stream);
+}
+extern "C" int mm_decode_gateup_swiglu_w8(int dtype, int M, int I, int K, const void* X, int ldx, const void* packed, void* ACT, int ldact,
+                                          const void* in_norm_w, float eps, void* stream) {
+  return decode_gateup_swiglu(true, dtype, M, I, K, X, ldx, packed, K, ACT, ldact, in_norm_w, eps, stream);
 }
 
-extern "C" int mm_decode_qkv_rope_append(int dtype, int M, int Hq, int Hkv, int D, int K, const void* X, int ldx, const void* W, int ldw,
-                                         const void* bias, void* QKV, int ldqkv, const float* cos_t, const float* sin_t, void* kdst, void* vdst,
-                                         int64_t dstride, const void* in_norm_w, float eps, void* stream) {
+static int decode_qkv_rope_append(bool packed, int dtype, int M, int Hq, int Hkv, int D, int K, const void* X, int ldx, const void* W, int ldw,
+                                  const void* bias, void* QKV, int ldqkv, const float* cos_t, const float* sin_t, void* kdst, void* vdst,
+                                  int64_t dstride, const void* in_norm_w, float eps, void* stream) {
+  if (packed && (K <= 0 || K % 32)) return MM_ERR_UNSUPPORTED;
   if (Hq <= 0 || Hkv <= 0) return MM_ERR_ARG;
   const int N = (Hq + 2 * Hkv) * D;
   int rc = skinny_common(dtype, M, K, X, ldx, W, ldw, N);
@@ -2591,11 +2648,24 @@ extern "C" int mm_decode_qkv_rope_append(int dtype, int M, int Hq, int Hkv, int 
   g.M = M; g.N = N; g.K = K; g.A = (const bf16*)X; g.lda = ldx; g.B = (const bf16*)W; g.ldb = ldw; g.C = (bf16*)QKV; g.ldc = ldqkv;
   g.bias = (const bf16*)bias; g.Hq = Hq; g.Hkv = Hkv; g.cos_t = cos_t; g.sin_t = sin_t; g.kdst = (bf16*)kdst; g.vdst = (bf16*)vdst; g.dstride = dstride;
   g.norm_w = (const bf16*)in_norm_w; g.eps = eps;
-  return gemv_stream_launch<2>(g, (unsigned)(N / 16), (hipStream_t)stream);
+  return gemv_stream_launch<2>(g, (unsigned)(N / 16), (hipStream_t)stream, packed, N);
+}
+extern "C" int mm_decode_qkv_rope_append(int dtype, int M, int Hq, int Hkv, int D, int K, const void* X, int ldx, const void* W, int ldw,
+                                         const void* bias, void* QKV, int ldqkv, const float* cos_t, const float* sin_t, void* kdst, void* vdst,
+                                         int64_t dstride, const void* in_norm_w, float eps, void* stream) {
+  return decode_qkv_rope_append(false, dtype, M, Hq, Hkv, D, K, X, ldx, W, ldw, bias, QKV, ldqkv, cos_t, sin_t, kdst, vdst, dstride, in_norm_w, eps,
+                                stream);
+}
+extern "C" int mm_decode_qkv_rope_append_w8(int dtype, int M, int Hq, int Hkv, int D, int K, const void* X, int ldx, const void* packed,
+                                            const void* bias, void* QKV, int ldqkv, const float* cos_t, const float* sin_t, void* kdst,
+                                            void* vdst, int64_t dstride, const void* in_norm_w, float eps, void* stream) {
+  return decode_qkv_rope_append(true, dtype, M, Hq, Hkv, D, K, X, ldx, packed, K, bias, QKV, ldqkv, cos_t, sin_t, kdst, vdst, dstride, in_norm_w,
+                                eps, stream);
 }
 
-extern "C" int mm_decode_linear(int dtype, int M, int N, int K, const void* X, int ldx, const void* W, int ldw, const void* bias,
-                                const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream) {
+static int decode_linear(bool packed, int dtype, int M, int N, int K, const void* X, int ldx, const void* W, int ldw, const void* bias,
+                         const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream) {
+  if (packed && (K <= 0 || K % 32)) return MM_ERR_UNSUPPORTED;
   int rc = skinny_common(dtype, M, K, X, ldx, W, ldw, N);
   if (rc != MM_OK) return rc;
   if (N <= 0 || !C) return MM_ERR_ARG;
@@ -2603,7 +2673,15 @@ extern "C" int mm_decode_linear(int dtype, int M, int N, int K, const void* X, i
   SkinnyArgs g{};
   g.M = M; g.N = N; g.K = K; g.A = (const bf16*)X; g.lda = ldx; g.B = (const bf16*)W; g.ldb = ldw; g.C = (bf16*)C; g.ldc = ldc;
   g.bias = (const bf16*)bias; g.residual = (const bf16*)residual; g.ldr = ldr; g.norm_w = (const bf16*)in_norm_w; g.eps = eps;
-  return gemv_stream_launch<0>(g, (unsigned)((N + 15) / 16), (hipStream_t)stream);
+  return gemv_stream_launch<0>(g, (unsigned)((N + 15) / 16), (hipStream_t)stream, packed, N);
+}
+extern "C" int mm_decode_linear(int dtype, int M, int N, int K, const void* X, int ldx, const void* W, int ldw, const void* bias,
+                                const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream) {
+  return decode_linear(false, dtype, M, N, K, X, ldx, W, ldw, bias, residual, ldr, C, ldc, in_norm_w, eps, stream);
+}
+extern "C" int mm_decode_linear_w8(int dtype, int M, int N, int K, const void* X, int ldx, const void* packed, const void* bias,
+                                   const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream) {
+  return decode_linear(true, dtype, M, N, K, X, ldx, packed, K, bias, residual, ldr, C, ldc, in_norm_w, eps, stream);
 }
 
 // ---- the launcher: a stand-alone call (t == nullptr, groups == 0) or `groups` equal-shaped problems in one grid (the MoE image

@@ -176,6 +176,67 @@ def decode_linear(x2d, w, bias=None, residual=None, norm_w=None, eps=0.0, ldc_pa
     return buf[:, :N] if ld != N else buf
 
 
+# ---- weight-only MXFP8 copies for the decode step (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 k) ---------------
+def mxfp8_bytes(N, K):
+    n = _lib.lib().mm_mxfp8_bytes(int(N), int(K))
+    if n < 0:
+        raise _lib.MMHipError(f"mm_mxfp8_bytes({N}, {K}) failed: {n} (K must be a multiple of 32)")
+    return n
+
+
+def quant_mxfp8(w, out=None):
+    """packed uint8 [mxfp8_bytes(N, K)] of a bf16 matrix w [N, K] (row stride w.stride(0)); the layout is the library's own."""
+    assert w.dim() == 2 and w.stride(1) == 1
+    if w.dtype != torch.bfloat16:
+        raise TypeError(f"quant_mxfp8 takes a bf16 matrix, got {w.dtype}")
+    N, Kd = w.shape
+    if out is None:
+        out = torch.empty((mxfp8_bytes(N, Kd),), dtype=torch.uint8, device=w.device)
+    call("mm_quant_mxfp8", _p(w), w.stride(0), N, Kd, _p(out), _stream())
+    return out
+
+
+def dequant_mxfp8(packed, N, K, out=None):
+    """The bf16 matrix W' [N, K] a packed buffer stands for (exact: e4m3 times a power of two is a bf16 number)."""
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=packed.device)
+    assert out.stride(1) == 1
+    call("mm_dequant_mxfp8", _p(packed), N, K, _p(out), out.stride(0), _stream())
+    return out
+
+
+def decode_gateup_swiglu_w8(x2d, packed, I, norm_w=None, eps=0.0, out=None):
+    """decode_gateup_swiglu on the MXFP8 copy of the fused [2I, K] gate|up matrix: the bits of the bf16 call on dequant_mxfp8(packed)."""
+    M, K = x2d.shape
+    act = torch.empty((M, I), dtype=x2d.dtype, device=x2d.device) if out is None else out
+    call("mm_decode_gateup_swiglu_w8", dt(x2d), M, I, K, _p(x2d), x2d.stride(0), _p(packed), _p(act), act.stride(0), _p(norm_w), float(eps),
+         _stream())
+    return act
+
+
+def decode_qkv_rope_append_w8(x2d, packed, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w=None, eps=0.0, out=None):
+    """decode_qkv_rope_append on the MXFP8 copy of the fused q|k|v matrix."""
+    M, K = x2d.shape
+    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
+    qkv = torch.empty((M, (Hq + 2 * Hkv) * D), dtype=x2d.dtype, device=x2d.device) if out is None else out
+    call("mm_decode_qkv_rope_append_w8", dt(x2d), M, Hq, Hkv, D, K, _p(x2d), x2d.stride(0), _p(packed), _p(bias), _p(qkv), qkv.stride(0),
+         _p(cos), _p(sin), _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0), _p(norm_w), float(eps), _stream())
+    return qkv
+
+
+def decode_linear_w8(x2d, packed, N, bias=None, residual=None, norm_w=None, eps=0.0, ldc_pad=False, out=None):
+    """decode_linear on the MXFP8 copy of w [N, K]."""
+    M, K = x2d.shape
+    if out is None:
+        ld = (N + 63) // 64 * 64 if ldc_pad else N
+        buf = torch.empty((M, ld), dtype=x2d.dtype, device=x2d.device)
+    else:
+        buf, ld = out, out.stride(0)
+    call("mm_decode_linear_w8", dt(x2d), M, N, K, _p(x2d), x2d.stride(0), _p(packed), _p(bias), _p(residual),
+         residual.stride(0) if residual is not None else 0, _p(buf), ld, _p(norm_w), float(eps), _stream())
+    return buf[:, :N] if buf.shape[1] != N else buf
+
+
 def decode_fusions():      # A/B switch (tools/decode_bench.py): MM_DECODE_FUSED=0 -> the separate launches
     return _os.environ.get("MM_DECODE_FUSED", "1") != "0"
 

@@ -196,38 +196,52 @@ class DecoderLayer(nn.Module):
         return getattr(self, self._norm_names[0]), getattr(self, self._norm_names[1])
 
     @torch.no_grad()
-    def decode_step(self, x, cos, sin, key_mask, B, cache):
+    def decode_step(self, x, cos, sin, key_mask, B, cache, w8=None):
         """One new token per sequence (generate's decode loop, reference model.py:595-602): the four linears take the
         weight-streaming GEMM (M <= 16), RoPE and the cache append are one pass, attention is the split-K stream over the
         cache.  Same arithmetic and rounding points as forward().  (Folding RMSNorm / SwiGLU into the GEMM's x operand was
         measured SLOWER: every workgroup redoes the transform on all 64 lanes and the kernel turns VALU-bound, 43 vs 27 us
-        and 57 vs 25 us per launch, so they stay separate launches.)"""
+        and 57 vs 25 us per launch, so they stay separate launches.)
+        w8: this layer's MXFP8 copies (CausalLM.quantize_decode_weights) -- the four linears stream those instead."""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         n1, n2 = self.norms()
         h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
-        qkv = K.linear_fwd(h, a._wqkv.tensor(), bias=a._bqkv.tensor() if a._bqkv is not None else None)
+        bqkv = a._bqkv.tensor() if a._bqkv is not None else None
+
+        def lin(name, t, w, **kw):
+            return K.linear_fwd(t, w, **kw) if w8 is None else K.decode_linear_w8(t, *w8[name], **kw)
+
+        qkv = lin("qkv", h, a._wqkv.tensor(), bias=bqkv)
         if a.q_norm is not None:
             K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, cache.k, cache.v, cache.len)
         else:
             K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, cache.k, cache.v, cache.len)
         cache.len += 1
         o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
-        x = K.linear_fwd(o.view(B, Hq * D), a.o_proj.weight, residual=x)
+        x = lin("o", o.view(B, Hq * D), a.o_proj.weight, residual=x)
         h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
-        u = K.linear_fwd(h, m._wgu.tensor())
+        u = lin("gu", h, m._wgu.tensor())
         act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
-        return K.linear_fwd(act, m.down_proj.weight, residual=x)
+        return lin("down", act, m.down_proj.weight, residual=x)
 
     @torch.no_grad()
-    def decode_step_fused(self, x, cos, sin, key_mask, B, cache):
+    def decode_step_fused(self, x, cos, sin, key_mask, B, cache, w8=None):
         """The same decode step with the tiny launches folded into the weight-streaming GEMMs (round 3; csrc/mm_gemm.hip
         gemv_stream_kernel): input RMSNorm + q|k|v + RoPE + cache append, o_proj + residual, post-attention RMSNorm + gate|up +
         SwiGLU, down_proj + residual -- 6 launches with the two attention kernels, none of them a norm.  x = residual stream in
-        and out.  Same bits as decode_step."""
+        and out.  Same bits as decode_step.  w8: this layer's MXFP8 copies -- the same four launches on half the weight bytes."""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         n1, n2 = self.norms()
+        if w8 is not None:
+            qkv = K.decode_qkv_rope_append_w8(x, w8["qkv"][0], a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
+                                              cache.k, cache.v, cache.len, norm_w=n1.weight, eps=n1.eps)
+            cache.len += 1
+            o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
+            x = K.decode_linear_w8(o.view(B, Hq * D), *w8["o"], residual=x)
+            act = K.decode_gateup_swiglu_w8(x, w8["gu"][0], m.I, norm_w=n2.weight, eps=n2.eps)
+            return K.decode_linear_w8(act, *w8["down"], residual=x)
         qkv = K.decode_qkv_rope_append(x, a._wqkv.tensor(), a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
                                        cache.k, cache.v, cache.len, norm_w=n1.weight, eps=n1.eps)
         cache.len += 1
@@ -247,13 +261,13 @@ class DecoderLayer(nn.Module):
                 and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
                 and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
 
-    def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None):
+    def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None, w8=None):
         """rows (functional.LossRows, LAST layer of a training forward only): nothing after this layer's attention reads the
         rows that carry no label -- their hidden states feed no later layer and no loss term -- so o_proj, the post-attention norm
         and the MLP run on the labelled rows alone and the layer returns [rows.n, H].  (Keys and values come from every row, so
         attention itself is computed in full.)  Same loss, same gradients."""
         if self.can_decode_step(x, B, S, cache):
-            return self.decode_step(x, cos, sin, key_mask, B, cache)
+            return self.decode_step(x, cos, sin, key_mask, B, cache, w8=w8)
         a = self.self_attn
         n1, n2 = self.norms()
         h, x = n1(x)
@@ -334,6 +348,7 @@ class CausalLM(nn.Module):
         if cfg.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight
         self._inv_freq = None
+        self._decode_w8 = None      # quantize_decode_weights(): plain tensors beside the modules, neither parameters nor buffers
 
     # -- reference surface -------------------------------------------------------------------------
     @property
@@ -365,6 +380,7 @@ class CausalLM(nn.Module):
                 nw[old:].normal_(mean=0.0, std=std)
             return nn.Parameter(nw, requires_grad=w.requires_grad)
 
+        self.drop_decode_weights()
         tied = self.lm_head.weight is emb.weight
         emb.weight = grow(emb.weight)
         emb.num_embeddings = new_num_tokens
@@ -372,6 +388,72 @@ class CausalLM(nn.Module):
         self.lm_head.out_features = new_num_tokens
         self.config.vocab_size = new_num_tokens
         return emb
+
+    # -- weight-only 8-bit copies for the decode step (opt-in) -------------------------------------------
+    @torch.no_grad()
+    def quantize_decode_weights(self, fmt: str = "mxfp8", lm_head: bool = True):
+        """Build MXFP8 copies (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 k; 1 + 1/32 byte per weight) of the
+        matrices a decode step streams: per layer the fused q|k|v, o_proj, the fused gate|up (Apertus: up_proj) and down_proj, and
+        (lm_head=True) the matrix lm_head reads at decode, a tied embedding included.  forward(..., decode_weights="mxfp8") then
+        reads them on decode steps; prefill and training always read the bf16 weights.  The bf16 weights stay: the copies cost
+        about half their size again in HBM (~8.3 GB on the 8B model).
+
+        The copies are plain tensors held beside the modules: absent from state_dict, checkpoints and FlatParams.  They are a
+        SNAPSHOT of the weights at the time of the call.  train(True), load_state_dict / from_pretrained,
+        resize_token_embeddings and .to() drop it; nothing else does -- the HIP optimiser writes parameters through raw pointers and
+        does not bump `_version`, so a change of the weights cannot be detected: after any other update, call this again (or
+        drop_decode_weights())."""
+        if fmt != "mxfp8":
+            raise ValueError(f"decode weight format {fmt!r}: only 'mxfp8' is supported")
+        if self.dtype != torch.bfloat16:
+            raise ValueError(f"MXFP8 decode weights need a bf16 model, this one is {self.dtype}")
+
+        def pack(w):
+            if w.shape[1] % 32:
+                raise ValueError(f"MXFP8 decode weights need in_features % 32 == 0, got a [{w.shape[0]}, {w.shape[1]}] matrix")
+            return K.quant_mxfp8(w), w.shape[0]
+
+        layers = []
+        for layer in self.model.layers:
+            a, m = layer.self_attn, layer.mlp
+            layers.append({"qkv": pack(a._wqkv.tensor()), "o": pack(a.o_proj.weight.data), "gu": pack(m._wgu.tensor()),
+                           "down": pack(m.down_proj.weight.data)})
+        self._decode_w8 = {"fmt": fmt, "layers": layers, "lm_head": pack(self.lm_head.weight.data) if lm_head else None}
+        return self
+
+    def drop_decode_weights(self):
+        """Free the copies of quantize_decode_weights()."""
+        self._decode_w8 = None
+
+    def decode_weights_ok(self, B: int):
+        """None when a decode step of B sequences can stream the MXFP8 copies, else the reason it cannot (the opt-in never falls
+        back silently: generate raises it before the prefill)."""
+        if self.dtype != torch.bfloat16:
+            return f"model dtype is {self.dtype}, not bfloat16"
+        if B > 16:
+            return f"batch of {B} sequences (the weight-streaming decode step takes at most 16)"
+        widths = {self.config.hidden_size}
+        for layer in self.model.layers:
+            widths |= {layer.self_attn.Hq * layer.self_attn.D, layer.mlp.I}
+        for Kd in sorted(widths):
+            if Kd % 32:
+                return f"a weight matrix with {Kd} input features (not a multiple of 32)"
+            if not K.decode_fits(B, Kd):
+                return f"{B} activation rows of {Kd} features do not fit the decode kernel's LDS stage"
+        return None
+
+    def train(self, mode: bool = True):
+        if mode:
+            self.drop_decode_weights()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.drop_decode_weights()
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):         # .to(device / dtype): the copies would describe other tensors
+        self.drop_decode_weights()
+        return super()._apply(fn, *args, **kwargs)
 
     # -- compute --------------------------------------------------------------------------------------
     def _tables(self, position_ids):
@@ -385,9 +467,16 @@ class CausalLM(nn.Module):
                 for _ in range(c.num_hidden_layers)]
 
     def forward(self, input_ids=None, inputs_embeds=None, attention_mask=None, position_ids=None,
-                past_key_values=None, labels=None, use_cache=None, return_dict=True, logits_to_keep: int = 0, **kwargs):
+                past_key_values=None, labels=None, use_cache=None, return_dict=True, logits_to_keep: int = 0,
+                decode_weights: Optional[str] = None, **kwargs):
+        """decode_weights="mxfp8": a decode step (one new token per sequence over a cache, can_decode_step) streams the copies of
+        quantize_decode_weights() instead of the bf16 weights; anything else (prefill, training) reads the bf16 weights."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
+        if decode_weights not in (None, "mxfp8"):
+            raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
+        if decode_weights is not None and (self._decode_w8 is None or self._decode_w8["fmt"] != decode_weights):
+            raise ValueError("decode_weights given without copies to read: call quantize_decode_weights() first")
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         B, S, H = inputs_embeds.shape
@@ -414,11 +503,15 @@ class CausalLM(nn.Module):
             x = x.contiguous()
         layers = self.model.layers
         fused_head = False
+        w8 = None
+        if decode_weights is not None and cache and len(layers) and all(layer.can_decode_step(x, B, S, cache[i]) for i, layer in enumerate(layers)):
+            w8 = self._decode_w8                                 # a decode step: every layer below takes decode_step(_fused)
+        lw8 = (lambda i: w8["layers"][i]) if w8 is not None else (lambda i: None)
         if cache and len(layers) and all(layer.can_decode_step_fused(x, B, S, cache[i]) for i, layer in enumerate(layers)):
             # decode step: every RMSNorm is applied by the projection that consumes it (DecoderLayer.decode_step_fused), the final
             # norm by lm_head below
             for i, layer in enumerate(layers):
-                x = layer.decode_step_fused(x, cos, sin, key_mask, B, cache[i])
+                x = layer.decode_step_fused(x, cos, sin, key_mask, B, cache[i], w8=lw8(i))
             fused_head = self.lm_head.bias is None and self.model.norm.bias is None       # S == 1: logits_to_keep keeps the one row
             if not fused_head:
                 x, _ = self.model.norm(x)
@@ -429,7 +522,7 @@ class CausalLM(nn.Module):
             # `logits` is then not returned
             last = len(layers) - 1
             for i, layer in enumerate(layers):
-                x = layer(x, cos, sin, key_mask, B, S, cache=cache[i] if cache else None, rows=rows if i == last else None)
+                x = layer(x, cos, sin, key_mask, B, S, cache=cache[i] if cache else None, rows=rows if i == last else None, w8=lw8(i))
             if rows is not None and not len(layers):
                 x = Fm.rows_select(x, rows)
             x, _ = self.model.norm(x)
@@ -439,7 +532,11 @@ class CausalLM(nn.Module):
             Sk = logits_to_keep
         else:
             Sk = S
-        if fused_head:
+        hw8 = w8["lm_head"] if w8 is not None else None
+        if hw8 is not None:
+            nw = dict(norm_w=self.model.norm.weight, eps=self.model.norm.eps) if fused_head else {}
+            logits2d = K.decode_linear_w8(x, *hw8, ldc_pad=True, **nw)
+        elif fused_head:
             logits2d = K.decode_linear(x, self.lm_head.weight, norm_w=self.model.norm.weight, eps=self.model.norm.eps, ldc_pad=True)
         else:
             logits2d = self.lm_head(x, ldc_pad=True)             # [B*Sk, V] view, row stride padded to 64

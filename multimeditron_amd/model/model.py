@@ -224,6 +224,7 @@ class MultiModalModelForCausalLM(nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         sd = dict(state_dict)
+        self.model.drop_decode_weights()           # the MXFP8 decode copies are a snapshot of the weights being replaced
         own = self._checkpoint_tensors()
         # the reference keeps the whole CLIPModel; accept and ignore its unused towers / buffers
         unused = [k for k in sd if k not in own and any(t in k for t in ("text_model", "text_projection", "visual_projection",
@@ -299,6 +300,7 @@ class MultiModalModelForCausalLM(nn.Module):
             files = ["model.safetensors"]
         else:
             raise FileNotFoundError(f"{path}: neither model.safetensors nor model.safetensors.index.json")
+        self.model.drop_decode_weights()
         own = self._checkpoint_tensors()
         seen, unexpected = set(), []
         tied = self._llm_cfg.tie_word_embeddings
@@ -459,7 +461,8 @@ class MultiModalModelForCausalLM(nn.Module):
 
     def generate(self, batch: Dict[str, Any], max_new_tokens=512, temperature=0.1, do_sample=True, sync_every: int = 16,
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
-                 seed: Optional[int] = None, generator: Optional[torch.Generator] = None, **kwargs) -> torch.Tensor:
+                 seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
+                 **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -471,7 +474,20 @@ class MultiModalModelForCausalLM(nn.Module):
             include/mm_hip.h), step i drawing with Philox offset i and call = row.  `seed` is used as given; without it one int64
             is drawn from `generator` (torch's default CPU generator when None), so torch.manual_seed still fixes the ids.
             top_k = 0, top_p = 1 and min_p = 0 switch a warper off.
-        Whether the device sampler should become the default is a separate decision."""
+        Whether the device sampler should become the default is a separate decision.
+
+        decode_weights="mxfp8" (opt-in): the decode steps stream weight-only MXFP8 copies of the decoder's matrices and lm_head
+        (CausalLM.quantize_decode_weights: about half the weight bytes per token, ~8.3 GB more HBM on the 8B model, and the
+        quantisation's error in the logits); the prefill reads the bf16 weights.  The copies are made on first use and reused:
+        they are a snapshot (train(), load_state_dict / from_pretrained and resize_token_embeddings drop it; after any other weight
+        update call model.model.quantize_decode_weights() again).  A call that cannot use them -- a model that is not bf16, more than
+        16 sequences, activation rows that do not fit the kernel's LDS stage -- raises ValueError before the prefill."""
+        if decode_weights not in (None, "mxfp8"):
+            raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
+        if decode_weights is not None:
+            why = self.model.decode_weights_ok(int(batch["input_ids"].shape[0]))
+            if why is not None:
+                raise ValueError(f"decode_weights={decode_weights!r} cannot be used: {why}")
         device_sample = do_sample and any(a is not None for a in (top_k, top_p, min_p, seed, generator))
         if device_sample:
             top_k = 0 if top_k is None else top_k
@@ -489,9 +505,9 @@ class MultiModalModelForCausalLM(nn.Module):
                 gdev = generator.device if generator is not None else "cpu"
                 seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
         return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
-                              (top_k, top_p, min_p, seed) if device_sample else None)
+                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights)
 
-    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler) -> torch.Tensor:
+    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None) -> torch.Tensor:
         """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
@@ -509,6 +525,9 @@ class MultiModalModelForCausalLM(nn.Module):
         eos = self.config.eos_token_idx
         if max_new_tokens <= 0:
             return torch.empty((B, 0), dtype=torch.int64)
+        if decode_weights is not None and self.model._decode_w8 is None:
+            self.model.quantize_decode_weights(decode_weights)
+        dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
         with torch.no_grad():
             nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
             attention_mask = batch["attention_mask"].to(dev)
@@ -530,7 +549,7 @@ class MultiModalModelForCausalLM(nn.Module):
                     position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
                     attention_mask = full_mask[:, : seq_length + i]
                 out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
-                                 past_key_values=cache, use_cache=True, logits_to_keep=1)
+                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw)
                 logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
                 if sampler is not None:
                     k_, p_, mp_, sd_ = sampler

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
-   python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7]
+   python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
-the greedy selection."""
+the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
+the copies are made by the warm-up call, outside the timed ones."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,6 +19,11 @@ if "--sample" in sys.argv:
     for kv in sys.argv[i + 1].split(","):
         k, val = kv.split("=")
         SAMPLE[k] = int(val) if k in ("top_k", "seed") else float(val)
+    del sys.argv[i:i + 2]
+DW = None
+if "--decode-weights" in sys.argv:
+    i = sys.argv.index("--decode-weights")
+    DW = sys.argv[i + 1]
     del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -37,13 +43,14 @@ batch["attention_mask"] = torch.ones(B, S, dtype=torch.long, device="cuda")
 def run(n):
     torch.cuda.synchronize()
     t = time.perf_counter()
+    dw = {"decode_weights": DW} if DW else {}
     if SAMPLE is None:
-        ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False)
+        ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False, **dw)
     else:
         kw = dict(SAMPLE)
         T = kw.pop("T", 1.0)
         kw.setdefault("seed", 0)
-        ids = model.generate(batch, max_new_tokens=n, temperature=T, do_sample=True, **kw)
+        ids = model.generate(batch, max_new_tokens=n, temperature=T, do_sample=True, **kw, **dw)
     torch.cuda.synchronize()
     return time.perf_counter() - t, ids
 
@@ -53,5 +60,12 @@ t1, _ = run(1)
 tn, ids = run(N)
 per_tok = (tn - t1) / (N - 1)
 wbytes = sum(p.numel() for p in model.model.parameters()) * 2
-print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
+if DW:          # what a decode step reads now: the packed copies, plus what stays bf16 (norm weights, biases; the embedding rows are a gather)
+    w8 = model.model._decode_w8
+    packed = [t[0] for lay in w8["layers"] for t in lay.values()] + ([w8["lm_head"][0]] if w8["lm_head"] else [])
+    copied = sum(sum(p.numel() for p in ps) for ps in (
+        [lay.self_attn._wqkv.params + [lay.self_attn.o_proj.weight] + lay.mlp._wgu.params + [lay.mlp.down_proj.weight] for lay in model.model.model.layers]
+        + [[model.model.lm_head.weight]])) * 2
+    wbytes = wbytes - copied + sum(t.numel() for t in packed)
+print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}{' decode_weights ' + DW if DW else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
       f"weight stream {wbytes / per_tok / 1e12:.2f} TB/s of 8 (floor {wbytes / 8e12 * 1e3:.2f} ms/token)  ids {tuple(ids.shape)}")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The decode step's weight-streaming kernels one by one at the 8B decoder's shapes (B rows of activations), each timed over L
 different layers' weights (L x 436 MB: far beyond the 256 MB Infinity Cache, as in a real token) -- us per launch and TB/s of
-weight bytes.   python tools/gemv_bench.py [B] [L]"""
+weight bytes, first on the bf16 weights and then on their weight-only MXFP8 copies (the bytes actually read: 1 + 1/32 per weight
+plus the layout's padding).   python tools/gemv_bench.py [B] [L]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -56,6 +57,20 @@ for nt in (0, 1):
     tot += timed("down + residual (K=14336)", lambda i: K.decode_linear(act, w_d[i], residual=x), w_d[0].numel() * 2)
     print(f"sum of the five per layer: {tot:.1f} us -> x32 layers = {tot * 32 / 1e3:.2f} ms/token (+ lm_head, embedding, select)")
 lib().mm_set_option(b"gemv_nt", 0)
+# the same five launches on the MXFP8 copies (attention reads no weights: repeated for the sum only)
+p_qkv, p_o, p_gu, p_d = ([K.quant_mxfp8(w) for w in ws] for ws in (w_qkv, w_o, w_gu, w_d))
+for nt in (0, 1):
+    lib().mm_set_option(b"gemv_nt", nt)
+    print(f"-- MXFP8 weights, loads: {'non-temporal' if nt else 'default policy'}")
+    tot = 0.0
+    tot += timed("w8 norm + q|k|v + RoPE + append", lambda i: K.decode_qkv_rope_append_w8(x, p_qkv[i], None, Hq, Hkv, D, cos, sin, kc[i], vc[i], S, norm_w=nw, eps=1e-5), p_qkv[0].numel())
+    tot += timed("attention partial+merge (S=2048)", lambda i: K.attn_decode(q, kc[i][:, :S], vc[i][:, :S], None, D ** -0.5), 2 * B * S * Hkv * D * 2)
+    tot += timed("w8 o_proj + residual", lambda i: K.decode_linear_w8(x, p_o[i], H, residual=x), p_o[0].numel())
+    tot += timed("w8 norm + gate|up + SwiGLU", lambda i: K.decode_gateup_swiglu_w8(x, p_gu[i], I, norm_w=nw, eps=1e-5), p_gu[0].numel())
+    tot += timed("w8 down + residual (K=14336)", lambda i: K.decode_linear_w8(act, p_d[i], H, residual=x), p_d[0].numel())
+    print(f"sum of the five per layer: {tot:.1f} us -> x32 layers = {tot * 32 / 1e3:.2f} ms/token (+ lm_head, embedding, select)")
+lib().mm_set_option(b"gemv_nt", 0)
+del p_qkv, p_o, p_gu, p_d
 for wgs in (1, 2, 3):
     lib().mm_set_option(b"gemv_wgs", wgs)
     print(f"-- persistent workgroups per CU: {wgs}")
