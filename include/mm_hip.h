@@ -389,6 +389,39 @@ int mm_attn_decode(int dtype, const void* q, const void* k, const void* v, int B
                    int64_t v_sh, const int64_t* key_mask, float scale, void* out, float* workspace, int nsplit, int* sync,
                    void* stream);
 
+/* ---- MXFP8 KV cache for the decode step (opt-in).  The K and V rows [Hkv, D] of every cached position, D = 128 only, are stored in
+ * the format of mm_quant_mxfp8 above: OCP e4m3fn elements, one E8M0 scale byte per 32 consecutive d of a head (4 per (position, kv
+ * head) for K and 4 for V), the same quantiser rule -- the smallest scale that keeps the block maximum <= 448, byte clamp [27, 254],
+ * 127 for a zero block, round to nearest even, sign of zero kept.  1 + 1/32 byte per element, 0.516 of bf16; the rows the buffer stands
+ * for are ordinary bf16 tensors, exactly.  One buffer per layer holds K and V of [B, Smax] positions; its layout is private to the
+ * library (csrc/mm_kv8.h), fixed by (B, Smax, Hkv); the buffer is 16-byte aligned (MM_ERR_ALIGN).  MM_BF16 and D = 128, else
+ * MM_ERR_UNSUPPORTED; non-positive sizes and NULL operands are MM_ERR_ARG.  All checks come before any launch.
+ * mm_kv8_bytes:    bytes of one layer's buffer (K and V, elements and scales), a multiple of 16, with
+ *                  2*B*Smax*Hkv*132 <= bytes <= 2*B*round_up(Smax,16)*Hkv*132 + 64; negative MM_ERR_UNSUPPORTED / MM_ERR_ARG.
+ * mm_kv8_append:   quantises the bf16 rows k / v [b, s, h, :] (strides in elements: k_sb, k_ss, v_sb, v_ss, head stride D -- strided
+ *                  views into a fused q|k|v row; multiples of 8 and k, v 16-byte aligned, else MM_ERR_ALIGN) into positions
+ *                  pos .. pos + S - 1.  One pass, both tensors in one launch; S = the prompt length at prefill, 1 in a decode step.
+ *                  Nothing outside those positions is written.  MM_ERR_ARG if pos < 0 or pos + S > Smax.
+ * mm_kv8_dequant:  the bf16 rows of positions pos .. pos + S - 1, exactly, into k_out / v_out [B, S, Hkv, D] (both with batch stride sb
+ *                  and position stride ss, multiples of 8; head stride D).  For tests and debugging.
+ * mm_attn_decode_kv8_chunk: keys per slice of mm_attn_decode_kv8 = ceil(Skv / nsplit) rounded up to the layout's alignment (a power
+ *                  of two <= 16, csrc/mm_kv8.h): slice s holds keys [s*chunk, min(Skv, (s+1)*chunk)).  MM_ERR_ARG for Skv <= 0 or nsplit < 1.
+ * mm_attn_decode_kv8: mm_attn_decode's two-launch form (sync = NULL) over the buffer: q, key_mask, out, workspace and nsplit as there
+ *                  (nsplit from mm_attn_decode_splits; any nsplit >= 1 is accepted), Skv <= Smax cached positions.  D = 128 and Hq/Hkv
+ *                  in {1, 2, 4} (MM_ERR_UNSUPPORTED otherwise).  Whenever the slices coincide -- nsplit == 1, or ceil(Skv / nsplit) a
+ *                  multiple of the alignment -- out is bit-identical to mm_attn_decode run on mm_kv8_dequant's rows with the same nsplit
+ *                  (the slice kernel is the same code: the stored bytes become the same MFMA operands).  Every slice's record is
+ *                  written, an empty slice's included.  The result does not depend on anything stored for positions >= Skv: slots
+ *                  never appended to may hold any bytes.                                                                           */
+int64_t mm_kv8_bytes(int B, int Smax, int Hkv, int D);
+int mm_kv8_append(int dtype, const void* k, const void* v, int B, int S, int Hkv, int D, int64_t k_sb, int64_t k_ss, int64_t v_sb,
+                  int64_t v_ss, void* cache, int Smax, int pos, void* stream);
+int mm_kv8_dequant(const void* cache, int B, int Smax, int Hkv, int D, int pos, int S, void* k_out, void* v_out, int64_t sb, int64_t ss,
+                   void* stream);
+int mm_attn_decode_kv8_chunk(int Skv, int nsplit);
+int mm_attn_decode_kv8(int dtype, const void* q, const void* cache, int B, int Skv, int Smax, int Hq, int Hkv, int D, int64_t q_sb,
+                       int64_t q_sh, const int64_t* key_mask, float scale, void* out, float* workspace, int nsplit, void* stream);
+
 /* ---- activations -----------------------------------------------------------------------------------------
  * SwiGLU: HF:llama:163-176.  gu [M, 2I] = [gate | up] from the fused gate/up GEMM; out [M,I] = silu(gate)*up.
  * Rounding points of the forward (T = the storage type): out = T(f32(T(silu(gate))) * up): silu(gate) is rounded to T BEFORE the

@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libmmhip.so")
-SOURCES = ["mm_gemm.hip", "mm_attn.hip", "mm_rowwise.hip", "mm_embed.hip", "mm_optim.hip", "mm_debug.hip", "mm_comm.hip", "mm_image.hip", "mm_xattn.hip", "mm_sample.hip", "mm_qknorm.hip", "mm_conv.hip", "mm_conv_bwd.hip", "mm_xielu.hip", "mm_quant.hip"]
+SOURCES = ["mm_gemm.hip", "mm_attn.hip", "mm_rowwise.hip", "mm_embed.hip", "mm_optim.hip", "mm_debug.hip", "mm_comm.hip", "mm_image.hip", "mm_xattn.hip", "mm_sample.hip", "mm_qknorm.hip", "mm_conv.hip", "mm_conv_bwd.hip", "mm_xielu.hip", "mm_quant.hip", "mm_kv8.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 
@@ -30,7 +30,7 @@ def build(force=False, verbose=True):
     gen, inc = os.path.join(HERE, "gen_gemm_w4.py"), os.path.join(HERE, "mm_gemm_w4.inc")
     if force or _stale(inc, [gen]):                     # the 4-wave GEMM's main loop (asm text) is generated
         subprocess.run([sys.executable, gen], check=True, stdout=subprocess.DEVNULL)
-    headers = [os.path.join(HERE, "mm_common.h"), os.path.join(HERE, "mm_gemm_plan.h"), os.path.join(HERE, "mm_mxfp8.h"), os.path.join(PKG, "..", "include", "mm_hip.h"), inc]
+    headers = [os.path.join(HERE, "mm_common.h"), os.path.join(HERE, "mm_gemm_plan.h"), os.path.join(HERE, "mm_mxfp8.h"), os.path.join(HERE, "mm_kv8.h"), os.path.join(PKG, "..", "include", "mm_hip.h"), inc]
     jobs = []
     for src in SOURCES:
         s = os.path.join(HERE, src)

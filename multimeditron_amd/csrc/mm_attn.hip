@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "mm_common.h"
+#include "mm_kv8.h"
 
 namespace {
 
@@ -1793,6 +1794,10 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(DecodeArgs a) 
 //   P V on the vector ALU with V rows as they lie in memory: lane (sub = l & 15, kq) holds 8 dims of keys 4 kq + u, and the
 //   probabilities it needs sit in lane g of ITS OWN 16-lane row: one DPP row broadcast each (no LDS traffic).
 // Same record format (m, l, o[D]) per slice: attn_decode_merge_kernel is unchanged.
+// KV8 (mm_attn_decode_kv8): the same slice over the MXFP8 cache buffer of mm_kv8.h.  a.k is the buffer, a.k_ss its Smax, a.v and the
+// other k / v strides are unused, a.chunk is a multiple of MM_KV8_ALIGN.  A lane loads the bytes of the same elements (two 16-byte
+// loads and one scale dword each for K and V) and mx8_to_bf16x8 makes of them the bf16x8 operands kf / vf below: every MFMA, the
+// softmax and every P V fma see what this kernel sees on the dequantised rows, so the record has the same bits.
 __device__ __forceinline__ float row_bcast(float x, int lane_in_row) {          // value of lane `lane_in_row` of this lane's 16-lane row
   return __shfl(x, (int)(threadIdx.x & 48u) | lane_in_row, 64);
 }
@@ -1801,7 +1806,7 @@ __device__ __forceinline__ float row_bcast_dpp(float x) {                       
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x150 + N, 0xf, 0xf, false));
 }
 
-template <int G>
+template <int G, bool KV8 = false>
 __global__ __launch_bounds__(256) void attn_decode_partial128_mfma_kernel(DecodeArgs a) {
   constexpr int D = 128;
   static_assert(G >= 1 && G <= 4, "row-broadcast unrolling and the LDS budget below are written for G <= 4");
@@ -1810,8 +1815,8 @@ __global__ __launch_bounds__(256) void attn_decode_partial128_mfma_kernel(Decode
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = l & 15, kq = l >> 4;
   const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
-  const bf16* Kb = (const bf16*)a.k + b * a.k_sb + hkv * a.k_sh;
-  const bf16* Vb = (const bf16*)a.v + b * a.v_sb + hkv * a.v_sh;
+  const bf16* Kb = KV8 ? nullptr : (const bf16*)a.k + b * a.k_sb + hkv * a.k_sh;
+  const bf16* Vb = KV8 ? nullptr : (const bf16*)a.v + b * a.v_sb + hkv * a.v_sh;
   const int kbeg = split * a.chunk, kend = min(a.Skv, kbeg + a.chunk);
   const float sc = a.scale * LOG2E;
   bf16x8 qf[4];
@@ -1827,19 +1832,40 @@ __global__ __launch_bounds__(256) void attn_decode_partial128_mfma_kernel(Decode
     for (int j = 0; j < 8; ++j) o[g][j] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   bf16x8 kf[4], vf[4];
+  Kv8Frag f8;                                                     // KV8: the next block as loaded; converted where kf / vf are consumed
+  const unsigned char* C8 = (const unsigned char*)a.k;
+  const Kv8Layout L8 = KV8 ? kv8_layout(a.B, (int)a.k_ss, a.Hkv) : Kv8Layout{};
+  const int64_t bh = (int64_t)b * a.Hkv + hkv;
   auto load_block = [&](int k0) {
     const int kk = min(k0 + row, kend - 1);                       // clamp: a valid address, the score is masked below
+    if constexpr (KV8) {
+      const u32x4* kp = (const u32x4*)(C8 + kv8_k_elem(L8, bh, kk, kq));         // chunk c = kq: K-step 0 of this lane, 32 contiguous bytes
+      f8.k[0] = kp[0];
+      f8.k[1] = kp[1];
+      f8.ks = *(const unsigned*)(C8 + kv8_k_scale(L8, bh, kk, 0));
+      const int gk = min(k0 + 4 * kq, (kend - 1) & ~3);           // the lane's group of four keys, clamped to the slice's last group
+      const u32x4* vp = (const u32x4*)(C8 + kv8_v_elem(L8, bh, gk, row));
+      f8.v[0] = vp[0];
+      f8.v[1] = vp[1];
+      f8.vs = *(const unsigned*)(C8 + kv8_v_scale(L8, bh, gk, row >> 2));
+    } else {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const bf16x8*)(Kb + (int64_t)kk * a.k_ss + ks * 32 + kq * 8);
+      for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const bf16x8*)(Kb + (int64_t)kk * a.k_ss + ks * 32 + kq * 8);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int kv = min(k0 + 4 * kq + u, kend - 1);
-      vf[u] = *(const bf16x8*)(Vb + (int64_t)kv * a.v_ss + row * 8);
+      for (int u = 0; u < 4; ++u) {
+        const int kv = min(k0 + 4 * kq + u, kend - 1);
+        vf[u] = *(const bf16x8*)(Vb + (int64_t)kv * a.v_ss + row * 8);
+      }
     }
   };
   int k0 = kbeg + w * 16;
   if (k0 < kend) load_block(k0);
   for (; k0 < kend; k0 += 64) {
+    if constexpr (KV8) {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) kf[ks] = kv8_k_piece(f8, ks);
+      kv8_v_pieces(f8, k0 + 4 * kq, kend - 1, vf);                // keys of the group from kend on: the clamped key, in registers
+    }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], acc, 0, 0, 0);
@@ -2091,6 +2117,37 @@ extern "C" int mm_attn_decode(int dtype, const void* q, const void* k, const voi
   if (sync) return MM_OK;
   if (D == 128) hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
   else hipLaunchKernelGGL(attn_decode_merge_kernel<64>, dim3(B * Hq), dim3(64), 0, s, workspace, nsplit, (bf16*)out);
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+extern "C" int mm_attn_decode_kv8_chunk(int Skv, int nsplit) {
+  if (Skv <= 0 || nsplit < 1) return MM_ERR_ARG;
+  const int c = (Skv + nsplit - 1) / nsplit;
+  return (c + MM_KV8_ALIGN - 1) & ~(MM_KV8_ALIGN - 1);
+}
+
+extern "C" int mm_attn_decode_kv8(int dtype, const void* q, const void* cache, int B, int Skv, int Smax, int Hq, int Hkv, int D, int64_t q_sb,
+                                  int64_t q_sh, const int64_t* key_mask, float scale, void* out, float* workspace, int nsplit, void* stream) {
+  if (B < 0 || Skv <= 0 || Smax <= 0 || Skv > Smax || Hq <= 0 || Hkv <= 0 || Hq % Hkv || nsplit < 1) return MM_ERR_ARG;
+  if (dtype != MM_BF16 || D != 128) return MM_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return MM_ERR_UNSUPPORTED;        // the MFMA slice kernel's range
+  if (!q || !cache || !out || !workspace) return MM_ERR_ARG;
+  if (B == 0) return MM_OK;
+  if ((q_sb | q_sh) & 7) return MM_ERR_ALIGN;
+  if (!mm_aligned16(q) || !mm_aligned16(cache)) return MM_ERR_ALIGN;
+  DecodeArgs a{q, cache, nullptr, B, Skv, Hq, Hkv, q_sb, q_sh, 0, Smax, 0, 0, 0, 0, key_mask, scale, out, workspace, nsplit, 0, nullptr};
+  a.chunk = mm_attn_decode_kv8_chunk(Skv, nsplit);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(nsplit, Hkv, B), block(256);
+  switch (G) {
+    case 1: hipLaunchKernelGGL((attn_decode_partial128_mfma_kernel<1, true>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_partial128_mfma_kernel<2, true>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((attn_decode_partial128_mfma_kernel<4, true>), grid, block, 0, s, a); break;
+  }
+  MM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }

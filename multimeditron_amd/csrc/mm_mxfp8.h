@@ -1,5 +1,6 @@
 // MXFP8 weight-only storage (include/mm_hip.h: mm_quant_mxfp8): OCP e4m3fn elements, one power-of-two E8M0 scale byte per 32
-// consecutive k of a row.  Shared by the quantiser (mm_quant.hip) and the decode kernel that streams the bytes (mm_gemm.hip).
+// consecutive k of a row.  Shared by the quantiser (mm_quant.hip) and the decode kernel that streams the bytes (mm_gemm.hip); the
+// element / scale conversions at the end also serve the MXFP8 KV cache (mm_kv8.h), which has its own layout.
 //
 // The layout of the packed buffer is private to the library and fixed by (N, K) alone.  It follows THE ORDER THE KERNEL WALKS W:
 // gemv_stream_kernel gives wave w of a workgroup the K-steps (blocks of 32) w*per .. w*per + per - 1, per = ceil(K/32 / 8), and a lane
@@ -47,5 +48,36 @@ __device__ __forceinline__ bf16x8 mx8_to_bf16x8(u32x2 q, float sc) {
                    __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], sc, false)),
                    __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], sc, true))};
   return __builtin_bit_cast(bf16x8, r);
+}
+// Scale byte of a block from the largest |w| as a bf16 bit pattern (sign cleared).  a16 orders like the magnitude, and
+// floor(log2 amax) and "amax * 2^-e0 > 448" are read from its fields: amax * 2^-e0 = 1.m * 2^8, above 448 = 1.75 * 2^8 when the 7
+// mantissa bits exceed 0x60.  A subnormal amax (exponent field 0) lands below the lower clamp like every amax < 2^-92.
+__device__ __forceinline__ unsigned mx8_scale_byte(unsigned a16) {
+  if (a16 == 0) return 127u;
+  const int e = (int)(a16 >> 7) - 127 - 8 + ((a16 & 0x7Fu) > 0x60u ? 1 : 0);
+  return (unsigned)min(max(e + 127, 27), 254);
+}
+// largest |w| of 8 bf16 (one 16-byte load) as that bit pattern
+__device__ __forceinline__ unsigned mx8_amax16(u32x4 raw) {
+  unsigned a16 = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a16 = max(a16, max(raw[e] & 0x7FFFu, (raw[e] >> 16) & 0x7FFFu));
+  return a16;
+}
+// 8 bf16 under their block's scale byte -> 8 e4m3 bytes: round to nearest even, sign of zero kept
+__device__ __forceinline__ u32x2 mx8_from_bf16x8(u32x4 raw, unsigned byte) {
+  const float inv = __builtin_bit_cast(float, (254u - byte) << 23);          // 2^-e, exact
+  const bf16x8 wv = __builtin_bit_cast(bf16x8, raw);
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = fmaxf(-448.f, fminf((float)wv[e] * inv, 448.f));      // never active; keeps the sign of zero
+  u32x2 q;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h], v[4 * h + 1], 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h + 2], v[4 * h + 3], p, true);
+    q[h] = (unsigned)p;
+  }
+  return q;
 }
 #endif

@@ -5,15 +5,6 @@
 
 namespace {
 
-// Scale byte of a block from the largest |w| as a bf16 bit pattern (sign cleared).  a16 orders like the magnitude, and
-// floor(log2 amax) and "amax * 2^-e0 > 448" are read from its fields: amax * 2^-e0 = 1.m * 2^8, above 448 = 1.75 * 2^8 when the 7
-// mantissa bits exceed 0x60.  A subnormal amax (exponent field 0) lands below the lower clamp like every amax < 2^-92.
-__device__ __forceinline__ unsigned mx8_scale_byte(unsigned a16) {
-  if (a16 == 0) return 127u;
-  const int e = (int)(a16 >> 7) - 127 - 8 + ((a16 & 0x7Fu) > 0x60u ? 1 : 0);
-  return (unsigned)min(max(e + 127, 27), 254);
-}
-
 // One thread per (row, wave run, step slot, kc): the slots of the layout, padding included, so every byte of the buffer is written.
 __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const bf16* W, int ldw, int N, int K, unsigned char* packed, Mx8Layout L) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;            // a slot's 4 lanes (kc) are all in or all out
@@ -24,24 +15,11 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const bf16* W, int ldw
   const bool real = i < L.per && ks < K / 32;                              // uniform over the 4 lanes
   u32x4 raw = {0u, 0u, 0u, 0u};
   if (real) raw = *(const u32x4*)(W + (int64_t)row * ldw + ks * 32 + kc * 8);
-  unsigned a16 = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) a16 = max(a16, max(raw[e] & 0x7FFFu, (raw[e] >> 16) & 0x7FFFu));
+  unsigned a16 = mx8_amax16(raw);
   a16 = max(a16, (unsigned)__shfl_xor((int)a16, 1, 64));
   a16 = max(a16, (unsigned)__shfl_xor((int)a16, 2, 64));
   const unsigned byte = mx8_scale_byte(a16);                                // a padding slot: zeros, byte 127
-  const float inv = __builtin_bit_cast(float, (254u - byte) << 23);          // 2^-e, exact
-  const bf16x8 wv = __builtin_bit_cast(bf16x8, raw);
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = fmaxf(-448.f, fminf((float)wv[e] * inv, 448.f));      // never active; keeps the sign of zero
-  u32x2 q;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    int p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h], v[4 * h + 1], 0, false);
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h + 2], v[4 * h + 3], p, true);
-    q[h] = (unsigned)p;
-  }
+  const u32x2 q = mx8_from_bf16x8(raw, byte);
   *(u32x2*)(packed + mx8_elem_off(L, run, i, kc)) = q;
   if (kc == 0) packed[L.scale_off + slot] = (unsigned char)byte;
   if (idx == 0)                                                              // the tail up to the 16-byte multiple

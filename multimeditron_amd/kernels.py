@@ -713,6 +713,46 @@ def attn_decode(q, k, v, key_mask, scale):
     return out
 
 
+# ---- MXFP8 KV cache (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 d of a head; the buffer layout is the library's) ----
+def kv8_bytes(B, Smax, Hkv, D):
+    n = _lib.lib().mm_kv8_bytes(int(B), int(Smax), int(Hkv), int(D))
+    if n < 0:
+        raise _lib.MMHipError(f"mm_kv8_bytes({B}, {Smax}, {Hkv}, {D}) failed: {n} (head_dim must be 128)")
+    return n
+
+
+def kv8_append(k, v, cache, Smax, pos):
+    """Quantise the bf16 rows k / v [B, S, Hkv, D] (strided views ok, head stride D) into positions pos .. pos + S - 1 of a cache buffer
+    (uint8 [kv8_bytes(B, Smax, Hkv, D)])."""
+    B, S, Hkv, D = k.shape
+    assert v.shape == k.shape and k.stride(3) == 1 and v.stride(3) == 1 and k.stride(2) == D and v.stride(2) == D
+    call("mm_kv8_append", dt(k), _p(k), _p(v), B, S, Hkv, D, k.stride(0), k.stride(1), v.stride(0), v.stride(1), _p(cache), Smax, pos,
+         _stream())
+    return cache
+
+
+def kv8_dequant(cache, B, Smax, Hkv, D, pos=0, S=None):
+    """The bf16 rows (k, v) [B, S, Hkv, D] the buffer stands for at positions pos .. pos + S - 1 (exact)."""
+    S = Smax - pos if S is None else S
+    k = torch.empty((B, S, Hkv, D), dtype=torch.bfloat16, device=cache.device)
+    v = torch.empty_like(k)
+    call("mm_kv8_dequant", _p(cache), B, Smax, Hkv, D, pos, S, _p(k), _p(v), k.stride(0), k.stride(1), _stream())
+    return k, v
+
+
+def attn_decode_kv8(q, cache, Skv, Smax, Hkv, key_mask, scale):
+    """attn_decode over the first Skv positions of an MXFP8 cache buffer: q [B,Hq,D] (strided view ok) -> out [B,Hq,D].  The bits of
+    attn_decode on kv8_dequant's rows whenever the slices coincide (mm_attn_decode_kv8)."""
+    B, Hq, D = q.shape
+    assert q.stride(2) == 1
+    ns = _lib.lib().mm_attn_decode_splits(B, Hkv, Skv)
+    ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+    out = torch.empty((B, Hq, D), dtype=q.dtype, device=q.device)
+    call("mm_attn_decode_kv8", dt(q), _p(q), _p(cache), B, Skv, Smax, Hq, Hkv, D, q.stride(0), q.stride(1), _p(key_mask), float(scale),
+         _p(out), _p(ws), ns, _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ small cross-attention + dropout
 def xattn_supported(dtype, Nkv, D):
     """Shapes mm_xattn_* takes: up to 1024 keys (a query's whole score row lives in a wave's registers: 64 MFMA tiles; above 512 keys

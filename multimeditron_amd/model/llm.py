@@ -199,7 +199,8 @@ class DecoderLayer(nn.Module):
     def decode_step(self, x, cos, sin, key_mask, B, cache, w8=None):
         """One new token per sequence (generate's decode loop, reference model.py:595-602): the four linears take the
         weight-streaming GEMM (M <= 16), RoPE and the cache append are one pass, attention is the split-K stream over the
-        cache.  Same arithmetic and rounding points as forward().  (Folding RMSNorm / SwiGLU into the GEMM's x operand was
+        cache (bf16 or MXFP8: the cache says where the append kernel writes the new row and attends over itself).  Same arithmetic and
+        rounding points as forward().  (Folding RMSNorm / SwiGLU into the GEMM's x operand was
         measured SLOWER: every workgroup redoes the transform on all 64 lanes and the kernel turns VALU-bound, 43 vs 27 us
         and 57 vs 25 us per launch, so they stay separate launches.)
         w8: this layer's MXFP8 copies (CausalLM.quantize_decode_weights) -- the four linears stream those instead."""
@@ -214,11 +215,10 @@ class DecoderLayer(nn.Module):
 
         qkv = lin("qkv", h, a._wqkv.tensor(), bias=bqkv)
         if a.q_norm is not None:
-            K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, cache.k, cache.v, cache.len)
+            K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, *cache.append_dst())
         else:
-            K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, cache.k, cache.v, cache.len)
-        cache.len += 1
-        o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
+            K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, *cache.append_dst())
+        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
         x = lin("o", o.view(B, Hq * D), a.o_proj.weight, residual=x)
         h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
         u = lin("gu", h, m._wgu.tensor())
@@ -236,16 +236,14 @@ class DecoderLayer(nn.Module):
         n1, n2 = self.norms()
         if w8 is not None:
             qkv = K.decode_qkv_rope_append_w8(x, w8["qkv"][0], a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
-                                              cache.k, cache.v, cache.len, norm_w=n1.weight, eps=n1.eps)
-            cache.len += 1
-            o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
+                                              *cache.append_dst(), norm_w=n1.weight, eps=n1.eps)
+            o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
             x = K.decode_linear_w8(o.view(B, Hq * D), *w8["o"], residual=x)
             act = K.decode_gateup_swiglu_w8(x, w8["gu"][0], m.I, norm_w=n2.weight, eps=n2.eps)
             return K.decode_linear_w8(act, *w8["down"], residual=x)
         qkv = K.decode_qkv_rope_append(x, a._wqkv.tensor(), a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
-                                       cache.k, cache.v, cache.len, norm_w=n1.weight, eps=n1.eps)
-        cache.len += 1
-        o = K.attn_decode(qkv[:, : Hq * D].view(B, Hq, D), cache.k[:, : cache.len], cache.v[:, : cache.len], key_mask, D ** -0.5)
+                                       *cache.append_dst(), norm_w=n1.weight, eps=n1.eps)
+        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
         x = K.decode_linear(o.view(B, Hq * D), a.o_proj.weight, residual=x)
         act = K.decode_gateup_swiglu(x, m._wgu.tensor(), m.I, norm_w=n2.weight, eps=n2.eps)
         return K.decode_linear(act, m.down_proj.weight, residual=x)
@@ -296,24 +294,77 @@ class LayerKVCache:
         self.v = torch.zeros((B, Smax, Hkv, D), dtype=dtype, device=device)
         self.len = 0
 
-    @torch.no_grad()
-    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
+    def append_dst(self):
+        """(kcache, vcache, pos) of the decode step's append kernels: where the new token's k / v rows go."""
+        return self.k, self.v, self.len
+
+    def decode_attend(self, q, key_mask, scale):
+        """The row of position `len` has been written: count it and attend q [B, Hq, D] over the cache (split-K stream)."""
+        self.len += 1
+        return K.attn_decode(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, scale)
+
+    @staticmethod
+    def rope_views(qkv, cos, sin, B, S, a: Attention):
+        """(per-head norm +) RoPE of the fused projection in place (prefill keeps no backward) -> its q, k, v as strided views."""
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         W = (Hq + 2 * Hkv) * D
-        if a.q_norm is not None:       # in place: prefill keeps no backward
+        if a.q_norm is not None:
             K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, out=qkv, want_rstd=False)
         else:
             K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
-        q = qkv[:, : Hq * D].view(B, S, Hq, D)
-        kn = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        vn = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
+        return (qkv[:, : Hq * D].view(B, S, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
+                qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
+
+    @torch.no_grad()
+    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
+        Hq, Hkv, D = a.Hq, a.Hkv, a.D
+        q, kn, vn = self.rope_views(qkv, cos, sin, B, S, a)
         self.k[:, self.len:self.len + S].copy_(kn)      # device-side memory plumbing
         self.v[:, self.len:self.len + S].copy_(vn)
-        self.len += S
         if S == 1 and K.attn_decode_supported(qkv.dtype, Hq, Hkv, D):      # decode step: stream the cache once (split-K)
-            out = K.attn_decode(q.view(B, Hq, D), self.k[:, : self.len], self.v[:, : self.len], key_mask, D ** -0.5)
-            return out.view(B, Hq * D)
+            return self.decode_attend(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+        self.len += S
         out, _ = K.attn_fwd(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, True, D ** -0.5)
+        return out.view(B * S, Hq * D)
+
+
+class LayerKVCacheMX8(LayerKVCache):
+    """The same cache in MXFP8 (include/mm_hip.h: mm_kv8_*): ONE uint8 buffer of mm_kv8_bytes for K and V, elements and scales
+    (1 + 1/32 byte per element, 0.516 of bf16; the layout is the library's), and a bf16 staging row [B, 1, Hkv, D] each for k and v.
+    A decode step's append kernels write the new row to the staging row (position 0) unchanged; mm_kv8_append quantises it into
+    position `len` and mm_attn_decode_kv8 streams the buffer.  The prefill attends over the bf16 k / v of the prompt (its output is
+    the bf16 cache's, bit for bit) and quantises them into the buffer in one pass; only later steps see quantised keys."""
+
+    def __init__(self, B, Smax, Hkv, D, dtype, device):
+        self.Smax, self.Hkv = Smax, Hkv
+        self.buf = torch.zeros((K.kv8_bytes(B, Smax, Hkv, D),), dtype=torch.uint8, device=device)
+        self.k = torch.zeros((B, 1, Hkv, D), dtype=dtype, device=device)
+        self.v = torch.zeros((B, 1, Hkv, D), dtype=dtype, device=device)
+        self.len = 0
+
+    def append_dst(self):
+        return self.k, self.v, 0
+
+    def decode_attend(self, q, key_mask, scale):
+        return self._attend_row(q, self.k, self.v, key_mask, scale)
+
+    def _attend_row(self, q, k1, v1, key_mask, scale):
+        K.kv8_append(k1, v1, self.buf, self.Smax, self.len)
+        self.len += 1
+        return K.attn_decode_kv8(q, self.buf, self.len, self.Smax, self.Hkv, key_mask, scale)
+
+    @torch.no_grad()
+    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
+        Hq, D = a.Hq, a.D
+        if S > 1 and self.len:
+            raise ValueError(f"{S} new positions on an MXFP8 KV cache that holds {self.len}: only a prefill into an empty cache or "
+                             "one token per step (attending over the cached prompt would need a dequantising prefill)")
+        q, kn, vn = self.rope_views(qkv, cos, sin, B, S, a)
+        if S == 1:
+            return self._attend_row(q.view(B, Hq, D), kn, vn, key_mask, D ** -0.5).view(B, Hq * D)
+        K.kv8_append(kn, vn, self.buf, self.Smax, 0)
+        self.len = S
+        out, _ = K.attn_fwd(q, kn, vn, key_mask, True, D ** -0.5)
         return out.view(B * S, Hq * D)
 
 
@@ -461,15 +512,34 @@ class CausalLM(nn.Module):
             self._inv_freq = rope_inv_freq(self.config).to(position_ids.device)
         return K.rope_table(position_ids.reshape(-1).contiguous(), self._inv_freq, self.dtype == torch.bfloat16)
 
-    def new_cache(self, B, Smax):
+    def kv_cache_ok(self, B: int):
+        """None when a batch of B sequences can keep its KV cache in MXFP8, else the reason it cannot (the opt-in never falls back
+        silently: new_cache and generate raise it before the prefill)."""
         c = self.config
-        return [LayerKVCache(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device)
-                for _ in range(c.num_hidden_layers)]
+        if self.dtype != torch.bfloat16:
+            return f"model dtype is {self.dtype}, not bfloat16"
+        if c.head_dim != 128:
+            return f"head_dim is {c.head_dim} (the MXFP8 cache and its decode kernel are written for 128)"
+        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
+        if Hq % Hkv or Hq // Hkv not in (1, 2, 4):
+            return f"{Hq} query heads on {Hkv} key/value heads (the MXFP8 decode kernel takes 1, 2 or 4 per key/value head)"
+        return None
+
+    def new_cache(self, B, Smax, kv_cache: Optional[str] = None):
+        """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot."""
+        c = self.config
+        if kv_cache not in (None, "mxfp8"):
+            raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
+        if kv_cache is not None and self.kv_cache_ok(B) is not None:
+            raise ValueError(f"kv_cache={kv_cache!r} cannot be used: {self.kv_cache_ok(B)}")
+        cls = LayerKVCache if kv_cache is None else LayerKVCacheMX8
+        return [cls(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device) for _ in range(c.num_hidden_layers)]
 
     def forward(self, input_ids=None, inputs_embeds=None, attention_mask=None, position_ids=None,
                 past_key_values=None, labels=None, use_cache=None, return_dict=True, logits_to_keep: int = 0,
-                decode_weights: Optional[str] = None, **kwargs):
-        """decode_weights="mxfp8": a decode step (one new token per sequence over a cache, can_decode_step) streams the copies of
+                decode_weights: Optional[str] = None, kv_cache: Optional[str] = None, **kwargs):
+        """kv_cache="mxfp8": the format of the cache this call allocates (use_cache without past_key_values); a cache handed in keeps
+        its own.  decode_weights="mxfp8": a decode step (one new token per sequence over a cache, can_decode_step) streams the copies of
         quantize_decode_weights() instead of the bf16 weights; anything else (prefill, training) reads the bf16 weights."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
@@ -487,7 +557,7 @@ class CausalLM(nn.Module):
         if rows is not None and (labels is None or cache or use_cache or logits_to_keep or rows.n == 0 or rows.total != B * S):
             rows = None                                      # anything but a plain training forward: every position's logits
         if use_cache and cache is None:
-            cache = self.new_cache(B, S + int(kwargs.get("max_new_tokens", 512)))
+            cache = self.new_cache(B, S + int(kwargs.get("max_new_tokens", 512)), kv_cache=kv_cache)
         if position_ids is None:
             position_ids = (torch.arange(S, device=dev) + past).unsqueeze(0).expand(B, S)
         cos, sin = self._tables(position_ids.to(dev))

@@ -462,7 +462,7 @@ class MultiModalModelForCausalLM(nn.Module):
     def generate(self, batch: Dict[str, Any], max_new_tokens=512, temperature=0.1, do_sample=True, sync_every: int = 16,
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                  seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
-                 **kwargs) -> torch.Tensor:
+                 kv_cache: Optional[str] = None, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -481,7 +481,21 @@ class MultiModalModelForCausalLM(nn.Module):
         quantisation's error in the logits); the prefill reads the bf16 weights.  The copies are made on first use and reused:
         they are a snapshot (train(), load_state_dict / from_pretrained and resize_token_embeddings drop it; after any other weight
         update call model.model.quantize_decode_weights() again).  A call that cannot use them -- a model that is not bf16, more than
-        16 sequences, activation rows that do not fit the kernel's LDS stage -- raises ValueError before the prefill."""
+        16 sequences, activation rows that do not fit the kernel's LDS stage -- raises ValueError before the prefill.
+
+        kv_cache="mxfp8" (opt-in): the K and V rows of every cached position are kept as e4m3 elements with one power-of-two scale
+        per 32 values of a head (include/mm_hip.h: mm_kv8_*): 132 bytes per head row against 256, so a cached position of the 8B
+        geometry costs 66 KiB over its 32 layers instead of 128 KiB.  The prefill is NOT quantised: it attends over the bf16 keys and
+        values of the prompt (its logits, hence the first token, are the bf16 cache's bit for bit) and stores them quantised; every
+        later step reads quantised keys and values, the current token's included.  Composes with decode_weights and every
+        sampler path.  A model that cannot use it -- not bf16, head_dim other than 128, a number of query heads per key/value
+        head other than 1, 2 or 4 -- raises ValueError before the prefill (CausalLM.kv_cache_ok)."""
+        if kv_cache not in (None, "mxfp8"):
+            raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
+        if kv_cache is not None:
+            why = self.model.kv_cache_ok(int(batch["input_ids"].shape[0]))
+            if why is not None:
+                raise ValueError(f"kv_cache={kv_cache!r} cannot be used: {why}")
         if decode_weights not in (None, "mxfp8"):
             raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
         if decode_weights is not None:
@@ -505,9 +519,9 @@ class MultiModalModelForCausalLM(nn.Module):
                 gdev = generator.device if generator is not None else "cpu"
                 seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
         return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
-                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights)
+                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache)
 
-    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None) -> torch.Tensor:
+    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None) -> torch.Tensor:
         """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
@@ -533,7 +547,7 @@ class MultiModalModelForCausalLM(nn.Module):
             attention_mask = batch["attention_mask"].to(dev)
             position_ids = batch["position_ids"].to(dev)
             seq_length = attention_mask.shape[1]
-            cache = self.model.new_cache(B, seq_length + max_new_tokens)
+            cache = self.model.new_cache(B, seq_length + max_new_tokens, kv_cache=kv_cache)
             # device-resident loop state (plumbing): the growing mask is a view of one preallocated buffer
             full_mask = torch.ones((B, seq_length + max_new_tokens), dtype=attention_mask.dtype, device=dev)
             full_mask[:, :seq_length] = attention_mask

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
-   python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8]
+   python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
-the copies are made by the warm-up call, outside the timed ones."""
+the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
+(generate(kv_cache=...)).  The KV bytes a decode step reads per token (every layer's K and V of B x S positions) are printed."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +26,11 @@ if "--decode-weights" in sys.argv:
     i = sys.argv.index("--decode-weights")
     DW = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+KV = None
+if "--kv-cache" in sys.argv:
+    i = sys.argv.index("--kv-cache")
+    KV = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 33
@@ -44,6 +50,8 @@ def run(n):
     torch.cuda.synchronize()
     t = time.perf_counter()
     dw = {"decode_weights": DW} if DW else {}
+    if KV:
+        dw["kv_cache"] = KV
     if SAMPLE is None:
         ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False, **dw)
     else:
@@ -67,5 +75,8 @@ if DW:          # what a decode step reads now: the packed copies, plus what sta
         [lay.self_attn._wqkv.params + [lay.self_attn.o_proj.weight] + lay.mlp._wgu.params + [lay.mlp.down_proj.weight] for lay in model.model.model.layers]
         + [[model.model.lm_head.weight]])) * 2
     wbytes = wbytes - copied + sum(t.numel() for t in packed)
-print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}{' decode_weights ' + DW if DW else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
-      f"weight stream {wbytes / per_tok / 1e12:.2f} TB/s of 8 (floor {wbytes / 8e12 * 1e3:.2f} ms/token)  ids {tuple(ids.shape)}")
+lc = model.model.config
+kv_row = 2 * lc.num_key_value_heads * (lc.head_dim + lc.head_dim // 32 if KV else lc.head_dim * 2)      # bytes of K and V per position and layer
+kvbytes = B * S * kv_row * lc.num_hidden_layers
+print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}{' decode_weights ' + DW if DW else ''}{' kv_cache ' + KV if KV else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
+      f"weight stream {wbytes / per_tok / 1e12:.2f} TB/s of 8 (floor {wbytes / 8e12 * 1e3:.2f} ms/token); KV {kvbytes / 1e9:.3f} GB/token ({kv_row} B per position and layer)  ids {tuple(ids.shape)}")

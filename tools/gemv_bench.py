@@ -2,7 +2,8 @@
 """The decode step's weight-streaming kernels one by one at the 8B decoder's shapes (B rows of activations), each timed over L
 different layers' weights (L x 436 MB: far beyond the 256 MB Infinity Cache, as in a real token) -- us per launch and TB/s of
 weight bytes, first on the bf16 weights and then on their weight-only MXFP8 copies (the bytes actually read: 1 + 1/32 per weight
-plus the layout's padding).   python tools/gemv_bench.py [B] [L]"""
+plus the layout's padding).  The attention launch and the S = 1 cache append are timed over the bf16 cache and over its MXFP8 form
+(the bytes actually read: 132 per head row against 256).   python tools/gemv_bench.py [B] [L]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -71,6 +72,15 @@ for nt in (0, 1):
     print(f"sum of the five per layer: {tot:.1f} us -> x32 layers = {tot * 32 / 1e3:.2f} ms/token (+ lm_head, embedding, select)")
 lib().mm_set_option(b"gemv_nt", 0)
 del p_qkv, p_o, p_gu, p_d
+# the KV cache in bf16 and in MXFP8: the attention launch over S keys, and what an MXFP8 step adds (the quantising append of one position)
+print("-- KV cache: bf16 and MXFP8")
+Smax = S + 8
+c8 = [K.kv8_append(kc[i], vc[i], torch.empty(K.kv8_bytes(B, Smax, Hkv, D), dtype=torch.uint8, device=dev), Smax, 0) for i in range(L)]
+k1, v1 = torch.randn(B, 1, Hkv, D, device=dev, dtype=bf), torch.randn(B, 1, Hkv, D, device=dev, dtype=bf)
+timed(f"attention, bf16 cache (S={S})", lambda i: K.attn_decode(q, kc[i][:, :S], vc[i][:, :S], None, D ** -0.5), 2 * B * S * Hkv * D * 2)
+timed(f"attention, MXFP8 cache (S={S})", lambda i: K.attn_decode_kv8(q, c8[i], S, Smax, Hkv, None, D ** -0.5), 2 * B * S * Hkv * (D + D // 32))
+timed("MXFP8 append of one position (S=1)", lambda i: K.kv8_append(k1, v1, c8[i], Smax, S), 2 * B * Hkv * (D * 2 + D + D // 32))
+del c8
 for wgs in (1, 2, 3):
     lib().mm_set_option(b"gemv_wgs", wgs)
     print(f"-- persistent workgroups per CU: {wgs}")
