@@ -66,7 +66,8 @@ int mm_set_option(const char* name, int value);
  * Also the read-only "gemm_last_kernel": which kernel the last mm_gemm* / mm_decode_* call launched -- 0 the 128x128 register-staged
  * kernel (also the fallback past the 32-bit offsets), 1..5 the LDS-DMA tiles 256x128, 256x256 (8-wave), 128x128, 64x128, 64x64, 10
  * the 4-wave 256x256 kernel, 20 / 21 the M <= 16 weight-streaming kernels (gemm_skinny / gemv_stream: plain M <= 16 NT and the
- * decode fusions), 22 gemv_stream on MXFP8 weights (the mm_decode_*_w8 entry points), 30 the fp32 kernel */
+ * decode fusions), 22 gemv_stream on MXFP8 weights (the mm_decode_*_w8 entry points), 23 the MXFP8 x MXFP8 scaled-MFMA kernel
+ * (mm_gemm_mx8), 30 the fp32 kernel */
 int mm_get_option(const char* name, int* value);
 /* What a GEMM call with these facts would do, under the current switches: host only, launches nothing, needs no device when ncu
  * is given, and leaves "gemm_last_kernel" alone.  It is the function the launcher itself runs (csrc/mm_gemm_plan.h).
@@ -371,6 +372,23 @@ int mm_decode_qkv_rope_append_w8(int dtype, int M, int Hq, int Hkv, int D, int K
                                  int64_t dstride, const void* in_norm_w, float eps, void* stream);
 int mm_decode_linear_w8(int dtype, int M, int N, int K, const void* X, int ldx, const void* packed, const void* bias,
                         const void* residual, int ldr, void* C, int ldc, const void* in_norm_w, float eps, void* stream);
+
+/* ---- MXFP8 x MXFP8 GEMM for the prefill (opt-in), on gfx950's block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 both sides).
+ * packedW: the buffer mm_quant_mxfp8 writes for W[N,K], byte for byte (the decode step's copy: no second one); packedA: the same
+ * format for the activation rows, mm_quant_mxfp8(X, ldx, M, K, ...).  Both 16-byte aligned and of mm_mxfp8_bytes; nothing past them
+ * is read.
+ *   C[m,n] = bf16( sum_k A'[m,k] W'[n,k] (+ bias[n]) (+ residual[m,n]) ),   A', W' = mm_dequant_mxfp8 of the two buffers,
+ * bf16 C (row stride ldc >= N), bias, residual (row stride ldr >= N); fp32 accumulation in a fixed order (no atomics, no split-K: the
+ * same call gives the same bits), bias then residual added in fp32, ONE rounding at the store.  residual may be C itself.  No alignment
+ * rule on C / residual / ldc beyond the bf16 element (8-byte groups are stored where the address allows).
+ * epi: MM_EPI_BIAS | MM_EPI_RESIDUAL only (MM_ERR_UNSUPPORTED for any other bit).  M, N >= 1 with row / column tails inside a tile;
+ * K % 128 == 0 and K <= 2^20, else MM_ERR_UNSUPPORTED (every such width is taken; the ones whose layout carries padding slots --
+ * 3584, 18944, ... -- walk the padding as zeros).  M, N, K <= 0, a NULL operand, ldc / ldr < N: MM_ERR_ARG; a misaligned buffer:
+ * MM_ERR_ALIGN.  All checks come before the launch; a refused call writes nothing.  "gemm_last_kernel" reads 23 after a launch.
+ * mm_gemm_mx8_supported: 0, or the MM_ERR_* the shape alone would get from mm_gemm_mx8; host only, launches nothing, needs no device. */
+int mm_gemm_mx8(int M, int N, int K, const void* packedA, const void* packedW, const void* bias, const void* residual, int ldr,
+                void* C, int ldc, int epi, void* stream);
+int mm_gemm_mx8_supported(int M, int N, int K);
 
 /* KV-cache decode step: ONE query token per sequence over the cached keys (reference model.py:595-602 calling the LLM with
  * past_key_values; HF:llama:217-281 with q_len = 1).  q [B,Hq,D] (strides q_sb,q_sh; D contiguous), k/v [B,Skv,Hkv,D] as

@@ -2391,6 +2391,7 @@ static GemmOptions g_opt = [] {
   return o;
 }();
 static int g_last_kernel = -1;      // which kernel the last mm_gemm* / mm_decode_* call launched ("gemm_last_kernel": ids in mm_hip.h)
+__attribute__((visibility("hidden"))) void mm_gemm_note_last_kernel(int id) { g_last_kernel = id; }      // mm_gemm_mx8.hip's launcher
 
 int mm_attn_option(const char* name, int value);
 int mm_attn_get_option(const char* name, int* value);

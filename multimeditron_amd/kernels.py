@@ -237,6 +237,38 @@ def decode_linear_w8(x2d, packed, N, bias=None, residual=None, norm_w=None, eps=
     return buf[:, :N] if buf.shape[1] != N else buf
 
 
+# ---- MXFP8 x MXFP8 GEMM for the prefill (include/mm_hip.h: mm_gemm_mx8, the block-scaled MFMA) -----------------------------------
+def gemm_mx8_supported(M, N, K):
+    """None, or why mm_gemm_mx8 refuses the shape (host only: no launch, no device)."""
+    rc = _lib.lib().mm_gemm_mx8_supported(int(M), int(N), int(K))
+    if rc == 0:
+        return None
+    if rc == _lib.ERR_UNSUPPORTED:
+        return f"mm_gemm_mx8 takes K % 128 == 0 (K <= 2^20), got K = {K}"
+    return f"mm_gemm_mx8 refuses M = {M}, N = {N}, K = {K} ({rc})"
+
+
+def gemm_mx8(packedA, M, packedW, N, K, bias=None, residual=None, out=None):
+    """c [M, N] (bf16) = A' @ W'^T (+ bias) (+ residual) from two quant_mxfp8 buffers (A' [M, K], W' [N, K] what dequant_mxfp8 returns);
+    residual may be out.  fp32 accumulation, one rounding, the same bits on every call."""
+    why = gemm_mx8_supported(M, N, K)
+    if why is not None:
+        raise _lib.MMHipError(why)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=packedA.device)
+    assert out.dtype == torch.bfloat16 and out.stride(1) == 1
+    epi = 0
+    if bias is not None:
+        assert bias.dtype == torch.bfloat16
+        epi |= EPI_BIAS
+    if residual is not None:
+        assert residual.dtype == torch.bfloat16 and residual.stride(-1) == 1
+        epi |= EPI_RESIDUAL
+    call("mm_gemm_mx8", int(M), int(N), int(K), _p(packedA), _p(packedW), _p(bias), _p(residual),
+         residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), epi, _stream())
+    return out
+
+
 def decode_fusions():      # A/B switch (tools/decode_bench.py): MM_DECODE_FUSED=0 -> the separate launches
     return _os.environ.get("MM_DECODE_FUSED", "1") != "0"
 

@@ -248,6 +248,35 @@ class DecoderLayer(nn.Module):
         act = K.decode_gateup_swiglu(x, m._wgu.tensor(), m.I, norm_w=n2.weight, eps=n2.eps)
         return K.decode_linear(act, m.down_proj.weight, residual=x)
 
+    @torch.no_grad()
+    def prefill_mx8(self, x, cos, sin, key_mask, B, S, cache, w8):
+        """forward() of a call that is not a decode step, without autograd, with the four linears as MXFP8 x MXFP8 GEMMs on the
+        block-scaled MFMA (kernels.gemm_mx8): each quantises its bf16 input (kernels.quant_mxfp8, at the rounding point where
+        forward() hands that tensor to its GEMM) and reads this layer's copy in w8 (CausalLM.quantize_decode_weights).  The
+        order of the launches: rmsnorm_fwd, quant, gemm (q|k|v + bias), RoPE / q-k norm + cache append + attn_fwd (the cache's
+        attend; without a cache rope_views + attn_fwd), quant, gemm (o_proj + residual), rmsnorm_fwd, quant, gemm (gate|up or
+        up_proj), swiglu_fwd / xIELU, quant, gemm (down_proj + residual).  Everything but the eight new launches is the existing
+        kernel on bf16 data."""
+        a, m = self.self_attn, self.mlp
+        n1, n2 = self.norms()
+
+        def lin(name, t, **kw):
+            packed, N = w8[name]
+            return K.gemm_mx8(K.quant_mxfp8(t), t.shape[0], packed, N, t.shape[1], **kw)
+
+        h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
+        qkv = lin("qkv", h, bias=a._bqkv.tensor() if a._bqkv is not None else None)
+        if cache is not None:
+            o = cache.attend(qkv, cos, sin, key_mask, B, S, a)
+        else:
+            q, kn, vn = LayerKVCache.rope_views(qkv, cos, sin, B, S, a)
+            o = K.attn_fwd(q, kn, vn, key_mask, True, a.D ** -0.5)[0].view(B * S, a.Hq * a.D)
+        x = lin("o", o, residual=x)
+        h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
+        u = lin("gu", h)
+        act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
+        return lin("down", act, residual=x)
+
     def can_decode_step(self, x, B, S, cache):
         a = self.self_attn
         return (cache is not None and S == 1 and B <= 16 and x.dtype == torch.bfloat16 and not torch.is_grad_enabled()
@@ -446,7 +475,8 @@ class CausalLM(nn.Module):
         """Build MXFP8 copies (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 k; 1 + 1/32 byte per weight) of the
         matrices a decode step streams: per layer the fused q|k|v, o_proj, the fused gate|up (Apertus: up_proj) and down_proj, and
         (lm_head=True) the matrix lm_head reads at decode, a tied embedding included.  forward(..., decode_weights="mxfp8") then
-        reads them on decode steps; prefill and training always read the bf16 weights.  The bf16 weights stay: the copies cost
+        reads them on decode steps and forward(..., prefill_weights="mxfp8") on every other call made without autograd (the prefill);
+        without those arguments, and in training always, the bf16 weights are read.  The bf16 weights stay: the copies cost
         about half their size again in HBM (~8.3 GB on the 8B model).
 
         The copies are plain tensors held beside the modules: absent from state_dict, checkpoints and FlatParams.  They are a
@@ -493,6 +523,23 @@ class CausalLM(nn.Module):
                 return f"{B} activation rows of {Kd} features do not fit the decode kernel's LDS stage"
         return None
 
+    def prefill_weights_ok(self, B: int, S: int, check_grad: bool = True):
+        """None when a forward of B x S positions can run its decoder-layer linears as MXFP8 x MXFP8 GEMMs (forward(...,
+        prefill_weights="mxfp8")), else the reason it cannot (the opt-in never falls back silently: forward and generate raise it
+        before any work).  check_grad=False: the caller switches autograd off itself (generate)."""
+        if self.dtype != torch.bfloat16:
+            return f"model dtype is {self.dtype}, not bfloat16"
+        if check_grad and torch.is_grad_enabled():
+            return "autograd is enabled (the MXFP8 prefill has no backward: run it under torch.no_grad())"
+        widths = {self.config.hidden_size}
+        for layer in self.model.layers:
+            widths |= {layer.self_attn.Hq * layer.self_attn.D, layer.mlp.I}
+        for Kd in sorted(widths):
+            why = K.gemm_mx8_supported(max(1, B * S), self.config.hidden_size, Kd)
+            if why is not None:
+                return f"a weight matrix with {Kd} input features: {why}"
+        return None
+
     def train(self, mode: bool = True):
         if mode:
             self.drop_decode_weights()
@@ -537,12 +584,21 @@ class CausalLM(nn.Module):
 
     def forward(self, input_ids=None, inputs_embeds=None, attention_mask=None, position_ids=None,
                 past_key_values=None, labels=None, use_cache=None, return_dict=True, logits_to_keep: int = 0,
-                decode_weights: Optional[str] = None, kv_cache: Optional[str] = None, **kwargs):
+                decode_weights: Optional[str] = None, kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, **kwargs):
         """kv_cache="mxfp8": the format of the cache this call allocates (use_cache without past_key_values); a cache handed in keeps
         its own.  decode_weights="mxfp8": a decode step (one new token per sequence over a cache, can_decode_step) streams the copies of
-        quantize_decode_weights() instead of the bf16 weights; anything else (prefill, training) reads the bf16 weights."""
+        quantize_decode_weights() instead of the bf16 weights; anything else (prefill, training) reads the bf16 weights -- unless
+        prefill_weights="mxfp8": a call that is NOT a decode step (S > 1, or can_decode_step false) then runs every decoder-layer
+        linear -- fused q|k|v (+ bias), o_proj (+ residual), fused gate|up (Apertus: up_proj), down_proj (+ residual) -- as an
+        MXFP8 x MXFP8 GEMM on the block-scaled MFMA (DecoderLayer.prefill_mx8): the same copies (built here if absent, under the
+        same snapshot rule) and the linear's bf16 input quantised on the way in.  Norms, RoPE, attention, the activation, the cache
+        append and the final norm stay the bf16 kernels, and lm_head -- which sees logits_to_keep rows -- keeps its bf16 weights on
+        this path.  It needs autograd off (there is no backward through it) and raises ValueError with prefill_weights_ok's reason
+        otherwise; on a decode step the argument is ignored (decode_weights governs those)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
+        if prefill_weights not in (None, "mxfp8"):
+            raise ValueError(f"prefill_weights={prefill_weights!r}: None or 'mxfp8'")
         if decode_weights not in (None, "mxfp8"):
             raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
         if decode_weights is not None and (self._decode_w8 is None or self._decode_w8["fmt"] != decode_weights):
@@ -577,7 +633,20 @@ class CausalLM(nn.Module):
         if decode_weights is not None and cache and len(layers) and all(layer.can_decode_step(x, B, S, cache[i]) for i, layer in enumerate(layers)):
             w8 = self._decode_w8                                 # a decode step: every layer below takes decode_step(_fused)
         lw8 = (lambda i: w8["layers"][i]) if w8 is not None else (lambda i: None)
-        if cache and len(layers) and all(layer.can_decode_step_fused(x, B, S, cache[i]) for i, layer in enumerate(layers)):
+        pw8 = None
+        if prefill_weights is not None and len(layers) and not (
+                cache and all(layer.can_decode_step(x, B, S, cache[i]) for i, layer in enumerate(layers))):
+            why = self.prefill_weights_ok(B, S)
+            if why is not None:
+                raise ValueError(f"prefill_weights={prefill_weights!r} cannot be used: {why}")
+            if self._decode_w8 is None or self._decode_w8["fmt"] != prefill_weights:
+                self.quantize_decode_weights(prefill_weights)
+            pw8, rows = self._decode_w8["layers"], None
+        if pw8 is not None:
+            for i, layer in enumerate(layers):
+                x = layer.prefill_mx8(x, cos, sin, key_mask, B, S, cache[i] if cache else None, pw8[i])
+            x, _ = self.model.norm(x)
+        elif cache and len(layers) and all(layer.can_decode_step_fused(x, B, S, cache[i]) for i, layer in enumerate(layers)):
             # decode step: every RMSNorm is applied by the projection that consumes it (DecoderLayer.decode_step_fused), the final
             # norm by lm_head below
             for i, layer in enumerate(layers):

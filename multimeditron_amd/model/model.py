@@ -462,7 +462,7 @@ class MultiModalModelForCausalLM(nn.Module):
     def generate(self, batch: Dict[str, Any], max_new_tokens=512, temperature=0.1, do_sample=True, sync_every: int = 16,
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                  seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
-                 kv_cache: Optional[str] = None, **kwargs) -> torch.Tensor:
+                 kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -489,7 +489,15 @@ class MultiModalModelForCausalLM(nn.Module):
         values of the prompt (its logits, hence the first token, are the bf16 cache's bit for bit) and stores them quantised; every
         later step reads quantised keys and values, the current token's included.  Composes with decode_weights and every
         sampler path.  A model that cannot use it -- not bf16, head_dim other than 128, a number of query heads per key/value
-        head other than 1, 2 or 4 -- raises ValueError before the prefill (CausalLM.kv_cache_ok)."""
+        head other than 1, 2 or 4 -- raises ValueError before the prefill (CausalLM.kv_cache_ok).
+
+        prefill_weights="mxfp8" (opt-in): the PREFILL call runs its decoder-layer linears as MXFP8 x MXFP8 GEMMs on the block-scaled
+        MFMA (include/mm_hip.h: mm_gemm_mx8) -- the same copies decode_weights reads (made on first use: the same ~8.3 GB of HBM on the 8B model, the same
+        snapshot rule), and each linear's input quantised on the way in (CausalLM.forward).  Only the prefill: the decode steps are governed by decode_weights as before; the vision towers, the
+        projector, the splice and lm_head stay bf16.  It adds the quantisation's error to the prompt's logits and cached keys /
+        values.  Composes with decode_weights, kv_cache and every sampler path.  A model that cannot use it -- not bf16, a linear
+        whose input width mm_gemm_mx8 refuses (not a multiple of 128) -- raises ValueError before the prefill
+        (CausalLM.prefill_weights_ok)."""
         if kv_cache not in (None, "mxfp8"):
             raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
         if kv_cache is not None:
@@ -502,6 +510,12 @@ class MultiModalModelForCausalLM(nn.Module):
             why = self.model.decode_weights_ok(int(batch["input_ids"].shape[0]))
             if why is not None:
                 raise ValueError(f"decode_weights={decode_weights!r} cannot be used: {why}")
+        if prefill_weights not in (None, "mxfp8"):
+            raise ValueError(f"prefill_weights={prefill_weights!r}: None or 'mxfp8'")
+        if prefill_weights is not None:
+            why = self.model.prefill_weights_ok(*batch["input_ids"].shape[:2], check_grad=False)      # the loop runs under no_grad
+            if why is not None:
+                raise ValueError(f"prefill_weights={prefill_weights!r} cannot be used: {why}")
         device_sample = do_sample and any(a is not None for a in (top_k, top_p, min_p, seed, generator))
         if device_sample:
             top_k = 0 if top_k is None else top_k
@@ -519,9 +533,9 @@ class MultiModalModelForCausalLM(nn.Module):
                 gdev = generator.device if generator is not None else "cpu"
                 seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
         return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
-                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache)
+                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache, prefill_weights)
 
-    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None) -> torch.Tensor:
+    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None, prefill_weights=None) -> torch.Tensor:
         """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
@@ -562,8 +576,9 @@ class MultiModalModelForCausalLM(nn.Module):
                 if i > 0:
                     position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
                     attention_mask = full_mask[:, : seq_length + i]
+                pw = {"prefill_weights": prefill_weights} if i == 0 and prefill_weights is not None else {}      # the prefill call only
                 out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
-                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw)
+                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw, **pw)
                 logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
                 if sampler is not None:
                     k_, p_, mp_, sd_ = sampler

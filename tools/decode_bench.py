@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
+                                [--prefill-weights mxfp8]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
-(generate(kv_cache=...)).  The KV bytes a decode step reads per token (every layer's K and V of B x S positions) are printed."""
+(generate(kv_cache=...)).  --prefill-weights mxfp8: the prefill runs its decoder linears as MXFP8 x MXFP8 GEMMs
+(generate(prefill_weights=...)); the first step alone (max_new_tokens = 1: the prefill and one token choice) is then timed for BOTH
+settings in this process, best of three after a warm-up each, before the usual line.  The KV bytes a decode step reads per token
+(every layer's K and V of B x S positions) are printed."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,6 +35,11 @@ if "--kv-cache" in sys.argv:
     i = sys.argv.index("--kv-cache")
     KV = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+PW = None
+if "--prefill-weights" in sys.argv:
+    i = sys.argv.index("--prefill-weights")
+    PW = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 33
@@ -46,10 +55,13 @@ batch, _ = bench.synthetic_batch(B, S, 1, 256, vocab, (llm["vocab_size"], llm["v
 batch["attention_mask"] = torch.ones(B, S, dtype=torch.long, device="cuda")
 
 
-def run(n):
+def run(n, pw="same"):
     torch.cuda.synchronize()
     t = time.perf_counter()
     dw = {"decode_weights": DW} if DW else {}
+    pw = PW if pw == "same" else pw
+    if pw:
+        dw["prefill_weights"] = pw
     if KV:
         dw["kv_cache"] = KV
     if SAMPLE is None:
@@ -64,6 +76,13 @@ def run(n):
 
 
 run(2)
+if PW:
+    first = {}
+    for pw in (None, PW):
+        run(1, pw)
+        first[pw] = min(run(1, pw)[0] for _ in range(3))
+    print(f"B={B} S={S}: first step (prefill + 1 token) bf16 {first[None] * 1e3:.1f} ms; prefill_weights {PW} {first[PW] * 1e3:.1f} ms "
+          f"({first[None] / first[PW]:.2f}x)")
 t1, _ = run(1)
 tn, ids = run(N)
 per_tok = (tn - t1) / (N - 1)
@@ -78,5 +97,5 @@ if DW:          # what a decode step reads now: the packed copies, plus what sta
 lc = model.model.config
 kv_row = 2 * lc.num_key_value_heads * (lc.head_dim + lc.head_dim // 32 if KV else lc.head_dim * 2)      # bytes of K and V per position and layer
 kvbytes = B * S * kv_row * lc.num_hidden_layers
-print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}{' decode_weights ' + DW if DW else ''}{' kv_cache ' + KV if KV else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
+print(f"B={B} S={S}{' sample ' + str(SAMPLE) if SAMPLE else ''}{' decode_weights ' + DW if DW else ''}{' kv_cache ' + KV if KV else ''}{' prefill_weights ' + PW if PW else ''}: prefill+1 token {t1 * 1e3:.1f} ms; decode {per_tok * 1e3:.2f} ms/token ({B / per_tok:.0f} tok/s); "
       f"weight stream {wbytes / per_tok / 1e12:.2f} TB/s of 8 (floor {wbytes / 8e12 * 1e3:.2f} ms/token); KV {kvbytes / 1e9:.3f} GB/token ({kv_row} B per position and layer)  ids {tuple(ids.shape)}")

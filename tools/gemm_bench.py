@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GEMM micro-benchmark on the shapes of the 8B training step (run on the GPU box).
-   python tools/gemm_bench.py [--quick]"""
+   python tools/gemm_bench.py [--quick]
+   python tools/gemm_bench.py --mx8      the 8B prefill linears (M = 8192): mm_gemm_mx8 beside the bf16 launch, and the activation quantiser"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -136,6 +137,32 @@ def main():
                 fl = 2.0 * M * N * Kd
                 med = {m: sorted(v)[len(v) // 2] for m, v in res.items()}
                 print(f"{lay} M={M:6d} N={N:6d} K={Kd:6d}  one-tile-per-wg {fl / med[0] / 1e9:7.1f} TF/s   persistent {fl / med[1] / 1e9:7.1f} TF/s", flush=True)
+        return
+    if "--mx8" in sys.argv:               # the 8B prefill linears: mm_gemm_mx8 beside the bf16 launch of the same shape, and the activation quantiser
+        def timed(fn, it=5):
+            for _ in range(2):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(it):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / it
+        tot = {"bf16": 0.0, "mx8": 0.0, "quant": 0.0}
+        for (M, N, Kd) in SHAPES["NT"][:4]:
+            a, b = operands("NT", M, N, Kd)
+            c = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            pa, pw = K.quant_mxfp8(a), K.quant_mxfp8(b)
+            t16 = timed(lambda: K.gemm(0, a, b, M, N, Kd, out=c))
+            t8 = timed(lambda: K.gemm_mx8(pa, M, pw, N, Kd, out=c))
+            tq = timed(lambda: K.quant_mxfp8(a, out=pa))
+            fl = 2.0 * M * N * Kd
+            for k, v in (("bf16", t16), ("mx8", t8), ("quant", tq)):
+                tot[k] += v
+            print(f"M={M:6d} N={N:6d} K={Kd:6d}  bf16 {t16:7.3f} ms {fl / t16 / 1e9:7.1f} TF/s   mx8 {t8:7.3f} ms {fl / t8 / 1e9:7.1f} TF/s   "
+                  f"quant A {tq * 1e3:6.1f} us {(M * Kd * 2 + pa.numel()) / tq / 1e9:5.2f} TB/s   mx8 + quant vs bf16: {t16 / (t8 + tq):.2f}x", flush=True)
+        print("TOTAL ms", {k: round(v, 3) for k, v in tot.items()})
         return
     tot_f = tot_t = 0.0
     for lay, shapes in SHAPES.items():
