@@ -407,6 +407,35 @@ int mm_attn_decode(int dtype, const void* q, const void* k, const void* v, int B
                    int64_t v_sh, const int64_t* key_mask, float scale, void* out, float* workspace, int nsplit, int* sync,
                    void* stream);
 
+/* Decode step of n samples per prompt over ONE copy of the prompt's keys (generate's num_return_sequences; opt-in).  Query row
+ * r = b*n + j of q [B*n,Hq,D] (strides q_sb,q_sh) is sample j of prompt b; it attends over Skv = Sp + Ss keys: prompt b's prefix
+ * kp/vp [B,Sp,Hkv,D] followed by row r's own suffix ks/vs [B*n,Ss,Hkv,D] (element strides as in mm_attn_decode), one softmax over the
+ * concatenation.  key_mask [B,Sp] or NULL applies to the prefix; suffix keys are always visible.  out [B*n,Hq,D] contiguous.
+ * MM_BF16, D = 128, Hq/Hkv = G in {1,2,4}, any n >= 1: the kernel packs 16/G samples per 16-column MFMA tile (the columns
+ * mm_attn_decode's MFMA slice kernel pads with zeros), so a prefix key is read once per tile, not once per sample; further samples
+ * take further tiles (workgroups).  Anything else is MM_ERR_UNSUPPORTED.
+ * Slices are mm_attn_decode's over the concatenation: chunk = ceil(Skv / nsplit), slice s holds keys [s*chunk, min(Skv, (s+1)*chunk))
+ * -- in the prefix, across Sp, in the suffix, or empty; every slice writes its record.  workspace: f32 [B*n*Hq*nsplit*(D+2)] in
+ * mm_attn_decode's record format, merged by the same second launch (there is no single-launch form).  Any nsplit >= 1 is accepted.
+ * Bit identity: for every accepted shape and nsplit, out has the bits of mm_attn_decode (sync = NULL, "attn_decode_mfma" = 1) run with
+ * the same nsplit on the materialised k/v [B*n,Sp+Ss,Hkv,D] and mask cat(mask.repeat_interleave(n,0), ones): a score is one MFMA
+ * output element, which does not depend on the other columns, and the softmax, the P.V chain and the merges keep that kernel's order.
+ * Masked prefix keys must hold finite values; rows of either cache beyond Sp / Ss are never read and nothing stored there matters.
+ * MM_ERR_ARG: a NULL operand, Sp < 1, Ss < 1, n < 1, nsplit < 1, Hq % Hkv != 0, more than 65535 (prompt, tile) pairs; MM_ERR_ALIGN: a
+ * stride that is not a multiple of 8 elements, q / kp / vp / ks / vs not 16-byte aligned.  Every check comes before any launch;
+ * B = 0: MM_OK, nothing written.
+ * mm_attn_decode_shared_splits: the slice count from the "attn_decode_wgs" workgroup target of mm_attn_decode_splits, at least 64
+ * keys per slice: ceil(T / (B * ceil(n/4) * Hkv)) with T = ceil(2 * attn_decode_wgs / 3).  The workgroups counted are this launch's
+ * at G = 4, the most an accepted shape launches (G is not an argument; G < 4 launches fewer, never more).  Two thirds: the option
+ * stands for ~3 workgroups per CU of mm_attn_decode's slice kernel, and this kernel's 16 columns of accumulators let a CU hold two
+ * (measured: profiles/r08_shared_prefix.md).  1 when the option is 1.                                                            */
+int mm_attn_decode_shared_splits(int B, int n, int Hkv, int Skv);
+int mm_attn_decode_shared(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+                          int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
+                          int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
+                          int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
+                          float* workspace, int nsplit, void* stream);
+
 /* ---- MXFP8 KV cache for the decode step (opt-in).  The K and V rows [Hkv, D] of every cached position, D = 128 only, are stored in
  * the format of mm_quant_mxfp8 above: OCP e4m3fn elements, one E8M0 scale byte per 32 consecutive d of a head (4 per (position, kv
  * head) for K and 4 for V), the same quantiser rule -- the smallest scale that keeps the block maximum <= 448, byte clamp [27, 254],

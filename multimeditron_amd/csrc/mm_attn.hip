@@ -1937,6 +1937,213 @@ __global__ __launch_bounds__(256) void attn_decode_partial128_mfma_kernel(Decode
   }
 }
 
+// mm_attn_decode_shared: the n samples of one prompt over ONE copy of the prompt's keys.  Query row r = b n + j attends the virtual
+// concatenation [prefix of prompt b | suffix of row r]; a workgroup takes one slice of that concatenation for one (prompt, kv head,
+// tile of P = 16 / G samples), and column c = jl G + g of the 16-column MFMA operand is head g of the tile's sample jl -- the columns
+// attn_decode_partial128_mfma_kernel pads with zeros.  A 16-key block that lies in the prefix is ONE set of 4 MFMAs and one set of
+// V rows for all live columns; a block that holds suffix keys takes the K and V rows of each sample in turn (4 MFMAs per sample, of
+// which the lanes of that sample's columns keep the result).  Everything a column sees is what the slice kernel above computes for
+// the row's materialised cache: the score is one MFMA output element (key row x query column, independent of the other columns), the
+// block softmax and the running (m, l) live in the column's lanes, the P V chain runs in the same order per (column, kq, d), clamped
+// keys are the same keys (min(key, kend - 1) of the concatenation), and the kq / wave merges below add in the same order.  So the
+// records, and after attn_decode_merge_kernel the output, have the same bits.
+struct DecodeSharedArgs {
+  const void *q, *kp, *vp, *ks, *vs;
+  int B, n, Sp, Ss, Hq, Hkv;
+  int64_t q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh, ks_sb, ks_ss, ks_sh, vs_sb, vs_ss, vs_sh;
+  const int64_t* kmask;          // [B, Sp]: the prefix only
+  float scale;
+  float* ws;
+  int nsplit, chunk, tiles;      // tiles = ceil(n / P)
+};
+
+// (x of kq row 0 + row 1) + (row 2 + row 3) of this lane's column, in every row: v_permlane16_swap exchanges the odd rows of its first
+// operand with the even rows of its second, v_permlane32_swap the upper half of the first with the lower half of the second
+// (inline assembly: this compiler's __builtin_amdgcn_permlane16_swap hands back its first result twice; s_nop 1 is the wait the
+// instruction needs after a vector write of its operands)
+__device__ __forceinline__ float kq_sum(float x) {
+  float a = x, b = x;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));        // a = (r0, r0, r2, r2), b = (r1, r1, r3, r3)
+  float c = a + b, d = c;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));        // c = (lower, lower), d = (upper, upper)
+  return c + d;
+}
+
+template <int C>
+__device__ __forceinline__ void decode_shared_head(float (&o)[16][8], float alpha, const float (&p)[4], const float (&vx)[4][8]) {
+  const float ag = row_bcast_dpp<C>(alpha);
+  const float p0 = row_bcast_dpp<C>(p[0]), p1 = row_bcast_dpp<C>(p[1]);
+  const float p2 = row_bcast_dpp<C>(p[2]), p3 = row_bcast_dpp<C>(p[3]);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float t = o[C][j] * ag;
+    t = __builtin_fmaf(p0, vx[0][j], t);
+    t = __builtin_fmaf(p1, vx[1][j], t);
+    t = __builtin_fmaf(p2, vx[2][j], t);
+    o[C][j] = __builtin_fmaf(p3, vx[3][j], t);
+  }
+}
+template <int JL, int G>              // the G columns of sample JL of the tile
+__device__ __forceinline__ void decode_shared_sample(float (&o)[16][8], float alpha, const float (&p)[4], const float (&vx)[4][8]) {
+  decode_shared_head<JL * G>(o, alpha, p, vx);
+  if constexpr (G > 1) decode_shared_head<JL * G + (G > 1 ? 1 : 0)>(o, alpha, p, vx);
+  if constexpr (G > 2) {
+    decode_shared_head<JL * G + (G > 2 ? 2 : 0)>(o, alpha, p, vx);
+    decode_shared_head<JL * G + (G > 2 ? 3 : 0)>(o, alpha, p, vx);
+  }
+}
+
+#define MM_SH_EACH16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+
+template <int G>
+__global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSharedArgs a) {
+  constexpr int D = 128, P = 16 / G;
+  static_assert(G == 1 || G == 2 || G == 4, "P = 16 / G samples share a column tile");
+  __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
+  __shared__ float red_ml[4][16][2];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int row = l & 15, kq = l >> 4;         // row: key of the block (K operand), column (scores), 8-dim group (V)
+  const int split = blockIdx.x, hkv = blockIdx.y;
+  const int b = blockIdx.z / a.tiles, j0 = (blockIdx.z % a.tiles) * P;
+  const int nlive = min(P, a.n - j0), ncols = nlive * G;
+  const int64_t r0 = (int64_t)b * a.n + j0;    // query row of the tile's first sample
+  const int Skv = a.Sp + a.Ss;
+  const bf16* Kp = (const bf16*)a.kp + b * a.kp_sb + hkv * a.kp_sh;
+  const bf16* Vp = (const bf16*)a.vp + b * a.vp_sb + hkv * a.vp_sh;
+  const bf16* Ks = (const bf16*)a.ks + hkv * a.ks_sh;
+  const bf16* Vs = (const bf16*)a.vs + hkv * a.vs_sh;
+  const int kbeg = split * a.chunk, kend = min(Skv, kbeg + a.chunk);
+  const float sc = a.scale * LOG2E;
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (row < ncols) qf[ks] = *(const bf16x8*)((const bf16*)a.q + (r0 + row / G) * a.q_sb + (hkv * G + row % G) * a.q_sh + ks * 32 + kq * 8);
+  }
+  float o[16][8];
+#pragma unroll
+  for (int c = 0; c < 16; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[c][j] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  bf16x8 kf[4], vf[4];
+  auto in_prefix = [&](int k0) { return min(k0 + 16, kend) <= a.Sp; };       // every key of the block, clamped ones included
+  auto load_prefix = [&](int k0) {
+    const int kk = min(k0 + row, kend - 1);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const bf16x8*)(Kp + (int64_t)kk * a.kp_ss + ks * 32 + kq * 8);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int kv = min(k0 + 4 * kq + u, kend - 1);
+      vf[u] = *(const bf16x8*)(Vp + (int64_t)kv * a.vp_ss + row * 8);
+    }
+  };
+  for (int k0 = kbeg + w * 16; k0 < kend; k0 += 64) {
+    const bool pre = in_prefix(k0);             // wave-uniform
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float vx[4][8];
+    if (pre) {
+      load_prefix(k0);      // no prefetch of the next block: 16 columns of o leave no registers for it at two workgroups per CU,
+                            // and a slice is one or two blocks per wave; the CU's other workgroup covers the latency
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], acc, 0, 0, 0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vx[u][j] = (float)vf[u][j];
+    } else {
+      // the block holds suffix keys: the rows of sample jl, of which the lanes of its columns keep the scores.  Samples past the
+      // tile's last live one repeat that one (a valid address; no lane keeps the result)
+      const int kk = min(k0 + row, kend - 1);
+#pragma unroll
+      for (int jl = 0; jl < P; ++jl) {
+        const int64_t r = r0 + min(jl, nlive - 1);
+        const bf16* kr = kk < a.Sp ? Kp + (int64_t)kk * a.kp_ss : Ks + r * a.ks_sb + (int64_t)(kk - a.Sp) * a.ks_ss;
+        f32x4 aj = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) aj = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(kr + ks * 32 + kq * 8), qf[ks], aj, 0, 0, 0);
+        if (row / G == jl) acc = aj;
+      }
+    }
+    float sv[4], bm = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = k0 + 4 * kq + r;
+      bool ok = key < kend;
+      if (ok && a.kmask && key < a.Sp) ok = a.kmask[(int64_t)b * a.Sp + key] != 0;      // suffix keys are always visible
+      sv[r] = ok ? acc[r] * sc : -INFINITY;
+      bm = fmaxf(bm, sv[r]);
+    }
+    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float mn = fmaxf(m_run, bm);
+    const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m_run - mn);
+    float p[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sv[r] - mn);
+    l_run = l_run * alpha + ((p[0] + p[1]) + (p[2] + p[3]));
+    m_run = mn;
+    if (pre) {
+#define MM_SH_COL(c) if (c < ncols) decode_shared_head<c>(o, alpha, p, vx);
+      MM_SH_EACH16(MM_SH_COL)
+#undef MM_SH_COL
+    } else {
+#define MM_SH_SAMPLE(jl)                                                                                                     \
+      if constexpr (jl < P) {                                                                                                \
+        if (jl < nlive) {                                                                                                    \
+          _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                    \
+            const int kv = min(k0 + 4 * kq + u, kend - 1);                                                                   \
+            const bf16* vr = kv < a.Sp ? Vp + (int64_t)kv * a.vp_ss : Vs + (r0 + jl) * a.vs_sb + (int64_t)(kv - a.Sp) * a.vs_ss; \
+            const bf16x8 vv = *(const bf16x8*)(vr + row * 8);                                                                \
+            _Pragma("unroll") for (int j = 0; j < 8; ++j) vx[u][j] = (float)vv[j];                                           \
+          }                                                                                                                  \
+          decode_shared_sample<(jl < P ? jl : 0), G>(o, alpha, p, vx);                                                       \
+        }                                                                                                                    \
+      }
+      MM_SH_EACH16(MM_SH_SAMPLE)
+#undef MM_SH_SAMPLE
+    }
+  }
+  // this wave's partial per live column: o summed over the 4 kq rows as ((kq0 + kq1) + (kq2 + kq3)) -- the order of the slice kernel
+  // above (the sums commute) -- across the rows by gfx950's row / half swaps (VALU, no LDS round trip: through ds_bpermute the 256
+  // dependent exchanges were most of the kernel's time), so that 16 columns fit 32 KB of LDS; and (m, l) per column
+#define MM_SH_RED(c)                                                                              \
+  if (c < ncols) {                                                                                \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) o[c][j] = kq_sum(o[c][j]);                      \
+  }
+  MM_SH_EACH16(MM_SH_RED)
+#undef MM_SH_RED
+  if (kq == 0) {
+#define MM_SH_PUT(c)                                                                              \
+    if (c < ncols) {                                                                              \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) red_o[w][c][row * 8 + j] = o[c][j];           \
+    }
+    MM_SH_EACH16(MM_SH_PUT)
+#undef MM_SH_PUT
+  }
+  float lt = l_run + __shfl_xor(l_run, 16, 64);
+  lt += __shfl_xor(lt, 32, 64);
+  if (kq == 0 && row < ncols) { red_ml[w][row][0] = m_run; red_ml[w][row][1] = lt; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncols * D; i += 256) {
+    const int c = i / D, d = i % D;
+    float mn = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) mn = fmaxf(mn, red_ml[ww][c][0]);
+    float ltot = 0.f, ot = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float al = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(red_ml[ww][c][0] - mn);
+      ltot += red_ml[ww][c][1] * al;
+      ot += red_o[ww][c][d] * al;
+    }
+    float* rec = a.ws + (((r0 + c / G) * a.Hq + hkv * G + c % G) * a.nsplit + split) * (D + 2);
+    rec[2 + d] = ot;
+    if (d == 0) { rec[0] = mn; rec[1] = ltot; }
+  }
+}
+#undef MM_SH_EACH16
+
 template <int D>
 __global__ void attn_decode_merge_kernel(const float* ws, int nsplit, bf16* out) {
   const int row = blockIdx.x, d = threadIdx.x;          // row = b * Hq + hq
@@ -2117,6 +2324,54 @@ extern "C" int mm_attn_decode(int dtype, const void* q, const void* k, const voi
   if (sync) return MM_OK;
   if (D == 128) hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
   else hipLaunchKernelGGL(attn_decode_merge_kernel<64>, dim3(B * Hq), dim3(64), 0, s, workspace, nsplit, (bf16*)out);
+  MM_CHECK_LAUNCH();
+  return MM_OK;
+}
+
+// column tiles of mm_attn_decode_shared per (prompt, kv head, slice): P = 16 / G samples each
+static int decode_shared_tiles(int n, int G) { const int P = 16 / G; return (n + P - 1) / P; }
+
+extern "C" int mm_attn_decode_shared_splits(int B, int n, int Hkv, int Skv) {
+  if (B <= 0 || n <= 0 || Hkv <= 0 || Skv <= 0) return 1;
+  // the launch has B * tiles * Hkv workgroups per slice.  The group size is not an argument: the count is that of G = 4 (4 samples
+  // per tile, the most workgroups an accepted shape launches), so a smaller G stays at or below the target.  The target is two
+  // thirds of "attn_decode_wgs": that option stands for ~3 workgroups per CU of the slice kernel, and this kernel's 16 columns of
+  // accumulators let a CU hold two (measured at B = 4, n = 4, 2048 + 32 keys: 38.7 us per launch at 768, 26.6 - 27.2 at 512 / 448 /
+  // 384, 25.9 at 256, 27.8 at 192; the replicated launch 29.5 - 31.8)
+  const int64_t per = (int64_t)B * decode_shared_tiles(n, 4) * Hkv, target = (2 * (int64_t)g_attn_decode_wgs + 2) / 3;
+  int64_t ns = (target + per - 1) / per;
+  const int cap = (Skv + 63) / 64;                  // at least 64 keys per slice
+  if (ns > cap) ns = cap;
+  return ns < 1 ? 1 : (int)ns;
+}
+
+extern "C" int mm_attn_decode_shared(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+                                     int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
+                                     int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
+                                     int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
+                                     float* workspace, int nsplit, void* stream) {
+  if (B < 0 || n < 1 || Sp < 1 || Ss < 1 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || nsplit < 1) return MM_ERR_ARG;
+  if (dtype != MM_BF16 || D != 128) return MM_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return MM_ERR_UNSUPPORTED;        // P = 16 / G samples per column tile
+  if (!q || !kp || !vp || !ks || !vs || !out || !workspace) return MM_ERR_ARG;
+  const int tiles = decode_shared_tiles(n, G);
+  if ((int64_t)B * tiles > 65535 || (int64_t)B * n * Hq > 0x7FFFFFFF || (int64_t)Sp + Ss > 0x7FFFFFFF) return MM_ERR_ARG;   // grid limits
+  if (B == 0) return MM_OK;
+  if ((q_sb | q_sh | kp_sb | kp_ss | kp_sh | vp_sb | vp_ss | vp_sh | ks_sb | ks_ss | ks_sh | vs_sb | vs_ss | vs_sh) & 7) return MM_ERR_ALIGN;
+  if (!mm_aligned16(q) || !mm_aligned16(kp) || !mm_aligned16(vp) || !mm_aligned16(ks) || !mm_aligned16(vs)) return MM_ERR_ALIGN;
+  DecodeSharedArgs a{q, kp, vp, ks, vs, B, n, Sp, Ss, Hq, Hkv, q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh,
+                     ks_sb, ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, workspace, nsplit, 0, tiles};
+  a.chunk = (Sp + Ss + nsplit - 1) / nsplit;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(nsplit, Hkv, B * tiles), block(256);
+  switch (G) {
+    case 1: hipLaunchKernelGGL(attn_decode_shared128_kernel<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(attn_decode_shared128_kernel<2>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(attn_decode_shared128_kernel<4>, grid, block, 0, s, a); break;
+  }
+  MM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * n * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }

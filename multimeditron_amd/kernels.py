@@ -745,6 +745,31 @@ def attn_decode(q, k, v, key_mask, scale):
     return out
 
 
+def attn_decode_shared_supported(q_dtype, Hq, Hkv, D):
+    """Shapes mm_attn_decode_shared takes: bf16, head_dim 128, 1, 2 or 4 query heads per key/value head (16 / G samples share a
+    16-column MFMA tile)."""
+    return q_dtype == torch.bfloat16 and D == 128 and Hq % Hkv == 0 and (Hq // Hkv) in (1, 2, 4)
+
+
+def attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale):
+    """One query token for each of the n samples of B prompts: q [B*n,Hq,D] (strided view ok; row b*n + j is sample j of prompt b)
+    over prompt b's prefix kp/vp [B,Sp,Hkv,D] followed by the row's own suffix ks/vs [B*n,Ss,Hkv,D] -> out [B*n,Hq,D].  key_mask
+    [B,Sp] or None covers the prefix; suffix keys are always visible.  The bits of attn_decode on the materialised concatenation
+    (mm_attn_decode_shared)."""
+    R, Hq, D = q.shape
+    B, Sp, Hkv = kp.shape[0], kp.shape[1], kp.shape[2]
+    Ss = ks.shape[1]
+    assert R == B * n and ks.shape[0] == R and vs.shape[0] == R and vp.shape[:3] == kp.shape[:3] and vs.shape[1] == Ss
+    assert q.stride(2) == 1 and kp.stride(3) == 1 and vp.stride(3) == 1 and ks.stride(3) == 1 and vs.stride(3) == 1
+    assert key_mask is None or (tuple(key_mask.shape) == (B, Sp) and key_mask.is_contiguous())
+    ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss)
+    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
+    call("mm_attn_decode_shared", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss, Hq, Hkv, D, q.stride(0), q.stride(1),
+         *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale), _p(out), _p(ws), ns, _stream())
+    return out
+
+
 # ---- MXFP8 KV cache (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 d of a head; the buffer layout is the library's) ----
 def kv8_bytes(B, Smax, Hkv, D):
     n = _lib.lib().mm_kv8_bytes(int(B), int(Smax), int(Hkv), int(D))

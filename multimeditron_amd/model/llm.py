@@ -397,6 +397,54 @@ class LayerKVCacheMX8(LayerKVCache):
         return out.view(B * S, Hq * D)
 
 
+class LayerKVCacheShared(LayerKVCache):
+    """The cache of generate(num_return_sequences=n): the prompt's keys and values ONCE per prompt, k / v [B, Sp_max, Hkv, D] (`len`
+    positions filled), and the tokens each of the B n sample rows has generated in ks / vs [B n, max_new, Hkv, D] (`slen` filled).
+    Row r = b n + j is sample j of prompt b and attends over [prefix of b | suffix of r] (include/mm_hip.h: mm_attn_decode_shared;
+    the bits of a LayerKVCache of B n rows that holds the prompt n times).  The prefill is a call of B rows into the empty cache;
+    every later call brings ONE token for each of the B n rows, and its key_mask is the PROMPT's [B, len] (suffix keys are always
+    visible)."""
+
+    def __init__(self, B, n, Sp_max, max_new, Hkv, D, dtype, device):
+        super().__init__(B, Sp_max, Hkv, D, dtype, device)
+        self.B, self.n = B, n
+        self.ks = torch.zeros((B * n, max(1, max_new), Hkv, D), dtype=dtype, device=device)
+        self.vs = torch.zeros((B * n, max(1, max_new), Hkv, D), dtype=dtype, device=device)
+        self.slen = 0
+
+    def append_dst(self):
+        """(suffix k, suffix v, slen): the append kernels write row r's new key / value at its own suffix position."""
+        if self.slen >= self.ks.shape[1]:
+            raise ValueError(f"the shared-prefix KV cache is full: {self.slen} generated tokens per sample row")
+        return self.ks, self.vs, self.slen
+
+    def decode_attend(self, q, key_mask, scale):
+        """The suffix row of position `slen` has been written for every sample: count it and attend q [B n, Hq, D]."""
+        if key_mask is not None and tuple(key_mask.shape) != (self.B, self.len):
+            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a shared-prefix cache: the prompt's mask "
+                             f"[{self.B}, {self.len}] is expected (generated tokens are always visible)")
+        self.slen += 1
+        return K.attn_decode_shared(q, self.k[:, : self.len], self.v[:, : self.len], self.ks[:, : self.slen], self.vs[:, : self.slen],
+                                    self.n, key_mask, scale)
+
+    @torch.no_grad()
+    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
+        Hq, D = a.Hq, a.D
+        if S > 1 and (self.len or B != self.B):
+            raise ValueError(f"{S} new positions for {B} rows on a shared-prefix KV cache of {self.B} prompts that holds {self.len}: only "
+                             "a prefill of the prompts into an empty cache or one token per sample row")
+        if S > 1:
+            return super().attend(qkv, cos, sin, key_mask, B, S, a)          # the prefill on B rows: writes the prefix
+        if B != self.B * self.n or not self.len:
+            raise ValueError(f"a step of {B} rows on a shared-prefix KV cache of {self.B} x {self.n} sample rows that holds {self.len} "
+                             "prompt positions")
+        ks, vs, pos = self.append_dst()
+        q, kn, vn = self.rope_views(qkv, cos, sin, B, 1, a)
+        ks[:, pos:pos + 1].copy_(kn)      # device-side memory plumbing
+        vs[:, pos:pos + 1].copy_(vn)
+        return self.decode_attend(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+
+
 class DecoderModel(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
@@ -572,13 +620,40 @@ class CausalLM(nn.Module):
             return f"{Hq} query heads on {Hkv} key/value heads (the MXFP8 decode kernel takes 1, 2 or 4 per key/value head)"
         return None
 
-    def new_cache(self, B, Smax, kv_cache: Optional[str] = None):
-        """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot."""
+    def samples_ok(self, B: int, n: int):
+        """None when B prompts can be decoded as n samples each over one shared copy of the prompt's keys and values
+        (LayerKVCacheShared), else the reason they cannot (the opt-in never falls back silently: new_cache and generate raise it
+        before the prefill)."""
+        c = self.config
+        if self.dtype != torch.bfloat16:
+            return f"model dtype is {self.dtype}, not bfloat16"
+        if c.head_dim != 128:
+            return f"head_dim is {c.head_dim} (the shared-prefix decode kernel is written for 128)"
+        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
+        if Hq % Hkv or Hq // Hkv not in (1, 2, 4):
+            return f"{Hq} query heads on {Hkv} key/value heads (the shared-prefix decode kernel takes 1, 2 or 4 per key/value head)"
+        return None
+
+    def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None):
+        """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot.
+        samples=n > 1: LayerKVCacheShared for B prompts of at most prompt_len positions and n sample rows each with room for
+        Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache."""
         c = self.config
         if kv_cache not in (None, "mxfp8"):
             raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
         if kv_cache is not None and self.kv_cache_ok(B) is not None:
             raise ValueError(f"kv_cache={kv_cache!r} cannot be used: {self.kv_cache_ok(B)}")
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise ValueError(f"samples must be an int >= 1, got {samples!r}")
+        if samples > 1:
+            if kv_cache is not None:
+                raise ValueError(f"samples={samples} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only")
+            if self.samples_ok(B, samples) is not None:
+                raise ValueError(f"samples={samples} cannot be used: {self.samples_ok(B, samples)}")
+            if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
+                raise ValueError(f"samples={samples} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
+            return [LayerKVCacheShared(B, samples, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
+                                       self.device) for _ in range(c.num_hidden_layers)]
         cls = LayerKVCache if kv_cache is None else LayerKVCacheMX8
         return [cls(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device) for _ in range(c.num_hidden_layers)]
 
@@ -608,7 +683,7 @@ class CausalLM(nn.Module):
         B, S, H = inputs_embeds.shape
         dev = inputs_embeds.device
         cache = past_key_values
-        past = cache[0].len if cache else 0
+        past = cache[0].len + getattr(cache[0], "slen", 0) if cache else 0
         rows = kwargs.get("loss_rows")
         if rows is not None and (labels is None or cache or use_cache or logits_to_keep or rows.n == 0 or rows.total != B * S):
             rows = None                                      # anything but a plain training forward: every position's logits

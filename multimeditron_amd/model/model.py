@@ -462,7 +462,8 @@ class MultiModalModelForCausalLM(nn.Module):
     def generate(self, batch: Dict[str, Any], max_new_tokens=512, temperature=0.1, do_sample=True, sync_every: int = 16,
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                  seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
-                 kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, **kwargs) -> torch.Tensor:
+                 kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, num_return_sequences: int = 1,
+                 **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -497,7 +498,31 @@ class MultiModalModelForCausalLM(nn.Module):
         projector, the splice and lm_head stay bf16.  It adds the quantisation's error to the prompt's logits and cached keys /
         values.  Composes with decode_weights, kv_cache and every sampler path.  A model that cannot use it -- not bf16, a linear
         whose input width mm_gemm_mx8 refuses (not a multiple of 128) -- raises ValueError before the prefill
-        (CausalLM.prefill_weights_ok)."""
+        (CausalLM.prefill_weights_ok).
+
+        num_return_sequences=n > 1 (opt-in; needs do_sample=True, greedy would return n equal rows): n sampled continuations of
+        every prompt.  The modalities are encoded, spliced and prefilled ONCE per prompt, and the prompt's keys and values are
+        stored once (LayerKVCacheShared: 2 Hkv D 2 (B Sp + B n max_new_tokens) bytes per layer instead of n copies of the prompt);
+        the prefill's last-row logits are repeated n times and every later step runs B n rows, whose decode attention reads a
+        prompt's keys once per 16 / (Hq / Hkv) samples (include/mm_hip.h: mm_attn_decode_shared -- the bits of the replicated
+        batch's attention).  Returns [B n, n_new]: row b n + j is sample j of prompt b (HF's order).  The device sampler draws
+        with Philox offset = step and call = row b n + j; the torch.multinomial path draws per row; eos bookkeeping, sync_every,
+        the early stop and the padded-length position quirk apply per row.  Composes with decode_weights (B n <= 16) and
+        prefill_weights.  NOT with kv_cache="mxfp8" (a shared-prefix MXFP8 cache is out of scope: ValueError).  A model that
+        cannot use it -- not bf16, head_dim other than 128, a number of query heads per key/value head other than 1, 2 or 4 --
+        raises ValueError before the prefill (CausalLM.samples_ok).  n = 1 is the path above, untouched."""
+        n = num_return_sequences
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
+        if n > 1:
+            if not do_sample:
+                raise ValueError(f"num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows")
+            if kv_cache is not None:
+                raise ValueError(f"num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
+                                 "shared-prefix cache is out of scope)")
+            why = self.model.samples_ok(int(batch["input_ids"].shape[0]), n)
+            if why is not None:
+                raise ValueError(f"num_return_sequences={n} cannot be used: {why}")
         if kv_cache not in (None, "mxfp8"):
             raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
         if kv_cache is not None:
@@ -507,7 +532,7 @@ class MultiModalModelForCausalLM(nn.Module):
         if decode_weights not in (None, "mxfp8"):
             raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
         if decode_weights is not None:
-            why = self.model.decode_weights_ok(int(batch["input_ids"].shape[0]))
+            why = self.model.decode_weights_ok(int(batch["input_ids"].shape[0]) * n)      # the decode steps run B n rows
             if why is not None:
                 raise ValueError(f"decode_weights={decode_weights!r} cannot be used: {why}")
         if prefill_weights not in (None, "mxfp8"):
@@ -533,16 +558,22 @@ class MultiModalModelForCausalLM(nn.Module):
                 gdev = generator.device if generator is not None else "cpu"
                 seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
         return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
-                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache, prefill_weights)
+                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache, prefill_weights,
+                              **({"samples": n} if n > 1 else {}))
 
-    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None, prefill_weights=None) -> torch.Tensor:
+    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None, prefill_weights=None,
+                  samples: int = 1) -> torch.Tensor:
         """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
         Here the chosen id, the eos bookkeeping and the next embedding lookup stay on the device (mm_decode_select +
         the embedding gather), so the host queues steps ahead of the GPU; it looks at `finished` only every `sync_every`
         tokens.  Steps issued past the point where every row had finished are cut off afterwards: the returned ids are
-        exactly the reference's (same length, same values)."""
+        exactly the reference's (same length, same values).
+
+        samples = n > 1 (generate's num_return_sequences): the prefill runs on the B prompts into a LayerKVCacheShared; its logits
+        are repeated n times and from there on B stands for the B n sample rows.  The decode steps hand the PROMPT's mask to the
+        cache (generated tokens are always visible)."""
         if self._flat is None:
             self.pack_parameters()
         dev = self.device
@@ -552,7 +583,7 @@ class MultiModalModelForCausalLM(nn.Module):
         V = self._llm_cfg.vocab_size
         eos = self.config.eos_token_idx
         if max_new_tokens <= 0:
-            return torch.empty((B, 0), dtype=torch.int64)
+            return torch.empty((B * samples, 0), dtype=torch.int64)
         if decode_weights is not None and self.model._decode_w8 is None:
             self.model.quantize_decode_weights(decode_weights)
         dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
@@ -561,10 +592,16 @@ class MultiModalModelForCausalLM(nn.Module):
             attention_mask = batch["attention_mask"].to(dev)
             position_ids = batch["position_ids"].to(dev)
             seq_length = attention_mask.shape[1]
-            cache = self.model.new_cache(B, seq_length + max_new_tokens, kv_cache=kv_cache)
+            if samples > 1:
+                cache = self.model.new_cache(B, seq_length + max_new_tokens, samples=samples, prompt_len=seq_length)
+                prompt_mask = attention_mask
+                B = B * samples                                # the rows of every buffer below and of every step after the prefill
+            else:
+                cache = self.model.new_cache(B, seq_length + max_new_tokens, kv_cache=kv_cache)
             # device-resident loop state (plumbing): the growing mask is a view of one preallocated buffer
-            full_mask = torch.ones((B, seq_length + max_new_tokens), dtype=attention_mask.dtype, device=dev)
-            full_mask[:, :seq_length] = attention_mask
+            if samples == 1:
+                full_mask = torch.ones((B, seq_length + max_new_tokens), dtype=attention_mask.dtype, device=dev)
+                full_mask[:, :seq_length] = attention_mask
             out_ids = torch.full((B, max_new_tokens), eos, dtype=torch.int64, device=dev)
             finished = torch.zeros(B, dtype=torch.uint8, device=dev)
             next_ids = torch.empty(B, dtype=torch.int64, device=dev)
@@ -575,11 +612,13 @@ class MultiModalModelForCausalLM(nn.Module):
             for i in range(max_new_tokens):
                 if i > 0:
                     position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
-                    attention_mask = full_mask[:, : seq_length + i]
+                    attention_mask = full_mask[:, : seq_length + i] if samples == 1 else prompt_mask
                 pw = {"prefill_weights": prefill_weights} if i == 0 and prefill_weights is not None else {}      # the prefill call only
                 out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
                                  past_key_values=cache, use_cache=True, logits_to_keep=1, **dw, **pw)
                 logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
+                if samples > 1 and i == 0:
+                    logits2d = logits2d.repeat_interleave(samples, dim=0)      # plumbing: sample j of prompt b is row b n + j
                 if sampler is not None:
                     k_, p_, mp_, sd_ = sampler
                     tok = K.sample(logits2d, V, temperature, top_k=k_, top_p=p_, min_p=mp_, seed=sd_, offset=i, ws=sample_ws,

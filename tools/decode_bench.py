@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
-                                [--prefill-weights mxfp8]
+                                [--prefill-weights mxfp8] [--samples n]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
 (generate(kv_cache=...)).  --prefill-weights mxfp8: the prefill runs its decoder linears as MXFP8 x MXFP8 GEMMs
 (generate(prefill_weights=...)); the first step alone (max_new_tokens = 1: the prefill and one token choice) is then timed for BOTH
 settings in this process, best of three after a warm-up each, before the usual line.  The KV bytes a decode step reads per token
-(every layer's K and V of B x S positions) are printed."""
+(every layer's K and V of B x S positions) are printed.
+--samples n: in this one process, (i) generate(num_return_sequences=n) on the B prompts against (ii) the existing path on the prompts
+repeated n times (a batch of B n rows), alternating, best of three each after a warm-up: prefill + 1 token, ms/token and the bytes of
+the KV cache each allocates; then the decode-attention launch alone at the last step's lengths, mm_attn_decode_shared on the shared
+cache against mm_attn_decode on B n rows, over 16 layers' caches.  Sampled (T = 1, seed 0 unless --sample says otherwise).  The other
+flags apply to both sides (--kv-cache is refused by generate with n > 1)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -40,6 +45,13 @@ if "--prefill-weights" in sys.argv:
     i = sys.argv.index("--prefill-weights")
     PW = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+NS = 1
+if "--samples" in sys.argv:
+    i = sys.argv.index("--samples")
+    NS = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    if SAMPLE is None:
+        SAMPLE = {"T": 1.0, "seed": 0}
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 33
@@ -53,6 +65,92 @@ model = MultiModalModelForCausalLM(cfg, device="cuda")
 model.pack_parameters()
 batch, _ = bench.synthetic_batch(B, S, 1, 256, vocab, (llm["vocab_size"], llm["vocab_size"] + 1, 128002), 7, "cuda", 224)
 batch["attention_mask"] = torch.ones(B, S, dtype=torch.long, device="cuda")
+
+
+def repeated(batch, n):
+    """the batch with every prompt n times in a row (row b n + j = prompt b): what a caller without num_return_sequences builds"""
+    mm = batch["processed_multimodal_inputs"]
+    P = mm["token_range"]["image"].numel() // B
+    return dict(input_ids=batch["input_ids"].repeat_interleave(n, 0), position_ids=batch["position_ids"].repeat_interleave(n, 0),
+                attention_mask=batch["attention_mask"].repeat_interleave(n, 0), labels=None,
+                processed_multimodal_inputs={"batch_idx": {"image": torch.arange(B * n, device="cuda").repeat_interleave(P)},
+                                             "token_range": {"image": mm["token_range"]["image"].view(B, P).repeat_interleave(n, 0).reshape(-1)},
+                                             "stacked": {"image": mm["stacked"]["image"].repeat_interleave(n, 0)}})
+
+
+def compare_samples(n):
+    from multimeditron_amd import kernels as K
+    kw = dict(SAMPLE)
+    T = kw.pop("T", 1.0)
+    kw.setdefault("seed", 0)
+    if DW:
+        kw["decode_weights"] = DW
+    if PW:
+        kw["prefill_weights"] = PW
+    rep = repeated(batch, n)
+    made = []
+    new_cache = model.model.new_cache
+    model.model.new_cache = lambda *a, **k: made.append(new_cache(*a, **k)) or made[-1]
+
+    def go(shared, new):
+        del made[:]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ids = model.generate(batch, max_new_tokens=new, temperature=T, num_return_sequences=n, **kw) if shared else \
+            model.generate(rep, max_new_tokens=new, temperature=T, **kw)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        nbytes = sum(t_.numel() * t_.element_size() for c in made[0] for t_ in vars(c).values() if torch.is_tensor(t_))
+        del made[:]
+        return dt, ids, nbytes
+
+    res = {}
+    for shared in (True, False):
+        go(shared, 2)                                      # warm-up (and the MXFP8 copies, if asked for)
+    t1, tn = {True: [], False: []}, {True: [], False: []}
+    for _ in range(3):                                     # alternating
+        for shared in (True, False):
+            t1[shared].append(go(shared, 1)[0])
+            dt, ids, nbytes = go(shared, N)
+            tn[shared].append(dt)
+            res[shared] = (tuple(ids.shape), nbytes)
+    for shared in (True, False):
+        a, b = min(t1[shared]), min(tn[shared])
+        name = f"num_return_sequences={n} on {B} prompts" if shared else f"{B} prompts repeated {n} times ({B * n} rows)"
+        print(f"{name}: prefill+1 token {a * 1e3:.1f} ms; decode {(b - a) / (N - 1) * 1e3:.2f} ms/token (all runs "
+              f"{', '.join(f'{(y - x) / (N - 1) * 1e3:.2f}' for x, y in zip(t1[shared], tn[shared]))}); KV cache {res[shared][1] / 1e9:.3f} GB allocated; "
+              f"ids {res[shared][0]}", flush=True)
+    model.model.new_cache = new_cache
+    # the decode-attention launch alone, at the last step's lengths
+    lc = model.model.config
+    Hq, Hkv, D, L, Ss = lc.num_attention_heads, lc.num_key_value_heads, lc.head_dim, 16, N - 1
+    bf = torch.bfloat16
+    q = torch.randn(B * n, Hq, D, device="cuda", dtype=bf)
+    kp = [torch.randn(B, S, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+    ks = [torch.randn(B * n, N, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+    kr = [torch.randn(B * n, S + N, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+
+    def timed(name, fn, nbytes, reps=6):
+        for i in range(L):
+            fn(i)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            for i in range(L):
+                fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / (reps * L)
+        print(f"{name:58s} {us:7.1f} us/launch   {nbytes / 1e6:6.1f} MB of keys and values   {nbytes / us / 1e6:5.2f} TB/s", flush=True)
+
+    row = 2 * Hkv * D * 2
+    for _ in range(2):
+        timed(f"attention, shared prefix ({B} x {S} + {B * n} x {Ss} keys)",
+              lambda i: K.attn_decode_shared(q, kp[2 * i], kp[2 * i + 1], ks[2 * i][:, :Ss], ks[2 * i + 1][:, :Ss], n, None, D ** -0.5),
+              (B * S + B * n * Ss) * row)
+        timed(f"attention, replicated ({B * n} x {S + Ss} keys)",
+              lambda i: K.attn_decode(q, kr[2 * i][:, :S + Ss], kr[2 * i + 1][:, :S + Ss], None, D ** -0.5), B * n * (S + Ss) * row)
 
 
 def run(n, pw="same"):
@@ -75,6 +173,9 @@ def run(n, pw="same"):
     return time.perf_counter() - t, ids
 
 
+if NS > 1:
+    compare_samples(NS)
+    sys.exit(0)
 run(2)
 if PW:
     first = {}
