@@ -17,7 +17,8 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional
+from functools import partial
+from typing import Any, Dict, List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -129,6 +130,17 @@ class Attention(nn.Module):
         """(q_norm weight, k_norm weight, eps) of a Qwen3 layer, else None."""
         return None if self.q_norm is None else (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps)
 
+    def rope_views(self, qkv, cos, sin, B, S):
+        """(per-head norm +) RoPE of the fused projection in place (no autograd: nothing keeps a backward) -> its q, k, v as strided
+        views."""
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        if self.q_norm is not None:
+            K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, *self.qkn(), cos, sin, out=qkv, want_rstd=False)
+        else:
+            K.rope_apply_(qkv, B * S, Hq + Hkv, D, (Hq + 2 * Hkv) * D, cos, sin)
+        return (qkv[:, : Hq * D].view(B, S, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
+                qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
+
 
 class MLP(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
@@ -180,6 +192,50 @@ class XIELUMLP(nn.Module):
         return K.xielu_fwd(u, f.alpha_p.data, f.alpha_n.data, *f.consts())
 
 
+class W16(NamedTuple):
+    """One matrix of the inference chains in the model's own format (a layer's fused q|k|v, o_proj, fused gate|up / up_proj,
+    down_proj, or lm_head): the launches that read it.  Holds where to read the tensor, not the tensor: packing, .to() and
+    resize_token_embeddings move it.  The chains queue these launches once per layer and token: plain positional calls."""
+    get: Any      # () -> the weight: a ParamGroup's tensor, or partial(getattr, linear, "weight")
+
+    def linear(self, x, mx8=False, **kw):
+        """mm_gemm (which streams the weights itself when x has at most 16 rows)."""
+        assert not mx8
+        return K.linear_fwd(x, self.get(), **kw)
+
+    def stream(self, x, residual=None, norm_w=None, eps=0.0, ldc_pad=False):
+        """The weight-streaming linear of a decode step, with its optional fused RMSNorm (norm_w, eps), residual and ldc_pad."""
+        return K.decode_linear(x, self.get(), None, residual, norm_w, eps, ldc_pad)
+
+    def qkv_rope_append(self, x, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w, eps):
+        return K.decode_qkv_rope_append(x, self.get(), bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w, eps)
+
+    def gateup_swiglu(self, x, I, norm_w, eps):
+        return K.decode_gateup_swiglu(x, self.get(), I, norm_w, eps)
+
+
+class W8(NamedTuple):
+    """The same matrix as its MXFP8 copy (CausalLM.quantize_decode_weights): the packed buffer and the number of output features."""
+    packed: torch.Tensor
+    N: int
+
+    def linear(self, x, mx8=False, **kw):
+        """Weight-only (a decode step: the bf16 x streams the copy), or mx8=True the prefill's MXFP8 x MXFP8 GEMM on the
+        block-scaled MFMA: x quantised at the rounding point where the bf16 chain hands it to its GEMM."""
+        if mx8:
+            return K.gemm_mx8(K.quant_mxfp8(x), x.shape[0], self.packed, self.N, x.shape[1], **kw)
+        return K.decode_linear_w8(x, self.packed, self.N, **kw)
+
+    def stream(self, x, residual=None, norm_w=None, eps=0.0, ldc_pad=False):
+        return K.decode_linear_w8(x, self.packed, self.N, None, residual, norm_w, eps, ldc_pad)
+
+    def qkv_rope_append(self, x, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w, eps):
+        return K.decode_qkv_rope_append_w8(x, self.packed, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w, eps)
+
+    def gateup_swiglu(self, x, I, norm_w, eps):
+        return K.decode_gateup_swiglu_w8(x, self.packed, I, norm_w, eps)
+
+
 class DecoderLayer(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
@@ -190,92 +246,68 @@ class DecoderLayer(nn.Module):
         setattr(self, n1, Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device))
         setattr(self, n2, Norm(cfg.hidden_size, cfg.rms_norm_eps, bias=False, dtype=dtype, device=device))
         self._norm_names = (n1, n2)
+        a, m = self.self_attn, self.mlp
+        self.w16 = {"qkv": W16(a._wqkv.tensor), "o": W16(partial(getattr, a.o_proj, "weight")), "gu": W16(m._wgu.tensor),
+                    "down": W16(partial(getattr, m.down_proj, "weight"))}
 
     def norms(self):
         """(the norm in front of attention, the norm in front of the MLP): HF names them differently for Apertus."""
         return getattr(self, self._norm_names[0]), getattr(self, self._norm_names[1])
 
     @torch.no_grad()
-    def decode_step(self, x, cos, sin, key_mask, B, cache, w8=None):
-        """One new token per sequence (generate's decode loop, reference model.py:595-602): the four linears take the
-        weight-streaming GEMM (M <= 16), RoPE and the cache append are one pass, attention is the split-K stream over the
-        cache (bf16 or MXFP8: the cache says where the append kernel writes the new row and attends over itself).  Same arithmetic and
-        rounding points as forward().  (Folding RMSNorm / SwiGLU into the GEMM's x operand was
-        measured SLOWER: every workgroup redoes the transform on all 64 lanes and the kernel turns VALU-bound, 43 vs 27 us
-        and 57 vs 25 us per launch, so they stay separate launches.)
-        w8: this layer's MXFP8 copies (CausalLM.quantize_decode_weights) -- the four linears stream those instead."""
+    def infer(self, w, x, cos, sin, key_mask, B, S, cache, step):
+        """The layer without autograd, on the matrices w (this layer's W16s, or its W8s from CausalLM.quantize_decode_weights): the
+        same arithmetic and rounding points as forward().  rmsnorm_fwd, linear (q|k|v + bias), attention, linear (o_proj + residual),
+        rmsnorm_fwd, linear (gate|up or up_proj), swiglu_fwd / xIELU, linear (down_proj + residual).
+
+        step: one new token per sequence (generate's decode loop, reference model.py:595-602).  The four linears stream their
+        weights (W16: mm_gemm at M <= 16; W8: the weight-only kernel), RoPE and the cache append are one pass (rope_append_ /
+        qk_norm_rope_append_) and attention is the split-K stream over the cache (bf16, MXFP8 or shared-prefix: the cache says
+        where the append kernel writes the new row and attends over itself).  (Folding RMSNorm / SwiGLU into the GEMM's x operand
+        was measured SLOWER: every workgroup redoes the transform on all 64 lanes and the kernel turns VALU-bound, 43 vs 27 us and
+        57 vs 25 us per launch, so they stay separate launches here; decode_step_fused folds them into the weight-streaming kernels.)
+
+        not step: the MXFP8 prefill (forward(prefill_weights="mxfp8"), w = the W8s).  Each linear is quant_mxfp8 of its bf16 input +
+        gemm_mx8; RoPE / q-k norm, the cache append and attn_fwd are the cache's attend, without a cache rope_views + attn_fwd.
+        Everything but the eight new launches is the existing kernel on bf16 data."""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         n1, n2 = self.norms()
+        mx8 = not step
         h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
-        bqkv = a._bqkv.tensor() if a._bqkv is not None else None
-
-        def lin(name, t, w, **kw):
-            return K.linear_fwd(t, w, **kw) if w8 is None else K.decode_linear_w8(t, *w8[name], **kw)
-
-        qkv = lin("qkv", h, a._wqkv.tensor(), bias=bqkv)
-        if a.q_norm is not None:
-            K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, *cache.append_dst())
-        else:
-            K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, *cache.append_dst())
-        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
-        x = lin("o", o.view(B, Hq * D), a.o_proj.weight, residual=x)
-        h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
-        u = lin("gu", h, m._wgu.tensor())
-        act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
-        return lin("down", act, m.down_proj.weight, residual=x)
-
-    @torch.no_grad()
-    def decode_step_fused(self, x, cos, sin, key_mask, B, cache, w8=None):
-        """The same decode step with the tiny launches folded into the weight-streaming GEMMs (round 3; csrc/mm_gemm.hip
-        gemv_stream_kernel): input RMSNorm + q|k|v + RoPE + cache append, o_proj + residual, post-attention RMSNorm + gate|up +
-        SwiGLU, down_proj + residual -- 6 launches with the two attention kernels, none of them a norm.  x = residual stream in
-        and out.  Same bits as decode_step.  w8: this layer's MXFP8 copies -- the same four launches on half the weight bytes."""
-        a, m = self.self_attn, self.mlp
-        Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        n1, n2 = self.norms()
-        if w8 is not None:
-            qkv = K.decode_qkv_rope_append_w8(x, w8["qkv"][0], a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
-                                              *cache.append_dst(), norm_w=n1.weight, eps=n1.eps)
-            o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
-            x = K.decode_linear_w8(o.view(B, Hq * D), *w8["o"], residual=x)
-            act = K.decode_gateup_swiglu_w8(x, w8["gu"][0], m.I, norm_w=n2.weight, eps=n2.eps)
-            return K.decode_linear_w8(act, *w8["down"], residual=x)
-        qkv = K.decode_qkv_rope_append(x, a._wqkv.tensor(), a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin,
-                                       *cache.append_dst(), norm_w=n1.weight, eps=n1.eps)
-        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
-        x = K.decode_linear(o.view(B, Hq * D), a.o_proj.weight, residual=x)
-        act = K.decode_gateup_swiglu(x, m._wgu.tensor(), m.I, norm_w=n2.weight, eps=n2.eps)
-        return K.decode_linear(act, m.down_proj.weight, residual=x)
-
-    @torch.no_grad()
-    def prefill_mx8(self, x, cos, sin, key_mask, B, S, cache, w8):
-        """forward() of a call that is not a decode step, without autograd, with the four linears as MXFP8 x MXFP8 GEMMs on the
-        block-scaled MFMA (kernels.gemm_mx8): each quantises its bf16 input (kernels.quant_mxfp8, at the rounding point where
-        forward() hands that tensor to its GEMM) and reads this layer's copy in w8 (CausalLM.quantize_decode_weights).  The
-        order of the launches: rmsnorm_fwd, quant, gemm (q|k|v + bias), RoPE / q-k norm + cache append + attn_fwd (the cache's
-        attend; without a cache rope_views + attn_fwd), quant, gemm (o_proj + residual), rmsnorm_fwd, quant, gemm (gate|up or
-        up_proj), swiglu_fwd / xIELU, quant, gemm (down_proj + residual).  Everything but the eight new launches is the existing
-        kernel on bf16 data."""
-        a, m = self.self_attn, self.mlp
-        n1, n2 = self.norms()
-
-        def lin(name, t, **kw):
-            packed, N = w8[name]
-            return K.gemm_mx8(K.quant_mxfp8(t), t.shape[0], packed, N, t.shape[1], **kw)
-
-        h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
-        qkv = lin("qkv", h, bias=a._bqkv.tensor() if a._bqkv is not None else None)
-        if cache is not None:
+        qkv = w["qkv"].linear(h, mx8, bias=a._bqkv.tensor() if a._bqkv is not None else None)
+        if step:
+            if a.q_norm is not None:
+                K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, *a.qkn(), cos, sin, *cache.append_dst())
+            else:
+                K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, *cache.append_dst())
+            o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+        elif cache is not None:
             o = cache.attend(qkv, cos, sin, key_mask, B, S, a)
         else:
-            q, kn, vn = LayerKVCache.rope_views(qkv, cos, sin, B, S, a)
-            o = K.attn_fwd(q, kn, vn, key_mask, True, a.D ** -0.5)[0].view(B * S, a.Hq * a.D)
-        x = lin("o", o, residual=x)
+            q, kn, vn = a.rope_views(qkv, cos, sin, B, S)
+            o = K.attn_fwd(q, kn, vn, key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
+        x = w["o"].linear(o, mx8, residual=x)
         h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
-        u = lin("gu", h)
+        u = w["gu"].linear(h, mx8)
         act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
-        return lin("down", act, residual=x)
+        return w["down"].linear(act, mx8, residual=x)
+
+    @torch.no_grad()
+    def decode_step_fused(self, w, x, cos, sin, key_mask, B, cache):
+        """The decode step with the tiny launches folded into the weight-streaming GEMMs (csrc/mm_gemm.hip gemv_stream_kernel):
+        input RMSNorm + q|k|v + RoPE + cache append, o_proj + residual, post-attention RMSNorm + gate|up + SwiGLU, down_proj +
+        residual -- 6 launches with the two attention kernels, none of them a norm.  x = residual stream in and out.  Same bits as
+        infer(step=True).  w: this layer's W16s, or its W8s -- the same four launches on half the weight bytes."""
+        a, m = self.self_attn, self.mlp
+        Hq, Hkv, D = a.Hq, a.Hkv, a.D
+        n1, n2 = self.norms()
+        qkv = w["qkv"].qkv_rope_append(x, a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin, *cache.append_dst(),
+                                       n1.weight, n1.eps)
+        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
+        x = w["o"].stream(o.view(B, Hq * D), x)
+        act = w["gu"].gateup_swiglu(x, m.I, n2.weight, n2.eps)
+        return w["down"].stream(act, x)
 
     def can_decode_step(self, x, B, S, cache):
         a = self.self_attn
@@ -288,13 +320,12 @@ class DecoderLayer(nn.Module):
                 and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
                 and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
 
-    def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None, w8=None):
-        """rows (functional.LossRows, LAST layer of a training forward only): nothing after this layer's attention reads the
+    def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None):
+        """The training / generic route (CausalLM.forward has decided that the call is neither a decode step nor an MXFP8 prefill).
+        rows (functional.LossRows, LAST layer of a training forward only): nothing after this layer's attention reads the
         rows that carry no label -- their hidden states feed no later layer and no loss term -- so o_proj, the post-attention norm
         and the MLP run on the labelled rows alone and the layer returns [rows.n, H].  (Keys and values come from every row, so
         attention itself is computed in full.)  Same loss, same gradients."""
-        if self.can_decode_step(x, B, S, cache):
-            return self.decode_step(x, cos, sin, key_mask, B, cache, w8=w8)
         a = self.self_attn
         n1, n2 = self.norms()
         h, x = n1(x)
@@ -316,12 +347,17 @@ class DecoderLayer(nn.Module):
 
 
 class LayerKVCache:
-    """Contiguous per-layer KV cache [B, Smax, Hkv, D] for the decode loop of generate (model.py:581-638)."""
+    """Contiguous per-layer KV cache [B, Smax, Hkv, D] for the decode loop of generate (model.py:581-638).  attend is the one
+    sequence every cache runs; a subclass overrides the small steps below it."""
 
     def __init__(self, B, Smax, Hkv, D, dtype, device):
         self.k = torch.zeros((B, Smax, Hkv, D), dtype=dtype, device=device)
         self.v = torch.zeros((B, Smax, Hkv, D), dtype=dtype, device=device)
         self.len = 0
+
+    def positions(self):
+        """How many positions of every sequence the cache holds: where the next one goes."""
+        return self.len
 
     def append_dst(self):
         """(kcache, vcache, pos) of the decode step's append kernels: where the new token's k / v rows go."""
@@ -332,29 +368,38 @@ class LayerKVCache:
         self.len += 1
         return K.attn_decode(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, scale)
 
-    @staticmethod
-    def rope_views(qkv, cos, sin, B, S, a: Attention):
-        """(per-head norm +) RoPE of the fused projection in place (prefill keeps no backward) -> its q, k, v as strided views."""
-        Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        W = (Hq + 2 * Hkv) * D
-        if a.q_norm is not None:
-            K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, a.q_norm.weight, a.k_norm.weight, a.q_norm.eps, cos, sin, out=qkv, want_rstd=False)
-        else:
-            K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
-        return (qkv[:, : Hq * D].view(B, S, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
-                qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
+    def accept(self, B, S):
+        """ValueError for a call of S new positions on B rows that this cache does not take."""
+
+    def streams(self, dtype, a: Attention):
+        """Whether ONE new position is attended by the decode stream (attend_row); attn_fwd otherwise."""
+        return K.attn_decode_supported(dtype, a.Hq, a.Hkv, a.D)
+
+    def store(self, kn, vn, S):
+        """The S new k / v rows go behind the `len` held ones (device-side memory plumbing)."""
+        self.k[:, self.len:self.len + S].copy_(kn)
+        self.v[:, self.len:self.len + S].copy_(vn)
+
+    def attend_row(self, q, key_mask, scale):
+        """The one new row is stored: count it and attend q over the cache."""
+        return self.decode_attend(q, key_mask, scale)
+
+    def prefill_kv(self, kn, vn):
+        """The keys and values attn_fwd reads once the new rows are stored and counted."""
+        return self.k[:, : self.len], self.v[:, : self.len]
 
     @torch.no_grad()
     def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
-        Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        q, kn, vn = self.rope_views(qkv, cos, sin, B, S, a)
-        self.k[:, self.len:self.len + S].copy_(kn)      # device-side memory plumbing
-        self.v[:, self.len:self.len + S].copy_(vn)
-        if S == 1 and K.attn_decode_supported(qkv.dtype, Hq, Hkv, D):      # decode step: stream the cache once (split-K)
-            return self.decode_attend(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+        """The fused projection of S new positions -> their attention output [B S, Hq D]: check what this cache accepts, RoPE,
+        store the new rows, attend over them."""
+        Hq, D = a.Hq, a.D
+        self.accept(B, S)
+        q, kn, vn = a.rope_views(qkv, cos, sin, B, S)
+        self.store(kn, vn, S)
+        if S == 1 and self.streams(qkv.dtype, a):      # decode step: stream the cache once (split-K)
+            return self.attend_row(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
         self.len += S
-        out, _ = K.attn_fwd(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, True, D ** -0.5)
-        return out.view(B * S, Hq * D)
+        return K.attn_fwd(q, *self.prefill_kv(kn, vn), key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
 
 
 class LayerKVCacheMX8(LayerKVCache):
@@ -375,35 +420,35 @@ class LayerKVCacheMX8(LayerKVCache):
         return self.k, self.v, 0
 
     def decode_attend(self, q, key_mask, scale):
-        return self._attend_row(q, self.k, self.v, key_mask, scale)
+        self.store(self.k, self.v, 1)
+        return self.attend_row(q, key_mask, scale)
 
-    def _attend_row(self, q, k1, v1, key_mask, scale):
-        K.kv8_append(k1, v1, self.buf, self.Smax, self.len)
-        self.len += 1
-        return K.attn_decode_kv8(q, self.buf, self.len, self.Smax, self.Hkv, key_mask, scale)
-
-    @torch.no_grad()
-    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
-        Hq, D = a.Hq, a.D
+    def accept(self, B, S):
         if S > 1 and self.len:
             raise ValueError(f"{S} new positions on an MXFP8 KV cache that holds {self.len}: only a prefill into an empty cache or "
                              "one token per step (attending over the cached prompt would need a dequantising prefill)")
-        q, kn, vn = self.rope_views(qkv, cos, sin, B, S, a)
-        if S == 1:
-            return self._attend_row(q.view(B, Hq, D), kn, vn, key_mask, D ** -0.5).view(B, Hq * D)
-        K.kv8_append(kn, vn, self.buf, self.Smax, 0)
-        self.len = S
-        out, _ = K.attn_fwd(q, kn, vn, key_mask, True, D ** -0.5)
-        return out.view(B * S, Hq * D)
+
+    def streams(self, dtype, a: Attention):
+        return True
+
+    def store(self, kn, vn, S):
+        K.kv8_append(kn, vn, self.buf, self.Smax, self.len)
+
+    def attend_row(self, q, key_mask, scale):
+        self.len += 1
+        return K.attn_decode_kv8(q, self.buf, self.len, self.Smax, self.Hkv, key_mask, scale)
+
+    def prefill_kv(self, kn, vn):
+        return kn, vn      # the cache was empty: the prompt's own bf16 rows
 
 
 class LayerKVCacheShared(LayerKVCache):
     """The cache of generate(num_return_sequences=n): the prompt's keys and values ONCE per prompt, k / v [B, Sp_max, Hkv, D] (`len`
     positions filled), and the tokens each of the B n sample rows has generated in ks / vs [B n, max_new, Hkv, D] (`slen` filled).
     Row r = b n + j is sample j of prompt b and attends over [prefix of b | suffix of r] (include/mm_hip.h: mm_attn_decode_shared;
-    the bits of a LayerKVCache of B n rows that holds the prompt n times).  The prefill is a call of B rows into the empty cache;
-    every later call brings ONE token for each of the B n rows, and its key_mask is the PROMPT's [B, len] (suffix keys are always
-    visible)."""
+    the bits of a LayerKVCache of B n rows that holds the prompt n times).  The prefill is a call of B rows into the empty cache
+    (the base class's steps: it writes the prefix); every later call brings ONE token for each of the B n rows, and its key_mask is
+    the PROMPT's [B, len] (suffix keys are always visible)."""
 
     def __init__(self, B, n, Sp_max, max_new, Hkv, D, dtype, device):
         super().__init__(B, Sp_max, Hkv, D, dtype, device)
@@ -411,6 +456,9 @@ class LayerKVCacheShared(LayerKVCache):
         self.ks = torch.zeros((B * n, max(1, max_new), Hkv, D), dtype=dtype, device=device)
         self.vs = torch.zeros((B * n, max(1, max_new), Hkv, D), dtype=dtype, device=device)
         self.slen = 0
+
+    def positions(self):
+        return self.len + self.slen
 
     def append_dst(self):
         """(suffix k, suffix v, slen): the append kernels write row r's new key / value at its own suffix position."""
@@ -427,22 +475,25 @@ class LayerKVCacheShared(LayerKVCache):
         return K.attn_decode_shared(q, self.k[:, : self.len], self.v[:, : self.len], self.ks[:, : self.slen], self.vs[:, : self.slen],
                                     self.n, key_mask, scale)
 
-    @torch.no_grad()
-    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
-        Hq, D = a.Hq, a.D
+    def accept(self, B, S):
         if S > 1 and (self.len or B != self.B):
             raise ValueError(f"{S} new positions for {B} rows on a shared-prefix KV cache of {self.B} prompts that holds {self.len}: only "
                              "a prefill of the prompts into an empty cache or one token per sample row")
-        if S > 1:
-            return super().attend(qkv, cos, sin, key_mask, B, S, a)          # the prefill on B rows: writes the prefix
-        if B != self.B * self.n or not self.len:
+        if S == 1 and (B != self.B * self.n or not self.len):
             raise ValueError(f"a step of {B} rows on a shared-prefix KV cache of {self.B} x {self.n} sample rows that holds {self.len} "
                              "prompt positions")
+        if S == 1:
+            self.append_dst()      # raises when the suffix is full
+
+    def streams(self, dtype, a: Attention):
+        return True
+
+    def store(self, kn, vn, S):
+        if S > 1:
+            return super().store(kn, vn, S)          # the prefill on B rows: writes the prefix
         ks, vs, pos = self.append_dst()
-        q, kn, vn = self.rope_views(qkv, cos, sin, B, 1, a)
         ks[:, pos:pos + 1].copy_(kn)      # device-side memory plumbing
         vs[:, pos:pos + 1].copy_(vn)
-        return self.decode_attend(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
 
 
 class DecoderModel(nn.Module):
@@ -477,6 +528,7 @@ class CausalLM(nn.Module):
             self.lm_head.weight = self.model.embed_tokens.weight
         self._inv_freq = None
         self._decode_w8 = None      # quantize_decode_weights(): plain tensors beside the modules, neither parameters nor buffers
+        self._w16 = {"fmt": None, "layers": [layer.w16 for layer in self.model.layers], "lm_head": W16(partial(getattr, self.lm_head, "weight"))}
 
     # -- reference surface -------------------------------------------------------------------------
     @property
@@ -537,22 +589,26 @@ class CausalLM(nn.Module):
         if self.dtype != torch.bfloat16:
             raise ValueError(f"MXFP8 decode weights need a bf16 model, this one is {self.dtype}")
 
-        def pack(w):
+        def pack(w16):
+            w = w16.get().data
             if w.shape[1] % 32:
                 raise ValueError(f"MXFP8 decode weights need in_features % 32 == 0, got a [{w.shape[0]}, {w.shape[1]}] matrix")
-            return K.quant_mxfp8(w), w.shape[0]
+            return W8(K.quant_mxfp8(w), w.shape[0])
 
-        layers = []
-        for layer in self.model.layers:
-            a, m = layer.self_attn, layer.mlp
-            layers.append({"qkv": pack(a._wqkv.tensor()), "o": pack(a.o_proj.weight.data), "gu": pack(m._wgu.tensor()),
-                           "down": pack(m.down_proj.weight.data)})
-        self._decode_w8 = {"fmt": fmt, "layers": layers, "lm_head": pack(self.lm_head.weight.data) if lm_head else None}
+        self._decode_w8 = {"fmt": fmt, "layers": [{name: pack(w) for name, w in lw.items()} for lw in self._w16["layers"]],
+                           "lm_head": pack(self._w16["lm_head"]) if lm_head else None}
         return self
 
     def drop_decode_weights(self):
         """Free the copies of quantize_decode_weights()."""
         self._decode_w8 = None
+
+    def _linear_widths(self):
+        """The input widths of the decoder layers' linears, ascending."""
+        widths = {self.config.hidden_size}
+        for layer in self.model.layers:
+            widths |= {layer.self_attn.Hq * layer.self_attn.D, layer.mlp.I}
+        return sorted(widths)
 
     def decode_weights_ok(self, B: int):
         """None when a decode step of B sequences can stream the MXFP8 copies, else the reason it cannot (the opt-in never falls
@@ -561,10 +617,7 @@ class CausalLM(nn.Module):
             return f"model dtype is {self.dtype}, not bfloat16"
         if B > 16:
             return f"batch of {B} sequences (the weight-streaming decode step takes at most 16)"
-        widths = {self.config.hidden_size}
-        for layer in self.model.layers:
-            widths |= {layer.self_attn.Hq * layer.self_attn.D, layer.mlp.I}
-        for Kd in sorted(widths):
+        for Kd in self._linear_widths():
             if Kd % 32:
                 return f"a weight matrix with {Kd} input features (not a multiple of 32)"
             if not K.decode_fits(B, Kd):
@@ -579,10 +632,7 @@ class CausalLM(nn.Module):
             return f"model dtype is {self.dtype}, not bfloat16"
         if check_grad and torch.is_grad_enabled():
             return "autograd is enabled (the MXFP8 prefill has no backward: run it under torch.no_grad())"
-        widths = {self.config.hidden_size}
-        for layer in self.model.layers:
-            widths |= {layer.self_attn.Hq * layer.self_attn.D, layer.mlp.I}
-        for Kd in sorted(widths):
+        for Kd in self._linear_widths():
             why = K.gemm_mx8_supported(max(1, B * S), self.config.hidden_size, Kd)
             if why is not None:
                 return f"a weight matrix with {Kd} input features: {why}"
@@ -607,49 +657,59 @@ class CausalLM(nn.Module):
             self._inv_freq = rope_inv_freq(self.config).to(position_ids.device)
         return K.rope_table(position_ids.reshape(-1).contiguous(), self._inv_freq, self.dtype == torch.bfloat16)
 
-    def kv_cache_ok(self, B: int):
-        """None when a batch of B sequences can keep its KV cache in MXFP8, else the reason it cannot (the opt-in never falls back
-        silently: new_cache and generate raise it before the prefill)."""
+    def _heads_ok(self, written, kernel):
+        """kv_cache_ok and samples_ok: both decode attention kernels take bf16, head_dim 128 and 1, 2 or 4 query heads per key/value
+        head; `written`, `kernel`: how each reason names them."""
         c = self.config
         if self.dtype != torch.bfloat16:
             return f"model dtype is {self.dtype}, not bfloat16"
         if c.head_dim != 128:
-            return f"head_dim is {c.head_dim} (the MXFP8 cache and its decode kernel are written for 128)"
+            return f"head_dim is {c.head_dim} ({written} for 128)"
         Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
         if Hq % Hkv or Hq // Hkv not in (1, 2, 4):
-            return f"{Hq} query heads on {Hkv} key/value heads (the MXFP8 decode kernel takes 1, 2 or 4 per key/value head)"
+            return f"{Hq} query heads on {Hkv} key/value heads ({kernel} takes 1, 2 or 4 per key/value head)"
         return None
+
+    def kv_cache_ok(self, B: int):
+        """None when a batch of B sequences can keep its KV cache in MXFP8, else the reason it cannot (the opt-in never falls back
+        silently: new_cache and generate raise it before the prefill)."""
+        return self._heads_ok("the MXFP8 cache and its decode kernel are written", "the MXFP8 decode kernel")
 
     def samples_ok(self, B: int, n: int):
         """None when B prompts can be decoded as n samples each over one shared copy of the prompt's keys and values
         (LayerKVCacheShared), else the reason they cannot (the opt-in never falls back silently: new_cache and generate raise it
         before the prefill)."""
-        c = self.config
-        if self.dtype != torch.bfloat16:
-            return f"model dtype is {self.dtype}, not bfloat16"
-        if c.head_dim != 128:
-            return f"head_dim is {c.head_dim} (the shared-prefix decode kernel is written for 128)"
-        Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
-        if Hq % Hkv or Hq // Hkv not in (1, 2, 4):
-            return f"{Hq} query heads on {Hkv} key/value heads (the shared-prefix decode kernel takes 1, 2 or 4 per key/value head)"
-        return None
+        return self._heads_ok("the shared-prefix decode kernel is written", "the shared-prefix decode kernel")
+
+    # option -> (the values it takes besides None; None: an int its caller has validated, the method that says why it cannot be used)
+    OPTIONS = {"decode_weights": (("mxfp8",), "decode_weights_ok"), "kv_cache": (("mxfp8",), "kv_cache_ok"),
+               "prefill_weights": (("mxfp8",), "prefill_weights_ok"), "samples": (None, "samples_ok"),
+               "num_return_sequences": (None, "samples_ok")}
+
+    def check_option(self, name, value, *args, **kw):
+        """ValueError when an opt-in is given a value it does not take, or -- with the arguments of its *_ok method -- when that
+        method has a reason why it cannot be used.  None (the option is off) passes."""
+        allowed, ok = self.OPTIONS[name]
+        if value is None:
+            return
+        if allowed is not None and value not in allowed:
+            raise ValueError(f"{name}={value!r}: None or 'mxfp8'")
+        why = getattr(self, ok)(*args, **kw) if args or kw else None
+        if why is not None:
+            raise ValueError(f"{name}={value!r} cannot be used: {why}")
 
     def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None):
         """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot.
         samples=n > 1: LayerKVCacheShared for B prompts of at most prompt_len positions and n sample rows each with room for
         Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache."""
         c = self.config
-        if kv_cache not in (None, "mxfp8"):
-            raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
-        if kv_cache is not None and self.kv_cache_ok(B) is not None:
-            raise ValueError(f"kv_cache={kv_cache!r} cannot be used: {self.kv_cache_ok(B)}")
+        self.check_option("kv_cache", kv_cache, B)
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
             raise ValueError(f"samples must be an int >= 1, got {samples!r}")
         if samples > 1:
             if kv_cache is not None:
                 raise ValueError(f"samples={samples} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only")
-            if self.samples_ok(B, samples) is not None:
-                raise ValueError(f"samples={samples} cannot be used: {self.samples_ok(B, samples)}")
+            self.check_option("samples", samples, B, samples)
             if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
                 raise ValueError(f"samples={samples} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
             return [LayerKVCacheShared(B, samples, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
@@ -665,17 +725,15 @@ class CausalLM(nn.Module):
         quantize_decode_weights() instead of the bf16 weights; anything else (prefill, training) reads the bf16 weights -- unless
         prefill_weights="mxfp8": a call that is NOT a decode step (S > 1, or can_decode_step false) then runs every decoder-layer
         linear -- fused q|k|v (+ bias), o_proj (+ residual), fused gate|up (Apertus: up_proj), down_proj (+ residual) -- as an
-        MXFP8 x MXFP8 GEMM on the block-scaled MFMA (DecoderLayer.prefill_mx8): the same copies (built here if absent, under the
+        MXFP8 x MXFP8 GEMM on the block-scaled MFMA (DecoderLayer.infer, W8.linear): the same copies (built here if absent, under the
         same snapshot rule) and the linear's bf16 input quantised on the way in.  Norms, RoPE, attention, the activation, the cache
         append and the final norm stay the bf16 kernels, and lm_head -- which sees logits_to_keep rows -- keeps its bf16 weights on
         this path.  It needs autograd off (there is no backward through it) and raises ValueError with prefill_weights_ok's reason
         otherwise; on a decode step the argument is ignored (decode_weights governs those)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
-        if prefill_weights not in (None, "mxfp8"):
-            raise ValueError(f"prefill_weights={prefill_weights!r}: None or 'mxfp8'")
-        if decode_weights not in (None, "mxfp8"):
-            raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
+        self.check_option("prefill_weights", prefill_weights)
+        self.check_option("decode_weights", decode_weights)
         if decode_weights is not None and (self._decode_w8 is None or self._decode_w8["fmt"] != decode_weights):
             raise ValueError("decode_weights given without copies to read: call quantize_decode_weights() first")
         if inputs_embeds is None:
@@ -683,7 +741,7 @@ class CausalLM(nn.Module):
         B, S, H = inputs_embeds.shape
         dev = inputs_embeds.device
         cache = past_key_values
-        past = cache[0].len + getattr(cache[0], "slen", 0) if cache else 0
+        past = cache[0].positions() if cache else 0
         rows = kwargs.get("loss_rows")
         if rows is not None and (labels is None or cache or use_cache or logits_to_keep or rows.n == 0 or rows.total != B * S):
             rows = None                                      # anything but a plain training forward: every position's logits
@@ -703,32 +761,31 @@ class CausalLM(nn.Module):
         if not x.is_contiguous():
             x = x.contiguous()
         layers = self.model.layers
-        fused_head = False
-        w8 = None
-        if decode_weights is not None and cache and len(layers) and all(layer.can_decode_step(x, B, S, cache[i]) for i, layer in enumerate(layers)):
-            w8 = self._decode_w8                                 # a decode step: every layer below takes decode_step(_fused)
-        lw8 = (lambda i: w8["layers"][i]) if w8 is not None else (lambda i: None)
-        pw8 = None
-        if prefill_weights is not None and len(layers) and not (
-                cache and all(layer.can_decode_step(x, B, S, cache[i]) for i, layer in enumerate(layers))):
-            why = self.prefill_weights_ok(B, S)
-            if why is not None:
-                raise ValueError(f"prefill_weights={prefill_weights!r} cannot be used: {why}")
+        # the route of the call, decided once: "fused" / "step" (a decode step: one new token per sequence over a cache, every layer
+        # takes decode_step_fused / infer), "prefill" (the MXFP8 prefill: every layer takes infer) or None (training and everything
+        # else: every layer takes forward)
+        route = None
+        if cache and len(layers):
+            if all(layer.can_decode_step_fused(x, B, S, c) for layer, c in zip(layers, cache)):
+                route = "fused"
+            elif all(layer.can_decode_step(x, B, S, c) for layer, c in zip(layers, cache)):
+                route = "step"
+        w = self._decode_w8 if route and decode_weights is not None else self._w16      # decode steps alone read decode_weights
+        if prefill_weights is not None and not route and len(layers):
+            self.check_option("prefill_weights", prefill_weights, B, S)
             if self._decode_w8 is None or self._decode_w8["fmt"] != prefill_weights:
                 self.quantize_decode_weights(prefill_weights)
-            pw8, rows = self._decode_w8["layers"], None
-        if pw8 is not None:
-            for i, layer in enumerate(layers):
-                x = layer.prefill_mx8(x, cos, sin, key_mask, B, S, cache[i] if cache else None, pw8[i])
-            x, _ = self.model.norm(x)
-        elif cache and len(layers) and all(layer.can_decode_step_fused(x, B, S, cache[i]) for i, layer in enumerate(layers)):
-            # decode step: every RMSNorm is applied by the projection that consumes it (DecoderLayer.decode_step_fused), the final
-            # norm by lm_head below
-            for i, layer in enumerate(layers):
-                x = layer.decode_step_fused(x, cos, sin, key_mask, B, cache[i], w8=lw8(i))
+            route, w, rows = "prefill", self._decode_w8, None
+        fused_head = False
+        if route == "fused":
+            # every RMSNorm is applied by the projection that consumes it (DecoderLayer.decode_step_fused), the final norm by
+            # lm_head below
+            for layer, lw, c in zip(layers, w["layers"], cache):
+                x = layer.decode_step_fused(lw, x, cos, sin, key_mask, B, c)
             fused_head = self.lm_head.bias is None and self.model.norm.bias is None       # S == 1: logits_to_keep keeps the one row
-            if not fused_head:
-                x, _ = self.model.norm(x)
+        elif route:
+            for i, layer in enumerate(layers):
+                x = layer.infer(w["layers"][i], x, cos, sin, key_mask, B, S, cache[i] if cache else None, step=route == "step")
         else:
             # training step (Trainer.compute_loss hands over `loss_rows`): the loss and every gradient depend only on the rows whose
             # shifted label is not -100 (HF:loss/loss_utils.py:36-71 ignores the others; their dlogits are exactly zero), so the
@@ -736,9 +793,10 @@ class CausalLM(nn.Module):
             # `logits` is then not returned
             last = len(layers) - 1
             for i, layer in enumerate(layers):
-                x = layer(x, cos, sin, key_mask, B, S, cache=cache[i] if cache else None, rows=rows if i == last else None, w8=lw8(i))
+                x = layer(x, cos, sin, key_mask, B, S, cache=cache[i] if cache else None, rows=rows if i == last else None)
             if rows is not None and not len(layers):
                 x = Fm.rows_select(x, rows)
+        if not fused_head:
             x, _ = self.model.norm(x)
         V = self.config.vocab_size
         if logits_to_keep:
@@ -746,12 +804,11 @@ class CausalLM(nn.Module):
             Sk = logits_to_keep
         else:
             Sk = S
-        hw8 = w8["lm_head"] if w8 is not None else None
-        if hw8 is not None:
-            nw = dict(norm_w=self.model.norm.weight, eps=self.model.norm.eps) if fused_head else {}
-            logits2d = K.decode_linear_w8(x, *hw8, ldc_pad=True, **nw)
-        elif fused_head:
-            logits2d = K.decode_linear(x, self.lm_head.weight, norm_w=self.model.norm.weight, eps=self.model.norm.eps, ldc_pad=True)
+        head = (w["lm_head"] or self._w16["lm_head"]) if route in ("fused", "step") else None
+        if fused_head:
+            logits2d = head.stream(x, norm_w=self.model.norm.weight, eps=self.model.norm.eps, ldc_pad=True)
+        elif head is not None:                                   # a decode step: lm_head's copy, when decode_weights made one
+            logits2d = head.linear(x, ldc_pad=True)
         else:
             logits2d = self.lm_head(x, ldc_pad=True)             # [B*Sk, V] view, row stride padded to 64
         loss = None

@@ -514,33 +514,19 @@ class MultiModalModelForCausalLM(nn.Module):
         n = num_return_sequences
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
-        if n > 1:
-            if not do_sample:
-                raise ValueError(f"num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows")
-            if kv_cache is not None:
-                raise ValueError(f"num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
-                                 "shared-prefix cache is out of scope)")
-            why = self.model.samples_ok(int(batch["input_ids"].shape[0]), n)
-            if why is not None:
-                raise ValueError(f"num_return_sequences={n} cannot be used: {why}")
-        if kv_cache not in (None, "mxfp8"):
-            raise ValueError(f"kv_cache={kv_cache!r}: None or 'mxfp8'")
-        if kv_cache is not None:
-            why = self.model.kv_cache_ok(int(batch["input_ids"].shape[0]))
-            if why is not None:
-                raise ValueError(f"kv_cache={kv_cache!r} cannot be used: {why}")
-        if decode_weights not in (None, "mxfp8"):
-            raise ValueError(f"decode_weights={decode_weights!r}: None or 'mxfp8'")
-        if decode_weights is not None:
-            why = self.model.decode_weights_ok(int(batch["input_ids"].shape[0]) * n)      # the decode steps run B n rows
-            if why is not None:
-                raise ValueError(f"decode_weights={decode_weights!r} cannot be used: {why}")
-        if prefill_weights not in (None, "mxfp8"):
-            raise ValueError(f"prefill_weights={prefill_weights!r}: None or 'mxfp8'")
-        if prefill_weights is not None:
-            why = self.model.prefill_weights_ok(*batch["input_ids"].shape[:2], check_grad=False)      # the loop runs under no_grad
-            if why is not None:
-                raise ValueError(f"prefill_weights={prefill_weights!r} cannot be used: {why}")
+        if n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights)):
+            llm = self.model
+            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
+            if n > 1:
+                if not do_sample:
+                    raise ValueError(f"num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows")
+                if kv_cache is not None:
+                    raise ValueError(f"num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
+                                     "shared-prefix cache is out of scope)")
+                llm.check_option("num_return_sequences", n, B, n)
+            llm.check_option("kv_cache", kv_cache, B)
+            llm.check_option("decode_weights", decode_weights, B * n)                             # the decode steps run B n rows
+            llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)         # the loop runs under no_grad
         device_sample = do_sample and any(a is not None for a in (top_k, top_p, min_p, seed, generator))
         if device_sample:
             top_k = 0 if top_k is None else top_k

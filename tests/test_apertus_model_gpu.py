@@ -140,7 +140,7 @@ def test_bf16_grads(gold, model_bf16):
 
 
 def test_bf16_kv_cache_decode_step_matches_full_forward(gold, model_bf16, monkeypatch):
-    """Prefill S-1 tokens into the KV cache, then one decode step (the unfused decode_step: q/k-norm layers never take the fused
+    """Prefill S-1 tokens into the KV cache, then one decode step (the unfused DecoderLayer.infer: q/k-norm layers never take the fused
     decode kernels): its MLP is up_proj, mm_xielu_fwd, down_proj, and its logits equal the last row of a full-sequence forward within
     bf16 noise."""
     from multimeditron_amd import kernels as K

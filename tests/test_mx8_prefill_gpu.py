@@ -1,6 +1,6 @@
 """The opt-in MXFP8 prefill (forward / generate with prefill_weights="mxfp8") through the model layers.
 
-Wiring, bitwise.  A test-side chain calls the public wrappers in the documented order (DecoderLayer.prefill_mx8: rmsnorm_fwd ->
+Wiring, bitwise.  A test-side chain calls the public wrappers in the documented order (DecoderLayer.infer, step=False: rmsnorm_fwd ->
 quant_mxfp8 -> gemm_mx8 -> RoPE or q/k norm + RoPE -> cache append -> attn_fwd -> quant -> gemm (+ residual) -> rmsnorm_fwd -> quant
 -> gemm -> swiglu_fwd / xielu_fwd -> quant -> gemm (+ residual), then the final norm and the bf16 lm_head); every kernel is
 deterministic, so forward(prefill_weights="mxfp8", use_cache=True) must give that chain's logits and cache rows bit for bit, on a
