@@ -436,6 +436,70 @@ int mm_attn_decode_shared(int dtype, const void* q, const void* kp, const void* 
                           int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
                           float* workspace, int nsplit, void* stream);
 
+/* mm_attn_decode_beam (generate's num_beams; opt-in): mm_attn_decode_shared with an ancestor table anc, int32 [Ss, anc_ld] with
+ * anc_ld >= B*n.  Query row r of prompt b attends over [prefix of b | suffix key t read from PHYSICAL suffix row anc[t*anc_ld + r],
+ * t < Ss]: a beam continues another row's generated suffix without a copy of the cache.  The kernel clamps every entry it reads into
+ * its own prompt's rows [b*n, b*n + n), so no table can make it read outside ks / vs.  Slices, workspace, the merge launch, the
+ * accepted shapes and every refusal are mm_attn_decode_shared's; a NULL anc or anc_ld < B*n is MM_ERR_ARG.
+ * Bit identity: the table anc[t][r] = r gives mm_attn_decode_shared's bits, and any table with entries in range gives the bits of
+ * mm_attn_decode_shared on the gathered suffix ks'[r, t] = ks[anc[t][r], t] (vs alike): only the row address of a suffix key
+ * changes.  mm_attn_decode_shared itself is the kernel it was (the table is a template argument of the kernel, not a branch). */
+int mm_attn_decode_beam(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+                        int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
+                        int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
+                        int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
+                        float* workspace, int nsplit, const int32_t* anc, int anc_ld, void* stream);
+
+/* ---- Beam search selection on the device (generate's num_beams = n; opt-in).  transformers' GenerationMixin._beam_search with one
+ * eos token, no logits processors and do_sample = False, restated without its -1e9 arithmetic.  Per prompt b the state is n running
+ * beams (fp32 score s[j] and a sequence), a finished set F of at most n entries (normalised score, sequence, length) and a flag
+ * open[b], initially true.  T = max_new_tokens, R = B*n.  mm_beam_step(step = i) -- i tokens generated so far -- does:
+ *  a. lp[j,v] = s[j] + (x[j,v] - lse_j) in fp32, x = float(logits[row j, v]) (-0 counts as +0), lse_j = m + logf(sum_v expf(x - m))
+ *     with m the row's maximum, summed per 4096-entry chunk and then over the chunks in chunk order.  Step 0 reads ONE row per prompt
+ *     (logits [B, ld], the prefill's), j = 0 and s = 0; every later step reads logits [B*n, ld], row b*n + j.  Columns [V, ld) are
+ *     never read.  A -inf logit (lp = -inf) is never chosen; a prompt must offer at least 2n finite lp.
+ *  b. C = the 2n largest lp of the prompt, descending.  Ties go to the smaller flat index j*V + v; where fp32 rounding has collapsed
+ *     two different logits of ONE row to the same lp, the larger logit goes first (exact same-row ties are equal logits, and those
+ *     go to the smaller token).  A candidate carries (parent j, token v, score lp).
+ *  c. stop[c] = (v == eos) or (i + 1 == T).
+ *  d. The next running beams are the first n candidates with stop false, in order: next_ids[b*n + r] (int64, the next embedding
+ *     lookup), parent, score.  At the last step there are none: next_ids = eos, parent r, score -inf, and s_new[0] of rule f is -inf.
+ *  e. Skipped when open[b] is false, and when early_stopping = 1 and F held n entries BEFORE this step.  Otherwise every candidate of
+ *     rank < n with stop true enters F with score lp / d_i, d_i = (float)pow(i + 1, length_penalty) (double pow, rounded once), length
+ *     i + 1 and its tokens (the parent's sequence, then v); F keeps its best n: a new entry needs a score strictly above the worst
+ *     entry's (on a tie the existing entry stays; among new ones the lower rank goes first), and the worst entry is the lowest score,
+ *     then the latest arrival.
+ *  f. If F holds n entries: open[b] &= s_new[0] / d_L > min(F), d_L = (float)pow(L, length_penalty) with L = T when
+ *     early_stopping = 2 ("never") and length_penalty > 0, else L = i + 1.  Otherwise open[b] stays.
+ *  g. done = no prompt is open, or early_stopping = 1 and every F holds n entries, or i + 1 == T.
+ * After done, further steps leave every F unchanged (rule e skips them: a closed prompt stays closed, a full F stays full), so the
+ * host may look at done only every few steps.  early_stopping: 0 False, 1 True, 2 "never".
+ * The step also writes the ancestor table of the COMING decode step for mm_attn_decode_beam: anc_new[t][r] = anc_old[t][b*n +
+ * parent[r]] for t < i and anc_new[i][r] = r (the slot that step appends to); two tables ping-pong, step i reads table i & 1 and
+ * writes table (i + 1) & 1 (entries are physical rows, clamped into the prompt's rows when read).  Sequences are not copied per
+ * step: token t of running beam r is tok[t][anc[t][r]].
+ * state: mm_beam_state_bytes(B, n, T) bytes, 16-byte aligned, owned by the caller for the whole call of generate; step 0 starts it
+ * (nothing needs clearing).  mm_beam_state_layout writes the byte offsets of its 11 fields: 0 score f32 [R], 1 parent i32 [R] (of the
+ * last step, relative to the prompt's first row), 2 tok i32 [T,R], 3 anc i32 [2,T,R] (anc_ld = R), 4 fscore f32 [R], 5 flen i32 [R]
+ * (0: empty slot), 6 fseqno i32 [R] (arrival number), 7 fseq i32 [R,T], 8 open i32 [B], 9 fcount i32 [B] (arrivals so far;
+ * min(fcount, n) slots hold entries), 10 done i32 [1].  F's slots are not kept sorted.
+ * ws: mm_beam_ws_bytes(B, n, V) bytes, 16-byte aligned, scratch of one step.  logits MM_BF16 or MM_F32, row stride ld >= V.
+ * Three short launches (per-row chunk maxima / sums / top-2n; one workgroup per prompt for b-f; g), no allocation, no host sync,
+ * no atomics: the same bits on every launch.
+ * MM_ERR_ARG before any launch: n outside [1, 16], B < 1, B*n > 65535, V < 2n or V > 2^24, ld < V, step outside [0, T), T < 1,
+ * early_stopping outside {0, 1, 2}, length_penalty not finite, a NULL pointer, a short state or ws; MM_ERR_ALIGN: state or ws not
+ * 16-byte aligned.
+ * mm_beam_finish: ranks every prompt's F (higher score, then the earlier arrival) and writes its num_return <= n best: ids int64
+ * [B*num_return, T] (row b*num_return + k; eos behind the hypothesis' end), scores f32 and lens i32 [B*num_return].              */
+int mm_beam_ws_bytes(int B, int n, int V, int64_t* bytes);
+int mm_beam_state_bytes(int B, int n, int max_new_tokens, int64_t* bytes);
+int mm_beam_state_layout(int B, int n, int max_new_tokens, int64_t* offsets);
+int mm_beam_step(int dtype, const void* logits, int B, int n, int V, int ld, int step, int max_new_tokens, int64_t eos,
+                 float length_penalty, int early_stopping, void* state, int64_t state_bytes, void* ws, int64_t ws_bytes,
+                 int64_t* next_ids, void* stream);
+int mm_beam_finish(const void* state, int64_t state_bytes, int B, int n, int max_new_tokens, int num_return, int64_t eos,
+                   int64_t* ids, float* scores, int32_t* lens, void* stream);
+
 /* ---- MXFP8 KV cache for the decode step (opt-in).  The K and V rows [Hkv, D] of every cached position, D = 128 only, are stored in
  * the format of mm_quant_mxfp8 above: OCP e4m3fn elements, one E8M0 scale byte per 32 consecutive d of a head (4 per (position, kv
  * head) for K and 4 for V), the same quantiser rule -- the smallest scale that keeps the block maximum <= 448, byte clamp [27, 254],

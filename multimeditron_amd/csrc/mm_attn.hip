@@ -1955,6 +1955,8 @@ struct DecodeSharedArgs {
   float scale;
   float* ws;
   int nsplit, chunk, tiles;      // tiles = ceil(n / P)
+  const int32_t* anc;            // mm_attn_decode_beam: [Ss, anc_ld] physical suffix row of (suffix key t, query row r); NULL: row r's own
+  int anc_ld;
 };
 
 // (x of kq row 0 + row 1) + (row 2 + row 3) of this lane's column, in every row: v_permlane16_swap exchanges the odd rows of its first
@@ -1995,8 +1997,12 @@ __device__ __forceinline__ void decode_shared_sample(float (&o)[16][8], float al
 
 #define MM_SH_EACH16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 
-template <int G>
-__global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSharedArgs a) {
+// ANC (mm_attn_decode_beam): suffix key t of query row r is read from the physical suffix row a.anc[t * anc_ld + r], clamped into the
+// rows [b n, b n + n) of the row's own prompt; everything else is the code above, so a table that names every row itself gives the bits
+// of ANC = false and any table the bits of ANC = false on the gathered suffix.  A template argument, not a run-time branch: the
+// NULL-table kernel stays the instruction stream it was (attn_decode_shared128_kernel / attn_decode_beam128_kernel below).
+template <int G, bool ANC>
+__device__ __forceinline__ void decode_shared128_body(const DecodeSharedArgs& a) {
   constexpr int D = 128, P = 16 / G;
   static_assert(G == 1 || G == 2 || G == 4, "P = 16 / G samples share a column tile");
   __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
@@ -2028,6 +2034,16 @@ __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSha
   float m_run = -INFINITY, l_run = 0.f;
   bf16x8 kf[4], vf[4];
   auto in_prefix = [&](int k0) { return min(k0 + 16, kend) <= a.Sp; };       // every key of the block, clamped ones included
+  // the physical suffix row that holds suffix key t (0 <= t < Ss) of query row r
+  auto suffix_row = [&](int64_t r, int t) -> int64_t {
+    if constexpr (ANC) {
+      const int64_t lo = (int64_t)b * a.n;
+      const int64_t p = a.anc[(int64_t)t * a.anc_ld + r];
+      return p < lo ? lo : (p > lo + a.n - 1 ? lo + a.n - 1 : p);
+    } else {
+      return r;
+    }
+  };
   auto load_prefix = [&](int k0) {
     const int kk = min(k0 + row, kend - 1);
 #pragma unroll
@@ -2055,10 +2071,10 @@ __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSha
       // the block holds suffix keys: the rows of sample jl, of which the lanes of its columns keep the scores.  Samples past the
       // tile's last live one repeat that one (a valid address; no lane keeps the result)
       const int kk = min(k0 + row, kend - 1);
-#pragma unroll
+#pragma unroll ANC ? (P < 4 ? P : 4) : P       // the table variant: at most 4 samples' independent row addresses in flight (16 spill)
       for (int jl = 0; jl < P; ++jl) {
         const int64_t r = r0 + min(jl, nlive - 1);
-        const bf16* kr = kk < a.Sp ? Kp + (int64_t)kk * a.kp_ss : Ks + r * a.ks_sb + (int64_t)(kk - a.Sp) * a.ks_ss;
+        const bf16* kr = kk < a.Sp ? Kp + (int64_t)kk * a.kp_ss : Ks + suffix_row(r, kk - a.Sp) * a.ks_sb + (int64_t)(kk - a.Sp) * a.ks_ss;
         f32x4 aj = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) aj = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(kr + ks * 32 + kq * 8), qf[ks], aj, 0, 0, 0);
@@ -2093,7 +2109,8 @@ __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSha
         if (jl < nlive) {                                                                                                    \
           _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                    \
             const int kv = min(k0 + 4 * kq + u, kend - 1);                                                                   \
-            const bf16* vr = kv < a.Sp ? Vp + (int64_t)kv * a.vp_ss : Vs + (r0 + jl) * a.vs_sb + (int64_t)(kv - a.Sp) * a.vs_ss; \
+            const bf16* vr = kv < a.Sp ? Vp + (int64_t)kv * a.vp_ss                                                          \
+                                       : Vs + suffix_row(r0 + jl, kv - a.Sp) * a.vs_sb + (int64_t)(kv - a.Sp) * a.vs_ss;     \
             const bf16x8 vv = *(const bf16x8*)(vr + row * 8);                                                                \
             _Pragma("unroll") for (int j = 0; j < 8; ++j) vx[u][j] = (float)vv[j];                                           \
           }                                                                                                                  \
@@ -2143,6 +2160,11 @@ __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSha
   }
 }
 #undef MM_SH_EACH16
+
+template <int G>
+__global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSharedArgs a) { decode_shared128_body<G, false>(a); }
+template <int G>
+__global__ __launch_bounds__(256, 2) void attn_decode_beam128_kernel(DecodeSharedArgs a) { decode_shared128_body<G, true>(a); }
 
 template <int D>
 __global__ void attn_decode_merge_kernel(const float* ws, int nsplit, bf16* out) {
@@ -2345,11 +2367,11 @@ extern "C" int mm_attn_decode_shared_splits(int B, int n, int Hkv, int Skv) {
   return ns < 1 ? 1 : (int)ns;
 }
 
-extern "C" int mm_attn_decode_shared(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+static int decode_shared_launch(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
                                      int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
                                      int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
                                      int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
-                                     float* workspace, int nsplit, void* stream) {
+                                     float* workspace, int nsplit, const int32_t* anc, int anc_ld, void* stream) {
   if (B < 0 || n < 1 || Sp < 1 || Ss < 1 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || nsplit < 1) return MM_ERR_ARG;
   if (dtype != MM_BF16 || D != 128) return MM_ERR_UNSUPPORTED;
   const int G = Hq / Hkv;
@@ -2361,19 +2383,47 @@ extern "C" int mm_attn_decode_shared(int dtype, const void* q, const void* kp, c
   if ((q_sb | q_sh | kp_sb | kp_ss | kp_sh | vp_sb | vp_ss | vp_sh | ks_sb | ks_ss | ks_sh | vs_sb | vs_ss | vs_sh) & 7) return MM_ERR_ALIGN;
   if (!mm_aligned16(q) || !mm_aligned16(kp) || !mm_aligned16(vp) || !mm_aligned16(ks) || !mm_aligned16(vs)) return MM_ERR_ALIGN;
   DecodeSharedArgs a{q, kp, vp, ks, vs, B, n, Sp, Ss, Hq, Hkv, q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh,
-                     ks_sb, ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, workspace, nsplit, 0, tiles};
+                     ks_sb, ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, workspace, nsplit, 0, tiles, anc, anc_ld};
   a.chunk = (Sp + Ss + nsplit - 1) / nsplit;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(nsplit, Hkv, B * tiles), block(256);
-  switch (G) {
-    case 1: hipLaunchKernelGGL(attn_decode_shared128_kernel<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(attn_decode_shared128_kernel<2>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(attn_decode_shared128_kernel<4>, grid, block, 0, s, a); break;
+  if (anc) {
+    switch (G) {
+      case 1: hipLaunchKernelGGL(attn_decode_beam128_kernel<1>, grid, block, 0, s, a); break;
+      case 2: hipLaunchKernelGGL(attn_decode_beam128_kernel<2>, grid, block, 0, s, a); break;
+      default: hipLaunchKernelGGL(attn_decode_beam128_kernel<4>, grid, block, 0, s, a); break;
+    }
+  } else {
+    switch (G) {
+      case 1: hipLaunchKernelGGL(attn_decode_shared128_kernel<1>, grid, block, 0, s, a); break;
+      case 2: hipLaunchKernelGGL(attn_decode_shared128_kernel<2>, grid, block, 0, s, a); break;
+      default: hipLaunchKernelGGL(attn_decode_shared128_kernel<4>, grid, block, 0, s, a); break;
+    }
   }
   MM_CHECK_LAUNCH();
   hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * n * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
   MM_CHECK_LAUNCH();
   return MM_OK;
+}
+
+extern "C" int mm_attn_decode_shared(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+                                     int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
+                                     int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
+                                     int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
+                                     float* workspace, int nsplit, void* stream) {
+  return decode_shared_launch(dtype, q, kp, vp, ks, vs, B, n, Sp, Ss, Hq, Hkv, D, q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh, ks_sb,
+                              ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, out, workspace, nsplit, nullptr, 0, stream);
+}
+
+// mm_attn_decode_beam: the same launch with an ancestor table (beam search: a row continues another row's generated suffix)
+extern "C" int mm_attn_decode_beam(int dtype, const void* q, const void* kp, const void* vp, const void* ks, const void* vs, int B, int n,
+                                   int Sp, int Ss, int Hq, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kp_sb, int64_t kp_ss,
+                                   int64_t kp_sh, int64_t vp_sb, int64_t vp_ss, int64_t vp_sh, int64_t ks_sb, int64_t ks_ss, int64_t ks_sh,
+                                   int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
+                                   float* workspace, int nsplit, const int32_t* anc, int anc_ld, void* stream) {
+  if (!anc || (int64_t)anc_ld < (int64_t)B * n) return MM_ERR_ARG;
+  return decode_shared_launch(dtype, q, kp, vp, ks, vs, B, n, Sp, Ss, Hq, Hkv, D, q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh, ks_sb,
+                              ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, out, workspace, nsplit, anc, anc_ld, stream);
 }
 
 extern "C" int mm_attn_decode_kv8_chunk(int Skv, int nsplit) {

@@ -770,6 +770,77 @@ def attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale):
     return out
 
 
+def attn_decode_beam(q, kp, vp, ks, vs, n, key_mask, scale, anc, nsplit=None):
+    """attn_decode_shared where suffix key t of row r is read from physical suffix row anc[t, r] (int32 [>= Ss, >= B*n], last stride 1):
+    the bits of attn_decode_shared on the gathered suffix (mm_attn_decode_beam)."""
+    R, Hq, D = q.shape
+    B, Sp, Hkv = kp.shape[0], kp.shape[1], kp.shape[2]
+    Ss = ks.shape[1]
+    assert R == B * n and ks.shape[0] == R and vs.shape[0] == R and vp.shape[:3] == kp.shape[:3] and vs.shape[1] == Ss
+    assert q.stride(2) == 1 and kp.stride(3) == 1 and vp.stride(3) == 1 and ks.stride(3) == 1 and vs.stride(3) == 1
+    assert key_mask is None or (tuple(key_mask.shape) == (B, Sp) and key_mask.is_contiguous())
+    assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] >= Ss and anc.shape[1] >= R and anc.stride(1) == 1
+    ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss) if nsplit is None else int(nsplit)
+    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
+    call("mm_attn_decode_beam", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss, Hq, Hkv, D, q.stride(0), q.stride(1),
+         *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale), _p(out), _p(ws), ns, _p(anc),
+         anc.stride(0), _stream())
+    return out
+
+
+# ---- beam search (include/mm_hip.h: mm_beam_step) ----
+BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+BEAM_FIELDS = (("score", torch.float32), ("parent", torch.int32), ("tok", torch.int32), ("anc", torch.int32), ("fscore", torch.float32),
+               ("flen", torch.int32), ("fseqno", torch.int32), ("fseq", torch.int32), ("open", torch.int32), ("fcount", torch.int32),
+               ("done", torch.int32))
+
+
+class BeamState:
+    """The device state of one beam search of B prompts x n beams over at most T tokens: one buffer in the library's layout
+    (mm_beam_state_layout) with a tensor view of every field, and the workspace of a step over V logits."""
+
+    def __init__(self, B, n, T, V, device):
+        import ctypes
+        nb, wb = ctypes.c_int64(0), ctypes.c_int64(0)
+        call("mm_beam_state_bytes", int(B), int(n), int(T), ctypes.byref(nb))
+        call("mm_beam_ws_bytes", int(B), int(n), int(V), ctypes.byref(wb))
+        off = (ctypes.c_int64 * len(BEAM_FIELDS))()
+        call("mm_beam_state_layout", int(B), int(n), int(T), off)
+        self.B, self.n, self.T, self.V = int(B), int(n), int(T), int(V)
+        self.buf = torch.zeros(nb.value, dtype=torch.uint8, device=device)
+        self.ws = torch.empty((wb.value + 15) // 16 * 2, dtype=torch.int64, device=device)
+        self.next_ids = torch.empty(B * n, dtype=torch.int64, device=device)
+        R = B * n
+        shapes = {"tok": (T, R), "anc": (2, T, R), "fseq": (R, T), "open": (B,), "fcount": (B,), "done": (1,)}
+        for (name, dtype), o in zip(BEAM_FIELDS, off):
+            shape = shapes.get(name, (R,))
+            numel = math.prod(shape)
+            setattr(self, name, self.buf[o:o + 4 * numel].view(dtype).view(shape))
+
+    def table(self, step):
+        """the ancestor table [T, R] of the decode step that produces the logits of `step` (mm_beam_step(step - 1) wrote it)"""
+        return self.anc[step & 1]
+
+
+def beam_step(logits2d, st: BeamState, step, eos, length_penalty=1.0, early_stopping=False):
+    """rules a-g of mm_beam_step on logits [B (step 0) or B*n, >= V]; returns st.next_ids (the next embedding lookup)."""
+    assert logits2d.stride(-1) == 1 and logits2d.shape[0] == (st.B if step == 0 else st.B * st.n)
+    call("mm_beam_step", dt(logits2d), _p(logits2d), st.B, st.n, st.V, logits2d.stride(0), int(step), st.T, int(eos), float(length_penalty),
+         BEAM_EARLY_STOPPING[early_stopping], _p(st.buf), st.buf.numel(), _p(st.ws), st.ws.numel() * 8, _p(st.next_ids), _stream())
+    return st.next_ids
+
+
+def beam_finish(st: BeamState, num_return, eos):
+    """-> (ids int64 [B*num_return, T] eos-filled, scores f32 [B*num_return], lens i32 [B*num_return]) on the device."""
+    rows = st.B * int(num_return)
+    ids = torch.empty((rows, st.T), dtype=torch.int64, device=st.buf.device)
+    scores = torch.empty(rows, dtype=torch.float32, device=st.buf.device)
+    lens = torch.empty(rows, dtype=torch.int32, device=st.buf.device)
+    call("mm_beam_finish", _p(st.buf), st.buf.numel(), st.B, st.n, st.T, int(num_return), int(eos), _p(ids), _p(scores), _p(lens), _stream())
+    return ids, scores, lens
+
+
 # ---- MXFP8 KV cache (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 d of a head; the buffer layout is the library's) ----
 def kv8_bytes(B, Smax, Hkv, D):
     n = _lib.lib().mm_kv8_bytes(int(B), int(Smax), int(Hkv), int(D))

@@ -496,6 +496,32 @@ class LayerKVCacheShared(LayerKVCache):
         vs[:, pos:pos + 1].copy_(vn)
 
 
+class LayerKVCacheBeam(LayerKVCacheShared):
+    """The cache of generate(num_beams=n): LayerKVCacheShared whose suffix is read through an ancestor table.  Row r still WRITES
+    its new key / value into its own suffix row, but suffix key t of row r is READ from physical row table[t, r] (include/mm_hip.h:
+    mm_attn_decode_beam), so a beam that continues another row's hypothesis costs a column of int32 instead of HF's reorder_cache
+    (an index_select over every layer's whole cache).  All layers share ONE table holder: the decode loop sets `tables.current` to
+    the table mm_beam_step wrote for the coming step (K.BeamState.table) before it calls the decoder."""
+
+    class Tables:
+        current = None           # int32 [>= slen, >= B n]
+
+    def __init__(self, B, n, Sp_max, max_new, Hkv, D, dtype, device, tables):
+        super().__init__(B, n, Sp_max, max_new, Hkv, D, dtype, device)
+        self.tables = tables
+
+    def decode_attend(self, q, key_mask, scale):
+        if key_mask is not None and tuple(key_mask.shape) != (self.B, self.len):
+            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a beam cache: the prompt's mask [{self.B}, {self.len}] is "
+                             "expected (generated tokens are always visible)")
+        anc = self.tables.current
+        if anc is None or anc.shape[0] <= self.slen:
+            raise ValueError(f"a step on a beam KV cache without an ancestor table of more than {self.slen} rows")
+        self.slen += 1
+        return K.attn_decode_beam(q, self.k[:, : self.len], self.v[:, : self.len], self.ks[:, : self.slen], self.vs[:, : self.slen],
+                                  self.n, key_mask, scale, anc)
+
+
 class DecoderModel(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
@@ -681,10 +707,17 @@ class CausalLM(nn.Module):
         before the prefill)."""
         return self._heads_ok("the shared-prefix decode kernel is written", "the shared-prefix decode kernel")
 
+    def beams_ok(self, B: int, n: int):
+        """None when B prompts can be decoded as n beams each over one shared copy of the prompt's keys and values (LayerKVCacheBeam
+        and mm_beam_step), else the reason they cannot."""
+        if self.config.vocab_size < 2 * n:
+            return f"vocab_size is {self.config.vocab_size}: beam search draws 2 n = {2 * n} candidates per step"
+        return self.samples_ok(B, n)
+
     # option -> (the values it takes besides None; None: an int its caller has validated, the method that says why it cannot be used)
     OPTIONS = {"decode_weights": (("mxfp8",), "decode_weights_ok"), "kv_cache": (("mxfp8",), "kv_cache_ok"),
                "prefill_weights": (("mxfp8",), "prefill_weights_ok"), "samples": (None, "samples_ok"),
-               "num_return_sequences": (None, "samples_ok")}
+               "num_return_sequences": (None, "samples_ok"), "num_beams": (None, "beams_ok"), "beams": (None, "beams_ok")}
 
     def check_option(self, name, value, *args, **kw):
         """ValueError when an opt-in is given a value it does not take, or -- with the arguments of its *_ok method -- when that
@@ -698,12 +731,25 @@ class CausalLM(nn.Module):
         if why is not None:
             raise ValueError(f"{name}={value!r} cannot be used: {why}")
 
-    def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None):
+    def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None, beams: int = 1):
         """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot.
         samples=n > 1: LayerKVCacheShared for B prompts of at most prompt_len positions and n sample rows each with room for
-        Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache."""
+        Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache.
+        beams=n > 1: LayerKVCacheBeam of the same sizes, every layer holding the SAME `tables` object (set tables.current to the
+        step's ancestor table); ValueError when beams_ok says it cannot, or together with kv_cache or samples."""
         c = self.config
         self.check_option("kv_cache", kv_cache, B)
+        if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= 16:
+            raise ValueError(f"beams must be an int in [1, 16], got {beams!r}")
+        if beams > 1:
+            if kv_cache is not None or samples != 1:
+                raise ValueError(f"beams={beams} with kv_cache={kv_cache!r}, samples={samples!r}: the beam cache is bf16 only and its rows are the beams")
+            self.check_option("beams", beams, B, beams)
+            if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
+                raise ValueError(f"beams={beams} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
+            tables = LayerKVCacheBeam.Tables()
+            return [LayerKVCacheBeam(B, beams, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
+                                     self.device, tables) for _ in range(c.num_hidden_layers)]
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
             raise ValueError(f"samples must be an int >= 1, got {samples!r}")
         if samples > 1:

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Union
@@ -463,6 +464,7 @@ class MultiModalModelForCausalLM(nn.Module):
                  top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                  seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
                  kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, num_return_sequences: int = 1,
+                 num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, return_beam_scores: bool = False,
                  **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
@@ -510,10 +512,51 @@ class MultiModalModelForCausalLM(nn.Module):
         the early stop and the padded-length position quirk apply per row.  Composes with decode_weights (B n <= 16) and
         prefill_weights.  NOT with kv_cache="mxfp8" (a shared-prefix MXFP8 cache is out of scope: ValueError).  A model that
         cannot use it -- not bf16, head_dim other than 128, a number of query heads per key/value head other than 1, 2 or 4 --
-        raises ValueError before the prefill (CausalLM.samples_ok).  n = 1 is the path above, untouched."""
+        raises ValueError before the prefill (CausalLM.samples_ok).  n = 1 is the path above, untouched.
+
+        num_beams=n > 1 (opt-in; needs do_sample=False): beam search as transformers' generate(num_beams=n, do_sample=False,
+        length_penalty=, early_stopping=) with one eos token and no logits processors; the rules are written out in
+        include/mm_hip.h (mm_beam_step).  One prefill per prompt into a LayerKVCacheBeam (the prompt's keys once, as above), then
+        B n rows per step; the selection over a prompt's n V continuations, the finished hypotheses and the stopping flags live on the
+        device (mm_beam_step), and a beam continues another row's suffix through an int32 ancestor table instead of a reordered
+        cache (mm_attn_decode_beam).  The host looks at the device's done flag every `sync_every` steps; steps issued past it change
+        nothing.  early_stopping in {False, True, "never"} and length_penalty have HF's meaning; temperature is ignored.  Returns
+        [B num_return_sequences, n_out] (num_return_sequences <= n, default 1): row b nrs + k is prompt b's k-th best finished
+        hypothesis, eos included and filled with eos behind its end, n_out the longest returned one; with return_beam_scores=True
+        (ids, scores), scores [B nrs] fp32 = sum of log-probabilities / length ** length_penalty, descending per prompt.
+        Composes with decode_weights (B n <= 16) and prefill_weights.  ValueError before the modalities are encoded for: num_beams
+        outside [1, 16], do_sample=True, any of top_k / top_p / min_p / seed / generator, kv_cache="mxfp8", num_return_sequences >
+        num_beams, a length_penalty that is not finite, another early_stopping, a vocabulary below 2 n, and a model samples_ok
+        refuses.  num_beams = 1 is the code above, untouched."""
         n = num_return_sequences
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
+        nb = num_beams
+        if isinstance(nb, bool) or not isinstance(nb, int) or not 1 <= nb <= 16:
+            raise ValueError(f"num_beams must be an int in [1, 16], got {nb!r}")
+        if nb == 1 and return_beam_scores:
+            raise ValueError("return_beam_scores needs num_beams > 1")
+        if nb > 1:
+            llm = self.model
+            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
+            if do_sample:
+                raise ValueError(f"num_beams={nb} needs do_sample=False: beam sampling is out of scope")
+            given = [k for k, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p), ("seed", seed), ("generator", generator)) if v is not None]
+            if given:
+                raise ValueError(f"num_beams={nb} with {', '.join(given)}: beam search does not sample")
+            if kv_cache is not None:
+                raise ValueError(f"num_beams={nb} with kv_cache={kv_cache!r}: the beam cache is bf16 only (an MXFP8 beam cache is out of scope)")
+            if n > nb:
+                raise ValueError(f"num_return_sequences={n} > num_beams={nb}")
+            if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+                raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+            if not (early_stopping is False or early_stopping is True or (isinstance(early_stopping, str) and early_stopping == "never")):
+                raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
+            llm.check_option("num_beams", nb, B, nb)
+            llm.check_option("decode_weights", decode_weights, B * nb)                            # the decode steps run B n rows
+            llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)
+            return self._generate_beams(batch, max_new_tokens, sync_every, nb, n, float(length_penalty), early_stopping,
+                                        return_beam_scores, decode_weights, prefill_weights)
         if n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights)):
             llm = self.model
             B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
@@ -628,6 +671,56 @@ class MultiModalModelForCausalLM(nn.Module):
         if bool(done.any()):
             ids = ids[:, : int(torch.nonzero(done)[0]) + 1]
         return ids
+
+
+    def _generate_beams(self, batch, max_new_tokens, sync_every, n, nrs, length_penalty, early_stopping, return_scores,
+                        decode_weights=None, prefill_weights=None):
+        """generate()'s beam-search loop (num_beams = n > 1, checked by generate).  The prefill runs on the B prompts into a
+        LayerKVCacheBeam; mm_beam_step reads its B rows of logits at step 0 and B n rows afterwards, and hands back the next ids
+        (the next embedding lookup) and the ancestor table of the coming step.  Nothing but the done flag comes to the host, every
+        sync_every steps; positions keep the padded-length quirk of _generate and the cache gets the PROMPT's mask."""
+        if self._flat is None:
+            self.pack_parameters()
+        dev = self.device
+        input_ids = batch["input_ids"].to(dev)
+        B = input_ids.shape[0]
+        V = self._llm_cfg.vocab_size
+        eos = self.config.eos_token_idx
+        if max_new_tokens <= 0:
+            ids = torch.empty((B * nrs, 0), dtype=torch.int64)
+            return (ids, torch.zeros(B * nrs, dtype=torch.float32)) if return_scores else ids
+        if decode_weights is not None and self.model._decode_w8 is None:
+            self.model.quantize_decode_weights(decode_weights)
+        dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
+        R = B * n
+        with torch.no_grad():
+            nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
+            attention_mask = prompt_mask = batch["attention_mask"].to(dev)
+            position_ids = batch["position_ids"].to(dev)
+            seq_length = attention_mask.shape[1]
+            cache = self.model.new_cache(B, seq_length + max_new_tokens, beams=n, prompt_len=seq_length)
+            tables = cache[0].tables
+            st = K.BeamState(B, n, max_new_tokens, V, dev)
+            emb = self.model.get_input_embeddings()
+            for i in range(max_new_tokens):
+                if i > 0:
+                    position_ids = torch.full((R, 1), seq_length + i - 1, dtype=torch.long, device=dev)
+                    attention_mask = prompt_mask
+                    tables.current = st.table(i)
+                pw = {"prefill_weights": prefill_weights} if i == 0 and prefill_weights is not None else {}      # the prefill call only
+                out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
+                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw, **pw)
+                next_ids = K.beam_step(out.logits[:, -1, :], st, i, eos, length_penalty, early_stopping)
+                if i + 1 == max_new_tokens:
+                    break
+                if (i + 1) % max(1, sync_every) == 0 and bool(st.done.item()):      # the only host sync of the loop
+                    break
+                nxt = emb(next_ids.view(R, 1))
+            ids, scores, lens = K.beam_finish(st, nrs, eos)
+            n_out = int(lens.max().item())
+            ids, scores = ids[:, :n_out].cpu(), scores.cpu()
+            K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
+        return (ids, scores) if return_scores else ids
 
 
 def bootstrap(config, tokenizer, modalities_config):

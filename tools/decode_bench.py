@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
-                                [--prefill-weights mxfp8] [--samples n]
+                                [--prefill-weights mxfp8] [--samples n] [--beams n]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
@@ -13,7 +13,12 @@ settings in this process, best of three after a warm-up each, before the usual l
 repeated n times (a batch of B n rows), alternating, best of three each after a warm-up: prefill + 1 token, ms/token and the bytes of
 the KV cache each allocates; then the decode-attention launch alone at the last step's lengths, mm_attn_decode_shared on the shared
 cache against mm_attn_decode on B n rows, over 16 layers' caches.  Sampled (T = 1, seed 0 unless --sample says otherwise).  The other
-flags apply to both sides (--kv-cache is refused by generate with n > 1)."""
+flags apply to both sides (--kv-cache is refused by generate with n > 1).
+--beams n: in this one process, (i) generate(num_beams=n, do_sample=False) against (ii) generate(num_return_sequences=n) sampled at
+T = 1, seed 0 -- the closest existing path: the same B n rows over one shared prompt cache, so the difference is the price of the
+selection and of the ancestor table -- alternating, best of three each after a warm-up; then mm_attn_decode_beam under an identity
+table against mm_attn_decode_shared at the last step's lengths, and the launches of one mm_beam_step against mm_sample (top_k = 50,
+top_p = 0.95) on 16 rows of the model's vocabulary."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -52,6 +57,11 @@ if "--samples" in sys.argv:
     del sys.argv[i:i + 2]
     if SAMPLE is None:
         SAMPLE = {"T": 1.0, "seed": 0}
+NB = 1
+if "--beams" in sys.argv:
+    i = sys.argv.index("--beams")
+    NB = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 33
@@ -153,6 +163,77 @@ def compare_samples(n):
               lambda i: K.attn_decode(q, kr[2 * i][:, :S + Ss], kr[2 * i + 1][:, :S + Ss], None, D ** -0.5), B * n * (S + Ss) * row)
 
 
+def compare_beams(n):
+    from multimeditron_amd import kernels as K
+    kw = {}
+    if DW:
+        kw["decode_weights"] = DW
+    if PW:
+        kw["prefill_weights"] = PW
+
+    def go(beams, new):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ids = model.generate(batch, max_new_tokens=new, do_sample=False, num_beams=n, num_return_sequences=n, **kw) if beams else \
+            model.generate(batch, max_new_tokens=new, temperature=1.0, seed=0, num_return_sequences=n, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, ids
+
+    for beams in (True, False):
+        go(beams, 2)                                       # warm-up (and the MXFP8 copies, if asked for)
+    t1, tn, shape = {True: [], False: []}, {True: [], False: []}, {}
+    for _ in range(3):                                     # alternating
+        for beams in (True, False):
+            t1[beams].append(go(beams, 1)[0])
+            dt, ids = go(beams, N)
+            tn[beams].append(dt)
+            shape[beams] = tuple(ids.shape)
+    for beams in (True, False):
+        a, b = min(t1[beams]), min(tn[beams])
+        name = f"num_beams={n} on {B} prompts" if beams else f"num_return_sequences={n} on {B} prompts (sampled)"
+        print(f"{name}: prefill+1 token {a * 1e3:.1f} ms; decode {(b - a) / (N - 1) * 1e3:.2f} ms/token (all runs "
+              f"{', '.join(f'{(y - x) / (N - 1) * 1e3:.2f}' for x, y in zip(t1[beams], tn[beams]))}); ids {shape[beams]}", flush=True)
+    lc = model.model.config
+    Hq, Hkv, D, L, Ss = lc.num_attention_heads, lc.num_key_value_heads, lc.head_dim, 16, N - 1
+    bf = torch.bfloat16
+    q = torch.randn(B * n, Hq, D, device="cuda", dtype=bf)
+    kp = [torch.randn(B, S, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+    ks = [torch.randn(B * n, N, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+    ident = torch.arange(B * n, dtype=torch.int32, device="cuda")[None, :].expand(N, B * n).contiguous()
+
+    def timed(name, fn, reps=6, per=L):
+        for i in range(per):
+            fn(i)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            for i in range(per):
+                fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"{name:66s} {e0.elapsed_time(e1) * 1e3 / (reps * per):7.1f} us/call", flush=True)
+
+    for _ in range(2):
+        timed(f"mm_attn_decode_beam, identity table ({B} x {S} + {B * n} x {Ss} keys)",
+              lambda i: K.attn_decode_beam(q, kp[2 * i], kp[2 * i + 1], ks[2 * i][:, :Ss], ks[2 * i + 1][:, :Ss], n, None, D ** -0.5, ident))
+        timed(f"mm_attn_decode_shared ({B} x {S} + {B * n} x {Ss} keys)",
+              lambda i: K.attn_decode_shared(q, kp[2 * i], kp[2 * i + 1], ks[2 * i][:, :Ss], ks[2 * i + 1][:, :Ss], n, None, D ** -0.5))
+    V = lc.vocab_size
+    rows = 16
+    logits = (3 * torch.randn(rows, V + 6, device="cuda")).to(bf)[:, :V]
+    for nb in sorted({n, 16}):
+        Bq = rows // nb
+        st = K.BeamState(Bq, nb, 64, V, "cuda")
+        K.beam_step(logits[:Bq], st, 0, V + 5, 1.0, False)
+        timed(f"mm_beam_step, {Bq} prompts x {nb} beams = {Bq * nb} rows of {V} (3 launches)",
+              lambda i: K.beam_step(logits[:Bq * nb], st, 1 + i % 8, V + 5, 1.0, False), per=8)
+    ws = K.sample_ws(rows, V, "cuda")
+    timed(f"mm_sample top_k=50 top_p=0.95, {rows} rows of {V} (9 launches)",
+          lambda i: K.sample(logits, V, 1.0, top_k=50, top_p=0.95, seed=0, offset=i, ws=ws), per=8)
+    timed(f"mm_sample plain, {rows} rows of {V} (3 launches)", lambda i: K.sample(logits, V, 1.0, seed=0, offset=i, ws=ws), per=8)
+
+
 def run(n, pw="same"):
     torch.cuda.synchronize()
     t = time.perf_counter()
@@ -173,6 +254,9 @@ def run(n, pw="same"):
     return time.perf_counter() - t, ids
 
 
+if NB > 1:
+    compare_beams(NB)
+    sys.exit(0)
 if NS > 1:
     compare_samples(NS)
     sys.exit(0)
