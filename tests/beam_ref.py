@@ -1,8 +1,8 @@
 """Beam search selection restated in fp64: rules a-g of mm_beam_step (include/mm_hip.h), one step at a time on explicit state.
 
 A step is *near* when its outcome could turn on fp32 rounding: two adjacent entries of the prompt's sorted top 2n + 1 log-probabilities
-closer than tau without being an exact tie inside one row (equal logits of one row stay equal in any precision; their order is by
-token), or a comparison of the finished set (a new entry against the worst one, rule f's s_new[0] / d_L against the worst one) closer
+closer than tau without being an exact tie (equal logits of one row stay equal in any precision, their order is by token; and so
+do equal values of two rows whose scores are equal and whose log-probability rows are bit-equal, their order is by row), or a comparison of the finished set (a new entry against the worst one, rule f's s_new[0] / d_L against the worst one) closer
 than tau.  A caller that compares a kernel against this file holds every step that is not near to exact equality."""
 import math
 
@@ -50,22 +50,24 @@ def top_candidates(lp, k):
     return [(-v, i // V, i % V) for v, i in cands]
 
 
-def step(p: Prompt, lp_rows, i, T, eos, length_penalty=1.0, early_stopping=False, tau=0.0):
+def step(p: Prompt, lp_rows, i, T, eos, length_penalty=1.0, early_stopping=False, tau=0.0, select=top_candidates):
     """One step of one prompt.  lp_rows [1 (i = 0) or n, V]: fp64 log-probabilities of every row's continuations (log_probs of the
-    logits).  Updates p; returns dict(tok, parent, score: the next running beams, entered: ranks that entered F, near)."""
+    logits).  Updates p; returns dict(tok, parent, score: the next running beams, entered: ranks that entered F, cands: the 2n
+    candidates of rule b and the first one left out, near).  select: rule b itself (tests/beam_chain.py swaps in a deliberately wrong one)."""
     n = p.n
     rows = 1 if i == 0 else n
     assert lp_rows.shape[0] == rows
     s = torch.tensor([0.0] if i == 0 else p.s, dtype=F64)
     lp = s[:, None] + lp_rows.to(F64)                                       # a
-    C = top_candidates(lp, 2 * n + 1)                                       # b (+ the first one left out)
+    C = select(lp, 2 * n + 1)                                               # b (+ the first one left out)
     near = False
     for (v0, j0, t0), (v1, j1, t1) in zip(C, C[1:]):
         if v0 == -math.inf or v1 == -math.inf:
             continue
-        if abs(v0 - v1) < tau and not (v0 == v1 and j0 == j1):
+        same = j0 == j1 or (float(s[j0]) == float(s[j1]) and torch.equal(lp_rows[j0], lp_rows[j1]))
+        if abs(v0 - v1) < tau and not (v0 == v1 and same):
             near = True
-    C = C[:2 * n]
+    ranked, C = C, C[:2 * n]
     last = i + 1 == T
     stop = [t == eos or last for _, _, t in C]                              # c
     run = [c for c, st in zip(C, stop) if not st][:n]                       # d
@@ -106,7 +108,7 @@ def step(p: Prompt, lp_rows, i, T, eos, length_penalty=1.0, early_stopping=False
         else:                                                               # the last step: not used again
             new_s.append(-math.inf), new_seq.append(list(old[r])), tok.append(eos), parent.append(r)
     p.s, p.seq = new_s, new_seq
-    return dict(tok=tok, parent=parent, score=new_s, entered=entered, near=near)
+    return dict(tok=tok, parent=parent, score=new_s, entered=entered, cands=ranked, near=near)
 
 
 def done(prompts, i, T, early_stopping):                                    # g

@@ -2,7 +2,9 @@
 (include/mm_hip.h).  Kernel: attn_decode_beam128_kernel<G> -- the body of attn_decode_shared128_kernel<G> with the suffix row looked up
 and clamped -- + attn_decode_merge_kernel.
 
-Every case runs three tables (identity, random inside each prompt, every row of a prompt pointing at one row) and is held to
+Every case runs four tables (identity, random inside each prompt, every row of a prompt pointing at one row, and the random one with
+a tenth of its entries outside the prompt's rows: -1, base - 1, base + n, 2^20, INT32_MIN -- the kernel clamps an entry into
+[base, base + n) before it forms an address, so the suffix it must read is the one gathered through the CLAMPED table) and is held to
   (a) the bits of mm_attn_decode_shared on the GATHERED suffix ks'[r, t] = ks[anc[t, r], t] with the same nsplit (for the identity
       table: on ks itself);
   (b) two runs giving the same bits;
@@ -40,6 +42,18 @@ def test_the_cases_cover_what_the_issue_lists():
         assert {c["n"] for c in cs} == {16 // G, 16 // G + 1, 3}
         assert {c["Sp"] for c in cs} == {1, 70, 150} and {c["Ss"] for c in cs} == {1, 17, 40} and {c["ns"] for c in cs} == {1, 3, "lib"}
     assert all(c["B"] == 2 and c["mask"] == "leftpad" for c in CASES)
+    # the out-of-range table: every case has entries outside its prompt's rows; every kind occurs below and above both prompts
+    kinds = set()
+    for c in CASES:
+        B, n, Ss = c["B"], c["n"], c["Ss"]
+        t = tables(B, n, Ss, 5 + c["Sp"] + Ss + n)
+        assert set(t) == {"identity", "random", "one-row", "out-of-range"}
+        oor, base = t["out-of-range"], (torch.arange(B * n) // n * n)[None, :].expand(Ss, B * n)
+        out = (oor < base) | (oor >= base + n)
+        assert bool(out.any()) and torch.equal(oor[~out], t["random"][~out]) and not torch.equal(clamped(oor, B, n), oor)
+        for v, b0 in zip(oor[out].tolist(), base[out].tolist()):
+            kinds.add(v if v in (-1, 1 << 20, -(1 << 31)) and not (v == -1 and b0 == 0) else ("below" if v < b0 else "above", b0 > 0))
+    assert kinds >= {1 << 20, -(1 << 31), -1, ("below", False), ("below", True), ("above", False), ("above", True)}, kinds
 
 
 def tables(B, n, Ss, seed):
@@ -49,7 +63,21 @@ def tables(B, n, Ss, seed):
     ident = torch.arange(R)[None, :].expand(Ss, R)
     rand = base + torch.randint(0, n, (Ss, R), generator=g)
     one = (base + (n - 1)).expand(Ss, R)
-    return {"identity": ident, "random": rand, "one-row": one}
+    hit = torch.rand(Ss, R, generator=g) < 0.1
+    hit.view(-1)[int(torch.randint(0, Ss * R, (1,), generator=g))] = True          # at least one, however small the table
+    kind = ((hit.view(-1).long().cumsum(0) - 1) % 5).view(Ss, R)
+    vals = (torch.full((Ss, R), -1), (base - 1).expand(Ss, R), (base + n).expand(Ss, R), torch.full((Ss, R), 1 << 20),
+            torch.full((Ss, R), -(1 << 31)))
+    oor = rand.clone()
+    for k, v in enumerate(vals):
+        oor = torch.where(hit & (kind == k), v, oor)
+    assert bool(((oor < base) | (oor >= base + n)).any())
+    return {"identity": ident, "random": rand, "one-row": one, "out-of-range": oor}
+
+
+def clamped(tab, B, n):
+    base = (torch.arange(B * n) // n * n)[None, :]
+    return torch.minimum(torch.maximum(tab, base), base + n - 1)
 
 
 def run_beam(q, kp, vp, ks, vs, n, key_mask, scale, ns, anc):
@@ -84,7 +112,8 @@ def test_beam_decode_contract(c):
         anc = wide.cuda()[:Ss, :R]
         got, g1 = run_beam(qd, kpd, vpd, ksd, vsd, n, mg, scale, ns, anc)
         again, g2 = run_beam(qd, kpd, vpd, ksd, vsd, n, mg, scale, ns, anc)
-        # ks'[r, t] = ks[anc[t, r], t]
+        # ks'[r, t] = ks[anc[t, r], t], every entry clamped into its prompt's rows as the kernel reads it
+        tab = clamped(tab, B, n)
         ksg, vsg = ks[tab, t_idx].transpose(0, 1).contiguous(), vs[tab, t_idx].transpose(0, 1).contiguous()
         if name == "identity":
             assert torch.equal(ksg.view(torch.int16), ks.view(torch.int16))

@@ -84,7 +84,8 @@ def test_the_cases_finish_early_and_run_out(hf):
 
 
 def test_reference_ties_and_nearness():
-    """ties go to the smaller flat index; an exact tie inside a row is not near, one across rows is"""
+    """ties go to the smaller flat index; an exact tie inside a row is not near, and neither is one across two rows of equal score
+    whose log-probability rows are bit-equal (fp32 keeps both equal); any other tie across rows is"""
     p = BR.Prompt(2)
     lp = BR.log_probs(torch.tensor([[1.0, 3.0, 3.0, 0.0, 3.0, -float("inf")]]))
     r = BR.step(p, lp, 0, 4, eos=9, tau=1e-4)
@@ -92,7 +93,15 @@ def test_reference_ties_and_nearness():
     p = BR.Prompt(2)
     p.s, p.seq = [-1.0, -1.0], [[1], [2]]
     rows = BR.log_probs(torch.tensor([[0.0, 5.0, 1.0, 1.0, 0.5, 0.2], [0.0, 5.0, 1.0, 1.0, 0.5, 0.2]]))
-    r = BR.step(p, rows, 1, 4, eos=9, tau=1e-4)
+    r = BR.step(p.copy(), rows, 1, 4, eos=9, tau=1e-4)
+    assert r["tok"] == [1, 1] and r["parent"] == [0, 1] and not r["near"]
+    # the same values from rows that are not bit-equal (the tail swapped: another sum), and bit-equal rows under different scores
+    swapped = BR.log_probs(torch.tensor([[0.0, 5.0, 1.0, 1.0, 0.5, 0.2], [0.0, 5.0, 1.0, 1.0, 0.2, 0.5]]))
+    r = BR.step(p.copy(), swapped, 1, 4, eos=9, tau=1e-4)
+    assert r["tok"] == [1, 1] and sorted(r["parent"]) == [0, 1] and r["near"]
+    q = p.copy()
+    q.s = [-1.0, -1.0 - 1e-6]
+    r = BR.step(q, rows, 1, 4, eos=9, tau=1e-4)
     assert r["tok"] == [1, 1] and r["parent"] == [0, 1] and r["near"]
 
 

@@ -271,6 +271,44 @@ def test_generate_beams_is_the_slow_loop(gold, model_bf16, monkeypatch):
     assert empty.shape == (2 * B, 0) and es_.shape == (2 * B,)
 
 
+def test_generate_sixteen_beams_over_a_long_table(gold, model_bf16):
+    """16 beams x 24 tokens: a table of more than 256 entries per prompt, evolved by mm_beam_step alone (the second trip of its copy
+    loops), goes through LayerKVCacheBeam into mm_attn_decode_beam; ids and score bits are the slow loop's (a plain reordered cache),
+    whatever sync_every"""
+    meta, w, v = gold
+    m = model_bf16
+    batch = R.golden_batch(v, "left")
+    B = batch["input_ids"].shape[0]
+    eos0 = m.config.eos_token_idx
+    m.model.drop_decode_weights()
+    n, T = 16, 24
+    assert (T - 1) * n > 256 and m.model.beams_ok(B, n) is None
+    calls = []
+    fwd = m.model.forward
+
+    def counting(*a, **kw):
+        calls.append(1)
+        return fwd(*a, **kw)
+
+    with options(attn_decode_wgs=1):
+        runs, steps = {}, {}
+        m.model.forward = counting
+        try:
+            for se in (1, 16):
+                del calls[:]
+                runs[se] = m.generate(batch, max_new_tokens=T, do_sample=False, num_beams=n, num_return_sequences=n, early_stopping="never",
+                                      sync_every=se, return_beam_scores=True)
+                steps[se] = len(calls)
+        finally:
+            del m.model.forward
+        want_ids, want_scores = slow_beams(m, batch, T, n, n, 1.0, "never", eos0)
+    ids, scores = runs[1]
+    assert ids.shape[0] == B * n and torch.equal(ids, want_ids) and torch.equal(scores.view(torch.int32), want_scores.view(torch.int32))
+    assert torch.equal(runs[16][0], ids) and torch.equal(runs[16][1].view(torch.int32), scores.view(torch.int32))
+    print(f"decoder calls: {steps}")
+    assert (steps[1] - 1) * n > 256, steps                                        # the run went past 256 table entries per prompt
+
+
 def _refused(m, batch, match, **kw):
     """generate raises ValueError naming the reason before the decoder runs at all"""
     def boom(*a, **k):
