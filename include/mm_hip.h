@@ -614,6 +614,35 @@ int mm_sample_uniforms(int64_t seed, int64_t offset, int rows, float* u, void* s
  * else is written (out [B, ld_out]: column col only).  MM_ERR_ARG: a NULL pointer, B < 0, col outside [0, ld_out); B = 0: MM_OK. */
 int mm_decode_select(const int64_t* tok, unsigned char* finished, int64_t eos, int B, int64_t* out, int ld_out, int col,
                      int64_t* next_ids, void* stream);
+/* generate()'s logits processors (repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=, suppress_tokens=) in one launch per
+ * step, between lm_head and the selection: logits [rows, ld] (MM_BF16 / MM_F32, V valid columns) -> out fp32 [rows, ld_out].
+ * Row history: hist int32 [rows, ld_hist]; the caller filled row r's plen[r] prompt ids (0 <= plen[r] <= max_plen; clamped) at
+ * hist[r, 0 .. plen[r]).  At step = i row r's history h has L = plen[r] + i entries; a call with i > 0 first stores
+ * (int32)last_ids[r] -- the id the previous step emitted, mm_decode_select's next_ids -- at hist[r, plen[r] + i - 1], so that it and
+ * every later call see it.  Calls are made with step = 0, 1, 2, ... (not checked); nothing else of hist is written.  History
+ * entries outside [0, V) never index a row: they are not penalised and not banned (as plain integers they still take part in the
+ * n-gram comparison of rule 2).
+ * Per row, x_v = float(logits[r, v]), fp32 arithmetic, p = repetition_penalty, in transformers' order (RepetitionPenalty ->
+ * NoRepeatNGram -> MinNewTokensLength -> SuppressTokens LogitsProcessor on fp32 scores):
+ *   1. p != 1: for every v that occurs in h, ONCE however often it occurs: x_v = x_v < 0 ? x_v * p : x_v / p (correctly rounded
+ *      division; -0 is not < 0, so -0 / p = -0; -inf stays -inf)
+ *   2. g = no_repeat_ngram_size > 0 and L + 1 >= g: for every i in [0, L - g] with h[i .. i+g-2] == h[L-g+1 .. L-1]:
+ *      x_{h[i+g-1]} = -inf  (g = 1: the empty tail, every id of h is banned)
+ *   3. step < min_new_tokens: x_eos = -inf
+ *   4. x_t = -inf for every t of suppress[0 .. n_suppress) (int32, device memory) inside [0, V); duplicates allowed
+ *   5. out[r, v] = x_v for v < V.  Columns [V, ld_out) of out are never written, columns [V, ld) of logits never read; out must
+ *      not overlap logits.
+ * hist and plen may be NULL iff p == 1 and g == 0 (no history is kept then and last_ids is not read); with hist given the newest id
+ * is stored whatever p and g are.  A row left without a finite score is out of contract, as for mm_sample.  Bitwise deterministic
+ * (integer LDS atomics only); no allocation, copy or synchronisation inside (capturable).
+ * MM_ERR_ARG before any launch: p not finite or <= 0, g < 0, min_new_tokens < 0, step < 0, eos outside [0, V) while step <
+ * min_new_tokens, V <= 0, ld < V, ld_out < V, rows < 0, n_suppress < 0, max_plen < 0 or max_plen + step > ld_hist (hist given), a
+ * required pointer that is NULL (logits, out; suppress when n_suppress > 0; hist and plen when p != 1 or g > 0; plen, and last_ids
+ * when step > 0, when hist is given), out == logits.  rows = 0: MM_OK.                                                          */
+int mm_logits_process(int dtype, const void* logits, int rows, int V, int ld, int step, const int64_t* last_ids, int32_t* hist,
+                      int ld_hist, const int32_t* plen, int max_plen, float repetition_penalty, int no_repeat_ngram_size,
+                      int min_new_tokens, int64_t eos, const int32_t* suppress, int n_suppress, float* out, int ld_out,
+                      void* stream);
 
 /* ---- MoE image modality: gating-weighted fusion of the experts' token features (modalities/image_modality_moe.py:163-205)
  * X [E, n, L] (L = P*C, expert-major), gate [n, E] fp32 (the gating network's softmax weights, expert order), idx[J] = the

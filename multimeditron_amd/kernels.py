@@ -1087,6 +1087,49 @@ def decode_select(tok, finished, eos, out, col, next_ids):
     call("mm_decode_select", _p(tok), _p(finished), int(eos), tok.numel(), _p(out), out.stride(0), int(col), _p(next_ids), _stream())
 
 
+class LogitsState:
+    """The device state of generate()'s logits processors for one call: the settings, the suppressed ids (int32), the fp32 score
+    rows the selectors read, and -- only when the repetition penalty or the n-gram ban is on -- the int32 history of every row
+    (mm_logits_process: the row's prompt ids first, then the emitted ids, appended by the kernel).
+
+    prompt_ids / prompt_mask [B, Sp] (device): a row's prompt history is its ids where the mask is not 0, in order; every prompt row
+    is repeated `samples` times (row b samples + j).  room = the number of steps the history must hold."""
+
+    def __init__(self, rows, V, device, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress=(), prompt_ids=None,
+                 prompt_mask=None, samples=1, room=0):
+        self.rows, self.V = int(rows), int(V)
+        self.p, self.g, self.min_new = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens)
+        self.suppress = torch.tensor([int(t) for t in suppress], dtype=torch.int32, device=device) if len(suppress) else None
+        self.ld_out = (self.V + 63) // 64 * 64
+        self.out = torch.empty((self.rows, self.ld_out), dtype=torch.float32, device=device)
+        self.hist = self.plen = None
+        self.max_plen = 0
+        if self.p != 1.0 or self.g > 0:
+            B, Sp = prompt_ids.shape
+            assert B * samples == self.rows and prompt_mask.shape == prompt_ids.shape
+            keep = prompt_mask != 0
+            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)              # the visible positions first, in order
+            plen = keep.sum(dim=1)
+            ids = torch.gather(prompt_ids, 1, order).masked_fill(torch.arange(Sp, device=device)[None, :] >= plen[:, None], -1)
+            hist = torch.full((B, Sp + int(room)), -1, dtype=torch.int32, device=device)
+            hist[:, :Sp] = ids.to(torch.int32)
+            self.hist = hist.repeat_interleave(samples, dim=0).contiguous() if samples > 1 else hist
+            self.plen = plen.to(torch.int32).repeat_interleave(samples).contiguous()
+            self.max_plen = int(Sp)
+
+
+def logits_process(logits2d, st: LogitsState, step, last_ids, eos):
+    """rules 1-5 of mm_logits_process on logits [rows, >= V] (bf16 / fp32) -> st.out[:, :V] (fp32, what the selectors read);
+    last_ids: the ids the previous step emitted (read when step > 0 and a history is kept)."""
+    assert logits2d.stride(-1) == 1 and logits2d.shape[0] == st.rows
+    hist = st.hist
+    call("mm_logits_process", dt(logits2d), _p(logits2d), st.rows, st.V, logits2d.stride(0), int(step),
+         _p(last_ids) if hist is not None else None, _p(hist), hist.stride(0) if hist is not None else 0, _p(st.plen), st.max_plen,
+         st.p, st.g, st.min_new, int(eos), _p(st.suppress), 0 if st.suppress is None else st.suppress.numel(), _p(st.out), st.ld_out,
+         _stream())
+    return st.out[:, :st.V]
+
+
 # ------------------------------------------------------------------------------------------------ optimizer
 def gradnorm(flat_grads, max_norm):
     """flat_grads: list of 1-D flat gradient buffers -> device tensor [2] = (total_norm, clip_coef)."""

@@ -15,7 +15,7 @@ import logging
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Union
+from typing import Any, Dict, List, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
@@ -465,7 +465,8 @@ class MultiModalModelForCausalLM(nn.Module):
                  seed: Optional[int] = None, generator: Optional[torch.Generator] = None, decode_weights: Optional[str] = None,
                  kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, num_return_sequences: int = 1,
                  num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, return_beam_scores: bool = False,
-                 **kwargs) -> torch.Tensor:
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                 min_new_tokens: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -527,7 +528,22 @@ class MultiModalModelForCausalLM(nn.Module):
         Composes with decode_weights (B n <= 16) and prefill_weights.  ValueError before the modalities are encoded for: num_beams
         outside [1, 16], do_sample=True, any of top_k / top_p / min_p / seed / generator, kv_cache="mxfp8", num_return_sequences >
         num_beams, a length_penalty that is not finite, another early_stopping, a vocabulary below 2 n, and a model samples_ok
-        refuses.  num_beams = 1 is the code above, untouched."""
+        refuses.  num_beams = 1 is the code above, untouched.
+
+        repetition_penalty= / no_repeat_ngram_size= / min_new_tokens= / suppress_tokens= (opt-in, each on its own): transformers'
+        RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength -> SuppressTokens logits processors, applied in that order to the
+        fp32 scores of every step by ONE kernel (include/mm_hip.h: mm_logits_process) between lm_head and the selection; greedy,
+        torch.multinomial and the device sampler then select from its fp32 output unchanged.  The history of a row -- what the
+        penalty and the n-gram ban look at -- lives on the device: the prompt's ids first, then every emitted id (the eos ids a
+        finished row keeps emitting included), appended by the kernel; the host sees no token.  As in transformers' decoder-only
+        generate the PROMPT counts, placeholder ids of spliced modalities like any id; the one deviation: positions whose
+        attention_mask is 0 (pads) do not count (a pad == eos tokenizer would otherwise penalise eos on every padded row).
+        repetition_penalty: a finite number > 0 (None or 1.0: off); no_repeat_ngram_size, min_new_tokens: ints >= 0 (None or 0: off;
+        min_new_tokens bans config.eos_token_idx while step < min_new_tokens); suppress_tokens: ids in [0, vocab_size) that are never
+        chosen, e.g. the attachment placeholder and pad ids (None or empty: off).  Compose with decode_weights, kv_cache,
+        prefill_weights, num_return_sequences (every sample row keeps its own history) and every sampler path.  NOT with num_beams > 1
+        (processors inside beam search act on log-probabilities inside mm_beam_step: out of scope, ValueError).  A bad value raises
+        ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids."""
         n = num_return_sequences
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
@@ -536,6 +552,11 @@ class MultiModalModelForCausalLM(nn.Module):
             raise ValueError(f"num_beams must be an int in [1, 16], got {nb!r}")
         if nb == 1 and return_beam_scores:
             raise ValueError("return_beam_scores needs num_beams > 1")
+        processors = self._logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+        if nb > 1 and processors is not None:
+            given = [k for k, on in zip(("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens"),
+                                        (processors[0] != 1.0, processors[1] > 0, processors[2] > 0, len(processors[3]) > 0)) if on]
+            raise ValueError(f"num_beams={nb} with {', '.join(given)}: logits processors inside beam search are out of scope")
         if nb > 1:
             llm = self.model
             B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
@@ -588,10 +609,35 @@ class MultiModalModelForCausalLM(nn.Module):
                 seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
         return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
                               (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache, prefill_weights,
-                              **({"samples": n} if n > 1 else {}))
+                              **({"samples": n} if n > 1 else {}), **({"processors": processors} if processors is not None else {}))
+
+    def _logits_processors(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens):
+        """generate()'s four processor arguments, checked -> (p, g, min_new_tokens, suppressed ids), or None when all are off."""
+        p = 1.0 if repetition_penalty is None else repetition_penalty
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not p > 0:
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
+        g = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+        if isinstance(g, bool) or not isinstance(g, int) or g < 0:
+            raise ValueError(f"no_repeat_ngram_size must be an int >= 0, got {no_repeat_ngram_size!r}")
+        mn = 0 if min_new_tokens is None else min_new_tokens
+        if isinstance(mn, bool) or not isinstance(mn, int) or mn < 0:
+            raise ValueError(f"min_new_tokens must be an int >= 0, got {min_new_tokens!r}")
+        if suppress_tokens is not None and (isinstance(suppress_tokens, (str, bytes)) or not hasattr(suppress_tokens, "__iter__")):
+            raise ValueError(f"suppress_tokens must be a sequence of ints, got {suppress_tokens!r}")
+        sup = [] if suppress_tokens is None else list(suppress_tokens)
+        if float(p) == 1.0 and g == 0 and mn == 0 and not sup:
+            return None
+        V = self._llm_cfg.vocab_size
+        for t in sup:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < V:
+                raise ValueError(f"suppress_tokens must be ints in [0, {V}), got {t!r}")
+        eos = self.config.eos_token_idx
+        if mn > 0 and (isinstance(eos, bool) or not isinstance(eos, int) or not 0 <= eos < V):
+            raise ValueError(f"min_new_tokens={mn} needs config.eos_token_idx in [0, {V}), got {eos!r}")
+        return float(p), g, mn, sup
 
     def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None, prefill_weights=None,
-                  samples: int = 1) -> torch.Tensor:
+                  samples: int = 1, processors=None) -> torch.Tensor:
         """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
 
         The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
@@ -602,7 +648,11 @@ class MultiModalModelForCausalLM(nn.Module):
 
         samples = n > 1 (generate's num_return_sequences): the prefill runs on the B prompts into a LayerKVCacheShared; its logits
         are repeated n times and from there on B stands for the B n sample rows.  The decode steps hand the PROMPT's mask to the
-        cache (generated tokens are always visible)."""
+        cache (generated tokens are always visible).
+
+        processors = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppressed ids), checked by generate, else None: every
+        step's logits go through mm_logits_process (one launch; the rows' history stays on the device, fed from next_ids) and the
+        selection reads its fp32 output."""
         if self._flat is None:
             self.pack_parameters()
         dev = self.device
@@ -638,6 +688,11 @@ class MultiModalModelForCausalLM(nn.Module):
             emb = self.model.get_input_embeddings()
             sample_ws = K.sample_ws(B, V, dev) if sampler is not None else None       # once per call
             tok_buf = torch.empty(B, dtype=torch.int64, device=dev) if sampler is not None else None
+            lp = None
+            if processors is not None:
+                p_, g_, mn_, sup_ = processors
+                lp = K.LogitsState(B, V, dev, p_, g_, mn_, sup_, prompt_ids=input_ids, prompt_mask=batch["attention_mask"].to(dev),
+                                   samples=samples, room=max_new_tokens)
             for i in range(max_new_tokens):
                 if i > 0:
                     position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
@@ -648,6 +703,8 @@ class MultiModalModelForCausalLM(nn.Module):
                 logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
                 if samples > 1 and i == 0:
                     logits2d = logits2d.repeat_interleave(samples, dim=0)      # plumbing: sample j of prompt b is row b n + j
+                if lp is not None:
+                    logits2d = K.logits_process(logits2d, lp, i, next_ids, eos)    # fp32 scores; the history takes next_ids in
                 if sampler is not None:
                     k_, p_, mp_, sd_ = sampler
                     tok = K.sample(logits2d, V, temperature, top_k=k_, top_p=p_, min_p=mp_, seed=sd_, offset=i, ws=sample_ws,

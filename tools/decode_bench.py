@@ -2,6 +2,7 @@
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
                                 [--prefill-weights mxfp8] [--samples n] [--beams n]
+                                [--processors repetition_penalty=1.2,no_repeat_ngram_size=3]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
@@ -18,7 +19,11 @@ flags apply to both sides (--kv-cache is refused by generate with n > 1).
 T = 1, seed 0 -- the closest existing path: the same B n rows over one shared prompt cache, so the difference is the price of the
 selection and of the ancestor table -- alternating, best of three each after a warm-up; then mm_attn_decode_beam under an identity
 table against mm_attn_decode_shared at the last step's lengths, and the launches of one mm_beam_step against mm_sample (top_k = 50,
-top_p = 0.95) on 16 rows of the model's vocabulary."""
+top_p = 0.95) on 16 rows of the model's vocabulary.
+--processors k=v,...: in this one process, generate with the listed logits processors (repetition_penalty, no_repeat_ngram_size,
+min_new_tokens, suppress_tokens=a+b+c) against the same call without them, alternating, best of three each after a warm-up:
+prefill + 1 token and ms/token of both and the difference (one mm_logits_process launch per step, and the selection reading fp32
+scores instead of bf16 logits).  The other flags apply to both sides."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -61,6 +66,14 @@ NB = 1
 if "--beams" in sys.argv:
     i = sys.argv.index("--beams")
     NB = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+PROC = None
+if "--processors" in sys.argv:
+    i = sys.argv.index("--processors")
+    PROC = {}
+    for kv in sys.argv[i + 1].split(","):
+        k, val = kv.split("=")
+        PROC[k] = float(val) if k == "repetition_penalty" else [int(t) for t in val.split("+")] if k == "suppress_tokens" else int(val)
     del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -234,7 +247,7 @@ def compare_beams(n):
     timed(f"mm_sample plain, {rows} rows of {V} (3 launches)", lambda i: K.sample(logits, V, 1.0, seed=0, offset=i, ws=ws), per=8)
 
 
-def run(n, pw="same"):
+def run(n, pw="same", proc=None):
     torch.cuda.synchronize()
     t = time.perf_counter()
     dw = {"decode_weights": DW} if DW else {}
@@ -243,6 +256,8 @@ def run(n, pw="same"):
         dw["prefill_weights"] = pw
     if KV:
         dw["kv_cache"] = KV
+    if proc:
+        dw.update(proc)
     if SAMPLE is None:
         ids = model.generate(batch, max_new_tokens=n, temperature=0.1, do_sample=False, **dw)
     else:
@@ -254,6 +269,26 @@ def run(n, pw="same"):
     return time.perf_counter() - t, ids
 
 
+def compare_processors(proc):
+    for on in (True, False):
+        run(2, proc=proc if on else None)                  # warm-up (and the MXFP8 copies, if asked for)
+    t1, tn = {True: [], False: []}, {True: [], False: []}
+    for _ in range(3):                                     # alternating
+        for on in (True, False):
+            t1[on].append(run(1, proc=proc if on else None)[0])
+            tn[on].append(run(N, proc=proc if on else None)[0])
+    per = {}
+    for on in (True, False):
+        a, b = min(t1[on]), min(tn[on])
+        per[on] = (b - a) / (N - 1) * 1e3
+        print(f"B={B} S={S} processors {proc if on else 'off'}: prefill+1 token {a * 1e3:.1f} ms; decode {per[on]:.3f} ms/token (all runs "
+              f"{', '.join(f'{(y - x) / (N - 1) * 1e3:.3f}' for x, y in zip(t1[on], tn[on]))})", flush=True)
+    print(f"processors on - off: {(per[True] - per[False]) * 1e3:+.1f} us/token ({(per[True] / per[False] - 1) * 100:+.2f} %)", flush=True)
+
+
+if PROC:
+    compare_processors(PROC)
+    sys.exit(0)
 if NB > 1:
     compare_beams(NB)
     sys.exit(0)

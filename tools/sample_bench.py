@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """mm_sample alone on the decoder's vocabulary (V = 128 258, bf16 logits) beside the greedy selection mm_argmax_softmax_split on the
-same rows (run on the GPU box).  HIP events around 200 back-to-back calls after 20 warm-up calls.
+same rows, and the logits processors' launch mm_logits_process (repetition penalty 1.2, 3-gram ban, a history of 2048 + 512 ids) on
+them (run on the GPU box).  HIP events around 200 back-to-back calls after 20 warm-up calls.
    python tools/sample_bench.py [--iters N]"""
 import argparse
 import os
@@ -46,6 +47,18 @@ def main():
             us = timed(lambda: K.sample(lg, V, 0.7, seed=1, offset=0, ws=ws, out=out, **kw), args.iters)
             line.append(f"{name} {us:6.1f} us")
         print(" | ".join(line), flush=True)
+        # the logits processors' one launch on the same rows: a history of 2048 prompt + 512 generated ids, p = 1.2, g = 3; then the
+        # history scans alone (p = 1, g = 0 with min_new_tokens: the copy to fp32 and one banned id)
+        hist_len, room = 2048 + 512, 8
+        st = K.LogitsState(rows, V, "cuda", 1.2, 3, prompt_ids=torch.randint(0, V, (rows, hist_len), device="cuda"),
+                           prompt_mask=torch.ones(rows, hist_len, dtype=torch.long, device="cuda"), room=room)
+        last = torch.randint(0, V, (rows,), device="cuda")
+        full = timed(lambda: K.logits_process(lg, st, room, last, 0), args.iters)          # step = room: the same slot every call
+        st0 = K.LogitsState(rows, V, "cuda", min_new_tokens=room + 1)
+        copy = timed(lambda: K.logits_process(lg, st0, room, last, 0), args.iters)
+        mb = rows * V * 6 / 1e6
+        print(f"rows={rows:2d}  logits_process p=1.2 g=3 history {hist_len + room} {full:6.1f} us | no history (min_new_tokens only) "
+              f"{copy:6.1f} us | {mb:.1f} MB of logits in and scores out, {mb / full:.2f} TB/s", flush=True)
 
 
 if __name__ == "__main__":
