@@ -450,6 +450,75 @@ int mm_attn_decode_beam(int dtype, const void* q, const void* kp, const void* vp
                         int64_t vs_sb, int64_t vs_ss, int64_t vs_sh, const int64_t* key_mask, float scale, void* out,
                         float* workspace, int nsplit, const int32_t* anc, int anc_ld, void* stream);
 
+/* mm_attn_decode_verify (generate's prompt_lookup_num_tokens; opt-in): Q causal query positions per sequence over ONE read of the
+ * sequence's keys, with per-sequence lengths that live on the device.  q [B*Q,Hq,D] (strides q_sb per row, q_sh; row b*Q + j is
+ * position j of sequence b), k/v [B,Scap,Hkv,D] a view of the cache (element strides as in mm_attn_decode), key_mask [B,Sp] or NULL
+ * over the prompt (0 <= Sp <= Scap; ignored when key_mask is NULL), base int32 [B] on the device, out [B*Q,Hq,D] contiguous.
+ * Query (b, j) sees key t iff t <= base[b] + j and (t >= Sp or key_mask[b,t] != 0).  The kernel clamps base[b] into [0, Scap - Q], so
+ * no value can make it read outside the view.  MM_BF16, D = 128, Hq/Hkv = G in {1,2,4}, 1 <= Q <= 16, Scap >= Q; another dtype, D
+ * or G is MM_ERR_UNSUPPORTED.  A 16-column MFMA tile packs 16/G query positions of one sequence (column jl*G + g is head g
+ * of the tile's position jl), so a key is read once per tile; further positions take further tiles (workgroups).
+ * Slices, workspace, merge: mm_attn_decode_shared's.  Slices cover [0, Scap) -- a bound the host knows without a sync -- with chunk =
+ * ceil(Scap / nsplit); slice s holds keys [s*chunk, min(Scap, (s+1)*chunk)); a slice past a row's length writes a neutral record
+ * (m = -inf, l = 0, o = 0).  workspace: f32 [B*Q*Hq*nsplit*(D+2)] in mm_attn_decode's record format, merged by the same second
+ * launch.  Any nsplit >= 1 is accepted.  Keys in [0, base[b] + Q) (after the clamp) are read and must be finite, masked ones
+ * included; rows from base[b] + Q on are never read and nothing stored there matters.  A row with no visible key gives 0.
+ * Bit identity: for every accepted shape and nsplit, out[b*Q + j] has the bits of mm_attn_decode (sync = NULL, "attn_decode_mfma" = 1,
+ * the same nsplit) run on ONE row: q[b*Q + j] over k/v[b, :Scap] (finite everywhere) with the mask [key_mask[b] | ones up to
+ * base[b] + j | zeros after]: a score is one MFMA output element, which does not depend on the other columns; a key the mask hides
+ * contributes p = 0 exactly, whatever finite value stands in its place; the softmax, the P.V chain and the merges keep that kernel's
+ * order.
+ * MM_ERR_ARG: a NULL operand (q, k, v, base, out, workspace), B < 0, Q outside [1, 16], Scap < Q, Sp outside [0, Scap] with a mask,
+ * nsplit < 1, Hq % Hkv != 0, more than 65535 (sequence, tile) pairs; MM_ERR_ALIGN: a stride that is not a multiple of 8 elements, q / k
+ * / v not 16-byte aligned.  Every check comes before any launch; B = 0: MM_OK, nothing written.  No allocation, copy or
+ * synchronisation inside (capturable).
+ * mm_attn_decode_verify_splits: mm_attn_decode_shared_splits with n = Q: ceil(T / (B * ceil(Q/4) * Hkv)) with T = ceil(2 *
+ * attn_decode_wgs / 3), at least 64 keys of Scap per slice, at least 1.                                                       */
+int mm_attn_decode_verify_splits(int B, int Q, int Hkv, int Scap);
+int mm_attn_decode_verify(int dtype, const void* q, const void* k, const void* v, int B, int Q, int Scap, int Sp, int Hq, int Hkv,
+                          int D, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
+                          int64_t v_sh, const int64_t* key_mask, const int32_t* base, float scale, void* out, float* workspace,
+                          int nsplit, void* stream);
+
+/* ---- Prompt-lookup speculative decoding (generate's prompt_lookup_num_tokens = k; opt-in; greedy only).  transformers'
+ * PromptLookupCandidateGenerator.get_candidates per row, for `rows` <= 16 rows at once, and the bookkeeping of a verify step, all on
+ * the device.  Row state (int32, device): hist [rows, ld_hist] the visible prompt ids followed by every emitted id (mm_logits_process'
+ * layout), hlen[r] its length, count[r] ids emitted so far, finished[r] (0 / 1: eos emitted), base[r] the position and cache slot of
+ * the row's newest id.  A row is ACTIVE iff finished[r] == 0 and count[r] < max_new.
+ *
+ * mm_lookup_draft: with h = hist[r], L = hlen[r] (clamped into [0, ld_hist]; L >= 1 is the caller's contract):
+ *   for g = min(max_ngram, L - 1) down to 1: the FIRST i (ascending) in [0, L - g) with h[i .. i+g) == h[L-g .. L) wins, at the largest
+ *   g that has one (windows may overlap the tail; i + g < L, so at least one id follows).  start = i + g; the candidate is
+ *   h[start .. min(start + k, L)), cut before its first eos (an empty result means no draft: no other match is tried, as in HF), then
+ *   clipped to max_new - count[r] - 1 ids.  n_draft[r] = its length, 0 for a row that is not active.
+ *   ids[r, 0] = h[L-1], ids[r, 1 .. n_draft] = the draft, the remaining columns repeat ids[r, 0]; pos[r, j] = base[r] + j.  ids, pos:
+ *   int64 [rows, k+1] contiguous.  One workgroup per row; the first match is an integer min-reduction: the same result on every launch.
+ *   MM_ERR_ARG before any launch: a NULL pointer, rows outside [0, 16], k outside [1, 15], max_ngram < 1, max_new < 1, ld_hist < 1.
+ *
+ * mm_kv_append_at: the roped k heads and the v heads of x [B*Q, ld] (a fused q|k|v row of (Hq + 2 Hkv) * D elements, MM_BF16, row
+ *   b*Q + j) are copied to kcache / vcache [B, Smax, Hkv, D] (element strides c_sb per sequence, c_ss per slot, D per head) at slot
+ *   base[b] + j: the bits LayerKVCache.store writes.  A slot outside [0, Smax) is skipped: nothing is written for it.
+ *   MM_ERR_ARG: a NULL pointer, B < 0, Q outside [1, 16], Hq < 1, Hkv < 1, Smax < 1, ld < (Hq + 2 Hkv) * D, c_ss < Hkv * D, c_sb < Smax * c_ss (B > 1); MM_ERR_UNSUPPORTED: another
+ *   dtype, D % 8 != 0; MM_ERR_ALIGN: ld, c_sb or c_ss not a multiple of 8 elements, x / kcache / vcache not 16-byte aligned.
+ *
+ * mm_lookup_accept: tok int64 [rows, Q] is the model's own choice behind every verify position (Q = k + 1; Q = 1 with ids and n_draft
+ *   NULL: the prefill's token, a verify step without drafts).  Per ACTIVE row: a = the number of leading j < n_draft[r] (clamped into
+ *   [0, Q - 1]) with ids[r, 1+j] == tok[r, j]; tok[r, 0 .. a] are emitted in order, stopping after the first eos (finished[r] = 1) or
+ *   when count[r] reaches max_new.  The m >= 1 emitted ids go to out[r, count[r] ..] (int64 [rows, ld_out], ld_out >= max_new) and to
+ *   hist[r, hlen[r] ..] (an index >= ld_hist is not written); count, hlen and base each grow by m; stats[r] += (1, m - 1) (int32
+ *   [rows, 2]: verify steps, accepted drafts).  A row that is not active changes nothing.  done[0] = 1 iff no row is active after the
+ *   call, else 0.  One workgroup.  MM_ERR_ARG before any launch: a NULL pointer (ids / n_draft: only when Q > 1), rows outside [0, 16],
+ *   Q outside [1, 16], max_new < 1, ld_out < max_new, ld_hist < 1.
+ * All three: no allocation, copy or synchronisation inside (capturable); rows / B = 0: MM_OK, nothing written.                    */
+int mm_lookup_draft(const int32_t* hist, int ld_hist, const int32_t* hlen, const int32_t* count, const int32_t* finished,
+                    const int32_t* base, int rows, int k, int max_ngram, int max_new, int64_t eos, int64_t* ids, int64_t* pos,
+                    int32_t* n_draft, void* stream);
+int mm_kv_append_at(int dtype, const void* x, int ld, int B, int Q, int Hq, int Hkv, int D, const int32_t* base, void* kcache,
+                    void* vcache, int64_t c_sb, int64_t c_ss, int Smax, void* stream);
+int mm_lookup_accept(const int64_t* tok, const int64_t* ids, const int32_t* n_draft, int rows, int Q, int max_new, int64_t eos,
+                     int64_t* out, int ld_out, int32_t* hist, int ld_hist, int32_t* hlen, int32_t* count, int32_t* finished,
+                     int32_t* base, int32_t* stats, int32_t* done, void* stream);
+
 /* ---- Beam search selection on the device (generate's num_beams = n; opt-in).  transformers' GenerationMixin._beam_search with one
  * eos token, no logits processors and do_sample = False, restated without its -1e9 arithmetic.  Per prompt b the state is n running
  * beams (fp32 score s[j] and a sequence), a finished set F of at most n entries (normalised score, sequence, length) and a flag

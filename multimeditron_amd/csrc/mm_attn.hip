@@ -2166,6 +2166,135 @@ __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSha
 template <int G>
 __global__ __launch_bounds__(256, 2) void attn_decode_beam128_kernel(DecodeSharedArgs a) { decode_shared128_body<G, true>(a); }
 
+// mm_attn_decode_verify: Q causal query positions of one sequence over ONE read of its keys (generate's prompt-lookup verify step).
+// The column tile of decode_shared128_body with positions in place of samples: column c = jl G + g is head g of position j0 + jl of
+// sequence b, every block is a "prefix" block (one set of 4 MFMAs and one set of V rows for all live columns), and what differs per
+// column is only which keys it sees: t <= lim = base[b] + j, with base read from the device and clamped into [0, Scap - Q].  Keys from
+// kstop = min(kend, base + j0 + nlive) on are visible to no column of the tile: their blocks are skipped and clamped loads stay below
+// kstop, so nothing behind the tile's last position is read.  For the single row mm_attn_decode would run under the mask [mask | ones
+// up to lim | zeros after] a skipped block is a no-op (alpha = 1, p = 0: o and l keep their bits), a hidden key inside a processed
+// block adds p = 0 times a finite value, and everything else is the code above -- the records and the merged output have its bits.
+struct DecodeVerifyArgs {
+  const void *q, *k, *v;
+  int B, Q, Scap, Sp, Hq, Hkv;
+  int64_t q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
+  const int64_t* kmask;          // [B, Sp]: the prompt only
+  const int32_t* base;           // [B], device
+  float scale;
+  float* ws;
+  int nsplit, chunk, tiles;      // tiles = ceil(Q / P)
+};
+
+#define MM_VF_EACH16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+template <int G>
+__global__ __launch_bounds__(256, 2) void attn_decode_verify128_kernel(DecodeVerifyArgs a) {
+  constexpr int D = 128, P = 16 / G;
+  static_assert(G == 1 || G == 2 || G == 4, "P = 16 / G positions share a column tile");
+  __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
+  __shared__ float red_ml[4][16][2];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int row = l & 15, kq = l >> 4;         // row: key of the block (K operand), column (scores), 8-dim group (V)
+  const int split = blockIdx.x, hkv = blockIdx.y;
+  const int b = blockIdx.z / a.tiles, j0 = (blockIdx.z % a.tiles) * P;
+  const int nlive = min(P, a.Q - j0), ncols = nlive * G;
+  const int64_t r0 = (int64_t)b * a.Q + j0;    // query row of the tile's first position
+  const int base = min(max(a.base[b], 0), a.Scap - a.Q);
+  const bf16* Kb = (const bf16*)a.k + b * a.k_sb + hkv * a.k_sh;
+  const bf16* Vb = (const bf16*)a.v + b * a.v_sb + hkv * a.v_sh;
+  const int kbeg = split * a.chunk, kend = min(a.Scap, kbeg + a.chunk);
+  const int kstop = min(kend, base + j0 + nlive);            // <= Scap: the first key no column of the tile sees
+  const int lim = base + j0 + min(row / G, nlive - 1);       // this lane's column sees keys t <= lim
+  const float sc = a.scale * LOG2E;
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (row < ncols) qf[ks] = *(const bf16x8*)((const bf16*)a.q + (r0 + row / G) * a.q_sb + (hkv * G + row % G) * a.q_sh + ks * 32 + kq * 8);
+  }
+  float o[16][8];
+#pragma unroll
+  for (int c = 0; c < 16; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[c][j] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  bf16x8 kf[4], vf[4];
+  for (int k0 = kbeg + w * 16; k0 < kstop; k0 += 64) {
+    const int kk = min(k0 + row, kstop - 1);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const bf16x8*)(Kb + (int64_t)kk * a.k_ss + ks * 32 + kq * 8);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int kv = min(k0 + 4 * kq + u, kstop - 1);
+      vf[u] = *(const bf16x8*)(Vb + (int64_t)kv * a.v_ss + row * 8);
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], acc, 0, 0, 0);
+    float vx[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vx[u][j] = (float)vf[u][j];
+    float sv[4], bm = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = k0 + 4 * kq + r;
+      bool ok = key < kend && key <= lim;                    // hence key < kstop: a key that was loaded, not a clamped one
+      if (ok && a.kmask && key < a.Sp) ok = a.kmask[(int64_t)b * a.Sp + key] != 0;      // generated keys are always visible
+      sv[r] = ok ? acc[r] * sc : -INFINITY;
+      bm = fmaxf(bm, sv[r]);
+    }
+    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float mn = fmaxf(m_run, bm);
+    const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m_run - mn);
+    float p[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sv[r] - mn);
+    l_run = l_run * alpha + ((p[0] + p[1]) + (p[2] + p[3]));
+    m_run = mn;
+#define MM_VF_COL(c) if (c < ncols) decode_shared_head<c>(o, alpha, p, vx);
+    MM_VF_EACH16(MM_VF_COL)
+#undef MM_VF_COL
+  }
+  // the wave's partial per live column, then the four waves: decode_shared128_body's reduction
+#define MM_VF_RED(c)                                                                              \
+  if (c < ncols) {                                                                                \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) o[c][j] = kq_sum(o[c][j]);                      \
+  }
+  MM_VF_EACH16(MM_VF_RED)
+#undef MM_VF_RED
+  if (kq == 0) {
+#define MM_VF_PUT(c)                                                                              \
+    if (c < ncols) {                                                                              \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) red_o[w][c][row * 8 + j] = o[c][j];           \
+    }
+    MM_VF_EACH16(MM_VF_PUT)
+#undef MM_VF_PUT
+  }
+  float lt = l_run + __shfl_xor(l_run, 16, 64);
+  lt += __shfl_xor(lt, 32, 64);
+  if (kq == 0 && row < ncols) { red_ml[w][row][0] = m_run; red_ml[w][row][1] = lt; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncols * D; i += 256) {
+    const int c = i / D, d = i % D;
+    float mn = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) mn = fmaxf(mn, red_ml[ww][c][0]);
+    float ltot = 0.f, ot = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float al = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(red_ml[ww][c][0] - mn);
+      ltot += red_ml[ww][c][1] * al;
+      ot += red_o[ww][c][d] * al;
+    }
+    float* rec = a.ws + (((r0 + c / G) * a.Hq + hkv * G + c % G) * a.nsplit + split) * (D + 2);
+    rec[2 + d] = ot;
+    if (d == 0) { rec[0] = mn; rec[1] = ltot; }
+  }
+}
+#undef MM_VF_EACH16
+
 template <int D>
 __global__ void attn_decode_merge_kernel(const float* ws, int nsplit, bf16* out) {
   const int row = blockIdx.x, d = threadIdx.x;          // row = b * Hq + hq
@@ -2424,6 +2553,40 @@ extern "C" int mm_attn_decode_beam(int dtype, const void* q, const void* kp, con
   if (!anc || (int64_t)anc_ld < (int64_t)B * n) return MM_ERR_ARG;
   return decode_shared_launch(dtype, q, kp, vp, ks, vs, B, n, Sp, Ss, Hq, Hkv, D, q_sb, q_sh, kp_sb, kp_ss, kp_sh, vp_sb, vp_ss, vp_sh, ks_sb,
                               ks_ss, ks_sh, vs_sb, vs_ss, vs_sh, key_mask, scale, out, workspace, nsplit, anc, anc_ld, stream);
+}
+
+// mm_attn_decode_verify: Q causal positions per sequence, lengths on the device (prompt-lookup verify step)
+extern "C" int mm_attn_decode_verify_splits(int B, int Q, int Hkv, int Scap) { return mm_attn_decode_shared_splits(B, Q, Hkv, Scap); }
+
+extern "C" int mm_attn_decode_verify(int dtype, const void* q, const void* k, const void* v, int B, int Q, int Scap, int Sp, int Hq,
+                                     int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb,
+                                     int64_t v_ss, int64_t v_sh, const int64_t* key_mask, const int32_t* base, float scale, void* out,
+                                     float* workspace, int nsplit, void* stream) {
+  if (B < 0 || Q < 1 || Q > 16 || Scap < Q || Hq <= 0 || Hkv <= 0 || Hq % Hkv || nsplit < 1) return MM_ERR_ARG;
+  if (key_mask && (Sp < 0 || Sp > Scap)) return MM_ERR_ARG;
+  if (dtype != MM_BF16 || D != 128) return MM_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return MM_ERR_UNSUPPORTED;        // P = 16 / G positions per column tile
+  if (!q || !k || !v || !base || !out || !workspace) return MM_ERR_ARG;
+  const int tiles = decode_shared_tiles(Q, G);
+  if ((int64_t)B * tiles > 65535 || (int64_t)B * Q * Hq > 0x7FFFFFFF) return MM_ERR_ARG;   // grid limits
+  if ((q_sb | q_sh | k_sb | k_ss | k_sh | v_sb | v_ss | v_sh) & 7) return MM_ERR_ALIGN;
+  if (!mm_aligned16(q) || !mm_aligned16(k) || !mm_aligned16(v)) return MM_ERR_ALIGN;
+  if (B == 0) return MM_OK;
+  DecodeVerifyArgs a{q, k, v, B, Q, Scap, key_mask ? Sp : 0, Hq, Hkv, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, key_mask, base, scale,
+                     workspace, nsplit, 0, tiles};
+  a.chunk = (Scap + nsplit - 1) / nsplit;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(nsplit, Hkv, B * tiles), block(256);
+  switch (G) {
+    case 1: hipLaunchKernelGGL(attn_decode_verify128_kernel<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(attn_decode_verify128_kernel<2>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(attn_decode_verify128_kernel<4>, grid, block, 0, s, a); break;
+  }
+  MM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_decode_merge_kernel<128>, dim3(B * Q * Hq), dim3(128), 0, s, workspace, nsplit, (bf16*)out);
+  MM_CHECK_LAUNCH();
+  return MM_OK;
 }
 
 extern "C" int mm_attn_decode_kv8_chunk(int Skv, int nsplit) {

@@ -1413,7 +1413,7 @@ extern "C" int mm_fill_zero(void* p, int64_t bytes, void* stream) {
   return hipMemsetAsync(p, 0, (size_t)bytes, (hipStream_t)stream) == hipSuccess ? MM_OK : MM_ERR_LAUNCH;
 }
 
-extern "C" int mm_version(void) { return 101; }
+extern "C" int mm_version(void) { return 102; }
 extern "C" const char* mm_error_string(int code) {
   switch (code) {
     case MM_OK: return "ok";

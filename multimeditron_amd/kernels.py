@@ -1087,6 +1087,23 @@ def decode_select(tok, finished, eos, out, col, next_ids):
     call("mm_decode_select", _p(tok), _p(finished), int(eos), tok.numel(), _p(out), out.stride(0), int(col), _p(next_ids), _stream())
 
 
+def prompt_history(prompt_ids, prompt_mask, samples=1, room=0):
+    """The rows' id history as mm_logits_process and mm_lookup_draft read it: (hist int32 [B samples, Sp + room] -- a row's prompt ids
+    where the mask is not 0, in order, then -1 --, plen int32 [B samples], Sp).  Every prompt row is repeated `samples` times."""
+    B, Sp = prompt_ids.shape
+    device = prompt_ids.device
+    assert prompt_mask.shape == prompt_ids.shape
+    keep = prompt_mask != 0
+    order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)              # the visible positions first, in order
+    plen = keep.sum(dim=1)
+    ids = torch.gather(prompt_ids, 1, order).masked_fill(torch.arange(Sp, device=device)[None, :] >= plen[:, None], -1)
+    hist = torch.full((B, Sp + int(room)), -1, dtype=torch.int32, device=device)
+    hist[:, :Sp] = ids.to(torch.int32)
+    if samples > 1:
+        hist = hist.repeat_interleave(samples, dim=0).contiguous()
+    return hist, plen.to(torch.int32).repeat_interleave(samples).contiguous(), int(Sp)
+
+
 class LogitsState:
     """The device state of generate()'s logits processors for one call: the settings, the suppressed ids (int32), the fp32 score
     rows the selectors read, and -- only when the repetition penalty or the n-gram ban is on -- the int32 history of every row
@@ -1105,17 +1122,8 @@ class LogitsState:
         self.hist = self.plen = None
         self.max_plen = 0
         if self.p != 1.0 or self.g > 0:
-            B, Sp = prompt_ids.shape
-            assert B * samples == self.rows and prompt_mask.shape == prompt_ids.shape
-            keep = prompt_mask != 0
-            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)              # the visible positions first, in order
-            plen = keep.sum(dim=1)
-            ids = torch.gather(prompt_ids, 1, order).masked_fill(torch.arange(Sp, device=device)[None, :] >= plen[:, None], -1)
-            hist = torch.full((B, Sp + int(room)), -1, dtype=torch.int32, device=device)
-            hist[:, :Sp] = ids.to(torch.int32)
-            self.hist = hist.repeat_interleave(samples, dim=0).contiguous() if samples > 1 else hist
-            self.plen = plen.to(torch.int32).repeat_interleave(samples).contiguous()
-            self.max_plen = int(Sp)
+            assert prompt_ids.shape[0] * samples == self.rows
+            self.hist, self.plen, self.max_plen = prompt_history(prompt_ids, prompt_mask, samples, room)
 
 
 def logits_process(logits2d, st: LogitsState, step, last_ids, eos):
@@ -1128,6 +1136,68 @@ def logits_process(logits2d, st: LogitsState, step, last_ids, eos):
          st.p, st.g, st.min_new, int(eos), _p(st.suppress), 0 if st.suppress is None else st.suppress.numel(), _p(st.out), st.ld_out,
          _stream())
     return st.out[:, :st.V]
+
+
+# ---- prompt-lookup speculative decoding (include/mm_hip.h: mm_lookup_draft, mm_kv_append_at, mm_lookup_accept) ----
+class LookupState:
+    """The device state of generate(prompt_lookup_num_tokens=k) for one call: per row the int32 history (prompt_history's layout: the
+    visible prompt ids, then every emitted id) with its length hlen, the emitted count, the finished flag, `base` (position and cache
+    slot of the row's newest id; LayerKVCacheLookup reads the same tensor), the stats (verify steps, accepted drafts) and one done
+    flag; the step's ids / position_ids / n_draft and the output ids [rows, max_new] (eos-filled)."""
+
+    def __init__(self, prompt_ids, prompt_mask, k, max_ngram, max_new, eos, base0):
+        dev = prompt_ids.device
+        self.rows, self.k, self.Q, self.G, self.max_new, self.eos = int(prompt_ids.shape[0]), int(k), int(k) + 1, int(max_ngram), int(max_new), int(eos)
+        self.hist, self.hlen, _ = prompt_history(prompt_ids, prompt_mask, 1, self.max_new)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        self.count, self.finished, self.n_draft, self.stats, self.done = z(self.rows), z(self.rows), z(self.rows), z(self.rows, 2), z(1)
+        self.base = torch.full((self.rows,), int(base0), dtype=torch.int32, device=dev)
+        self.ids = torch.zeros((self.rows, self.Q), dtype=torch.int64, device=dev)
+        self.pos = torch.zeros((self.rows, self.Q), dtype=torch.int64, device=dev)
+        self.out = torch.full((self.rows, self.max_new), self.eos, dtype=torch.int64, device=dev)
+
+
+def lookup_draft(st: LookupState):
+    """mm_lookup_draft: st.ids / st.pos [rows, k+1] and st.n_draft of the coming verify step, from the rows' histories."""
+    call("mm_lookup_draft", _p(st.hist), st.hist.stride(0), _p(st.hlen), _p(st.count), _p(st.finished), _p(st.base), st.rows, st.k, st.G,
+         st.max_new, st.eos, _p(st.ids), _p(st.pos), _p(st.n_draft), _stream())
+    return st.ids, st.pos
+
+
+def lookup_accept(st: LookupState, tok, Q=None):
+    """mm_lookup_accept of the selector's tok [rows * Q] (Q = k + 1; Q = 1: the prefill's token, no drafts): emits, appends to the
+    history and advances count / hlen / base / stats / done."""
+    Q = st.Q if Q is None else int(Q)
+    assert tok.dtype == torch.int64 and tok.numel() == st.rows * Q and tok.is_contiguous()
+    call("mm_lookup_accept", _p(tok), _p(st.ids) if Q > 1 else None, _p(st.n_draft) if Q > 1 else None, st.rows, Q, st.max_new, st.eos,
+         _p(st.out), st.out.stride(0), _p(st.hist), st.hist.stride(0), _p(st.hlen), _p(st.count), _p(st.finished), _p(st.base),
+         _p(st.stats), _p(st.done), _stream())
+
+
+def lookup_append(qkv, B, Q, Hq, Hkv, D, base, kcache, vcache):
+    """mm_kv_append_at: the (roped) k and the v heads of qkv [B*Q, (Hq+2Hkv)*D] -> cache[b, base[b] + j] (a pure copy; a slot past the
+    cache is skipped)."""
+    assert qkv.shape[0] == B * Q and qkv.stride(1) == 1 and base.dtype == torch.int32 and base.numel() == B
+    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride() == kcache.stride() and kcache.shape[0] == B
+    call("mm_kv_append_at", dt(qkv), _p(qkv), qkv.stride(0), B, Q, Hq, Hkv, D, _p(base), _p(kcache), _p(vcache), kcache.stride(0),
+         kcache.stride(1), kcache.shape[1], _stream())
+
+
+def attn_decode_verify(q, k, v, Q, key_mask, base, scale, nsplit=None):
+    """Q causal query positions per sequence: q [B*Q,Hq,D] (strided view ok; row b*Q + j) over k/v [B,Scap,Hkv,D], query (b, j) seeing
+    keys t <= base[b] + j (base int32 [B] on the device) minus the prompt keys key_mask [B,Sp] hides -> out [B*Q,Hq,D].  The bits of
+    attn_decode per row under the equivalent mask (mm_attn_decode_verify)."""
+    R, Hq, D = q.shape
+    B, Scap, Hkv = k.shape[0], k.shape[1], k.shape[2]
+    assert R == B * Q and v.shape[:3] == k.shape[:3] and q.stride(2) == 1 and k.stride(3) == 1 and v.stride(3) == 1
+    assert base.dtype == torch.int32 and base.numel() == B and base.is_contiguous()
+    assert key_mask is None or (key_mask.dim() == 2 and key_mask.shape[0] == B and key_mask.is_contiguous() and key_mask.dtype == torch.int64)
+    ns = _lib.lib().mm_attn_decode_verify_splits(B, Q, Hkv, Scap) if nsplit is None else int(nsplit)
+    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
+    call("mm_attn_decode_verify", dt(q), _p(q), _p(k), _p(v), B, Q, Scap, 0 if key_mask is None else key_mask.shape[1], Hq, Hkv, D,
+         q.stride(0), q.stride(1), *_strides3(k), *_strides3(v), _p(key_mask), _p(base), float(scale), _p(out), _p(ws), ns, _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ optimizer

@@ -320,6 +320,46 @@ class DecoderLayer(nn.Module):
                 and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
                 and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
 
+    def can_verify_fused(self, x, M):
+        """Whether verify_step may fold the norms and SwiGLU into the weight-streaming launches at M = B (k + 1) rows: what
+        can_decode_step_fused asks of a decode step -- but for down_proj's input rows, which verify_step places on its own (16 rows of
+        the 8B model's 14336 features do not fit the LDS stage; its 4096-wide inputs do) --, and no q|k|v bias (the plain streaming
+        linear carries none here)."""
+        a = self.self_attn
+        return (a.D == 128 and a.q_norm is None and not self.xielu and a._bqkv is None and K.decode_fusions() and x.shape[-1] <= 8192
+                and self.mlp.I % 4 == 0 and K.decode_fits(M, x.shape[-1]) and K.decode_fits(M, a.Hq * a.D)
+                and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
+
+    @torch.no_grad()
+    def verify_step(self, w, x, cos, sin, key_mask, B, Q, cache, fused):
+        """The verify step of prompt-lookup decoding: Q = k + 1 positions for each of B sequences, M = B Q <= 16 rows, so every linear
+        is one weight-streaming launch that reads its matrix once (w: the layer's W16s or W8s).  norm + q|k|v, the in-place RoPE
+        (rope_apply_ / qk_norm_rope_fwd), the append of the Q new k / v rows at the slots base[b] + j (mm_kv_append_at), the Q-position
+        decode attention over one read of the keys (mm_attn_decode_verify), o_proj + residual, norm + gate|up + activation, down +
+        residual.  fused (can_verify_fused): the norms and SwiGLU ride in the streaming kernels as in decode_step_fused; otherwise
+        infer(step=True)'s separate launches.  Either way the arithmetic and rounding points of a decode step."""
+        a, m = self.self_attn, self.mlp
+        Hq, Hkv, D = a.Hq, a.Hkv, a.D
+        n1, n2 = self.norms()
+        M = B * Q
+        if fused:
+            qkv = w["qkv"].stream(x, norm_w=n1.weight, eps=n1.eps)
+        else:
+            h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
+            qkv = w["qkv"].linear(h, bias=a._bqkv.tensor() if a._bqkv is not None else None)
+        a.rope_views(qkv, cos, sin, B, Q)
+        o = cache.verify_attend(qkv, B, Q, Hq, Hkv, D, key_mask, D ** -0.5).view(M, Hq * D)
+        if fused:
+            x = w["o"].stream(o, x)
+            act = w["gu"].gateup_swiglu(x, m.I, n2.weight, n2.eps)
+            # down_proj: the LDS-staged launch where the M rows of I features fit it, else mm_gemm's M <= 16 kernel (the same bits)
+            return w["down"].stream(act, x) if K.decode_fits(M, m.I) else w["down"].linear(act, residual=x)
+        x = w["o"].linear(o, residual=x)
+        h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
+        u = w["gu"].linear(h)
+        act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
+        return w["down"].linear(act, residual=x)
+
     def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None):
         """The training / generic route (CausalLM.forward has decided that the call is neither a decode step nor an MXFP8 prefill).
         rows (functional.LossRows, LAST layer of a training forward only): nothing after this layer's attention reads the
@@ -522,6 +562,36 @@ class LayerKVCacheBeam(LayerKVCacheShared):
                                   self.n, key_mask, scale, anc)
 
 
+class LayerKVCacheLookup(LayerKVCache):
+    """The cache of generate(prompt_lookup_num_tokens=k): a bf16 LayerKVCache [B, Smax, Hkv, D] whose rows advance by DIFFERENT
+    amounts per verify step, so where a row stands is not a host integer: `shared.base` (int32 [B] on the device, advanced by
+    mm_lookup_accept) is the position and cache slot of every row's newest id.  The prefill is the base class's (it fills `len`
+    positions of every row); a verify step writes its Q = k + 1 new k / v rows at the slots base[b] + j (mm_kv_append_at) and attends
+    query (b, j) over the keys t <= base[b] + j (mm_attn_decode_verify).  Slots behind a row's accepted ids hold rejected drafts: no
+    query sees them and the next step overwrites them.  All layers share ONE `Shared` object, as LayerKVCacheBeam's layers share their
+    tables: the decode loop sets `shared.bound`, a host-side upper bound of every base[b], before it calls the decoder."""
+
+    class Shared:
+        base = None              # int32 [B], device
+        bound = 0                # base[b] <= bound for every row (known without a sync)
+
+    def __init__(self, B, Smax, Hkv, D, dtype, device, shared):
+        super().__init__(B, Smax, Hkv, D, dtype, device)
+        self.shared = shared
+
+    def verify_attend(self, qkv, B, Q, Hq, Hkv, D, key_mask, scale):
+        """The roped fused projection qkv [B Q, (Hq + 2 Hkv) D] of a verify step: append its k / v rows, attend its q rows."""
+        sh = self.shared
+        if sh.base is None or not self.len:
+            raise ValueError("a verify step on a prompt-lookup KV cache without a prefill or without its base positions")
+        if key_mask is not None and tuple(key_mask.shape) != (B, self.len):
+            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a prompt-lookup cache: the prompt's mask [{B}, {self.len}] is "
+                             "expected (generated tokens are visible up to each query's own position)")
+        K.lookup_append(qkv, B, Q, Hq, Hkv, D, sh.base, self.k, self.v)
+        Scap = min(self.k.shape[1], max(int(sh.bound), self.len) + Q)
+        return K.attn_decode_verify(qkv[:, : Hq * D].view(B * Q, Hq, D), self.k[:, :Scap], self.v[:, :Scap], Q, key_mask, sh.base, scale)
+
+
 class DecoderModel(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
@@ -714,10 +784,25 @@ class CausalLM(nn.Module):
             return f"vocab_size is {self.config.vocab_size}: beam search draws 2 n = {2 * n} candidates per step"
         return self.samples_ok(B, n)
 
+    def lookup_ok(self, B: int, k: int):
+        """None when B sequences can be decoded with prompt-lookup drafts of k tokens -- verify steps of B (k + 1) rows through the
+        weight-streaming linears and mm_attn_decode_verify over a LayerKVCacheLookup --, else the reason they cannot.  The bf16
+        weights stream at any input width (mm_gemm's M <= 16 kernels; the LDS-staged, fused forms are taken where K.decode_fits says
+        the rows fit: DecoderLayer.can_verify_fused).  The MXFP8 copies have the staged kernel only: with decode_weights="mxfp8" the
+        width rule is decode_weights_ok(B (k + 1))'s, which generate asks as well."""
+        why = self._heads_ok("the verify decode kernel is written", "the verify decode kernel")
+        if why is not None:
+            return why
+        M = B * (k + 1)
+        if M > 16:
+            return f"{B} sequences x (k + 1 = {k + 1}) positions = {M} rows (a verify step is one weight-streaming launch of at most 16)"
+        return None
+
     # option -> (the values it takes besides None; None: an int its caller has validated, the method that says why it cannot be used)
     OPTIONS = {"decode_weights": (("mxfp8",), "decode_weights_ok"), "kv_cache": (("mxfp8",), "kv_cache_ok"),
                "prefill_weights": (("mxfp8",), "prefill_weights_ok"), "samples": (None, "samples_ok"),
-               "num_return_sequences": (None, "samples_ok"), "num_beams": (None, "beams_ok"), "beams": (None, "beams_ok")}
+               "num_return_sequences": (None, "samples_ok"), "num_beams": (None, "beams_ok"), "beams": (None, "beams_ok"),
+               "prompt_lookup_num_tokens": (None, "lookup_ok"), "lookup": (None, "lookup_ok")}
 
     def check_option(self, name, value, *args, **kw):
         """ValueError when an opt-in is given a value it does not take, or -- with the arguments of its *_ok method -- when that
@@ -731,13 +816,27 @@ class CausalLM(nn.Module):
         if why is not None:
             raise ValueError(f"{name}={value!r} cannot be used: {why}")
 
-    def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None, beams: int = 1):
+    def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None, beams: int = 1,
+                  lookup: Optional[int] = None):
         """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot.
         samples=n > 1: LayerKVCacheShared for B prompts of at most prompt_len positions and n sample rows each with room for
         Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache.
         beams=n > 1: LayerKVCacheBeam of the same sizes, every layer holding the SAME `tables` object (set tables.current to the
-        step's ancestor table); ValueError when beams_ok says it cannot, or together with kv_cache or samples."""
+        step's ancestor table); ValueError when beams_ok says it cannot, or together with kv_cache or samples.
+        lookup=k >= 1: LayerKVCacheLookup (prompt-lookup decoding with drafts of k tokens; Smax includes the k slots a last verify step
+        may write behind the last emitted id), every layer holding the SAME `shared` object (its base / bound are the decode loop's to
+        set); ValueError when lookup_ok says it cannot, or together with kv_cache, samples or beams."""
         c = self.config
+        if lookup is not None:
+            if isinstance(lookup, bool) or not isinstance(lookup, int) or lookup < 1:
+                raise ValueError(f"lookup must be an int >= 1, got {lookup!r}")
+            if kv_cache is not None or samples != 1 or beams != 1:
+                raise ValueError(f"lookup={lookup} with kv_cache={kv_cache!r}, samples={samples!r}, beams={beams!r}: the prompt-lookup cache is "
+                                 "bf16 only, one row per sequence")
+            self.check_option("lookup", lookup, B, lookup)
+            shared = LayerKVCacheLookup.Shared()
+            return [LayerKVCacheLookup(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device, shared)
+                    for _ in range(c.num_hidden_layers)]
         self.check_option("kv_cache", kv_cache, B)
         if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= 16:
             raise ValueError(f"beams must be an int in [1, 16], got {beams!r}")
@@ -808,10 +907,17 @@ class CausalLM(nn.Module):
             x = x.contiguous()
         layers = self.model.layers
         # the route of the call, decided once: "fused" / "step" (a decode step: one new token per sequence over a cache, every layer
-        # takes decode_step_fused / infer), "prefill" (the MXFP8 prefill: every layer takes infer) or None (training and everything
-        # else: every layer takes forward)
+        # takes decode_step_fused / infer), "prefill" (the MXFP8 prefill: every layer takes infer), "verify" (a prompt-lookup verify
+        # step: S = k + 1 positions per sequence over a prefilled LayerKVCacheLookup, every layer takes verify_step) or None
+        # (training and everything else: every layer takes forward)
         route = None
-        if cache and len(layers):
+        verify_fused = False
+        if cache and len(layers) and isinstance(cache[0], LayerKVCacheLookup) and past:
+            if x.dtype != torch.bfloat16 or torch.is_grad_enabled() or B * S > 16:
+                raise ValueError(f"a verify step of {B} x {S} {x.dtype} rows on a prompt-lookup cache: bf16, at most 16 rows, no autograd")
+            route = "verify"
+            verify_fused = all(layer.can_verify_fused(x, B * S) for layer in layers)
+        elif cache and len(layers):
             if all(layer.can_decode_step_fused(x, B, S, c) for layer, c in zip(layers, cache)):
                 route = "fused"
             elif all(layer.can_decode_step(x, B, S, c) for layer, c in zip(layers, cache)):
@@ -829,6 +935,10 @@ class CausalLM(nn.Module):
             for layer, lw, c in zip(layers, w["layers"], cache):
                 x = layer.decode_step_fused(lw, x, cos, sin, key_mask, B, c)
             fused_head = self.lm_head.bias is None and self.model.norm.bias is None       # S == 1: logits_to_keep keeps the one row
+        elif route == "verify":
+            for layer, lw, c in zip(layers, w["layers"], cache):
+                x = layer.verify_step(lw, x, cos, sin, key_mask, B, S, c, verify_fused)
+            fused_head = verify_fused and self.lm_head.bias is None and self.model.norm.bias is None and not logits_to_keep
         elif route:
             for i, layer in enumerate(layers):
                 x = layer.infer(w["layers"][i], x, cos, sin, key_mask, B, S, cache[i] if cache else None, step=route == "step")
@@ -850,7 +960,7 @@ class CausalLM(nn.Module):
             Sk = logits_to_keep
         else:
             Sk = S
-        head = (w["lm_head"] or self._w16["lm_head"]) if route in ("fused", "step") else None
+        head = (w["lm_head"] or self._w16["lm_head"]) if route in ("fused", "step", "verify") else None
         if fused_head:
             logits2d = head.stream(x, norm_w=self.model.norm.weight, eps=self.model.norm.eps, ldc_pad=True)
         elif head is not None:                                   # a decode step: lm_head's copy, when decode_weights made one

@@ -466,7 +466,9 @@ class MultiModalModelForCausalLM(nn.Module):
                  kv_cache: Optional[str] = None, prefill_weights: Optional[str] = None, num_return_sequences: int = 1,
                  num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, return_beam_scores: bool = False,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                 min_new_tokens: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, **kwargs) -> torch.Tensor:
+                 min_new_tokens: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 return_lookup_stats: bool = False, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -543,7 +545,24 @@ class MultiModalModelForCausalLM(nn.Module):
         chosen, e.g. the attachment placeholder and pad ids (None or empty: off).  Compose with decode_weights, kv_cache,
         prefill_weights, num_return_sequences (every sample row keeps its own history) and every sampler path.  NOT with num_beams > 1
         (processors inside beam search act on log-probabilities inside mm_beam_step: out of scope, ValueError).  A bad value raises
-        ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids."""
+        ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids.
+
+        prompt_lookup_num_tokens=k (opt-in; greedy: needs do_sample=False): prompt-lookup speculative decoding, transformers'
+        generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=G) for B rows at once.  Each iteration proposes up to k next
+        tokens per row by matching the row's last n-gram (n <= G, default 2; the first match of the longest n) in its own visible
+        prompt and output (include/mm_hip.h: mm_lookup_draft -- PromptLookupCandidateGenerator.get_candidates per row), runs ONE
+        decoder pass over k + 1 positions per row -- B (k + 1) <= 16 rows, the rows a weight-streaming launch has to spare -- and keeps
+        every proposed token the model would have chosen itself (mm_lookup_accept), so the ids are plain greedy decoding's up to the
+        rounding of a differently sliced attention sum.  Rows advance by different amounts; their positions, histories and the done
+        flag live on the device and the host reads only that flag, every `sync_every` iterations.  As everywhere here the prompt's
+        masked positions do not count as history.  Returns the ids as above; with return_lookup_stats=True (ids, stats), stats int32
+        [B, 2] on the CPU: verify steps run (the prefill's included) and draft tokens accepted, per row.  Composes with
+        decode_weights (the verify step reads the copies) and prefill_weights.  Out of scope, ValueError before the modalities are
+        encoded: sampling (do_sample=True, top_k / top_p / min_p / seed / generator), logits processors, num_beams > 1,
+        num_return_sequences > 1 (shared-prefix samples), kv_cache="mxfp8", k not an int >= 1, B (k + 1) > 16, a model
+        CausalLM.lookup_ok refuses, and return_lookup_stats / max_matching_ngram_size without k.  Not here either: a draft model
+        (assistant_model), adaptive k, the append fused into the RoPE pass, tuned slice counts of the verify attention.  With
+        prompt_lookup_num_tokens=None nothing changes: no launch, no buffer, the same ids."""
         n = num_return_sequences
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
@@ -553,6 +572,37 @@ class MultiModalModelForCausalLM(nn.Module):
         if nb == 1 and return_beam_scores:
             raise ValueError("return_beam_scores needs num_beams > 1")
         processors = self._logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+        pk = prompt_lookup_num_tokens
+        if pk is None:
+            if return_lookup_stats or max_matching_ngram_size is not None:
+                raise ValueError("return_lookup_stats / max_matching_ngram_size need prompt_lookup_num_tokens")
+        else:
+            if isinstance(pk, bool) or not isinstance(pk, int) or pk < 1:
+                raise ValueError(f"prompt_lookup_num_tokens must be an int >= 1, got {pk!r}")
+            mg = 2 if max_matching_ngram_size is None else max_matching_ngram_size
+            if isinstance(mg, bool) or not isinstance(mg, int) or mg < 1:
+                raise ValueError(f"max_matching_ngram_size must be an int >= 1, got {max_matching_ngram_size!r}")
+            given = [a for a, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p), ("seed", seed), ("generator", generator)) if v is not None]
+            if do_sample or given:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} with {', '.join((['do_sample=True'] if do_sample else []) + given)}: the lookup "
+                                 "is greedy only (speculative sampling is out of scope)")
+            if nb > 1:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} with num_beams={nb}: out of scope")
+            if n > 1:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} with num_return_sequences={n}: out of scope")
+            if kv_cache is not None:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} with kv_cache={kv_cache!r}: the prompt-lookup cache is bf16 only")
+            if processors is not None:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} with logits processors: filtering the candidates through them is out of scope")
+            llm = self.model
+            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
+            if B * (pk + 1) > 16:
+                raise ValueError(f"prompt_lookup_num_tokens={pk} on {B} sequences: B (k + 1) = {B * (pk + 1)} rows, a verify step takes at most 16")
+            llm.check_option("prompt_lookup_num_tokens", pk, B, pk)
+            llm.check_option("decode_weights", decode_weights, B * (pk + 1))                    # the verify steps run B (k + 1) rows
+            llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)
+            return self._generate_lookup(batch, max_new_tokens, temperature, sync_every, pk, mg, bool(return_lookup_stats), decode_weights,
+                                         prefill_weights)
         if nb > 1 and processors is not None:
             given = [k for k, on in zip(("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens"),
                                         (processors[0] != 1.0, processors[1] > 0, processors[2] > 0, len(processors[3]) > 0)) if on]
@@ -778,6 +828,63 @@ class MultiModalModelForCausalLM(nn.Module):
             ids, scores = ids[:, :n_out].cpu(), scores.cpu()
             K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
         return (ids, scores) if return_scores else ids
+
+
+    def _generate_lookup(self, batch, max_new_tokens, temperature, sync_every, k, G, return_stats, decode_weights=None, prefill_weights=None):
+        """generate()'s prompt-lookup loop (prompt_lookup_num_tokens = k, max_matching_ngram_size = G, checked by generate).  The
+        prefill runs as in _generate into a LayerKVCacheLookup with room for k slots behind the last id; its token goes through
+        mm_lookup_accept as a verify step without drafts, so count, finished, the history and base (seq_length - 1 -> seq_length: the
+        "padded prompt length + i - 1" position and cache slot of the first generated token) start out the way later steps update
+        them.  An iteration is mm_lookup_draft -> embedding gather -> one decoder pass over k + 1 positions per row (CausalLM.forward's
+        "verify" route) with lm_head on all B (k + 1) rows -> the selector plain greedy uses, at the caller's temperature ->
+        mm_lookup_accept.  At most max_new_tokens accept calls (every one emits at least one id per active row); the host reads the
+        device's done flag every sync_every of them, and iterations issued after done change nothing."""
+        if self._flat is None:
+            self.pack_parameters()
+        dev = self.device
+        input_ids = batch["input_ids"].to(dev)
+        temperature = max(temperature, 1e-6)
+        B = input_ids.shape[0]
+        V = self._llm_cfg.vocab_size
+        eos = self.config.eos_token_idx
+        if max_new_tokens <= 0:
+            ids = torch.empty((B, 0), dtype=torch.int64)
+            return (ids, torch.zeros((B, 2), dtype=torch.int32)) if return_stats else ids
+        if decode_weights is not None and self.model._decode_w8 is None:
+            self.model.quantize_decode_weights(decode_weights)
+        dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
+        pw = {"prefill_weights": prefill_weights} if prefill_weights is not None else {}
+        Q = k + 1
+        with torch.no_grad():
+            nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
+            attention_mask = batch["attention_mask"].to(dev)
+            position_ids = batch["position_ids"].to(dev)
+            seq_length = attention_mask.shape[1]
+            cache = self.model.new_cache(B, seq_length + max_new_tokens + k, lookup=k)
+            st = K.LookupState(input_ids, attention_mask, k, G, max_new_tokens, eos, seq_length - 1)
+            shared = cache[0].shared
+            shared.base = st.base
+            emb = self.model.get_input_embeddings()
+            out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids, past_key_values=cache,
+                             use_cache=True, logits_to_keep=1, **dw, **pw)
+            K.lookup_accept(st, K.argmax_softmax(out.logits[:, -1, :], V, temperature), 1)
+            prompt_mask = attention_mask.to(torch.int64).contiguous()
+            for it in range(1, max_new_tokens):
+                if it % max(1, sync_every) == 0 and bool(st.done.item()):      # the only host sync of the loop
+                    break
+                shared.bound = min(seq_length + (it - 1) * Q, seq_length + max_new_tokens - 1)      # base[b] <= bound, known here
+                ids, pos = K.lookup_draft(st)
+                out = self.model(inputs_embeds=emb(ids), attention_mask=prompt_mask, position_ids=pos, past_key_values=cache,
+                                 use_cache=True, **dw)
+                K.lookup_accept(st, K.argmax_softmax(out.logits.reshape(B * Q, V), V, temperature))
+            ids, stats, count = st.out.cpu(), st.stats.cpu(), st.count.cpu()
+            K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
+        ids = ids[:, : int(count.max())]
+        # the reference stops right after the first step at which every row has emitted eos
+        done = (ids == eos).to(torch.int8).cummax(dim=1).values.bool().all(dim=0)
+        if bool(done.any()):
+            ids = ids[:, : int(torch.nonzero(done)[0]) + 1]
+        return (ids, stats) if return_stats else ids
 
 
 def bootstrap(config, tokenizer, modalities_config):

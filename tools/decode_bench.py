@@ -2,7 +2,7 @@
 """generate() timing on the 8B workload: prefill and per-token decode (run on the GPU box).
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
                                 [--prefill-weights mxfp8] [--samples n] [--beams n]
-                                [--processors repetition_penalty=1.2,no_repeat_ngram_size=3]
+                                [--processors repetition_penalty=1.2,no_repeat_ngram_size=3] [--lookup K[,G]]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
@@ -23,7 +23,12 @@ top_p = 0.95) on 16 rows of the model's vocabulary.
 --processors k=v,...: in this one process, generate with the listed logits processors (repetition_penalty, no_repeat_ngram_size,
 min_new_tokens, suppress_tokens=a+b+c) against the same call without them, alternating, best of three each after a warm-up:
 prefill + 1 token and ms/token of both and the difference (one mm_logits_process launch per step, and the selection reading fp32
-scores instead of bf16 logits).  The other flags apply to both sides."""
+scores instead of bf16 logits).  The other flags apply to both sides.
+--lookup K[,G]: in this one process, greedy generate(prompt_lookup_num_tokens=K, max_matching_ngram_size=G) against the same call
+without the lookup, alternating, best of three each after a warm-up: ms per verify iteration against ms per plain step (their ratio
+is the number that transfers), accepted drafts per iteration and tokens/s (this model's weights are random: its acceptance rate is
+whatever its loops give); then the launches alone -- mm_attn_decode_verify against mm_attn_decode over 16 layers' caches, and
+mm_lookup_draft / mm_kv_append_at / mm_lookup_accept.  --decode-weights and --prefill-weights apply to both sides."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -74,6 +79,11 @@ if "--processors" in sys.argv:
     for kv in sys.argv[i + 1].split(","):
         k, val = kv.split("=")
         PROC[k] = float(val) if k == "repetition_penalty" else [int(t) for t in val.split("+")] if k == "suppress_tokens" else int(val)
+    del sys.argv[i:i + 2]
+LOOKUP = None
+if "--lookup" in sys.argv:
+    i = sys.argv.index("--lookup")
+    LOOKUP = [int(t) for t in sys.argv[i + 1].split(",")]
     del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -286,6 +296,87 @@ def compare_processors(proc):
     print(f"processors on - off: {(per[True] - per[False]) * 1e3:+.1f} us/token ({(per[True] / per[False] - 1) * 100:+.2f} %)", flush=True)
 
 
+def compare_lookup(k, G=2):
+    from multimeditron_amd import kernels as K
+    kw = {"decode_weights": DW} if DW else {}
+    if PW:
+        kw["prefill_weights"] = PW
+
+    def go(on, new):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        if on:
+            ids, st = model.generate(batch, max_new_tokens=new, temperature=0.1, do_sample=False, prompt_lookup_num_tokens=k,
+                                     max_matching_ngram_size=G, return_lookup_stats=True, **kw)
+        else:
+            ids, st = model.generate(batch, max_new_tokens=new, temperature=0.1, do_sample=False, **kw), None
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, ids, st
+
+    for on in (True, False):
+        go(on, 2)                                          # warm-up (and the MXFP8 copies, if asked for)
+    t1, tn, res = {True: [], False: []}, {True: [], False: []}, {}
+    for _ in range(3):                                     # alternating
+        for on in (True, False):
+            t1[on].append(go(on, 1)[0])
+            dt, ids, st = go(on, N)
+            tn[on].append(dt)
+            res[on] = (ids, st)
+    a, b = min(t1[False]), min(tn[False])
+    step = (b - a) / (N - 1) * 1e3
+    print(f"B={B} S={S}{' decode_weights ' + DW if DW else ''} plain greedy: prefill+1 token {a * 1e3:.1f} ms; {step:.3f} ms/step = ms/token "
+          f"({B / step * 1e3:.0f} tok/s)", flush=True)
+    a, b = min(t1[True]), min(tn[True])
+    ids, st = res[True]
+    iters = int(st[:, 0].max()) - 1                        # verify iterations behind the prefill's step (sync_every = 16: a few more may be queued)
+    per_it = (b - a) / max(iters, 1) * 1e3
+    acc = float(st[:, 1].sum()) / max(B * iters, 1)
+    tok = (N - 1) * B / (b - a)
+    print(f"B={B} S={S}{' decode_weights ' + DW if DW else ''} lookup k={k} G={G}: prefill+1 token {a * 1e3:.1f} ms; {iters} verify iterations for {N - 1} "
+          f"tokens per row; {per_it:.3f} ms/iteration = {per_it / step:.3f} x a plain step; {acc:.2f} accepted drafts per row and iteration "
+          f"(random weights: the loops of this model, no estimate of a real one); {tok:.0f} tok/s ({tok / (B / step * 1e3):.2f} x plain); "
+          f"ids equal plain: {torch.equal(ids, res[False][0])} (first column that differs, per row: "
+          f"{[int((ids[r] != res[False][0][r]).int().argmax()) if bool((ids[r] != res[False][0][r]).any()) else None for r in range(B)]}); break-even at {per_it / step - 1:.2f} accepted drafts per iteration", flush=True)
+    # the launches alone
+    lc = model.model.config
+    Hq, Hkv, D, L, Q = lc.num_attention_heads, lc.num_key_value_heads, lc.head_dim, 16, k + 1
+    bf = torch.bfloat16
+    Scap = S + N + Q
+    q = torch.randn(B * Q, Hq, D, device="cuda", dtype=bf)
+    kc = [torch.randn(B, Scap, Hkv, D, device="cuda", dtype=bf) for _ in range(2 * L)]
+    base = torch.full((B,), S + N - 1, dtype=torch.int32, device="cuda")
+    qkv = torch.randn(B * Q, (Hq + 2 * Hkv) * D, device="cuda", dtype=bf)
+
+    def timed(name, fn, reps=6):
+        for i in range(L):
+            fn(i)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            for i in range(L):
+                fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"{name:74s} {e0.elapsed_time(e1) * 1e3 / (reps * L):7.1f} us/launch", flush=True)
+
+    for _ in range(2):
+        timed(f"attention, verify ({B} x {Q} positions over {Scap} keys, 2 launches)",
+              lambda i: K.attn_decode_verify(q, kc[2 * i], kc[2 * i + 1], Q, None, base, D ** -0.5))
+        timed(f"attention, plain step ({B} rows over {S + N} keys, 2 launches)",
+              lambda i: K.attn_decode(q[:B], kc[2 * i][:, :S + N], kc[2 * i + 1][:, :S + N], None, D ** -0.5))
+    timed(f"mm_kv_append_at ({B} x {Q} rows)", lambda i: K.lookup_append(qkv, B, Q, Hq, Hkv, D, base, kc[2 * i], kc[2 * i + 1]))
+    st = K.LookupState(batch["input_ids"], batch["attention_mask"], k, G, N, model.config.eos_token_idx, S - 1)
+    st.hlen += N - 1                                       # the history at the last step's length (the -1 fill matches itself: a full scan)
+    tokq = torch.zeros(B * Q, dtype=torch.int64, device="cuda")
+    timed(f"mm_lookup_draft ({B} rows, history {S + N - 1}, G = {G})", lambda i: K.lookup_draft(st))
+    st.finished.fill_(1)                                   # the accept's launch without advancing the state
+    timed(f"mm_lookup_accept ({B} rows)", lambda i: K.lookup_accept(st, tokq))
+
+
+if LOOKUP:
+    compare_lookup(*LOOKUP)
+    sys.exit(0)
 if PROC:
     compare_processors(PROC)
     sys.exit(0)
