@@ -1997,16 +1997,83 @@ __device__ __forceinline__ void decode_shared_sample(float (&o)[16][8], float al
 
 #define MM_SH_EACH16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 
+// One 16-key block of a column tile, online softmax: sv = the four scores of this lane's kq row (scaled, -inf where the caller's mask
+// hides the key) -> p = their weights under the new running maximum; m_run and l_run (this kq row's share of the column's sum) are
+// updated, and the factor alpha that brings the column's o to the new maximum is returned.
+__device__ __forceinline__ float decode_tile_softmax(const float (&sv)[4], float& m_run, float& l_run, float (&p)[4]) {
+  float bm = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) bm = fmaxf(bm, sv[r]);
+  bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+  bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+  const float mn = fmaxf(m_run, bm);
+  const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m_run - mn);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) p[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sv[r] - mn);
+  l_run = l_run * alpha + ((p[0] + p[1]) + (p[2] + p[3]));
+  m_run = mn;
+  return alpha;
+}
+
+// The end of a column tile's workgroup (4 waves, every thread calls it): this wave's partial per live column -- o summed over the 4 kq
+// rows as ((kq0 + kq1) + (kq2 + kq3)), the order of the slice kernel above (the sums commute), across the rows by gfx950's row / half
+// swaps (VALU, no LDS round trip: through ds_bpermute the 256 dependent exchanges were most of the kernel's time), so that 16 columns
+// fit 32 KB of LDS; and (m, l) per column -- then the four waves merged into the slice's (m, l, o) record of every live column: column
+// c is head hkv G + c % G of query row r0 + c / G.  It takes nlive and forms ncols = nlive G itself: handed ncols, the compiler no longer
+// groups the `c < ncols` tests below by sample (2 % more instructions at G = 4).
+template <int G>
+__device__ __forceinline__ void decode_tile_store(float (&o)[16][8], float m_run, float l_run, int nlive, int64_t r0, int hkv, int Hq,
+                                                  int nsplit, int split, float* ws) {
+  constexpr int D = 128;
+  const int ncols = nlive * G;
+  __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
+  __shared__ float red_ml[4][16][2];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int row = l & 15, kq = l >> 4;
+#define MM_SH_RED(c)                                                                              \
+  if (c < ncols) {                                                                                \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) o[c][j] = kq_sum(o[c][j]);                      \
+  }
+  MM_SH_EACH16(MM_SH_RED)
+#undef MM_SH_RED
+  if (kq == 0) {
+#define MM_SH_PUT(c)                                                                              \
+    if (c < ncols) {                                                                              \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) red_o[w][c][row * 8 + j] = o[c][j];           \
+    }
+    MM_SH_EACH16(MM_SH_PUT)
+#undef MM_SH_PUT
+  }
+  float lt = l_run + __shfl_xor(l_run, 16, 64);
+  lt += __shfl_xor(lt, 32, 64);
+  if (kq == 0 && row < ncols) { red_ml[w][row][0] = m_run; red_ml[w][row][1] = lt; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncols * D; i += 256) {
+    const int c = i / D, d = i % D;
+    float mn = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) mn = fmaxf(mn, red_ml[ww][c][0]);
+    float ltot = 0.f, ot = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float al = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(red_ml[ww][c][0] - mn);
+      ltot += red_ml[ww][c][1] * al;
+      ot += red_o[ww][c][d] * al;
+    }
+    float* rec = ws + (((r0 + c / G) * Hq + hkv * G + c % G) * nsplit + split) * (D + 2);
+    rec[2 + d] = ot;
+    if (d == 0) { rec[0] = mn; rec[1] = ltot; }
+  }
+}
+
 // ANC (mm_attn_decode_beam): suffix key t of query row r is read from the physical suffix row a.anc[t * anc_ld + r], clamped into the
 // rows [b n, b n + n) of the row's own prompt; everything else is the code above, so a table that names every row itself gives the bits
 // of ANC = false and any table the bits of ANC = false on the gathered suffix.  A template argument, not a run-time branch: the
 // NULL-table kernel stays the instruction stream it was (attn_decode_shared128_kernel / attn_decode_beam128_kernel below).
 template <int G, bool ANC>
 __device__ __forceinline__ void decode_shared128_body(const DecodeSharedArgs& a) {
-  constexpr int D = 128, P = 16 / G;
+  constexpr int P = 16 / G;
   static_assert(G == 1 || G == 2 || G == 4, "P = 16 / G samples share a column tile");
-  __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
-  __shared__ float red_ml[4][16][2];
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = l & 15, kq = l >> 4;         // row: key of the block (K operand), column (scores), 8-dim group (V)
   const int split = blockIdx.x, hkv = blockIdx.y;
@@ -2081,24 +2148,15 @@ __device__ __forceinline__ void decode_shared128_body(const DecodeSharedArgs& a)
         if (row / G == jl) acc = aj;
       }
     }
-    float sv[4], bm = -INFINITY;
+    float sv[4], p[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = k0 + 4 * kq + r;
       bool ok = key < kend;
       if (ok && a.kmask && key < a.Sp) ok = a.kmask[(int64_t)b * a.Sp + key] != 0;      // suffix keys are always visible
       sv[r] = ok ? acc[r] * sc : -INFINITY;
-      bm = fmaxf(bm, sv[r]);
     }
-    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float mn = fmaxf(m_run, bm);
-    const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m_run - mn);
-    float p[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sv[r] - mn);
-    l_run = l_run * alpha + ((p[0] + p[1]) + (p[2] + p[3]));
-    m_run = mn;
+    const float alpha = decode_tile_softmax(sv, m_run, l_run, p);
     if (pre) {
 #define MM_SH_COL(c) if (c < ncols) decode_shared_head<c>(o, alpha, p, vx);
       MM_SH_EACH16(MM_SH_COL)
@@ -2121,45 +2179,8 @@ __device__ __forceinline__ void decode_shared128_body(const DecodeSharedArgs& a)
 #undef MM_SH_SAMPLE
     }
   }
-  // this wave's partial per live column: o summed over the 4 kq rows as ((kq0 + kq1) + (kq2 + kq3)) -- the order of the slice kernel
-  // above (the sums commute) -- across the rows by gfx950's row / half swaps (VALU, no LDS round trip: through ds_bpermute the 256
-  // dependent exchanges were most of the kernel's time), so that 16 columns fit 32 KB of LDS; and (m, l) per column
-#define MM_SH_RED(c)                                                                              \
-  if (c < ncols) {                                                                                \
-    _Pragma("unroll") for (int j = 0; j < 8; ++j) o[c][j] = kq_sum(o[c][j]);                      \
-  }
-  MM_SH_EACH16(MM_SH_RED)
-#undef MM_SH_RED
-  if (kq == 0) {
-#define MM_SH_PUT(c)                                                                              \
-    if (c < ncols) {                                                                              \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) red_o[w][c][row * 8 + j] = o[c][j];           \
-    }
-    MM_SH_EACH16(MM_SH_PUT)
-#undef MM_SH_PUT
-  }
-  float lt = l_run + __shfl_xor(l_run, 16, 64);
-  lt += __shfl_xor(lt, 32, 64);
-  if (kq == 0 && row < ncols) { red_ml[w][row][0] = m_run; red_ml[w][row][1] = lt; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ncols * D; i += 256) {
-    const int c = i / D, d = i % D;
-    float mn = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) mn = fmaxf(mn, red_ml[ww][c][0]);
-    float ltot = 0.f, ot = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) {
-      const float al = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(red_ml[ww][c][0] - mn);
-      ltot += red_ml[ww][c][1] * al;
-      ot += red_o[ww][c][d] * al;
-    }
-    float* rec = a.ws + (((r0 + c / G) * a.Hq + hkv * G + c % G) * a.nsplit + split) * (D + 2);
-    rec[2 + d] = ot;
-    if (d == 0) { rec[0] = mn; rec[1] = ltot; }
-  }
+  decode_tile_store<G>(o, m_run, l_run, nlive, r0, hkv, a.Hq, a.nsplit, split, a.ws);
 }
-#undef MM_SH_EACH16
 
 template <int G>
 __global__ __launch_bounds__(256, 2) void attn_decode_shared128_kernel(DecodeSharedArgs a) { decode_shared128_body<G, false>(a); }
@@ -2185,13 +2206,10 @@ struct DecodeVerifyArgs {
   int nsplit, chunk, tiles;      // tiles = ceil(Q / P)
 };
 
-#define MM_VF_EACH16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 template <int G>
 __global__ __launch_bounds__(256, 2) void attn_decode_verify128_kernel(DecodeVerifyArgs a) {
-  constexpr int D = 128, P = 16 / G;
+  constexpr int P = 16 / G;
   static_assert(G == 1 || G == 2 || G == 4, "P = 16 / G positions share a column tile");
-  __shared__ float red_o[4][16][D];            // [wave][column][d], already summed over the 4 kq rows
-  __shared__ float red_ml[4][16][2];
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = l & 15, kq = l >> 4;         // row: key of the block (K operand), column (scores), 8-dim group (V)
   const int split = blockIdx.x, hkv = blockIdx.y;
@@ -2235,65 +2253,22 @@ __global__ __launch_bounds__(256, 2) void attn_decode_verify128_kernel(DecodeVer
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int j = 0; j < 8; ++j) vx[u][j] = (float)vf[u][j];
-    float sv[4], bm = -INFINITY;
+    float sv[4], p[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = k0 + 4 * kq + r;
       bool ok = key < kend && key <= lim;                    // hence key < kstop: a key that was loaded, not a clamped one
       if (ok && a.kmask && key < a.Sp) ok = a.kmask[(int64_t)b * a.Sp + key] != 0;      // generated keys are always visible
       sv[r] = ok ? acc[r] * sc : -INFINITY;
-      bm = fmaxf(bm, sv[r]);
     }
-    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float mn = fmaxf(m_run, bm);
-    const float alpha = mn == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m_run - mn);
-    float p[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sv[r] - mn);
-    l_run = l_run * alpha + ((p[0] + p[1]) + (p[2] + p[3]));
-    m_run = mn;
-#define MM_VF_COL(c) if (c < ncols) decode_shared_head<c>(o, alpha, p, vx);
-    MM_VF_EACH16(MM_VF_COL)
-#undef MM_VF_COL
+    const float alpha = decode_tile_softmax(sv, m_run, l_run, p);
+#define MM_SH_COL(c) if (c < ncols) decode_shared_head<c>(o, alpha, p, vx);
+    MM_SH_EACH16(MM_SH_COL)
+#undef MM_SH_COL
   }
-  // the wave's partial per live column, then the four waves: decode_shared128_body's reduction
-#define MM_VF_RED(c)                                                                              \
-  if (c < ncols) {                                                                                \
-    _Pragma("unroll") for (int j = 0; j < 8; ++j) o[c][j] = kq_sum(o[c][j]);                      \
-  }
-  MM_VF_EACH16(MM_VF_RED)
-#undef MM_VF_RED
-  if (kq == 0) {
-#define MM_VF_PUT(c)                                                                              \
-    if (c < ncols) {                                                                              \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) red_o[w][c][row * 8 + j] = o[c][j];           \
-    }
-    MM_VF_EACH16(MM_VF_PUT)
-#undef MM_VF_PUT
-  }
-  float lt = l_run + __shfl_xor(l_run, 16, 64);
-  lt += __shfl_xor(lt, 32, 64);
-  if (kq == 0 && row < ncols) { red_ml[w][row][0] = m_run; red_ml[w][row][1] = lt; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ncols * D; i += 256) {
-    const int c = i / D, d = i % D;
-    float mn = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) mn = fmaxf(mn, red_ml[ww][c][0]);
-    float ltot = 0.f, ot = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) {
-      const float al = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(red_ml[ww][c][0] - mn);
-      ltot += red_ml[ww][c][1] * al;
-      ot += red_o[ww][c][d] * al;
-    }
-    float* rec = a.ws + (((r0 + c / G) * a.Hq + hkv * G + c % G) * a.nsplit + split) * (D + 2);
-    rec[2 + d] = ot;
-    if (d == 0) { rec[0] = mn; rec[1] = ltot; }
-  }
+  decode_tile_store<G>(o, m_run, l_run, nlive, r0, hkv, a.Hq, a.nsplit, split, a.ws);
 }
-#undef MM_VF_EACH16
+#undef MM_SH_EACH16
 
 template <int D>
 __global__ void attn_decode_merge_kernel(const float* ws, int nsplit, bf16* out) {

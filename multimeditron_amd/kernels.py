@@ -751,42 +751,33 @@ def attn_decode_shared_supported(q_dtype, Hq, Hkv, D):
     return q_dtype == torch.bfloat16 and D == 128 and Hq % Hkv == 0 and (Hq // Hkv) in (1, 2, 4)
 
 
-def attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale):
+def attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale, anc=None, nsplit=None):
     """One query token for each of the n samples of B prompts: q [B*n,Hq,D] (strided view ok; row b*n + j is sample j of prompt b)
     over prompt b's prefix kp/vp [B,Sp,Hkv,D] followed by the row's own suffix ks/vs [B*n,Ss,Hkv,D] -> out [B*n,Hq,D].  key_mask
     [B,Sp] or None covers the prefix; suffix keys are always visible.  The bits of attn_decode on the materialised concatenation
-    (mm_attn_decode_shared)."""
+    (mm_attn_decode_shared).  With anc (int32 [>= Ss, >= B*n], last stride 1) suffix key t of row r is read from physical suffix row
+    anc[t, r]: the bits of the call without it on the gathered suffix (mm_attn_decode_beam; attn_decode_beam below)."""
     R, Hq, D = q.shape
     B, Sp, Hkv = kp.shape[0], kp.shape[1], kp.shape[2]
     Ss = ks.shape[1]
     assert R == B * n and ks.shape[0] == R and vs.shape[0] == R and vp.shape[:3] == kp.shape[:3] and vs.shape[1] == Ss
     assert q.stride(2) == 1 and kp.stride(3) == 1 and vp.stride(3) == 1 and ks.stride(3) == 1 and vs.stride(3) == 1
     assert key_mask is None or (tuple(key_mask.shape) == (B, Sp) and key_mask.is_contiguous())
-    ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss)
+    assert anc is None or (anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] >= Ss and anc.shape[1] >= R and anc.stride(1) == 1)
+    ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss) if nsplit is None else int(nsplit)
     ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
     out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
-    call("mm_attn_decode_shared", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss, Hq, Hkv, D, q.stride(0), q.stride(1),
-         *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale), _p(out), _p(ws), ns, _stream())
+    table = () if anc is None else (_p(anc), anc.stride(0))
+    call("mm_attn_decode_shared" if anc is None else "mm_attn_decode_beam", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss,
+         Hq, Hkv, D, q.stride(0), q.stride(1), *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale),
+         _p(out), _p(ws), ns, *table, _stream())
     return out
 
 
 def attn_decode_beam(q, kp, vp, ks, vs, n, key_mask, scale, anc, nsplit=None):
-    """attn_decode_shared where suffix key t of row r is read from physical suffix row anc[t, r] (int32 [>= Ss, >= B*n], last stride 1):
-    the bits of attn_decode_shared on the gathered suffix (mm_attn_decode_beam)."""
-    R, Hq, D = q.shape
-    B, Sp, Hkv = kp.shape[0], kp.shape[1], kp.shape[2]
-    Ss = ks.shape[1]
-    assert R == B * n and ks.shape[0] == R and vs.shape[0] == R and vp.shape[:3] == kp.shape[:3] and vs.shape[1] == Ss
-    assert q.stride(2) == 1 and kp.stride(3) == 1 and vp.stride(3) == 1 and ks.stride(3) == 1 and vs.stride(3) == 1
-    assert key_mask is None or (tuple(key_mask.shape) == (B, Sp) and key_mask.is_contiguous())
-    assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] >= Ss and anc.shape[1] >= R and anc.stride(1) == 1
-    ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss) if nsplit is None else int(nsplit)
-    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
-    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
-    call("mm_attn_decode_beam", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss, Hq, Hkv, D, q.stride(0), q.stride(1),
-         *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale), _p(out), _p(ws), ns, _p(anc),
-         anc.stride(0), _stream())
-    return out
+    """attn_decode_shared through the ancestor table anc, which this name requires (mm_attn_decode_beam)."""
+    assert anc is not None
+    return attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale, anc, nsplit)
 
 
 # ---- beam search (include/mm_hip.h: mm_beam_step) ----

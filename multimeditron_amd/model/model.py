@@ -24,6 +24,7 @@ from .. import functional as Fm
 from .. import kernels as K
 from ..nn import FlatParams, grad_dummy
 from ..utils import get_torch_dtype, trace_range
+from .decoding import BeamSearch, PromptLookup, Sampling
 from .llm import XIELU, CausalLM, CausalLMOutput, LLMConfig
 from .modalities import AutoModality, BaseModality, BaseModalityConfig, BaseModalityProcessor
 from .presets import resolve_llm_config
@@ -505,173 +506,63 @@ class MultiModalModelForCausalLM(nn.Module):
         whose input width mm_gemm_mx8 refuses (not a multiple of 128) -- raises ValueError before the prefill
         (CausalLM.prefill_weights_ok).
 
-        num_return_sequences=n > 1 (opt-in; needs do_sample=True, greedy would return n equal rows): n sampled continuations of
-        every prompt.  The modalities are encoded, spliced and prefilled ONCE per prompt, and the prompt's keys and values are
-        stored once (LayerKVCacheShared: 2 Hkv D 2 (B Sp + B n max_new_tokens) bytes per layer instead of n copies of the prompt);
-        the prefill's last-row logits are repeated n times and every later step runs B n rows, whose decode attention reads a
-        prompt's keys once per 16 / (Hq / Hkv) samples (include/mm_hip.h: mm_attn_decode_shared -- the bits of the replicated
-        batch's attention).  Returns [B n, n_new]: row b n + j is sample j of prompt b (HF's order).  The device sampler draws
-        with Philox offset = step and call = row b n + j; the torch.multinomial path draws per row; eos bookkeeping, sync_every,
-        the early stop and the padded-length position quirk apply per row.  Composes with decode_weights (B n <= 16) and
-        prefill_weights.  NOT with kv_cache="mxfp8" (a shared-prefix MXFP8 cache is out of scope: ValueError).  A model that
-        cannot use it -- not bf16, head_dim other than 128, a number of query heads per key/value head other than 1, 2 or 4 --
-        raises ValueError before the prefill (CausalLM.samples_ok).  n = 1 is the path above, untouched.
-
-        num_beams=n > 1 (opt-in; needs do_sample=False): beam search as transformers' generate(num_beams=n, do_sample=False,
-        length_penalty=, early_stopping=) with one eos token and no logits processors; the rules are written out in
-        include/mm_hip.h (mm_beam_step).  One prefill per prompt into a LayerKVCacheBeam (the prompt's keys once, as above), then
-        B n rows per step; the selection over a prompt's n V continuations, the finished hypotheses and the stopping flags live on the
-        device (mm_beam_step), and a beam continues another row's suffix through an int32 ancestor table instead of a reordered
-        cache (mm_attn_decode_beam).  The host looks at the device's done flag every `sync_every` steps; steps issued past it change
-        nothing.  early_stopping in {False, True, "never"} and length_penalty have HF's meaning; temperature is ignored.  Returns
-        [B num_return_sequences, n_out] (num_return_sequences <= n, default 1): row b nrs + k is prompt b's k-th best finished
-        hypothesis, eos included and filled with eos behind its end, n_out the longest returned one; with return_beam_scores=True
-        (ids, scores), scores [B nrs] fp32 = sum of log-probabilities / length ** length_penalty, descending per prompt.
-        Composes with decode_weights (B n <= 16) and prefill_weights.  ValueError before the modalities are encoded for: num_beams
-        outside [1, 16], do_sample=True, any of top_k / top_p / min_p / seed / generator, kv_cache="mxfp8", num_return_sequences >
-        num_beams, a length_penalty that is not finite, another early_stopping, a vocabulary below 2 n, and a model samples_ok
-        refuses.  num_beams = 1 is the code above, untouched.
-
-        repetition_penalty= / no_repeat_ngram_size= / min_new_tokens= / suppress_tokens= (opt-in, each on its own): transformers'
-        RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength -> SuppressTokens logits processors, applied in that order to the
-        fp32 scores of every step by ONE kernel (include/mm_hip.h: mm_logits_process) between lm_head and the selection; greedy,
-        torch.multinomial and the device sampler then select from its fp32 output unchanged.  The history of a row -- what the
-        penalty and the n-gram ban look at -- lives on the device: the prompt's ids first, then every emitted id (the eos ids a
-        finished row keeps emitting included), appended by the kernel; the host sees no token.  As in transformers' decoder-only
-        generate the PROMPT counts, placeholder ids of spliced modalities like any id; the one deviation: positions whose
-        attention_mask is 0 (pads) do not count (a pad == eos tokenizer would otherwise penalise eos on every padded row).
-        repetition_penalty: a finite number > 0 (None or 1.0: off); no_repeat_ngram_size, min_new_tokens: ints >= 0 (None or 0: off;
-        min_new_tokens bans config.eos_token_idx while step < min_new_tokens); suppress_tokens: ids in [0, vocab_size) that are never
-        chosen, e.g. the attachment placeholder and pad ids (None or empty: off).  Compose with decode_weights, kv_cache,
-        prefill_weights, num_return_sequences (every sample row keeps its own history) and every sampler path.  NOT with num_beams > 1
-        (processors inside beam search act on log-probabilities inside mm_beam_step: out of scope, ValueError).  A bad value raises
-        ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids.
-
-        prompt_lookup_num_tokens=k (opt-in; greedy: needs do_sample=False): prompt-lookup speculative decoding, transformers'
-        generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=G) for B rows at once.  Each iteration proposes up to k next
-        tokens per row by matching the row's last n-gram (n <= G, default 2; the first match of the longest n) in its own visible
-        prompt and output (include/mm_hip.h: mm_lookup_draft -- PromptLookupCandidateGenerator.get_candidates per row), runs ONE
-        decoder pass over k + 1 positions per row -- B (k + 1) <= 16 rows, the rows a weight-streaming launch has to spare -- and keeps
-        every proposed token the model would have chosen itself (mm_lookup_accept), so the ids are plain greedy decoding's up to the
-        rounding of a differently sliced attention sum.  Rows advance by different amounts; their positions, histories and the done
-        flag live on the device and the host reads only that flag, every `sync_every` iterations.  As everywhere here the prompt's
-        masked positions do not count as history.  Returns the ids as above; with return_lookup_stats=True (ids, stats), stats int32
-        [B, 2] on the CPU: verify steps run (the prefill's included) and draft tokens accepted, per row.  Composes with
-        decode_weights (the verify step reads the copies) and prefill_weights.  Out of scope, ValueError before the modalities are
-        encoded: sampling (do_sample=True, top_k / top_p / min_p / seed / generator), logits processors, num_beams > 1,
-        num_return_sequences > 1 (shared-prefix samples), kv_cache="mxfp8", k not an int >= 1, B (k + 1) > 16, a model
-        CausalLM.lookup_ok refuses, and return_lookup_stats / max_matching_ngram_size without k.  Not here either: a draft model
-        (assistant_model), adaptive k, the append fused into the RoPE pass, tuned slice counts of the verify attention.  With
-        prompt_lookup_num_tokens=None nothing changes: no launch, no buffer, the same ids."""
-        n = num_return_sequences
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
-            raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
-        nb = num_beams
-        if isinstance(nb, bool) or not isinstance(nb, int) or not 1 <= nb <= 16:
-            raise ValueError(f"num_beams must be an int in [1, 16], got {nb!r}")
-        if nb == 1 and return_beam_scores:
-            raise ValueError("return_beam_scores needs num_beams > 1")
+        num_return_sequences=n > 1, repetition_penalty= / no_repeat_ngram_size= / min_new_tokens= / suppress_tokens=, num_beams=n > 1 and
+        prompt_lookup_num_tokens=k (each opt-in): see decoding.Sampling, decoding.BeamSearch and decoding.PromptLookup, the strategies
+        the one decode loop (_decode) runs for them."""
+        n = _int_arg("num_return_sequences", num_return_sequences, 1)
+        nb = _int_arg("num_beams", num_beams, 1, 16)
+        pk, mg = prompt_lookup_num_tokens, max_matching_ngram_size
+        given = [k for k, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p), ("seed", seed), ("generator", generator)) if v is not None]
+        on = {"beams": nb > 1, "no beams": nb == 1, "lookup": pk is not None, "no lookup": pk is None, "samples": n > 1 and nb == 1,
+              "return_beam_scores": bool(return_beam_scores), "lookup arguments": bool(return_lookup_stats) or mg is not None,
+              "do_sample": bool(do_sample), "greedy": not do_sample, "sampler": bool(given), "sampling": bool(do_sample) or bool(given),
+              "kv_cache": kv_cache is not None}
+        val = dict(n=n, nb=nb, pk=pk, kv_cache=kv_cache, sampler=", ".join(given),
+                   sampling=", ".join((["do_sample=True"] if do_sample else []) + given))
+        _refuse(_REFUSALS[:1], on, val)          # as ever: this one before the processors' values are looked at, the others after
         processors = self._logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
-        pk = prompt_lookup_num_tokens
-        if pk is None:
-            if return_lookup_stats or max_matching_ngram_size is not None:
-                raise ValueError("return_lookup_stats / max_matching_ngram_size need prompt_lookup_num_tokens")
-        else:
-            if isinstance(pk, bool) or not isinstance(pk, int) or pk < 1:
-                raise ValueError(f"prompt_lookup_num_tokens must be an int >= 1, got {pk!r}")
-            mg = 2 if max_matching_ngram_size is None else max_matching_ngram_size
-            if isinstance(mg, bool) or not isinstance(mg, int) or mg < 1:
-                raise ValueError(f"max_matching_ngram_size must be an int >= 1, got {max_matching_ngram_size!r}")
-            given = [a for a, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p), ("seed", seed), ("generator", generator)) if v is not None]
-            if do_sample or given:
-                raise ValueError(f"prompt_lookup_num_tokens={pk} with {', '.join((['do_sample=True'] if do_sample else []) + given)}: the lookup "
-                                 "is greedy only (speculative sampling is out of scope)")
-            if nb > 1:
-                raise ValueError(f"prompt_lookup_num_tokens={pk} with num_beams={nb}: out of scope")
-            if n > 1:
-                raise ValueError(f"prompt_lookup_num_tokens={pk} with num_return_sequences={n}: out of scope")
-            if kv_cache is not None:
-                raise ValueError(f"prompt_lookup_num_tokens={pk} with kv_cache={kv_cache!r}: the prompt-lookup cache is bf16 only")
-            if processors is not None:
-                raise ValueError(f"prompt_lookup_num_tokens={pk} with logits processors: filtering the candidates through them is out of scope")
-            llm = self.model
-            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
+        on["processors"] = processors is not None
+        if processors is not None:
+            val["processors"] = ", ".join(k for k, v in zip(("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens"),
+                                                            (processors[0] != 1.0, processors[1] > 0, processors[2] > 0, len(processors[3]) > 0)) if v)
+        if pk is not None:
+            _int_arg("prompt_lookup_num_tokens", pk, 1)
+            mg = _int_arg("max_matching_ngram_size", 2 if mg is None else mg, 1)
+        _refuse(_REFUSALS[1:], on, val)
+        opt_in = pk is not None or nb > 1 or n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights))
+        B, Sp = (int(d) for d in batch["input_ids"].shape[:2]) if opt_in else (None, None)
+        own = None                               # the mode's own entry of CausalLM.OPTIONS
+        if pk is not None:
             if B * (pk + 1) > 16:
                 raise ValueError(f"prompt_lookup_num_tokens={pk} on {B} sequences: B (k + 1) = {B * (pk + 1)} rows, a verify step takes at most 16")
-            llm.check_option("prompt_lookup_num_tokens", pk, B, pk)
-            llm.check_option("decode_weights", decode_weights, B * (pk + 1))                    # the verify steps run B (k + 1) rows
-            llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)
-            return self._generate_lookup(batch, max_new_tokens, temperature, sync_every, pk, mg, bool(return_lookup_stats), decode_weights,
-                                         prefill_weights)
-        if nb > 1 and processors is not None:
-            given = [k for k, on in zip(("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens"),
-                                        (processors[0] != 1.0, processors[1] > 0, processors[2] > 0, len(processors[3]) > 0)) if on]
-            raise ValueError(f"num_beams={nb} with {', '.join(given)}: logits processors inside beam search are out of scope")
-        if nb > 1:
-            llm = self.model
-            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
-            if do_sample:
-                raise ValueError(f"num_beams={nb} needs do_sample=False: beam sampling is out of scope")
-            given = [k for k, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p), ("seed", seed), ("generator", generator)) if v is not None]
-            if given:
-                raise ValueError(f"num_beams={nb} with {', '.join(given)}: beam search does not sample")
-            if kv_cache is not None:
-                raise ValueError(f"num_beams={nb} with kv_cache={kv_cache!r}: the beam cache is bf16 only (an MXFP8 beam cache is out of scope)")
+            strategy, own = PromptLookup(pk, mg, temperature, bool(return_lookup_stats)), ("prompt_lookup_num_tokens", pk)
+        elif nb > 1:
             if n > nb:
                 raise ValueError(f"num_return_sequences={n} > num_beams={nb}")
-            if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
-                raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+            _number_arg("length_penalty", length_penalty)
             if not (early_stopping is False or early_stopping is True or (isinstance(early_stopping, str) and early_stopping == "never")):
                 raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
-            llm.check_option("num_beams", nb, B, nb)
-            llm.check_option("decode_weights", decode_weights, B * nb)                            # the decode steps run B n rows
-            llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)
-            return self._generate_beams(batch, max_new_tokens, sync_every, nb, n, float(length_penalty), early_stopping,
-                                        return_beam_scores, decode_weights, prefill_weights)
-        if n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights)):
-            llm = self.model
-            B, Sp = (int(d) for d in batch["input_ids"].shape[:2])
+            strategy, own = BeamSearch(nb, n, float(length_penalty), early_stopping, return_beam_scores), ("num_beams", nb)
+        else:
+            strategy = Sampling(temperature, do_sample, None, n, kv_cache, processors)
             if n > 1:
-                if not do_sample:
-                    raise ValueError(f"num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows")
-                if kv_cache is not None:
-                    raise ValueError(f"num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
-                                     "shared-prefix cache is out of scope)")
-                llm.check_option("num_return_sequences", n, B, n)
+                own = ("num_return_sequences", n)
+        if opt_in:                               # a call without opt-ins reads neither the batch nor the decoder before _decode
+            llm = self.model
+            if own is not None:
+                llm.check_option(*own, B, own[1])
             llm.check_option("kv_cache", kv_cache, B)
-            llm.check_option("decode_weights", decode_weights, B * n)                             # the decode steps run B n rows
+            llm.check_option("decode_weights", decode_weights, strategy.rows(B))                  # the rows of a decode step
             llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)         # the loop runs under no_grad
-        device_sample = do_sample and any(a is not None for a in (top_k, top_p, min_p, seed, generator))
-        if device_sample:
-            top_k = 0 if top_k is None else top_k
-            top_p = 1.0 if top_p is None else top_p
-            min_p = 0.0 if min_p is None else min_p
-            if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
-                raise ValueError(f"top_k must be an int >= 0, got {top_k!r}")
-            if not (isinstance(top_p, (int, float)) and 0.0 < float(top_p) <= 1.0):
-                raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
-            if not (isinstance(min_p, (int, float)) and 0.0 <= float(min_p) <= 1.0):
-                raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
-            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64):
-                raise ValueError(f"seed must be an int in [0, 2**64), got {seed!r}")
-            if seed is None:
-                gdev = generator.device if generator is not None else "cpu"
-                seed = int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
-        return self._generate(batch, max_new_tokens, temperature, do_sample, sync_every,
-                              (top_k, top_p, min_p, seed) if device_sample else None, decode_weights, kv_cache, prefill_weights,
-                              **({"samples": n} if n > 1 else {}), **({"processors": processors} if processors is not None else {}))
+        if do_sample and given:
+            strategy.sampler = _device_sampler(top_k, top_p, min_p, seed, generator)
+        return self._decode(strategy, batch, max_new_tokens, sync_every, decode_weights, prefill_weights)
 
     def _logits_processors(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens):
         """generate()'s four processor arguments, checked -> (p, g, min_new_tokens, suppressed ids), or None when all are off."""
-        p = 1.0 if repetition_penalty is None else repetition_penalty
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not p > 0:
-            raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
-        g = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
-        if isinstance(g, bool) or not isinstance(g, int) or g < 0:
-            raise ValueError(f"no_repeat_ngram_size must be an int >= 0, got {no_repeat_ngram_size!r}")
-        mn = 0 if min_new_tokens is None else min_new_tokens
-        if isinstance(mn, bool) or not isinstance(mn, int) or mn < 0:
-            raise ValueError(f"min_new_tokens must be an int >= 0, got {min_new_tokens!r}")
+        p = _number_arg("repetition_penalty", 1.0 if repetition_penalty is None else repetition_penalty, positive=True)
+        g = _int_arg("no_repeat_ngram_size", 0 if no_repeat_ngram_size is None else no_repeat_ngram_size, 0)
+        mn = _int_arg("min_new_tokens", 0 if min_new_tokens is None else min_new_tokens, 0)
         if suppress_tokens is not None and (isinstance(suppress_tokens, (str, bytes)) or not hasattr(suppress_tokens, "__iter__")):
             raise ValueError(f"suppress_tokens must be a sequence of ints, got {suppress_tokens!r}")
         sup = [] if suppress_tokens is None else list(suppress_tokens)
@@ -686,205 +577,101 @@ class MultiModalModelForCausalLM(nn.Module):
             raise ValueError(f"min_new_tokens={mn} needs config.eos_token_idx in [0, {V}), got {eos!r}")
         return float(p), g, mn, sup
 
-    def _generate(self, batch, max_new_tokens, temperature, do_sample, sync_every, sampler, decode_weights=None, kv_cache=None, prefill_weights=None,
-                  samples: int = 1, processors=None) -> torch.Tensor:
-        """generate()'s decode loop; sampler = (top_k, top_p, min_p, seed) for the device sampler, else None.
-
-        The reference synchronises with the host after EVERY token (`.cpu()`, `finished.all()`, model.py:618-625,637-638).
-        Here the chosen id, the eos bookkeeping and the next embedding lookup stay on the device (mm_decode_select +
-        the embedding gather), so the host queues steps ahead of the GPU; it looks at `finished` only every `sync_every`
-        tokens.  Steps issued past the point where every row had finished are cut off afterwards: the returned ids are
-        exactly the reference's (same length, same values).
-
-        samples = n > 1 (generate's num_return_sequences): the prefill runs on the B prompts into a LayerKVCacheShared; its logits
-        are repeated n times and from there on B stands for the B n sample rows.  The decode steps hand the PROMPT's mask to the
-        cache (generated tokens are always visible).
-
-        processors = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppressed ids), checked by generate, else None: every
-        step's logits go through mm_logits_process (one launch; the rows' history stays on the device, fed from next_ids) and the
-        selection reads its fp32 output."""
+    def _decode(self, strategy, batch, max_new_tokens, sync_every, decode_weights=None, prefill_weights=None):
+        """generate()'s one decode loop: the prefill and up to max_new_tokens - 1 further decoder passes, with what is chosen from
+        their logits and what the next pass is fed left to `strategy` (decoding.py).  Everything between two passes stays on the
+        device; the host looks at the strategy's done flag every sync_every passes -- the only synchronisation of the loop -- and
+        passes issued after every row had finished change nothing that is returned."""
         if self._flat is None:
             self.pack_parameters()
-        dev = self.device
+        dev, llm = self.device, self.model
         input_ids = batch["input_ids"].to(dev)
-        temperature = max(temperature, 1e-6)
-        B = input_ids.shape[0]
-        V = self._llm_cfg.vocab_size
-        eos = self.config.eos_token_idx
         if max_new_tokens <= 0:
-            return torch.empty((B * samples, 0), dtype=torch.int64)
-        if decode_weights is not None and self.model._decode_w8 is None:
-            self.model.quantize_decode_weights(decode_weights)
+            ids, extra = strategy.empty(input_ids.shape[0])
+            return (ids, extra) if strategy.returns_extra else ids
+        if decode_weights is not None and llm._decode_w8 is None:
+            llm.quantize_decode_weights(decode_weights)
         dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
+        pw = {"prefill_weights": prefill_weights} if prefill_weights is not None else {}      # the prefill call only
         with torch.no_grad():
-            nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
-            attention_mask = batch["attention_mask"].to(dev)
-            position_ids = batch["position_ids"].to(dev)
-            seq_length = attention_mask.shape[1]
-            if samples > 1:
-                cache = self.model.new_cache(B, seq_length + max_new_tokens, samples=samples, prompt_len=seq_length)
-                prompt_mask = attention_mask
-                B = B * samples                                # the rows of every buffer below and of every step after the prefill
-            else:
-                cache = self.model.new_cache(B, seq_length + max_new_tokens, kv_cache=kv_cache)
-            # device-resident loop state (plumbing): the growing mask is a view of one preallocated buffer
-            if samples == 1:
-                full_mask = torch.ones((B, seq_length + max_new_tokens), dtype=attention_mask.dtype, device=dev)
-                full_mask[:, :seq_length] = attention_mask
-            out_ids = torch.full((B, max_new_tokens), eos, dtype=torch.int64, device=dev)
-            finished = torch.zeros(B, dtype=torch.uint8, device=dev)
-            next_ids = torch.empty(B, dtype=torch.int64, device=dev)
-            steps = 0
-            emb = self.model.get_input_embeddings()
-            sample_ws = K.sample_ws(B, V, dev) if sampler is not None else None       # once per call
-            tok_buf = torch.empty(B, dtype=torch.int64, device=dev) if sampler is not None else None
-            lp = None
-            if processors is not None:
-                p_, g_, mn_, sup_ = processors
-                lp = K.LogitsState(B, V, dev, p_, g_, mn_, sup_, prompt_ids=input_ids, prompt_mask=batch["attention_mask"].to(dev),
-                                   samples=samples, room=max_new_tokens)
+            feed = dict(inputs_embeds=self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"]),
+                        attention_mask=batch["attention_mask"].to(dev), position_ids=batch["position_ids"].to(dev), logits_to_keep=1)
+            mask = feed["attention_mask"]
+            Smax, kw = strategy.cache_args(mask.shape[1], max_new_tokens)
+            cache = llm.new_cache(mask.shape[0], Smax, **kw)
+            strategy.begin(self, cache, input_ids, mask, max_new_tokens)
             for i in range(max_new_tokens):
-                if i > 0:
-                    position_ids = torch.full((B, 1), seq_length + i - 1, dtype=torch.long, device=dev)
-                    attention_mask = full_mask[:, : seq_length + i] if samples == 1 else prompt_mask
-                pw = {"prefill_weights": prefill_weights} if i == 0 and prefill_weights is not None else {}      # the prefill call only
-                out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
-                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw, **pw)
-                logits2d = out.logits[:, -1, :]                       # [B, V] view, stride padded
-                if samples > 1 and i == 0:
-                    logits2d = logits2d.repeat_interleave(samples, dim=0)      # plumbing: sample j of prompt b is row b n + j
-                if lp is not None:
-                    logits2d = K.logits_process(logits2d, lp, i, next_ids, eos)    # fp32 scores; the history takes next_ids in
-                if sampler is not None:
-                    k_, p_, mp_, sd_ = sampler
-                    tok = K.sample(logits2d, V, temperature, top_k=k_, top_p=p_, min_p=mp_, seed=sd_, offset=i, ws=sample_ws,
-                                   out=tok_buf)
-                elif do_sample:
-                    probs = torch.softmax(logits2d.float() / temperature, dim=-1)
-                    tok = torch.multinomial(probs, num_samples=1).view(B)
-                else:
-                    tok = K.argmax_softmax(logits2d, V, temperature)
-                K.decode_select(tok, finished, eos, out_ids, i, next_ids)
-                steps = i + 1
-                if steps == max_new_tokens:
-                    break
-                if steps % max(1, sync_every) == 0 and bool(finished.all()):      # the only host sync of the loop
-                    break
-                nxt = emb(next_ids.view(B, 1))
-            ids = out_ids[:, :steps].cpu()
-            K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
-        # the reference stops right after the first step at which every row has emitted eos
-        done = (ids == eos).to(torch.int8).cummax(dim=1).values.bool().all(dim=0)
-        if bool(done.any()):
-            ids = ids[:, : int(torch.nonzero(done)[0]) + 1]
-        return ids
-
-
-    def _generate_beams(self, batch, max_new_tokens, sync_every, n, nrs, length_penalty, early_stopping, return_scores,
-                        decode_weights=None, prefill_weights=None):
-        """generate()'s beam-search loop (num_beams = n > 1, checked by generate).  The prefill runs on the B prompts into a
-        LayerKVCacheBeam; mm_beam_step reads its B rows of logits at step 0 and B n rows afterwards, and hands back the next ids
-        (the next embedding lookup) and the ancestor table of the coming step.  Nothing but the done flag comes to the host, every
-        sync_every steps; positions keep the padded-length quirk of _generate and the cache gets the PROMPT's mask."""
-        if self._flat is None:
-            self.pack_parameters()
-        dev = self.device
-        input_ids = batch["input_ids"].to(dev)
-        B = input_ids.shape[0]
-        V = self._llm_cfg.vocab_size
-        eos = self.config.eos_token_idx
-        if max_new_tokens <= 0:
-            ids = torch.empty((B * nrs, 0), dtype=torch.int64)
-            return (ids, torch.zeros(B * nrs, dtype=torch.float32)) if return_scores else ids
-        if decode_weights is not None and self.model._decode_w8 is None:
-            self.model.quantize_decode_weights(decode_weights)
-        dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
-        R = B * n
-        with torch.no_grad():
-            nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
-            attention_mask = prompt_mask = batch["attention_mask"].to(dev)
-            position_ids = batch["position_ids"].to(dev)
-            seq_length = attention_mask.shape[1]
-            cache = self.model.new_cache(B, seq_length + max_new_tokens, beams=n, prompt_len=seq_length)
-            tables = cache[0].tables
-            st = K.BeamState(B, n, max_new_tokens, V, dev)
-            emb = self.model.get_input_embeddings()
-            for i in range(max_new_tokens):
-                if i > 0:
-                    position_ids = torch.full((R, 1), seq_length + i - 1, dtype=torch.long, device=dev)
-                    attention_mask = prompt_mask
-                    tables.current = st.table(i)
-                pw = {"prefill_weights": prefill_weights} if i == 0 and prefill_weights is not None else {}      # the prefill call only
-                out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids,
-                                 past_key_values=cache, use_cache=True, logits_to_keep=1, **dw, **pw)
-                next_ids = K.beam_step(out.logits[:, -1, :], st, i, eos, length_penalty, early_stopping)
+                out = llm(past_key_values=cache, use_cache=True, **feed, **dw, **pw)
+                pw = {}
+                strategy.consume(out.logits, i)
                 if i + 1 == max_new_tokens:
                     break
-                if (i + 1) % max(1, sync_every) == 0 and bool(st.done.item()):      # the only host sync of the loop
+                if (i + 1) % max(1, sync_every) == 0 and bool(strategy.done()):      # the only host sync of the loop
                     break
-                nxt = emb(next_ids.view(R, 1))
-            ids, scores, lens = K.beam_finish(st, nrs, eos)
-            n_out = int(lens.max().item())
-            ids, scores = ids[:, :n_out].cpu(), scores.cpu()
+                feed = strategy.feed(i + 1)
+            ids, extra = strategy.finish()
             K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
-        return (ids, scores) if return_scores else ids
+        if strategy.trim_eos:
+            # the reference stops right after the first step at which every row has emitted eos
+            done = (ids == self.config.eos_token_idx).to(torch.int8).cummax(dim=1).values.bool().all(dim=0)
+            if bool(done.any()):
+                ids = ids[:, : int(torch.nonzero(done)[0]) + 1]
+        return (ids, extra) if strategy.returns_extra else ids
 
 
-    def _generate_lookup(self, batch, max_new_tokens, temperature, sync_every, k, G, return_stats, decode_weights=None, prefill_weights=None):
-        """generate()'s prompt-lookup loop (prompt_lookup_num_tokens = k, max_matching_ngram_size = G, checked by generate).  The
-        prefill runs as in _generate into a LayerKVCacheLookup with room for k slots behind the last id; its token goes through
-        mm_lookup_accept as a verify step without drafts, so count, finished, the history and base (seq_length - 1 -> seq_length: the
-        "padded prompt length + i - 1" position and cache slot of the first generated token) start out the way later steps update
-        them.  An iteration is mm_lookup_draft -> embedding gather -> one decoder pass over k + 1 positions per row (CausalLM.forward's
-        "verify" route) with lm_head on all B (k + 1) rows -> the selector plain greedy uses, at the caller's temperature ->
-        mm_lookup_accept.  At most max_new_tokens accept calls (every one emits at least one id per active row); the host reads the
-        device's done flag every sync_every of them, and iterations issued after done change nothing."""
-        if self._flat is None:
-            self.pack_parameters()
-        dev = self.device
-        input_ids = batch["input_ids"].to(dev)
-        temperature = max(temperature, 1e-6)
-        B = input_ids.shape[0]
-        V = self._llm_cfg.vocab_size
-        eos = self.config.eos_token_idx
-        if max_new_tokens <= 0:
-            ids = torch.empty((B, 0), dtype=torch.int64)
-            return (ids, torch.zeros((B, 2), dtype=torch.int32)) if return_stats else ids
-        if decode_weights is not None and self.model._decode_w8 is None:
-            self.model.quantize_decode_weights(decode_weights)
-        dw = {"decode_weights": decode_weights} if decode_weights is not None else {}
-        pw = {"prefill_weights": prefill_weights} if prefill_weights is not None else {}
-        Q = k + 1
-        with torch.no_grad():
-            nxt = self.embed_modalities_with_text(input_ids, batch["processed_multimodal_inputs"])
-            attention_mask = batch["attention_mask"].to(dev)
-            position_ids = batch["position_ids"].to(dev)
-            seq_length = attention_mask.shape[1]
-            cache = self.model.new_cache(B, seq_length + max_new_tokens + k, lookup=k)
-            st = K.LookupState(input_ids, attention_mask, k, G, max_new_tokens, eos, seq_length - 1)
-            shared = cache[0].shared
-            shared.base = st.base
-            emb = self.model.get_input_embeddings()
-            out = self.model(inputs_embeds=nxt, attention_mask=attention_mask, position_ids=position_ids, past_key_values=cache,
-                             use_cache=True, logits_to_keep=1, **dw, **pw)
-            K.lookup_accept(st, K.argmax_softmax(out.logits[:, -1, :], V, temperature), 1)
-            prompt_mask = attention_mask.to(torch.int64).contiguous()
-            for it in range(1, max_new_tokens):
-                if it % max(1, sync_every) == 0 and bool(st.done.item()):      # the only host sync of the loop
-                    break
-                shared.bound = min(seq_length + (it - 1) * Q, seq_length + max_new_tokens - 1)      # base[b] <= bound, known here
-                ids, pos = K.lookup_draft(st)
-                out = self.model(inputs_embeds=emb(ids), attention_mask=prompt_mask, position_ids=pos, past_key_values=cache,
-                                 use_cache=True, **dw)
-                K.lookup_accept(st, K.argmax_softmax(out.logits.reshape(B * Q, V), V, temperature))
-            ids, stats, count = st.out.cpu(), st.stats.cpu(), st.count.cpu()
-            K.embed_check_pending()          # the host has just synchronised: an out-of-range input id raises here (IndexError)
-        ids = ids[:, : int(count.max())]
-        # the reference stops right after the first step at which every row has emitted eos
-        done = (ids == eos).to(torch.int8).cummax(dim=1).values.bool().all(dim=0)
-        if bool(done.any()):
-            ids = ids[:, : int(torch.nonzero(done)[0]) + 1]
-        return (ids, stats) if return_stats else ids
+def _int_arg(name, v, lo, hi=None, rng=None):
+    """generate()'s "int in range, not bool" check; -> v"""
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        rng = rng or (f">= {lo}" if hi is None else f"in [{lo}, {hi}]")
+        raise ValueError(f"{name} must be an int {rng}, got {v!r}")
+    return v
+
+
+def _number_arg(name, v, positive=False):
+    """generate()'s "finite number" check; -> v"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (positive and not v > 0):
+        raise ValueError(f"{name} must be a finite number{' > 0' if positive else ''}, got {v!r}")
+    return v
+
+
+# generate(): which option excludes which, first match raised -- (the option that is on, what it meets, the message over `val`)
+_REFUSALS = (
+    ("no beams", "return_beam_scores", "return_beam_scores needs num_beams > 1"),
+    ("no lookup", "lookup arguments", "return_lookup_stats / max_matching_ngram_size need prompt_lookup_num_tokens"),
+    ("lookup", "sampling", "prompt_lookup_num_tokens={pk} with {sampling}: the lookup is greedy only (speculative sampling is out of scope)"),
+    ("lookup", "beams", "prompt_lookup_num_tokens={pk} with num_beams={nb}: out of scope"),
+    ("lookup", "samples", "prompt_lookup_num_tokens={pk} with num_return_sequences={n}: out of scope"),
+    ("lookup", "kv_cache", "prompt_lookup_num_tokens={pk} with kv_cache={kv_cache!r}: the prompt-lookup cache is bf16 only"),
+    ("lookup", "processors", "prompt_lookup_num_tokens={pk} with logits processors: filtering the candidates through them is out of scope"),
+    ("beams", "processors", "num_beams={nb} with {processors}: logits processors inside beam search are out of scope"),
+    ("beams", "do_sample", "num_beams={nb} needs do_sample=False: beam sampling is out of scope"),
+    ("beams", "sampler", "num_beams={nb} with {sampler}: beam search does not sample"),
+    ("beams", "kv_cache", "num_beams={nb} with kv_cache={kv_cache!r}: the beam cache is bf16 only (an MXFP8 beam cache is out of scope)"),
+    ("samples", "greedy", "num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows"),
+    ("samples", "kv_cache", "num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
+                            "shared-prefix cache is out of scope)"),
+)
+
+
+def _refuse(rows, on, val):
+    for a, b, message in rows:
+        if on[a] and on[b]:
+            raise ValueError(message.format(**val))
+
+
+def _device_sampler(top_k, top_p, min_p, seed, generator):
+    """generate()'s device-sampler arguments, checked -> (top_k, top_p, min_p, seed); a missing seed is drawn from `generator`."""
+    top_k = _int_arg("top_k", 0 if top_k is None else top_k, 0)
+    top_p = 1.0 if top_p is None else top_p
+    min_p = 0.0 if min_p is None else min_p
+    if not (isinstance(top_p, (int, float)) and 0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if not (isinstance(min_p, (int, float)) and 0.0 <= float(min_p) <= 1.0):
+        raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+    if seed is not None:
+        return top_k, top_p, min_p, _int_arg("seed", seed, 0, (1 << 64) - 1, "in [0, 2**64)")
+    gdev = generator.device if generator is not None else "cpu"
+    return top_k, top_p, min_p, int(torch.randint(0, 1 << 62, (1,), generator=generator, device=gdev).item())
 
 
 def bootstrap(config, tokenizer, modalities_config):

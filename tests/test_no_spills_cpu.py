@@ -11,7 +11,10 @@ BUILD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOT = {
     "mm_gemm.o.resources.txt": ["gemm_bf16_dma_kernel", "gemm_bf16_kernel", "gemm_skinny_kernel"],
     "mm_attn.o.resources.txt": ["attn_fwd128q_kernel", "attn_fwd128p_kernel", "attn_bwd_dq128p_kernel", "attn_bwd_dkv128_pairp_kernel",
-                                "attn_decode_partial_kernel"],
+                                "attn_decode_partial_kernel", "attn_decode_partial128_mfma_kernel",
+                                # every decode step of generate's samples, beams and prompt-lookup modes; the beam kernel sits at the 256
+                                # VGPRs of its launch bounds
+                                "attn_decode_shared128_kernel", "attn_decode_beam128_kernel", "attn_decode_verify128_kernel"],
     "mm_optim.o.resources.txt": ["adamw_kernel", "sumsq_kernel"],
 }
 

@@ -10,7 +10,8 @@ init), inputs, per-stage activations, logits, loss, selected grads, greedy token
 collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 
 `python tools/make_golden.py gemm_plan` is a mode apart: it rewrites tests/golden/gemm_plan.jsonl (the GEMM launch decisions) from
-the built library and needs neither the reference nor a GPU (gemm_plan_table below).
+the built library and needs neither the reference nor a GPU (gemm_plan_table below).  `python tools/make_golden.py generate_launches`
+is another: it records generate()'s launches on a GPU into tests/golden/generate_launches.jsonl (generate_launches_table below).
 
 Import recipe = SURVEY.md Appendix A (three harness-side shims, none edits the reference).
 The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 / Apertus modules as called
@@ -55,8 +56,26 @@ def gemm_plan_table():
     print(f"gemm_plan: {len(rows)} rows, {moved} changed")
 
 
+def generate_launches_table():
+    """`make_golden.py generate_launches`: write tests/golden/generate_launches.jsonl, the C symbols every mode of generate() queues
+    (tests/generate_trace.py holds the cases and the recorder; tests/test_generate_launch_trace_gpu.py replays them).  Needs the built
+    library and a GPU, not the reference.  Run it on the revision whose launch order is the contract -- the parent of a change that
+    is meant to keep it -- and commit the file as recorded."""
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    sys.path.insert(0, root)
+    from tests import generate_trace as T
+    golden = os.path.join(root, "tests", "golden")
+    with tempfile.TemporaryDirectory() as tmp:
+        rows = T.record(*T.load(golden, tmp))
+    T.write(rows, golden)
+    print(f"generate_launches: {len(rows)} cases, {sum(len(n) for _, n in rows)} launches")
+
+
 if sys.argv[1:] == ["gemm_plan"]:
     gemm_plan_table()
+    sys.exit(0)
+if sys.argv[1:] == ["generate_launches"]:
+    generate_launches_table()
     sys.exit(0)
 
 import numpy as np
