@@ -199,7 +199,7 @@ class PromptLookup:
     mm_lookup_accept as a verify step without drafts, so count, finished, the history and base (seq_length - 1 -> seq_length: the
     "padded prompt length + i - 1" position and cache slot of the first generated token) start out the way later steps update
     them.  An iteration is mm_lookup_draft -> embedding gather -> one decoder pass over k + 1 positions per row (CausalLM.forward's
-    "verify" route) with lm_head on all B (k + 1) rows -> the selector plain greedy uses, at the caller's temperature ->
+    verify step) with lm_head on all B (k + 1) rows -> the selector plain greedy uses, at the caller's temperature ->
     mm_lookup_accept.  At most max_new_tokens accept calls (every one emits at least one id per active row); iterations issued
     after done change nothing."""
     trim_eos = True

@@ -141,6 +141,13 @@ class Attention(nn.Module):
         return (qkv[:, : Hq * D].view(B, S, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
                 qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
 
+    def rope_append_(self, qkv, B, cos, sin, kcache, vcache, pos):
+        """A decode step's (per-head norm +) RoPE of q / k in place and the write of the new k / v rows to cache[:, pos]: one pass."""
+        if self.q_norm is not None:
+            K.qk_norm_rope_append_(qkv, B, self.Hq, self.Hkv, self.D, *self.qkn(), cos, sin, kcache, vcache, pos)
+        else:
+            K.rope_append_(qkv, B, self.Hq, self.Hkv, self.D, cos, sin, kcache, vcache, pos)
+
 
 class MLP(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
@@ -236,6 +243,14 @@ class W8(NamedTuple):
         return K.decode_gateup_swiglu_w8(x, self.packed, I, norm_w, eps)
 
 
+class Plan(NamedTuple):
+    """How a call without autograd runs its layers: CausalLM.forward decides it once per call, DecoderLayer.infer picks the form of
+    every stage from it."""
+    rows: str       # "step": at most 16 bf16 rows over a filled cache (one new token per sequence, or the k + 1 positions of a
+                    # prompt-lookup verify step), every linear one weight-streaming launch; "prefill": the MXFP8 prefill
+    fused: bool     # a step whose norms and SwiGLU ride in the weight-streaming launches (can_decode_step_fused / can_verify_fused)
+
+
 class DecoderLayer(nn.Module):
     def __init__(self, cfg: LLMConfig, dtype, device):
         super().__init__()
@@ -255,110 +270,79 @@ class DecoderLayer(nn.Module):
         return getattr(self, self._norm_names[0]), getattr(self, self._norm_names[1])
 
     @torch.no_grad()
-    def infer(self, w, x, cos, sin, key_mask, B, S, cache, step):
-        """The layer without autograd, on the matrices w (this layer's W16s, or its W8s from CausalLM.quantize_decode_weights): the
-        same arithmetic and rounding points as forward().  rmsnorm_fwd, linear (q|k|v + bias), attention, linear (o_proj + residual),
-        rmsnorm_fwd, linear (gate|up or up_proj), swiglu_fwd / xIELU, linear (down_proj + residual).
+    def infer(self, w, x, cos, sin, key_mask, B, S, cache, plan: Plan):
+        """The layer without autograd, on the matrices w (this layer's W16s, or its W8s from CausalLM.quantize_decode_weights -- the
+        same launches on half the weight bytes): q|k|v -> attend -> o_proj + residual -> gate|up (Apertus: up_proj) + activation ->
+        down_proj + residual, with the arithmetic and rounding points of forward() in every form.  x = residual stream in and out.
 
-        step: one new token per sequence (generate's decode loop, reference model.py:595-602).  The four linears stream their
-        weights (W16: mm_gemm at M <= 16; W8: the weight-only kernel), RoPE and the cache append are one pass (rope_append_ /
-        qk_norm_rope_append_) and attention is the split-K stream over the cache (bf16, MXFP8 or shared-prefix: the cache says
-        where the append kernel writes the new row and attends over itself).  (Folding RMSNorm / SwiGLU into the GEMM's x operand
-        was measured SLOWER: every workgroup redoes the transform on all 64 lanes and the kernel turns VALU-bound, 43 vs 27 us and
-        57 vs 25 us per launch, so they stay separate launches here; decode_step_fused folds them into the weight-streaming kernels.)
-
-        not step: the MXFP8 prefill (forward(prefill_weights="mxfp8"), w = the W8s).  Each linear is quant_mxfp8 of its bf16 input +
-        gemm_mx8; RoPE / q-k norm, the cache append and attn_fwd are the cache's attend, without a cache rope_views + attn_fwd.
-        Everything but the eight new launches is the existing kernel on bf16 data."""
+        plan.rows == "step": M = B S <= 16 rows over a filled cache -- a decode step (S = 1, generate's loop, reference
+        model.py:595-602) or a prompt-lookup verify step (S = k + 1 positions per sequence) --, so every linear is one
+        weight-streaming launch that reads its matrix once (W16: mm_gemm's M <= 16 kernel; W8: the weight-only kernel), and the cache
+        places and attends the new rows (its `step`).  plan.fused folds the tiny launches into those (csrc/mm_gemm.hip
+        gemv_stream_kernel): a decode step is 6 launches with the two attention kernels, none of them a norm, and has the bits of
+        the separate form.
+        plan.rows == "prefill": the MXFP8 prefill (forward(prefill_weights="mxfp8"), w = the W8s).  Each linear is quant_mxfp8 of its
+        bf16 input + gemm_mx8; everything but those eight launches is the existing kernel on bf16 data."""
         a, m = self.self_attn, self.mlp
         Hq, Hkv, D = a.Hq, a.Hkv, a.D
         n1, n2 = self.norms()
+        step = plan.rows == "step"
         mx8 = not step
-        h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
-        qkv = w["qkv"].linear(h, mx8, bias=a._bqkv.tensor() if a._bqkv is not None else None)
+        bias = a._bqkv.tensor() if a._bqkv is not None else None
+        # q|k|v.  fused: input RMSNorm + q|k|v + RoPE + cache append in one launch where the cache knows on the host where the new
+        # row goes, else input RMSNorm + q|k|v where there is no bias (the plain streaming linear carries none: a fused verify
+        # step, can_verify_fused) and the cache ropes and places the rows itself.  separate:
+        # folding RMSNorm / SwiGLU into the GEMM's own x operand was measured SLOWER (every workgroup redoes the transform on all 64
+        # lanes and the kernel turns VALU-bound, 43 vs 27 us and 57 vs 25 us per launch), so they are launches of their own
+        dst = cache.append_dst() if plan.fused else None
+        if dst is not None:
+            qkv = w["qkv"].qkv_rope_append(x, bias, Hq, Hkv, D, cos, sin, *dst, n1.weight, n1.eps)
+        elif plan.fused and bias is None:
+            qkv = w["qkv"].stream(x, None, n1.weight, n1.eps)
+        else:
+            h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
+            qkv = w["qkv"].linear(h, mx8, bias=bias)
+        # attend: RoPE / q-k norm, the cache append and the attention kernel are the cache's; without a cache rope_views + attn_fwd
         if step:
-            if a.q_norm is not None:
-                K.qk_norm_rope_append_(qkv, B, Hq, Hkv, D, *a.qkn(), cos, sin, *cache.append_dst())
-            else:
-                K.rope_append_(qkv, B, Hq, Hkv, D, cos, sin, *cache.append_dst())
-            o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+            o = cache.step(qkv, cos, sin, key_mask, B, S, a, dst is not None)
         elif cache is not None:
             o = cache.attend(qkv, cos, sin, key_mask, B, S, a)
         else:
             q, kn, vn = a.rope_views(qkv, cos, sin, B, S)
             o = K.attn_fwd(q, kn, vn, key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
+        # tail.  fused: o_proj + residual, post-attention RMSNorm + gate|up + SwiGLU, down_proj + residual -- down_proj in the
+        # LDS-staged launch where its M rows of I features fit it, else in mm_gemm's M <= 16 kernel (the same bits): 16 rows of the
+        # 8B model's 14336 features do not fit, its 4096-wide inputs do; a decode step always fits (can_decode_step_fused)
+        if plan.fused:
+            x = w["o"].stream(o, x)
+            act = w["gu"].gateup_swiglu(x, m.I, n2.weight, n2.eps)
+            return w["down"].stream(act, x) if K.decode_fits(B * S, m.I) else w["down"].linear(act, residual=x)
         x = w["o"].linear(o, mx8, residual=x)
         h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
         u = w["gu"].linear(h, mx8)
         act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
         return w["down"].linear(act, mx8, residual=x)
 
-    @torch.no_grad()
-    def decode_step_fused(self, w, x, cos, sin, key_mask, B, cache):
-        """The decode step with the tiny launches folded into the weight-streaming GEMMs (csrc/mm_gemm.hip gemv_stream_kernel):
-        input RMSNorm + q|k|v + RoPE + cache append, o_proj + residual, post-attention RMSNorm + gate|up + SwiGLU, down_proj +
-        residual -- 6 launches with the two attention kernels, none of them a norm.  x = residual stream in and out.  Same bits as
-        infer(step=True).  w: this layer's W16s, or its W8s -- the same four launches on half the weight bytes."""
-        a, m = self.self_attn, self.mlp
-        Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        n1, n2 = self.norms()
-        qkv = w["qkv"].qkv_rope_append(x, a._bqkv.tensor() if a._bqkv is not None else None, Hq, Hkv, D, cos, sin, *cache.append_dst(),
-                                       n1.weight, n1.eps)
-        o = cache.decode_attend(qkv[:, : Hq * D].view(B, Hq, D), key_mask, D ** -0.5)
-        x = w["o"].stream(o.view(B, Hq * D), x)
-        act = w["gu"].gateup_swiglu(x, m.I, n2.weight, n2.eps)
-        return w["down"].stream(act, x)
-
     def can_decode_step(self, x, B, S, cache):
         a = self.self_attn
         return (cache is not None and S == 1 and B <= 16 and x.dtype == torch.bfloat16 and not torch.is_grad_enabled()
                 and K.attn_decode_supported(x.dtype, a.Hq, a.Hkv, a.D))
 
-    def can_decode_step_fused(self, x, B, S, cache):
+    def _can_fuse(self, x, M):
+        """What folding the norms and SwiGLU into the weight-streaming launches asks of the layer and of M rows, whatever the step."""
         a = self.self_attn
-        return (self.can_decode_step(x, B, S, cache) and a.D == 128 and a.q_norm is None and K.decode_fusions() and x.shape[-1] <= 8192 and self.mlp.I % 4 == 0
-                and K.decode_fits(B, x.shape[-1]) and K.decode_fits(B, self.mlp.I) and K.decode_fits(B, a.Hq * a.D)
+        return (a.D == 128 and a.q_norm is None and K.decode_fusions() and x.shape[-1] <= 8192 and self.mlp.I % 4 == 0
+                and K.decode_fits(M, x.shape[-1]) and K.decode_fits(M, a.Hq * a.D)
                 and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
+
+    def can_decode_step_fused(self, x, B, S, cache):
+        """... of a decode step: down_proj's B input rows fit the LDS stage as well."""
+        return self.can_decode_step(x, B, S, cache) and self._can_fuse(x, B) and K.decode_fits(B, self.mlp.I)
 
     def can_verify_fused(self, x, M):
-        """Whether verify_step may fold the norms and SwiGLU into the weight-streaming launches at M = B (k + 1) rows: what
-        can_decode_step_fused asks of a decode step -- but for down_proj's input rows, which verify_step places on its own (16 rows of
-        the 8B model's 14336 features do not fit the LDS stage; its 4096-wide inputs do) --, and no q|k|v bias (the plain streaming
-        linear carries none here)."""
-        a = self.self_attn
-        return (a.D == 128 and a.q_norm is None and not self.xielu and a._bqkv is None and K.decode_fusions() and x.shape[-1] <= 8192
-                and self.mlp.I % 4 == 0 and K.decode_fits(M, x.shape[-1]) and K.decode_fits(M, a.Hq * a.D)
-                and a.o_proj.bias is None and self.mlp.down_proj.bias is None and self.norms()[0].bias is None)
-
-    @torch.no_grad()
-    def verify_step(self, w, x, cos, sin, key_mask, B, Q, cache, fused):
-        """The verify step of prompt-lookup decoding: Q = k + 1 positions for each of B sequences, M = B Q <= 16 rows, so every linear
-        is one weight-streaming launch that reads its matrix once (w: the layer's W16s or W8s).  norm + q|k|v, the in-place RoPE
-        (rope_apply_ / qk_norm_rope_fwd), the append of the Q new k / v rows at the slots base[b] + j (mm_kv_append_at), the Q-position
-        decode attention over one read of the keys (mm_attn_decode_verify), o_proj + residual, norm + gate|up + activation, down +
-        residual.  fused (can_verify_fused): the norms and SwiGLU ride in the streaming kernels as in decode_step_fused; otherwise
-        infer(step=True)'s separate launches.  Either way the arithmetic and rounding points of a decode step."""
-        a, m = self.self_attn, self.mlp
-        Hq, Hkv, D = a.Hq, a.Hkv, a.D
-        n1, n2 = self.norms()
-        M = B * Q
-        if fused:
-            qkv = w["qkv"].stream(x, norm_w=n1.weight, eps=n1.eps)
-        else:
-            h, _ = K.rmsnorm_fwd(x, n1.weight, n1.eps)
-            qkv = w["qkv"].linear(h, bias=a._bqkv.tensor() if a._bqkv is not None else None)
-        a.rope_views(qkv, cos, sin, B, Q)
-        o = cache.verify_attend(qkv, B, Q, Hq, Hkv, D, key_mask, D ** -0.5).view(M, Hq * D)
-        if fused:
-            x = w["o"].stream(o, x)
-            act = w["gu"].gateup_swiglu(x, m.I, n2.weight, n2.eps)
-            # down_proj: the LDS-staged launch where the M rows of I features fit it, else mm_gemm's M <= 16 kernel (the same bits)
-            return w["down"].stream(act, x) if K.decode_fits(M, m.I) else w["down"].linear(act, residual=x)
-        x = w["o"].linear(o, residual=x)
-        h, _ = K.rmsnorm_fwd(x, n2.weight, n2.eps)
-        u = w["gu"].linear(h)
-        act = m.act(u) if self.xielu else K.swiglu_fwd(u, m.I)
-        return w["down"].linear(act, residual=x)
+        """... of a verify step of M = B (k + 1) rows: no q|k|v bias (the plain streaming linear carries none here) and, by name,
+        no xIELU; infer places down_proj by itself."""
+        return self._can_fuse(x, M) and self.self_attn._bqkv is None and not self.xielu
 
     def forward(self, x, cos, sin, key_mask, B, S, cache=None, rows=None):
         """The training / generic route (CausalLM.forward has decided that the call is neither a decode step nor an MXFP8 prefill).
@@ -387,8 +371,13 @@ class DecoderLayer(nn.Module):
 
 
 class LayerKVCache:
-    """Contiguous per-layer KV cache [B, Smax, Hkv, D] for the decode loop of generate (model.py:581-638).  attend is the one
-    sequence every cache runs; a subclass overrides the small steps below it."""
+    """Contiguous per-layer KV cache [B, Smax, Hkv, D] for the decode loop of generate (model.py:581-638).  A cache answers three
+    things: how many positions it holds (positions), the attention of S new positions from an unroped fused projection (attend: the
+    prefill, and the steps of the generic route) and the attention of a decode or verify step (step).  A subclass changes where the
+    rows are kept and which decode attention reads them."""
+
+    stream_only = False      # whether ONE new position can be attended by the decode stream alone (else: where attn_decode takes it)
+    staged = False           # whether append_dst() is a staging row that store() moves into place
 
     def __init__(self, B, Smax, Hkv, D, dtype, device):
         self.k = torch.zeros((B, Smax, Hkv, D), dtype=dtype, device=device)
@@ -400,33 +389,25 @@ class LayerKVCache:
         return self.len
 
     def append_dst(self):
-        """(kcache, vcache, pos) of the decode step's append kernels: where the new token's k / v rows go."""
+        """(kcache, vcache, pos) of a decode step's append kernels: where the new token's k / v rows go.  None from a cache that
+        does not know the position on the host."""
         return self.k, self.v, self.len
-
-    def decode_attend(self, q, key_mask, scale):
-        """The row of position `len` has been written: count it and attend q [B, Hq, D] over the cache (split-K stream)."""
-        self.len += 1
-        return K.attn_decode(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, scale)
 
     def accept(self, B, S):
         """ValueError for a call of S new positions on B rows that this cache does not take."""
 
-    def streams(self, dtype, a: Attention):
-        """Whether ONE new position is attended by the decode stream (attend_row); attn_fwd otherwise."""
-        return K.attn_decode_supported(dtype, a.Hq, a.Hkv, a.D)
-
     def store(self, kn, vn, S):
-        """The S new k / v rows go behind the `len` held ones (device-side memory plumbing)."""
+        """The S new k / v rows go behind the `len` held ones (device-side memory plumbing) -> the keys and values attn_fwd reads
+        once they are counted."""
         self.k[:, self.len:self.len + S].copy_(kn)
         self.v[:, self.len:self.len + S].copy_(vn)
+        return self.k[:, : self.len + S], self.v[:, : self.len + S]
 
-    def attend_row(self, q, key_mask, scale):
-        """The one new row is stored: count it and attend q over the cache."""
-        return self.decode_attend(q, key_mask, scale)
-
-    def prefill_kv(self, kn, vn):
-        """The keys and values attn_fwd reads once the new rows are stored and counted."""
-        return self.k[:, : self.len], self.v[:, : self.len]
+    def decode_attend(self, q, key_mask, scale):
+        """The row of position `len` has been written and nothing has attended over it yet: count it and attend q [B, Hq, D] over
+        the cache (split-K stream)."""
+        self.len += 1
+        return K.attn_decode(q, self.k[:, : self.len], self.v[:, : self.len], key_mask, scale)
 
     @torch.no_grad()
     def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
@@ -435,11 +416,21 @@ class LayerKVCache:
         Hq, D = a.Hq, a.D
         self.accept(B, S)
         q, kn, vn = a.rope_views(qkv, cos, sin, B, S)
-        self.store(kn, vn, S)
-        if S == 1 and self.streams(qkv.dtype, a):      # decode step: stream the cache once (split-K)
-            return self.attend_row(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
+        kv = self.store(kn, vn, S)
+        if S == 1 and (self.stream_only or K.attn_decode_supported(qkv.dtype, Hq, a.Hkv, D)):      # stream the cache once (split-K)
+            return self.decode_attend(q.view(B, Hq, D), key_mask, D ** -0.5).view(B, Hq * D)
         self.len += S
-        return K.attn_fwd(q, *self.prefill_kv(kn, vn), key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
+        return K.attn_fwd(q, *kv, key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
+
+    def step(self, qkv, cos, sin, key_mask, B, S, a: Attention, appended):
+        """The fused projection of a decode step (S = 1; B <= 16 bf16 rows) -> its attention output [B, Hq D].  appended: the
+        projection's launch has roped q / k and written the new rows to append_dst() already; else that is one pass here
+        (rope_append_ / qk_norm_rope_append_)."""
+        if not appended:
+            a.rope_append_(qkv, B, cos, sin, *self.append_dst())
+        if self.staged:
+            self.store(self.k, self.v, 1)
+        return self.decode_attend(qkv[:, : a.Hq * a.D].view(B, a.Hq, a.D), key_mask, a.D ** -0.5).view(B, a.Hq * a.D)
 
 
 class LayerKVCacheMX8(LayerKVCache):
@@ -448,6 +439,9 @@ class LayerKVCacheMX8(LayerKVCache):
     A decode step's append kernels write the new row to the staging row (position 0) unchanged; mm_kv8_append quantises it into
     position `len` and mm_attn_decode_kv8 streams the buffer.  The prefill attends over the bf16 k / v of the prompt (its output is
     the bf16 cache's, bit for bit) and quantises them into the buffer in one pass; only later steps see quantised keys."""
+
+    stream_only = True
+    staged = True
 
     def __init__(self, B, Smax, Hkv, D, dtype, device):
         self.Smax, self.Hkv = Smax, Hkv
@@ -459,27 +453,18 @@ class LayerKVCacheMX8(LayerKVCache):
     def append_dst(self):
         return self.k, self.v, 0
 
-    def decode_attend(self, q, key_mask, scale):
-        self.store(self.k, self.v, 1)
-        return self.attend_row(q, key_mask, scale)
-
     def accept(self, B, S):
         if S > 1 and self.len:
             raise ValueError(f"{S} new positions on an MXFP8 KV cache that holds {self.len}: only a prefill into an empty cache or "
                              "one token per step (attending over the cached prompt would need a dequantising prefill)")
 
-    def streams(self, dtype, a: Attention):
-        return True
-
     def store(self, kn, vn, S):
         K.kv8_append(kn, vn, self.buf, self.Smax, self.len)
+        return kn, vn      # a prefill's cache was empty: the prompt's own bf16 rows
 
-    def attend_row(self, q, key_mask, scale):
+    def decode_attend(self, q, key_mask, scale):
         self.len += 1
         return K.attn_decode_kv8(q, self.buf, self.len, self.Smax, self.Hkv, key_mask, scale)
-
-    def prefill_kv(self, kn, vn):
-        return kn, vn      # the cache was empty: the prompt's own bf16 rows
 
 
 class LayerKVCacheShared(LayerKVCache):
@@ -489,6 +474,9 @@ class LayerKVCacheShared(LayerKVCache):
     the bits of a LayerKVCache of B n rows that holds the prompt n times).  The prefill is a call of B rows into the empty cache
     (the base class's steps: it writes the prefix); every later call brings ONE token for each of the B n rows, and its key_mask is
     the PROMPT's [B, len] (suffix keys are always visible)."""
+
+    stream_only = True
+    kind = "a shared-prefix cache"
 
     def __init__(self, B, n, Sp_max, max_new, Hkv, D, dtype, device):
         super().__init__(B, Sp_max, Hkv, D, dtype, device)
@@ -506,14 +494,19 @@ class LayerKVCacheShared(LayerKVCache):
             raise ValueError(f"the shared-prefix KV cache is full: {self.slen} generated tokens per sample row")
         return self.ks, self.vs, self.slen
 
+    def ancestors(self):
+        """The table through which the suffix keys are read: None, every row reads its own."""
+        return None
+
     def decode_attend(self, q, key_mask, scale):
         """The suffix row of position `slen` has been written for every sample: count it and attend q [B n, Hq, D]."""
         if key_mask is not None and tuple(key_mask.shape) != (self.B, self.len):
-            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a shared-prefix cache: the prompt's mask "
-                             f"[{self.B}, {self.len}] is expected (generated tokens are always visible)")
+            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on {self.kind}: the prompt's mask [{self.B}, {self.len}] is "
+                             "expected (generated tokens are always visible)")
+        anc = self.ancestors()
         self.slen += 1
         return K.attn_decode_shared(q, self.k[:, : self.len], self.v[:, : self.len], self.ks[:, : self.slen], self.vs[:, : self.slen],
-                                    self.n, key_mask, scale)
+                                    self.n, key_mask, scale, anc)
 
     def accept(self, B, S):
         if S > 1 and (self.len or B != self.B):
@@ -524,9 +517,6 @@ class LayerKVCacheShared(LayerKVCache):
                              "prompt positions")
         if S == 1:
             self.append_dst()      # raises when the suffix is full
-
-    def streams(self, dtype, a: Attention):
-        return True
 
     def store(self, kn, vn, S):
         if S > 1:
@@ -543,6 +533,8 @@ class LayerKVCacheBeam(LayerKVCacheShared):
     (an index_select over every layer's whole cache).  All layers share ONE table holder: the decode loop sets `tables.current` to
     the table mm_beam_step wrote for the coming step (K.BeamState.table) before it calls the decoder."""
 
+    kind = "a beam cache"
+
     class Tables:
         current = None           # int32 [>= slen, >= B n]
 
@@ -550,16 +542,11 @@ class LayerKVCacheBeam(LayerKVCacheShared):
         super().__init__(B, n, Sp_max, max_new, Hkv, D, dtype, device)
         self.tables = tables
 
-    def decode_attend(self, q, key_mask, scale):
-        if key_mask is not None and tuple(key_mask.shape) != (self.B, self.len):
-            raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a beam cache: the prompt's mask [{self.B}, {self.len}] is "
-                             "expected (generated tokens are always visible)")
+    def ancestors(self):
         anc = self.tables.current
         if anc is None or anc.shape[0] <= self.slen:
             raise ValueError(f"a step on a beam KV cache without an ancestor table of more than {self.slen} rows")
-        self.slen += 1
-        return K.attn_decode_beam(q, self.k[:, : self.len], self.v[:, : self.len], self.ks[:, : self.slen], self.vs[:, : self.slen],
-                                  self.n, key_mask, scale, anc)
+        return anc
 
 
 class LayerKVCacheLookup(LayerKVCache):
@@ -579,17 +566,29 @@ class LayerKVCacheLookup(LayerKVCache):
         super().__init__(B, Smax, Hkv, D, dtype, device)
         self.shared = shared
 
-    def verify_attend(self, qkv, B, Q, Hq, Hkv, D, key_mask, scale):
-        """The roped fused projection qkv [B Q, (Hq + 2 Hkv) D] of a verify step: append its k / v rows, attend its q rows."""
+    def append_dst(self):
+        """The empty cache's: every row stands at 0 (a one-token prompt's prefill is an ordinary decode step).  Afterwards None: the
+        rows stand at base[b], on the device."""
+        return None if self.len else super().append_dst()
+
+    def step(self, qkv, cos, sin, key_mask, B, Q, a: Attention, appended):
+        """The unroped fused projection qkv [B Q, (Hq + 2 Hkv) D] of a verify step, Q = k + 1 positions for each of B sequences:
+        the in-place RoPE (rope_apply_ / qk_norm_rope_fwd), the append of the Q new k / v rows, the Q-position decode attention
+        over one read of the keys -> [B Q, Hq D].  Into the empty cache (Q = 1): the base class's decode step."""
+        if not self.len:
+            return super().step(qkv, cos, sin, key_mask, B, Q, a, appended)
+        Hq, Hkv, D = a.Hq, a.Hkv, a.D
         sh = self.shared
-        if sh.base is None or not self.len:
+        if sh.base is None:
             raise ValueError("a verify step on a prompt-lookup KV cache without a prefill or without its base positions")
         if key_mask is not None and tuple(key_mask.shape) != (B, self.len):
             raise ValueError(f"key_mask of shape {tuple(key_mask.shape)} on a prompt-lookup cache: the prompt's mask [{B}, {self.len}] is "
                              "expected (generated tokens are visible up to each query's own position)")
+        a.rope_views(qkv, cos, sin, B, Q)
         K.lookup_append(qkv, B, Q, Hq, Hkv, D, sh.base, self.k, self.v)
         Scap = min(self.k.shape[1], max(int(sh.bound), self.len) + Q)
-        return K.attn_decode_verify(qkv[:, : Hq * D].view(B * Q, Hq, D), self.k[:, :Scap], self.v[:, :Scap], Q, key_mask, sh.base, scale)
+        return K.attn_decode_verify(qkv[:, : Hq * D].view(B * Q, Hq, D), self.k[:, :Scap], self.v[:, :Scap], Q, key_mask, sh.base,
+                                    D ** -0.5).view(B * Q, Hq * D)
 
 
 class DecoderModel(nn.Module):
@@ -610,6 +609,23 @@ class CausalLMOutput:
 
     def __getitem__(self, k):
         return getattr(self, k) if isinstance(k, str) else (self.loss, self.logits, self.past_key_values)[k]
+
+
+def _int_arg(name, v, lo, hi=None):
+    """new_cache's "int in range, not bool" check; -> v"""
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} must be an int {f'>= {lo}' if hi is None else f'in [{lo}, {hi}]'}, got {v!r}")
+    return v
+
+
+# new_cache's modes in the order they are looked at: (argument, its largest value, the arguments it cannot be combined with, the refusal)
+_CACHE_MODES = (
+    ("lookup", None, ("kv_cache", "samples", "beams"),
+     "lookup={lookup} with kv_cache={kv_cache!r}, samples={samples!r}, beams={beams!r}: the prompt-lookup cache is bf16 only, one row per sequence"),
+    ("beams", 16, ("kv_cache", "samples"),
+     "beams={beams} with kv_cache={kv_cache!r}, samples={samples!r}: the beam cache is bf16 only and its rows are the beams"),
+    ("samples", None, ("kv_cache",), "samples={samples} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only"),
+)
 
 
 class CausalLM(nn.Module):
@@ -827,40 +843,36 @@ class CausalLM(nn.Module):
         may write behind the last emitted id), every layer holding the SAME `shared` object (its base / bound are the decode loop's to
         set); ValueError when lookup_ok says it cannot, or together with kv_cache, samples or beams."""
         c = self.config
-        if lookup is not None:
-            if isinstance(lookup, bool) or not isinstance(lookup, int) or lookup < 1:
-                raise ValueError(f"lookup must be an int >= 1, got {lookup!r}")
-            if kv_cache is not None or samples != 1 or beams != 1:
-                raise ValueError(f"lookup={lookup} with kv_cache={kv_cache!r}, samples={samples!r}, beams={beams!r}: the prompt-lookup cache is "
-                                 "bf16 only, one row per sequence")
-            self.check_option("lookup", lookup, B, lookup)
+        val = dict(lookup=lookup, beams=beams, samples=samples, kv_cache=kv_cache)
+        on = dict(lookup=lookup is not None, beams=beams != 1, samples=samples != 1, kv_cache=kv_cache is not None)
+        shape = (c.num_key_value_heads, c.head_dim, self.dtype, self.device)
+        if not on["lookup"]:
+            self.check_option("kv_cache", kv_cache, B)
+        mode = None
+        for name, hi, excludes, text in _CACHE_MODES:
+            if name == "lookup" and lookup is None:          # the one mode that is off as None: no integer to check
+                continue
+            n = _int_arg(name, val[name], 1, hi)
+            if on[name]:
+                if any(on[other] for other in excludes):
+                    raise ValueError(text.format(**val))
+                self.check_option(name, n, B, n)
+                mode = name
+                break
+        layers = range(c.num_hidden_layers)
+        if mode is None:
+            cls = LayerKVCache if kv_cache is None else LayerKVCacheMX8
+            return [cls(B, Smax, *shape) for _ in layers]
+        if mode == "lookup":
             shared = LayerKVCacheLookup.Shared()
-            return [LayerKVCacheLookup(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device, shared)
-                    for _ in range(c.num_hidden_layers)]
-        self.check_option("kv_cache", kv_cache, B)
-        if isinstance(beams, bool) or not isinstance(beams, int) or not 1 <= beams <= 16:
-            raise ValueError(f"beams must be an int in [1, 16], got {beams!r}")
-        if beams > 1:
-            if kv_cache is not None or samples != 1:
-                raise ValueError(f"beams={beams} with kv_cache={kv_cache!r}, samples={samples!r}: the beam cache is bf16 only and its rows are the beams")
-            self.check_option("beams", beams, B, beams)
-            if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
-                raise ValueError(f"beams={beams} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
-            tables = LayerKVCacheBeam.Tables()
-            return [LayerKVCacheBeam(B, beams, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
-                                     self.device, tables) for _ in range(c.num_hidden_layers)]
-        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
-            raise ValueError(f"samples must be an int >= 1, got {samples!r}")
-        if samples > 1:
-            if kv_cache is not None:
-                raise ValueError(f"samples={samples} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only")
-            self.check_option("samples", samples, B, samples)
-            if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
-                raise ValueError(f"samples={samples} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
-            return [LayerKVCacheShared(B, samples, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
-                                       self.device) for _ in range(c.num_hidden_layers)]
-        cls = LayerKVCache if kv_cache is None else LayerKVCacheMX8
-        return [cls(B, Smax, c.num_key_value_heads, c.head_dim, self.dtype, self.device) for _ in range(c.num_hidden_layers)]
+            return [LayerKVCacheLookup(B, Smax, *shape, shared) for _ in layers]
+        if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
+            raise ValueError(f"{mode}={n} needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
+        Sp = int(prompt_len)
+        if mode == "samples":
+            return [LayerKVCacheShared(B, n, Sp, Smax - Sp, *shape) for _ in layers]
+        tables = LayerKVCacheBeam.Tables()
+        return [LayerKVCacheBeam(B, n, Sp, Smax - Sp, *shape, tables) for _ in layers]
 
     def forward(self, input_ids=None, inputs_embeds=None, attention_mask=None, position_ids=None,
                 past_key_values=None, labels=None, use_cache=None, return_dict=True, logits_to_keep: int = 0,
@@ -906,42 +918,30 @@ class CausalLM(nn.Module):
         if not x.is_contiguous():
             x = x.contiguous()
         layers = self.model.layers
-        # the route of the call, decided once: "fused" / "step" (a decode step: one new token per sequence over a cache, every layer
-        # takes decode_step_fused / infer), "prefill" (the MXFP8 prefill: every layer takes infer), "verify" (a prompt-lookup verify
-        # step: S = k + 1 positions per sequence over a prefilled LayerKVCacheLookup, every layer takes verify_step) or None
-        # (training and everything else: every layer takes forward)
-        route = None
-        verify_fused = False
-        if cache and len(layers) and isinstance(cache[0], LayerKVCacheLookup) and past:
+        # the plan of the call, decided once.  A step (every layer takes infer): one new token per sequence over a cache, or S = k + 1
+        # positions per sequence over a prefilled LayerKVCacheLookup (a prompt-lookup verify step); fused where every layer can fold
+        # its norms and SwiGLU into the weight-streaming launches.  The MXFP8 prefill (every layer takes infer).  None: training and
+        # everything else (every layer takes forward)
+        plan = None
+        verify = bool(cache and len(layers) and isinstance(cache[0], LayerKVCacheLookup) and past)
+        if verify:
             if x.dtype != torch.bfloat16 or torch.is_grad_enabled() or B * S > 16:
                 raise ValueError(f"a verify step of {B} x {S} {x.dtype} rows on a prompt-lookup cache: bf16, at most 16 rows, no autograd")
-            route = "verify"
-            verify_fused = all(layer.can_verify_fused(x, B * S) for layer in layers)
+            plan = Plan("step", all(layer.can_verify_fused(x, B * S) for layer in layers))
         elif cache and len(layers):
             if all(layer.can_decode_step_fused(x, B, S, c) for layer, c in zip(layers, cache)):
-                route = "fused"
+                plan = Plan("step", True)
             elif all(layer.can_decode_step(x, B, S, c) for layer, c in zip(layers, cache)):
-                route = "step"
-        w = self._decode_w8 if route and decode_weights is not None else self._w16      # decode steps alone read decode_weights
-        if prefill_weights is not None and not route and len(layers):
+                plan = Plan("step", False)
+        w = self._decode_w8 if plan and decode_weights is not None else self._w16      # steps alone read decode_weights
+        if prefill_weights is not None and not plan and len(layers):
             self.check_option("prefill_weights", prefill_weights, B, S)
             if self._decode_w8 is None or self._decode_w8["fmt"] != prefill_weights:
                 self.quantize_decode_weights(prefill_weights)
-            route, w, rows = "prefill", self._decode_w8, None
-        fused_head = False
-        if route == "fused":
-            # every RMSNorm is applied by the projection that consumes it (DecoderLayer.decode_step_fused), the final norm by
-            # lm_head below
-            for layer, lw, c in zip(layers, w["layers"], cache):
-                x = layer.decode_step_fused(lw, x, cos, sin, key_mask, B, c)
-            fused_head = self.lm_head.bias is None and self.model.norm.bias is None       # S == 1: logits_to_keep keeps the one row
-        elif route == "verify":
-            for layer, lw, c in zip(layers, w["layers"], cache):
-                x = layer.verify_step(lw, x, cos, sin, key_mask, B, S, c, verify_fused)
-            fused_head = verify_fused and self.lm_head.bias is None and self.model.norm.bias is None and not logits_to_keep
-        elif route:
+            plan, w, rows = Plan("prefill", False), self._decode_w8, None
+        if plan:
             for i, layer in enumerate(layers):
-                x = layer.infer(w["layers"][i], x, cos, sin, key_mask, B, S, cache[i] if cache else None, step=route == "step")
+                x = layer.infer(w["layers"][i], x, cos, sin, key_mask, B, S, cache[i] if cache else None, plan)
         else:
             # training step (Trainer.compute_loss hands over `loss_rows`): the loss and every gradient depend only on the rows whose
             # shifted label is not -100 (HF:loss/loss_utils.py:36-71 ignores the others; their dlogits are exactly zero), so the
@@ -952,6 +952,10 @@ class CausalLM(nn.Module):
                 x = layer(x, cos, sin, key_mask, B, S, cache=cache[i] if cache else None, rows=rows if i == last else None)
             if rows is not None and not len(layers):
                 x = Fm.rows_select(x, rows)
+        # on a fused step every RMSNorm is applied by the projection that consumes it, the final norm by lm_head -- when lm_head
+        # sees the rows the layers returned (a decode step's one position per sequence, or every position of a verify step)
+        fused_head = (bool(plan) and plan.fused and not (verify and logits_to_keep)
+                      and self.lm_head.bias is None and self.model.norm.bias is None)
         if not fused_head:
             x, _ = self.model.norm(x)
         V = self.config.vocab_size
@@ -960,9 +964,10 @@ class CausalLM(nn.Module):
             Sk = logits_to_keep
         else:
             Sk = S
-        head = (w["lm_head"] or self._w16["lm_head"]) if route in ("fused", "step", "verify") else None
+        # a step reads lm_head's copy when decode_weights made one; everything else the module (autograd, bf16 weights)
+        head = (w["lm_head"] or self._w16["lm_head"]) if plan and plan.rows == "step" else None
         if fused_head:
-            logits2d = head.stream(x, norm_w=self.model.norm.weight, eps=self.model.norm.eps, ldc_pad=True)
+            logits2d = head.stream(x, None, self.model.norm.weight, self.model.norm.eps, True)
         elif head is not None:                                   # a decode step: lm_head's copy, when decode_weights made one
             logits2d = head.linear(x, ldc_pad=True)
         else:

@@ -11,7 +11,9 @@ collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 
 `python tools/make_golden.py gemm_plan` is a mode apart: it rewrites tests/golden/gemm_plan.jsonl (the GEMM launch decisions) from
 the built library and needs neither the reference nor a GPU (gemm_plan_table below).  `python tools/make_golden.py generate_launches`
-is another: it records generate()'s launches on a GPU into tests/golden/generate_launches.jsonl (generate_launches_table below).
+is another: it records generate()'s launches on a GPU into tests/golden/generate_launches.jsonl (generate_launches_table below);
+`python tools/make_golden.py decoder_routes` records the decoder's launches per inference route, without a GPU, into
+tests/golden/decoder_routes.jsonl (decoder_routes_table below).
 
 Import recipe = SURVEY.md Appendix A (three harness-side shims, none edits the reference).
 The numbers pin the semantics of transformers==5.15.0 CLIP / Llama / Qwen2 / Qwen3 / Apertus modules as called
@@ -71,11 +73,28 @@ def generate_launches_table():
     print(f"generate_launches: {len(rows)} cases, {sum(len(n) for _, n in rows)} launches")
 
 
+def decoder_routes_table():
+    """`make_golden.py decoder_routes`: write tests/golden/decoder_routes.jsonl, the C symbols CausalLM.forward queues on every
+    inference route (tests/decoder_routes.py holds the cases and the recorder; tests/test_decoder_routes_cpu.py replays them).  Needs
+    the built library, neither a GPU nor the reference.  As generate_launches: run it on the revision whose routes are the contract
+    and commit the file as recorded."""
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    sys.path.insert(0, root)
+    from tests import decoder_routes as T
+    rows = T.record()
+    T.write(rows, os.path.join(root, "tests", "golden"))
+    n = sum(len(v) for _, r in rows for v in r.values() if isinstance(v, list))
+    print(f"decoder_routes: {len(rows)} cases, {n} launches, {sum(isinstance(v, str) for _, r in rows for v in r.values())} refusals")
+
+
 if sys.argv[1:] == ["gemm_plan"]:
     gemm_plan_table()
     sys.exit(0)
 if sys.argv[1:] == ["generate_launches"]:
     generate_launches_table()
+    sys.exit(0)
+if sys.argv[1:] == ["decoder_routes"]:
+    decoder_routes_table()
     sys.exit(0)
 
 import numpy as np
