@@ -7,12 +7,13 @@ step, accumulate afterwards) instead of being returned to autograd: no extra pas
 trainer can point `.grad` at its flat all-reduce buckets.  See `grad_target`."""
 from __future__ import annotations
 
+import weakref
 from typing import Callable, Optional
 
 import torch
 
 from . import kernels as K
-from ._lib import EPI_GELU_ERF, EPI_QUICK_GELU, GELU_KIND  # noqa: F401
+from ._lib import EPI_GELU_ERF, EPI_QUICK_GELU, GELU_KIND, get_option, lib  # noqa: F401
 
 # called as hook(param) right after a parameter's gradient for this step is complete (DP bucket scheduling)
 _grad_ready_hook: Optional[Callable] = None
@@ -54,7 +55,6 @@ _defer = None
 def set_wgrad_deferral(stream, params):
     """stream: side HIP stream for the deferred GEMMs; params: the first Parameter of every deferred group (held weakly).
     stream=None disables."""
-    import weakref
     global _defer
     _defer = None if stream is None else {"stream": stream, "params": {id(p): weakref.ref(p) for p in params}, "items": [],
                                           "event": None}
@@ -65,16 +65,49 @@ def _is_deferred(p):
     return r is not None and r() is p        # the weak reference guards against id() reuse by a later model
 
 
+def _target(p):
+    return p.grad_target() if isinstance(p, ParamGroup) else grad_target(p)
+
+
+def _announce(p):
+    p.ready() if isinstance(p, ParamGroup) else _ready(p)
+
+
+def _write_grads(kernel, args, p, q=None):
+    """THE gradient write, of one Parameter / ParamGroup p or of the two (p, q) that one launch writes (a LayerNorm's weight and bias,
+    xIELU's scalars).  Nothing happens unless all of them train; else kernel(*args, buffer(s)..., accumulate flag(s)...) on their
+    grad_target, then the ready hooks.  -> whether the launch ran.  The kernel and its leading arguments travel apart so that a call
+    site on the ViT's backward (some 700 short launches) builds no closure."""
+    if not (p.requires_grad and (q is None or q.requires_grad)):
+        return False
+    group = isinstance(p, ParamGroup)               # spelled out for p, the common case: two calls fewer per write
+    g, acc = p.grad_target() if group else grad_target(p)
+    if q is None:
+        kernel(*args, g, acc)
+    else:
+        g2, acc2 = _target(q)
+        kernel(*args, g, g2, acc, acc2)
+    p.ready() if group else _ready(p)
+    if q is not None:
+        _announce(q)
+    return True
+
+
 def _wgrad(dy, x, wg):
     """The weight-gradient GEMM of one parameter group: now on this stream, or held back."""
-    if not wg.requires_grad:
-        return
-    if _is_deferred(wg.params[0]):
+    if wg.requires_grad and _is_deferred(wg.params[0]):
         _defer["items"].append((dy, x, wg))
         return
-    g, acc = wg.grad_target()
-    K.linear_wgrad(dy, x, g, acc)
-    wg.ready()
+    _write_grads(K.linear_wgrad, (dy, x), wg)
+
+
+def _proj_backward(dy, x, wg, bg, need_dx):
+    """THE backward of y = x @ W^T + b, in this order: the bias gradient (column sums of dy), the weight gradient (`_wgrad`: skipped
+    for a frozen group, held back for a deferred one), then dx if the input needs one."""
+    if bg is not None:
+        _write_grads(K.colsum, (dy,), bg)
+    _wgrad(dy, x, wg)
+    return K.linear_dgrad(dy, wg.tensor()) if need_dx else None
 
 
 def flush_deferred_wgrads():
@@ -84,7 +117,6 @@ def flush_deferred_wgrads():
     if d is None:
         return None
     if d["items"]:
-        from ._lib import get_option, lib
         main, side = torch.cuda.current_stream(), d["stream"]
         side.wait_stream(main)
         persist = get_option("gemm_persist")         # restore what the trainer / the user had set, not a constant
@@ -94,9 +126,7 @@ def flush_deferred_wgrads():
                 for dy, x, wg in d["items"]:
                     dy.record_stream(side)
                     x.record_stream(side)
-                    g, acc = wg.grad_target()
-                    K.linear_wgrad(dy, x, g, acc)
-                    wg.ready()
+                    _write_grads(K.linear_wgrad, (dy, x), wg)
                 ev = torch.cuda.Event()
                 ev.record(side)
         finally:
@@ -139,7 +169,10 @@ class ParamGroup:
 
     @property
     def requires_grad(self):
-        return any(p.requires_grad for p in self.params)
+        for p in self.params:           # a loop, not any(...): asked on every launch of a backward that the host bounds
+            if p.requires_grad:
+                return True
+        return False
 
     def grad_target(self):
         tg = [grad_target(p) for p in self.params]
@@ -152,8 +185,9 @@ class ParamGroup:
         return g, accs.pop()
 
     def ready(self):
-        for p in self.params:
-            _ready(p)
+        if _grad_ready_hook is not None:
+            for p in self.params:
+                _grad_ready_hook(p)
 
 
 def as_group(p):
@@ -161,6 +195,26 @@ def as_group(p):
 
 
 # --------------------------------------------------------------------------------------------------- linear
+def _gemm_rows(dy):
+    """dy as a GEMM operand: unit last stride, row stride a multiple of 8 elements; a copy only if it is not one already"""
+    return dy.contiguous() if dy.stride(-1) != 1 or (dy.stride(0) % 8) else dy
+
+
+def _linear_forward(fwd, act_fwd, x, w, b, residual, act, keep_pre, *ldc_pad):
+    """-> (pre, y) of y = act(x @ W^T + b) + residual, for LinearFn (fwd, act_fwd = K.linear_fwd, K.linear_act_fwd) and GroupedLinearFn
+    (their _batched forms, w and b lists): the two differ in nothing else.  An activation whose node someone needs a gradient from
+    keeps its pre-activation: act_fwd writes it AND y in one launch where the shape qualifies (None otherwise), else the projection +
+    bias alone, the GELU and the add are three launches.  Everything else is one GEMM with its epilogue, pre = None."""
+    if not keep_pre:
+        return None, fwd(x, w, b, residual, act, *ldc_pad)
+    both = act_fwd(x, w, b, act, residual)
+    if both is not None:
+        return both
+    pre = fwd(x, w, b)
+    y = K.gelu_fwd(pre, GELU_KIND[act])
+    return pre, (K.add(y, residual) if residual is not None else y)
+
+
 class LinearFn(torch.autograd.Function):
     """y = act(x @ W^T + b) + residual.  x, y 2-D.  W/b are ParamGroups (not autograd inputs); `dummy` is a
     requires-grad scalar that keeps the node in the graph when only the weights need gradients."""
@@ -169,18 +223,7 @@ class LinearFn(torch.autograd.Function):
     def forward(ctx, x, residual, dummy, wg: ParamGroup, bg: Optional[ParamGroup], act: int, ldc_pad: bool):
         w = wg.tensor()
         b = bg.tensor() if bg is not None else None
-        pre = None
-        if act and (x.requires_grad or wg.requires_grad):
-            fused = K.linear_act_fwd(x, w, b, act, residual)      # one launch: the epilogue writes the pre-activation AND the output
-            if fused is not None:
-                pre, y = fused
-            else:
-                pre = K.linear_fwd(x, w, bias=b)                  # keep the pre-activation for backward
-                y = K.gelu_fwd(pre, GELU_KIND[act])
-                if residual is not None:
-                    y = K.add(y, residual)
-        else:
-            y = K.linear_fwd(x, w, bias=b, residual=residual, act=act, ldc_pad=ldc_pad)
+        pre, y = _linear_forward(K.linear_fwd, K.linear_act_fwd, x, w, b, residual, act, act and (x.requires_grad or wg.requires_grad), ldc_pad)
         ctx.wg, ctx.bg, ctx.act = wg, bg, act
         ctx.has_res = residual is not None
         ctx.save_for_backward(x, pre)
@@ -189,19 +232,11 @@ class LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, pre = ctx.saved_tensors
-        wg, bg = ctx.wg, ctx.bg
-        if dy.stride(-1) != 1 or (dy.stride(0) % 8):
-            dy = dy.contiguous()
+        dy = _gemm_rows(dy)                       # a copy only when the strides ask for one (GroupedLinearFn: always)
         dres = dy if ctx.has_res else None
         if ctx.act:
             dy = K.gelu_bwd(pre, dy, GELU_KIND[ctx.act])
-        if bg is not None and bg.requires_grad:
-            g, acc = bg.grad_target()
-            K.colsum(dy, g, acc)
-            bg.ready()
-        _wgrad(dy, x, wg)
-        dx = K.linear_dgrad(dy, wg.tensor()) if ctx.needs_input_grad[0] else None
-        return dx, dres, None, None, None, None, None
+        return _proj_backward(dy, x, ctx.wg, ctx.bg, ctx.needs_input_grad[0]), dres, None, None, None, None, None
 
 
 def linear(x, wg, bg=None, residual=None, act=0, ldc_pad=False, dummy=None):
@@ -209,6 +244,11 @@ def linear(x, wg, bg=None, residual=None, act=0, ldc_pad=False, dummy=None):
 
 
 # --------------------------------------------------------------------------------------------------- norms
+def _reduce_into(p, partials):
+    """the gradient of a norm weight / bias p from its backward kernel's per-workgroup partial sums"""
+    _write_grads(K.reduce_partials, (partials,), p)
+
+
 class RMSNormFn(torch.autograd.Function):
     """-> (y, x_res): x_res aliases x and is what the caller feeds to the residual add, so the gradient of the residual
     branch arrives HERE and is added inside the norm-backward kernel (no separate autograd accumulation pass)."""
@@ -227,10 +267,7 @@ class RMSNormFn(torch.autograd.Function):
         if dy is None:
             return dres, None, None, None
         dx, dwp = K.rmsnorm_bwd(dy.contiguous(), x, w.data, rstd, dres.contiguous() if dres is not None else None)
-        if w.requires_grad:
-            g, acc = grad_target(w)
-            K.reduce_partials(dwp, g, acc)
-            _ready(w)
+        _reduce_into(w, dwp)
         return dx, None, None, None
 
 
@@ -253,20 +290,10 @@ class LayerNormFn(torch.autograd.Function):
         if dy is None:
             return dres, None, None, None, None
         dx, dwp, dbp = K.layernorm_bwd(dy.contiguous(), x, w.data, mean, rstd, dres.contiguous() if dres is not None else None)
-        if w.requires_grad and b.requires_grad:          # dw and db in one launch
-            (gw, aw), (gb, ab) = grad_target(w), grad_target(b)
-            K.reduce_partials2(dwp, dbp, gw, gb, aw, ab)
-            _ready(w)
-            _ready(b)
-            return dx, None, None, None, None
-        if w.requires_grad:
-            g, acc = grad_target(w)
-            K.reduce_partials(dwp, g, acc)
-            _ready(w)
-        if b.requires_grad:
-            g, acc = grad_target(b)
-            K.reduce_partials(dbp, g, acc)
-            _ready(b)
+        # dw and db in one launch when both train, else one reduction for the one that does
+        if not _write_grads(K.reduce_partials2, (dwp, dbp), w, b):
+            _reduce_into(w, dwp)
+            _reduce_into(b, dbp)
         return dx, None, None, None, None
 
 
@@ -288,11 +315,7 @@ def _grouped_grad_write(slots, batched, single, partly=None):
     E = len(slots[0])
 
     def single_if_live(e):
-        if all(s[e].requires_grad for s in slots):
-            tg = [s[e].grad_target() for s in slots]
-            single(e, *[t for t, _ in tg], *[a for _, a in tg])
-            for s in slots:
-                s[e].ready()
+        _write_grads(single, (e,), *[s[e] for s in slots])
 
     if not all(g.requires_grad for s in slots for g in s):
         for e in range(E):
@@ -317,18 +340,8 @@ class GroupedLinearFn(torch.autograd.Function):
     def forward(ctx, x, residual, dummy, wgs, bgs, act: int):
         ws = [wg.tensor() for wg in wgs]
         bs = [bg.tensor() for bg in bgs] if bgs is not None else None
-        pre = None
-        if act and (x.requires_grad or any(wg.requires_grad for wg in wgs)):
-            fused = K.linear_act_fwd_batched(x, ws, bs, act, residual)
-            if fused is not None:
-                pre, y = fused
-            else:
-                pre = K.linear_fwd_batched(x, ws, biases=bs)
-                y = K.gelu_fwd(pre, GELU_KIND[act])
-                if residual is not None:
-                    y = K.add(y, residual)
-        else:
-            y = K.linear_fwd_batched(x, ws, biases=bs, residual=residual, act=act)
+        pre, y = _linear_forward(K.linear_fwd_batched, K.linear_act_fwd_batched, x, ws, bs, residual, act,
+                                 act and (x.requires_grad or any(wg.requires_grad for wg in wgs)))
         ctx.wgs, ctx.bgs, ctx.act = wgs, bgs, act
         ctx.has_res = residual is not None
         ctx.save_for_backward(x, pre)
@@ -339,7 +352,7 @@ class GroupedLinearFn(torch.autograd.Function):
         x, pre = ctx.saved_tensors
         wgs, bgs = ctx.wgs, ctx.bgs
         E = len(wgs)
-        dy = dy.contiguous()
+        dy = dy.contiguous()                      # unconditionally, where LinearFn (_gemm_rows) copies only when the strides require it
         dres = dy if ctx.has_res else None
         if ctx.act:
             dy = K.gelu_bwd(pre, dy, GELU_KIND[ctx.act])
@@ -380,12 +393,9 @@ class GroupedLayerNormFn(torch.autograd.Function):
         nb = dwp.shape[0] // E
         blocks = [slice(e * nb, (e + 1) * nb) for e in range(E)]
 
-        def partly(e):                                   # partly frozen norms: what LayerNormFn does, per expert
-            for p, part in ((ws[e], dwp), (bs[e], dbp)):
-                if p.requires_grad:
-                    g, acc = grad_target(p)
-                    K.reduce_partials(part[blocks[e]], g, acc)
-                    _ready(p)
+        def partly(e):                                   # some norm is partly frozen: one reduction per trainable parameter
+            _reduce_into(ws[e], dwp[blocks[e]])
+            _reduce_into(bs[e], dbp[blocks[e]])
 
         _grouped_grad_write([ws, bs], lambda gw, gb, aw, ab: K.reduce_partials2_batched(dwp, dbp, gw, gb, aw, ab),
                             lambda e, gw, gb, aw, ab: K.reduce_partials2(dwp[blocks[e]], dbp[blocks[e]], gw, gb, aw, ab), partly)
@@ -397,41 +407,71 @@ def grouped_layernorm(x, ws, bs, eps, dummy=None):
 
 
 # --------------------------------------------------------------------------------------------------- attention
+def qkv_views(buf, B, S, Hq, Hkv, D, v_of=None):
+    """THE q|k|v split: the q, k, v views [B, S, heads, D] of a fused projection output [T, (Hq+2Hkv)*D] (or of its gradient).
+    v_of: the fused buffer v is taken from when buf holds q|k alone (Qwen3's normed, roped copy `qk`, and its gradient)."""
+    v = buf if v_of is None else v_of
+    return (buf[:, : Hq * D].view(B, S, Hq, D), buf[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
+            v[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
+
+
+def _attn_grad_like(t, atomics=True):
+    """the buffer an attention backward writes the gradient of t into: the fp32 flash backward accumulates with atomics and needs zeros"""
+    return torch.zeros_like(t) if atomics and t.dtype == torch.float32 else torch.empty_like(t)
+
+
+def _rope_attention_forward(qkv, cos, sin, key_mask, dims, roped=False, qkn=None):
+    """The RoPE stage, then flash attention, on a fused projection output qkv -> (out, lse, qk, rstd).  The stage is one of: nothing
+    (cos is None, or `roped`: the projection's epilogue did it), RoPE of the q|k heads in place, or -- qkn = (q_norm weight, k_norm
+    weight, eps), Qwen3 -- per-head RMSNorm + RoPE of q|k into a separate buffer qk (the raw values stay in qkv for backward, v is read
+    where it is) with the norms' rstd; qk and rstd are None otherwise."""
+    B, S, Hq, Hkv, D, causal, scale = dims
+    qk = rstd = None
+    if qkn is not None:
+        assert cos is not None, "the q/k norm path always applies RoPE"
+        qk, rstd = K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, qkn[0].data, qkn[1].data, qkn[2], cos, sin)
+    elif cos is not None and not roped:
+        K.rope_apply_(qkv, B * S, Hq + Hkv, D, (Hq + 2 * Hkv) * D, cos, sin)
+    out, lse = K.attn_fwd(*qkv_views(qkv if qk is None else qk, B, S, Hq, Hkv, D, v_of=qkv), key_mask, causal, scale)
+    return out, lse, qk, rstd
+
+
+def _rope_attention_backward(dout, qkv, out, lse, cos, sin, key_mask, dims, qkn=None, qk=None, rstd=None):
+    """-> dqkv, the gradient of the fused projection output: attention backward, then the RoPE stage's.  Plain: d(q|k) lands in dqkv
+    beside dv and is un-roped in place.  qkn = (q_norm weight, k_norm weight) (Qwen3): d(q|k) lands in dqk (qk's strides),
+    mm_qk_norm_rope_bwd fills the q|k columns of dqkv from it, and the norm weights' gradients are written."""
+    B, S, Hq, Hkv, D, causal, scale = dims
+    dqkv = _attn_grad_like(qkv)
+    dqk = dqkv if qk is None else _attn_grad_like(qk)
+    K.attn_bwd(*qkv_views(qkv if qk is None else qk, B, S, Hq, Hkv, D, v_of=qkv), out, dout.contiguous().view(B, S, Hq, D), lse, key_mask,
+               causal, scale, *qkv_views(dqk, B, S, Hq, Hkv, D, v_of=dqkv))
+    if qkn is not None:
+        qn, kn = qkn
+        dwq, dwk = K.qk_norm_rope_bwd(dqk, qkv, B * S, Hq, Hkv, D, qn.data, kn.data, rstd, cos, sin, dqkv,
+                                      want_dw=qn.requires_grad or kn.requires_grad)
+        _reduce_into(qn, dwq)
+        _reduce_into(kn, dwk)
+    elif cos is not None:
+        K.rope_apply_(dqkv, B * S, Hq + Hkv, D, (Hq + 2 * Hkv) * D, cos, sin, inverse=True)
+    return dqkv
+
+
 class RopeAttentionFn(torch.autograd.Function):
     """qkv [T, (Hq+2Hkv)*D] (fused projection output, consumed in place) -> out [T, Hq*D].
-    RoPE (optional) is applied in place to the q and k heads, then flash attention.  Returns roped k/v views via
-    ctx-free attributes for KV caching (see `attention`)."""
+    RoPE (optional) is applied in place to the q and k heads, then flash attention."""
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale):
-        W = (Hq + 2 * Hkv) * D
-        assert qkv.shape == (B * S, W) and qkv.is_contiguous()
-        if cos is not None:
-            K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
-        q = qkv[:, : Hq * D].view(B, S, Hq, D)
-        k = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        out, lse = K.attn_fwd(q, k, v, key_mask, causal, scale)
+        assert qkv.shape == (B * S, (Hq + 2 * Hkv) * D) and qkv.is_contiguous()
         ctx.dims = (B, S, Hq, Hkv, D, causal, scale)
+        out, lse, _, _ = _rope_attention_forward(qkv, cos, sin, key_mask, ctx.dims)
         ctx.save_for_backward(qkv, out, lse, cos, sin, key_mask)
         return out.view(B * S, Hq * D)
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, cos, sin, key_mask = ctx.saved_tensors
-        B, S, Hq, Hkv, D, causal, scale = ctx.dims
-        W = (Hq + 2 * Hkv) * D
-        q = qkv[:, : Hq * D].view(B, S, Hq, D)
-        k = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        dqkv = torch.zeros_like(qkv) if qkv.dtype == torch.float32 else torch.empty_like(qkv)
-        dq = dqkv[:, : Hq * D].view(B, S, Hq, D)
-        dk = dqkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        dv = dqkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        K.attn_bwd(q, k, v, out, dout.contiguous().view(B, S, Hq, D), lse, key_mask, causal, scale, dq, dk, dv)
-        if cos is not None:
-            K.rope_apply_(dqkv, B * S, Hq + Hkv, D, W, cos, sin, inverse=True)
-        return (dqkv,) + (None,) * 10
+        return (_rope_attention_backward(dout, qkv, out, lse, cos, sin, key_mask, ctx.dims),) + (None,) * 10
 
 
 def rope_attention(qkv, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale):
@@ -439,109 +479,30 @@ def rope_attention(qkv, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale):
 
 
 class QKVRopeAttentionFn(torch.autograd.Function):
-    """The decoder's attention front half as ONE node: fused q|k|v projection with RoPE in its epilogue (mm_gemm_rope_fwd; the
-    projection + mm_rope_apply when a shape does not qualify: same bits), then flash attention.  h [T, H] -> out [T, Hq*D].
-    Backward = attention backward, inverse RoPE on d(q|k) in place, then the projection's wgrad / bias / dgrad (LinearFn's).
-
-    qkn = (q_norm weight, k_norm weight, eps) (Qwen3): the projection (never the RoPE epilogue), then the per-head RMSNorm + RoPE of
-    q|k into a separate buffer `qk` (the raw values stay in qkv for backward, v is read where it is), then attention on q / k of qk
-    and v of qkv.  Backward: attention writes d(q|k) into dqk (qk's strides) and dv into dqkv, mm_qk_norm_rope_bwd fills the q|k
-    columns of dqkv (and the norm weights' gradients), then the projection's backward as above."""
+    """The decoder's attention front half as ONE node: the fused q|k|v projection, then RopeAttentionFn's two halves.  The projection
+    carries RoPE in its epilogue (mm_gemm_rope_fwd) where the shape qualifies and no q/k norm stands in between; the projection +
+    the RoPE stage otherwise: same bits.  h [T, H] -> out [T, Hq*D].  Backward = _rope_attention_backward, then the projection's
+    (`_proj_backward`: LinearFn's).  qkn: (q_norm weight, k_norm weight, eps) of a Qwen3 layer, see _rope_attention_forward."""
 
     @staticmethod
     def forward(ctx, h, dummy, wg: ParamGroup, bg: Optional[ParamGroup], cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn=None):
-        if qkn is not None:
-            return QKVRopeAttentionFn._forward_qk_norm(ctx, h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn)
-        ctx.qkn = None
         w = wg.tensor()
         b = bg.tensor() if bg is not None else None
-        W = (Hq + 2 * Hkv) * D
-        qkv = K.gemm_rope_fwd(h, w, b, (Hq + Hkv) * D, D, cos, sin) if cos is not None else None
-        if qkv is None:
+        qkv = K.gemm_rope_fwd(h, w, b, (Hq + Hkv) * D, D, cos, sin) if cos is not None and qkn is None else None
+        roped = qkv is not None
+        if not roped:
             qkv = K.linear_fwd(h, w, bias=b)
-            if cos is not None:
-                K.rope_apply_(qkv, B * S, Hq + Hkv, D, W, cos, sin)
-        q = qkv[:, : Hq * D].view(B, S, Hq, D)
-        k = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        out, lse = K.attn_fwd(q, k, v, key_mask, causal, scale)
         ctx.dims = (B, S, Hq, Hkv, D, causal, scale)
-        ctx.wg, ctx.bg = wg, bg
-        ctx.save_for_backward(h, qkv, out, lse, cos, sin, key_mask)
-        return out.view(B * S, Hq * D)
-
-    @staticmethod
-    def _forward_qk_norm(ctx, h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, qkn):
-        assert cos is not None, "the q/k norm path always applies RoPE"
-        qn, kn, eps = qkn
-        qkv = K.linear_fwd(h, wg.tensor(), bias=bg.tensor() if bg is not None else None)
-        qk, rstd = K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, qn.data, kn.data, eps, cos, sin)
-        q = qk[:, : Hq * D].view(B, S, Hq, D)
-        k = qk[:, Hq * D:].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        out, lse = K.attn_fwd(q, k, v, key_mask, causal, scale)
-        ctx.dims = (B, S, Hq, Hkv, D, causal, scale)
-        ctx.wg, ctx.bg, ctx.qkn = wg, bg, (qn, kn)
+        out, lse, qk, rstd = _rope_attention_forward(qkv, cos, sin, key_mask, ctx.dims, roped, qkn)
+        ctx.wg, ctx.bg, ctx.qkn = wg, bg, (qkn[:2] if qkn is not None else None)
         ctx.save_for_backward(h, qkv, out, lse, cos, sin, key_mask, qk, rstd)
         return out.view(B * S, Hq * D)
 
     @staticmethod
-    def _backward_qk_norm(ctx, dout):
-        h, qkv, out, lse, cos, sin, key_mask, qk, rstd = ctx.saved_tensors
-        B, S, Hq, Hkv, D, causal, scale = ctx.dims
-        wg, bg = ctx.wg, ctx.bg
-        qn, kn = ctx.qkn
-        f32 = qkv.dtype == torch.float32          # the fp32 attention backward accumulates with atomics
-        dqkv = torch.zeros_like(qkv) if f32 else torch.empty_like(qkv)
-        dqk = torch.zeros_like(qk) if f32 else torch.empty_like(qk)
-        dq = dqk[:, : Hq * D].view(B, S, Hq, D)
-        dk = dqk[:, Hq * D:].view(B, S, Hkv, D)
-        dv = dqkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        q = qk[:, : Hq * D].view(B, S, Hq, D)
-        k = qk[:, Hq * D:].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        K.attn_bwd(q, k, v, out, dout.contiguous().view(B, S, Hq, D), lse, key_mask, causal, scale, dq, dk, dv)
-        del dq, dk
-        want_dw = qn.requires_grad or kn.requires_grad
-        dwq, dwk = K.qk_norm_rope_bwd(dqk, qkv, B * S, Hq, Hkv, D, qn.data, kn.data, rstd, cos, sin, dqkv, want_dw=want_dw)
-        for p, part in ((qn, dwq), (kn, dwk)):
-            if p.requires_grad:
-                g, acc = grad_target(p)
-                K.reduce_partials(part, g, acc)
-                _ready(p)
-        if bg is not None and bg.requires_grad:
-            g, acc = bg.grad_target()
-            K.colsum(dqkv, g, acc)
-            bg.ready()
-        _wgrad(dqkv, h, wg)
-        dh = K.linear_dgrad(dqkv, wg.tensor()) if ctx.needs_input_grad[0] else None
-        return (dh,) + (None,) * 14
-
-    @staticmethod
     def backward(ctx, dout):
-        if ctx.qkn is not None:
-            return QKVRopeAttentionFn._backward_qk_norm(ctx, dout)
-        h, qkv, out, lse, cos, sin, key_mask = ctx.saved_tensors
-        B, S, Hq, Hkv, D, causal, scale = ctx.dims
-        wg, bg = ctx.wg, ctx.bg
-        W = (Hq + 2 * Hkv) * D
-        q = qkv[:, : Hq * D].view(B, S, Hq, D)
-        k = qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        v = qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        dqkv = torch.zeros_like(qkv) if qkv.dtype == torch.float32 else torch.empty_like(qkv)
-        dq = dqkv[:, : Hq * D].view(B, S, Hq, D)
-        dk = dqkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D)
-        dv = dqkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D)
-        K.attn_bwd(q, k, v, out, dout.contiguous().view(B, S, Hq, D), lse, key_mask, causal, scale, dq, dk, dv)
-        if cos is not None:
-            K.rope_apply_(dqkv, B * S, Hq + Hkv, D, W, cos, sin, inverse=True)
-        if bg is not None and bg.requires_grad:
-            g, acc = bg.grad_target()
-            K.colsum(dqkv, g, acc)
-            bg.ready()
-        _wgrad(dqkv, h, wg)
-        dh = K.linear_dgrad(dqkv, wg.tensor()) if ctx.needs_input_grad[0] else None
-        return (dh,) + (None,) * 14
+        h, qkv, out, lse, cos, sin, key_mask, qk, rstd = ctx.saved_tensors
+        dqkv = _rope_attention_backward(dout, qkv, out, lse, cos, sin, key_mask, ctx.dims, ctx.qkn, qk, rstd)
+        return (_proj_backward(dqkv, h, ctx.wg, ctx.bg, ctx.needs_input_grad[0]),) + (None,) * 14
 
 
 def qkv_rope_attention(h, wg, bg, cos, sin, key_mask, B, S, Hq, Hkv, D, causal, scale, dummy=None, qkn=None):
@@ -625,8 +586,7 @@ class CrossAttentionFn(torch.autograd.Function):
         q2d, kv2d, out, lse = ctx.saved_tensors
         n, Nq, Nkv, heads, d, scale, drop_p, seed, off, small = ctx.dims
         C = heads * d
-        mk = torch.zeros_like if (q2d.dtype == torch.float32 and not small) else torch.empty_like
-        dq2d, dkv2d = mk(q2d), mk(kv2d)
+        dq2d, dkv2d = _attn_grad_like(q2d, atomics=not small), _attn_grad_like(kv2d, atomics=not small)    # mm_xattn_bwd: no atomics
         args = (q2d.view(n, Nq, heads, d), kv2d[:, :C].view(n, Nkv, heads, d), kv2d[:, C:].view(n, Nkv, heads, d), out,
                 dout.contiguous().view(n, Nq, heads, d), lse)
         grads = (dq2d.view(n, Nq, heads, d), dkv2d[:, :C].view(n, Nkv, heads, d), dkv2d[:, C:].view(n, Nkv, heads, d))
@@ -732,18 +692,13 @@ class SwiGLUMLPFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, gu, act = ctx.saved_tensors
         wgu, wd, I = ctx.wgu, ctx.wd, ctx.I
-        if dy.stride(-1) != 1 or (dy.stride(0) % 8):
-            dy = dy.contiguous()
+        dy = _gemm_rows(dy)
         dres = dy if ctx.has_res else None
-
-        wgrad = _wgrad
-        wgrad(dy, act, wd)
+        _proj_backward(dy, act, wd, None, False)              # down_proj: the weight gradient first; its dgrad carries the SwiGLU backward
         dgu = K.gemm_swiglu_bwd(dy, wd.tensor(), gu, I)
         if dgu is None:
             dgu = K.swiglu_bwd(gu, K.linear_dgrad(dy, wd.tensor()), I)
-        wgrad(dgu, x, wgu)
-        dx = K.linear_dgrad(dgu, wgu.tensor()) if ctx.needs_input_grad[0] else None
-        return dx, dres, None, None, None, None
+        return _proj_backward(dgu, x, wgu, None, ctx.needs_input_grad[0]), dres, None, None, None, None
 
 
 def swiglu_mlp(x, wgu, wd, I, residual=None, dummy=None):
@@ -773,24 +728,16 @@ class XIELUMLPFn(torch.autograd.Function):
         x, u, a = ctx.saved_tensors
         wu, wd, act = ctx.wu, ctx.wd, ctx.act
         beta, eps = ctx.consts
-        if dy.stride(-1) != 1 or (dy.stride(0) % 8):
-            dy = dy.contiguous()
+        dy = _gemm_rows(dy)
         dres = dy if ctx.has_res else None
-        _wgrad(dy, a, wd)
-        da = K.linear_dgrad(dy, wd.tensor())
+        da = _proj_backward(dy, a, wd, None, True)
         ap, an = act.alpha_p, act.alpha_n
         train = ap.requires_grad or an.requires_grad
         du, partials = K.xielu_bwd(u, da, ap.data, an.data, beta, eps, want_dalpha=train)
-        if train:
-            if not (ap.requires_grad and an.requires_grad):
-                raise NotImplementedError("xIELU: alpha_p and alpha_n are trained or frozen together")
-            (gp, accp), (gn, accn) = grad_target(ap), grad_target(an)
-            K.xielu_reduce(partials, ap.data, an.data, gp, gn, accp, accn)
-            _ready(ap)
-            _ready(an)
-        _wgrad(du, x, wu)
-        dx = K.linear_dgrad(du, wu.tensor()) if ctx.needs_input_grad[0] else None
-        return dx, dres, None, None, None, None
+        # one launch writes both scalars' gradients; unlike a LayerNorm's pair they have no one-parameter form
+        if train and not _write_grads(K.xielu_reduce, (partials, ap.data, an.data), ap, an):
+            raise NotImplementedError("xIELU: alpha_p and alpha_n are trained or frozen together")
+        return _proj_backward(du, x, wu, None, ctx.needs_input_grad[0]), dres, None, None, None, None
 
 
 def xielu_mlp(h, w_up, w_down, act, residual=None, dummy=None):
@@ -924,13 +871,11 @@ class PatchEmbedFn(torch.autograd.Function):
             if gp is not None:
                 K.colsum(dpatch.view(n, P * Dv), gp.view(-1), accp)
         if need_b:
-            g, acc = grad_target(b_conv)
-            K.colsum(dpatch, g, acc)
-            _ready(b_conv)
-        if need_w:
+            _write_grads(K.colsum, (dpatch,), b_conv)
+        if need_w:      # the GEMM runs on the K-padded patches: into a padded buffer, whose first kk columns then reach the filter's gradient
             gw = torch.empty((Dv, kpad), dtype=dx.dtype, device=dx.device)
             K.linear_wgrad(dpatch, patches, gw, False)
-            g, acc = grad_target(w_conv)
+            g, acc = grad_target(w_conv)          # not _write_grads: torch's add_ / copy_ stand where a kernel would
             if acc:
                 g.add_(gw[:, :kk].reshape(g.shape))
             else:

@@ -2,8 +2,10 @@
 HIP stream only; every arithmetic step below is a libmmhip kernel.  No autograd here (see functional.py)."""
 from __future__ import annotations
 
+import ctypes
 import math
-from typing import Optional, Tuple
+import os
+from typing import Optional
 
 import torch
 
@@ -37,6 +39,45 @@ def pad8(n: int) -> int:
     return (n + 7) // 8 * 8
 
 
+# A/B switches of the environment (tools/step_ab.py, tools/decode_bench.py, the tests): name -> (default, what the other value selects).
+# Read at call time: the tools and the tests flip them inside one process.
+SWITCHES = {
+    "MM_FUSED_GELU": ("1", "0: Linear + GELU as mm_gemm + mm_gelu_fwd (+ mm_add) instead of mm_gemm_act_fwd"),
+    "MM_FUSED_SWIGLU": ("1", "0: mm_gemm + the separate SwiGLU kernels instead of mm_gemm_swiglu_fwd / _bwd"),
+    "MM_FUSED_ROPE": ("1", "0: mm_gemm + mm_rope_apply instead of mm_gemm_rope_fwd"),
+    "MM_DECODE_FUSED": ("1", "0: a decode step's norms and SwiGLU as separate launches"),
+    "MM_DECODE_MERGE": ("launch", "fused: mm_attn_decode merges its slices itself (arrival counters) instead of a second launch"),
+    "MM_ARGMAX_SPLIT": ("1", "0: mm_argmax_softmax on long rows too, instead of mm_argmax_softmax_split"),
+}
+
+
+def switch(name: str) -> str:
+    return os.environ.get(name, SWITCHES[name][0])
+
+
+def _on(name: str) -> bool:
+    return os.environ.get(name, SWITCHES[name][0]) != "0"
+
+
+def _sizes(symbol: str, *args, n: int = 1):
+    """the int64_t* out-parameter(s) at the end of a size query: one value, or a tuple of n"""
+    outs = [ctypes.c_int64(0) for _ in range(n)]
+    call(symbol, *args, *[ctypes.byref(o) for o in outs])
+    return outs[0].value if n == 1 else tuple(o.value for o in outs)
+
+
+def _rows_out(M: int, N: int, like: torch.Tensor, ldc_pad: bool = False) -> torch.Tensor:
+    """a new [M, N] output in like's dtype on its device; ldc_pad: a view of a buffer whose row stride is N rounded up to 64"""
+    ld = (N + 63) // 64 * 64 if ldc_pad else N
+    buf = torch.empty((M, ld), dtype=like.dtype, device=like.device)
+    return buf[:, :N] if ld != N else buf
+
+
+def fused_gelu_ok(dtype, rows: int) -> bool:
+    """what mm_gemm_act_fwd (and its grouped form, per problem) takes: bf16 and more than 16 rows"""
+    return dtype == torch.bfloat16 and rows > 16 and _on("MM_FUSED_GELU")
+
+
 # ------------------------------------------------------------------------------------------------ GEMM
 def gemm(layout: int, a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, out: Optional[torch.Tensor] = None,
          bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: int = 0,
@@ -45,12 +86,7 @@ def gemm(layout: int, a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, 
     buffer when ldc_pad)."""
     assert a.dim() == 2 and b.dim() == 2 and a.stride(1) == 1 and b.stride(1) == 1
     if out is None:
-        if ldc_pad:
-            ld = (N + 63) // 64 * 64
-            buf = torch.empty((M, ld), dtype=a.dtype, device=a.device)
-            out = buf[:, :N]
-        else:
-            out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+        out = _rows_out(M, N, a, True) if ldc_pad else torch.empty((M, N), dtype=a.dtype, device=a.device)     # the common case without a call
     assert out.stride(1) == 1
     epi = act
     if bias is not None:
@@ -78,7 +114,7 @@ def linear_act_fwd(x2d, w, bias, act, residual=None):
     separate launches otherwise (this function returns None then)."""
     M, K = x2d.shape
     N = w.shape[0]
-    if x2d.dtype != torch.bfloat16 or M <= 16 or _os.environ.get("MM_FUSED_GELU", "1") == "0":
+    if not fused_gelu_ok(x2d.dtype, M):
         return None
     assert x2d.stride(1) == 1 and w.stride(1) == 1
     pre = torch.empty((M, N), dtype=x2d.dtype, device=x2d.device)
@@ -103,17 +139,10 @@ def linear_wgrad(dy2d, x2d, out, accumulate):
     return gemm(GEMM_TN, dy2d, x2d, N, K, M, out=out, accumulate=accumulate)
 
 
-import os as _os
-
-
-def _fused_swiglu():      # A/B switch (tools/step_ab.py): MM_FUSED_SWIGLU=0 -> GEMM + separate SwiGLU kernels
-    return _os.environ.get("MM_FUSED_SWIGLU", "1") != "0"
-
-
 def gemm_swiglu_fwd(x2d, wgu, I):
     """(gu [M, 2I], act [M, I]) = fused gate|up GEMM + SwiGLU; None when the shape must take the two-launch form."""
     M, K = x2d.shape
-    if x2d.dtype != torch.bfloat16 or (I % 128) or (K % 64) or M < 256 or not _fused_swiglu():
+    if x2d.dtype != torch.bfloat16 or (I % 128) or (K % 64) or M < 256 or not _on("MM_FUSED_SWIGLU"):
         return None
     gu = torch.empty((M, 2 * I), dtype=x2d.dtype, device=x2d.device)
     act = torch.empty((M, I), dtype=x2d.dtype, device=x2d.device)
@@ -122,16 +151,12 @@ def gemm_swiglu_fwd(x2d, wgu, I):
     return gu, act
 
 
-def _fused_rope():         # A/B switch (tools/step_ab.py): MM_FUSED_ROPE=0 -> GEMM + separate RoPE kernel
-    return _os.environ.get("MM_FUSED_ROPE", "1") != "0"
-
-
 def gemm_rope_fwd(x2d, w, bias, rope_cols, D, cos, sin):
     """qkv [M, N] = x @ w^T (+ bias) with RoPE on the first rope_cols columns, in one launch; None when the shape must take the
     two-launch form (mm_gemm + mm_rope_apply: same bits)."""
     M, K = x2d.shape
     N = w.shape[0]
-    if (x2d.dtype != torch.bfloat16 or D != 128 or (N % 128) or (rope_cols % 128) or M < 256 or not _fused_rope()
+    if (x2d.dtype != torch.bfloat16 or D != 128 or (N % 128) or (rope_cols % 128) or M < 256 or not _on("MM_FUSED_ROPE")
             or cos.dtype != torch.float32 or cos.shape[-1] != D // 2):
         return None
     out = torch.empty((M, N), dtype=x2d.dtype, device=x2d.device)
@@ -146,34 +171,50 @@ def decode_fits(M, K):
     return K % 8 == 0 and M * K * 2 <= 143 * 1024        # csrc/mm_gemm.hip GEMV_X_LDS_MAX (160 KB minus the kernel's static reduction scratch)
 
 
-def decode_gateup_swiglu(x2d, wgu, I, norm_w=None, eps=0.0):
-    """act [M, I] = silu(x' Wg^T) * (x' Wu^T), x' = rmsnorm(x) * norm_w when norm_w is given."""
+def _cache_rows(kcache, vcache, D, pos):
+    """a decode step's cache arguments: the pointers of cache[:, pos] ([B, Smax, Hkv, D], contiguous in the last two) and the batch stride"""
+    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
+    return _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0)
+
+
+def _weight_args(w, packed):
+    """how a weight-streaming launch takes its matrix: (symbol suffix, arguments) of the bf16 matrix w, or of its MXFP8 copy"""
+    return ("_w8", (_p(packed),)) if packed is not None else ("", (_p(w), w.stride(0)))
+
+
+def decode_gateup_swiglu(x2d, wgu, I, norm_w=None, eps=0.0, out=None, packed=None):
+    """act [M, I] = silu(x' Wg^T) * (x' Wu^T), x' = rmsnorm(x) * norm_w when norm_w is given.  packed: the MXFP8 copy of the fused
+    [2I, K] gate|up matrix, read in place of wgu: the bits of the bf16 call on dequant_mxfp8(packed)."""
     M, K = x2d.shape
-    act = torch.empty((M, I), dtype=x2d.dtype, device=x2d.device)
-    call("mm_decode_gateup_swiglu", dt(x2d), M, I, K, _p(x2d), x2d.stride(0), _p(wgu), wgu.stride(0), _p(act), act.stride(0), _p(norm_w), float(eps),
+    act = _rows_out(M, I, x2d) if out is None else out
+    sfx, wargs = _weight_args(wgu, packed)
+    call("mm_decode_gateup_swiglu" + sfx, dt(x2d), M, I, K, _p(x2d), x2d.stride(0), *wargs, _p(act), act.stride(0), _p(norm_w), float(eps),
          _stream())
     return act
 
 
-def decode_qkv_rope_append(x2d, w, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w=None, eps=0.0):
-    """qkv [B, (Hq+2Hkv)*D] = x' @ w^T (+ bias) with RoPE on q / k and the append of roped k / v to cache[:, pos]."""
+def decode_qkv_rope_append(x2d, w, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w=None, eps=0.0, out=None, packed=None):
+    """qkv [B, (Hq+2Hkv)*D] = x' @ w^T (+ bias) with RoPE on q / k and the append of roped k / v to cache[:, pos].  packed: the MXFP8
+    copy of the fused q|k|v matrix, read in place of w."""
     M, K = x2d.shape
-    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
-    qkv = torch.empty((M, (Hq + 2 * Hkv) * D), dtype=x2d.dtype, device=x2d.device)
-    call("mm_decode_qkv_rope_append", dt(x2d), M, Hq, Hkv, D, K, _p(x2d), x2d.stride(0), _p(w), w.stride(0), _p(bias), _p(qkv), qkv.stride(0),
-         _p(cos), _p(sin), _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0), _p(norm_w), float(eps), _stream())
+    cache = _cache_rows(kcache, vcache, D, pos)
+    qkv = _rows_out(M, (Hq + 2 * Hkv) * D, x2d) if out is None else out
+    sfx, wargs = _weight_args(w, packed)
+    call("mm_decode_qkv_rope_append" + sfx, dt(x2d), M, Hq, Hkv, D, K, _p(x2d), x2d.stride(0), *wargs, _p(bias), _p(qkv), qkv.stride(0),
+         _p(cos), _p(sin), *cache, _p(norm_w), float(eps), _stream())
     return qkv
 
 
-def decode_linear(x2d, w, bias=None, residual=None, norm_w=None, eps=0.0, ldc_pad=False):
-    """c [M, N] = x' @ w^T (+ bias) (+ residual), x' = rmsnorm(x) * norm_w when norm_w is given; ldc_pad: row stride padded to 64."""
+def decode_linear(x2d, w, bias=None, residual=None, norm_w=None, eps=0.0, ldc_pad=False, out=None, packed=None, N=None):
+    """c [M, N] = x' @ w^T (+ bias) (+ residual), x' = rmsnorm(x) * norm_w when norm_w is given; ldc_pad: row stride padded to 64.
+    packed: the MXFP8 copy of w [N, K], read in place of w (N must be given then)."""
     M, K = x2d.shape
-    N = w.shape[0]
-    ld = (N + 63) // 64 * 64 if ldc_pad else N
-    buf = torch.empty((M, ld), dtype=x2d.dtype, device=x2d.device)
-    call("mm_decode_linear", dt(x2d), M, N, K, _p(x2d), x2d.stride(0), _p(w), w.stride(0), _p(bias), _p(residual),
-         residual.stride(0) if residual is not None else 0, _p(buf), ld, _p(norm_w), float(eps), _stream())
-    return buf[:, :N] if ld != N else buf
+    N = w.shape[0] if packed is None else N
+    c = _rows_out(M, N, x2d, ldc_pad) if out is None else out
+    sfx, wargs = _weight_args(w, packed)
+    call("mm_decode_linear" + sfx, dt(x2d), M, N, K, _p(x2d), x2d.stride(0), *wargs, _p(bias), _p(residual),
+         residual.stride(0) if residual is not None else 0, _p(c), c.stride(0), _p(norm_w), float(eps), _stream())
+    return c[:, :N] if c.shape[1] != N else c
 
 
 # ---- weight-only MXFP8 copies for the decode step (include/mm_hip.h: e4m3 elements, one power-of-two scale per 32 k) ---------------
@@ -206,35 +247,15 @@ def dequant_mxfp8(packed, N, K, out=None):
 
 
 def decode_gateup_swiglu_w8(x2d, packed, I, norm_w=None, eps=0.0, out=None):
-    """decode_gateup_swiglu on the MXFP8 copy of the fused [2I, K] gate|up matrix: the bits of the bf16 call on dequant_mxfp8(packed)."""
-    M, K = x2d.shape
-    act = torch.empty((M, I), dtype=x2d.dtype, device=x2d.device) if out is None else out
-    call("mm_decode_gateup_swiglu_w8", dt(x2d), M, I, K, _p(x2d), x2d.stride(0), _p(packed), _p(act), act.stride(0), _p(norm_w), float(eps),
-         _stream())
-    return act
+    return decode_gateup_swiglu(x2d, None, I, norm_w, eps, out, packed)
 
 
 def decode_qkv_rope_append_w8(x2d, packed, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w=None, eps=0.0, out=None):
-    """decode_qkv_rope_append on the MXFP8 copy of the fused q|k|v matrix."""
-    M, K = x2d.shape
-    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
-    qkv = torch.empty((M, (Hq + 2 * Hkv) * D), dtype=x2d.dtype, device=x2d.device) if out is None else out
-    call("mm_decode_qkv_rope_append_w8", dt(x2d), M, Hq, Hkv, D, K, _p(x2d), x2d.stride(0), _p(packed), _p(bias), _p(qkv), qkv.stride(0),
-         _p(cos), _p(sin), _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0), _p(norm_w), float(eps), _stream())
-    return qkv
+    return decode_qkv_rope_append(x2d, None, bias, Hq, Hkv, D, cos, sin, kcache, vcache, pos, norm_w, eps, out, packed)
 
 
 def decode_linear_w8(x2d, packed, N, bias=None, residual=None, norm_w=None, eps=0.0, ldc_pad=False, out=None):
-    """decode_linear on the MXFP8 copy of w [N, K]."""
-    M, K = x2d.shape
-    if out is None:
-        ld = (N + 63) // 64 * 64 if ldc_pad else N
-        buf = torch.empty((M, ld), dtype=x2d.dtype, device=x2d.device)
-    else:
-        buf, ld = out, out.stride(0)
-    call("mm_decode_linear_w8", dt(x2d), M, N, K, _p(x2d), x2d.stride(0), _p(packed), _p(bias), _p(residual),
-         residual.stride(0) if residual is not None else 0, _p(buf), ld, _p(norm_w), float(eps), _stream())
-    return buf[:, :N] if buf.shape[1] != N else buf
+    return decode_linear(x2d, None, bias, residual, norm_w, eps, ldc_pad, out, packed, N)
 
 
 # ---- MXFP8 x MXFP8 GEMM for the prefill (include/mm_hip.h: mm_gemm_mx8, the block-scaled MFMA) -----------------------------------
@@ -269,14 +290,14 @@ def gemm_mx8(packedA, M, packedW, N, K, bias=None, residual=None, out=None):
     return out
 
 
-def decode_fusions():      # A/B switch (tools/decode_bench.py): MM_DECODE_FUSED=0 -> the separate launches
-    return _os.environ.get("MM_DECODE_FUSED", "1") != "0"
+def decode_fusions():
+    return _on("MM_DECODE_FUSED")
 
 
 def gemm_swiglu_bwd(dy2d, wd, gu, I):
     """dgu [M, 2I] from dy [M, H], down_proj weight [H, I] and the saved pre-activations; None -> two-launch form."""
     M, H = dy2d.shape
-    if dy2d.dtype != torch.bfloat16 or (I % 4) or not _fused_swiglu():
+    if dy2d.dtype != torch.bfloat16 or (I % 4) or not _on("MM_FUSED_SWIGLU"):
         return None
     dgu = torch.empty_like(gu)
     call("mm_gemm_swiglu_bwd", dt(dy2d), M, I, H, _p(dy2d), dy2d.stride(0), _p(wd), wd.stride(0), _p(gu), gu.stride(0), _p(dgu),
@@ -294,10 +315,14 @@ def colsum(x2d, out, accumulate):
 # tensors with equal strides; the pointers travel as host arrays (include/mm_hip.h, "grouped launches").
 def _pa(ts):
     """host array of device pointers (None for an absent operand)"""
-    import ctypes
     if ts is None:
         return None
     return (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])
+
+
+def _pat(ts, g):
+    """the pointer of problem g's operand (None for an absent operand)"""
+    return _p(ts[g]) if ts is not None else None
 
 
 def _same_stride(ts):
@@ -306,8 +331,15 @@ def _same_stride(ts):
     return ld
 
 
-def _unsupported(err):
-    return getattr(err, "code", None) == _lib.ERR_UNSUPPORTED
+def _grouped_or_each(G, grouped, each):
+    """grouped(): one launch for G problems; the problems the grouped kernels do not cover (MM_ERR_UNSUPPORTED) run each(g) one by one"""
+    try:
+        grouped()
+    except _lib.MMHipError as err:
+        if getattr(err, "code", None) != _lib.ERR_UNSUPPORTED:
+            raise
+        for g in range(G):
+            each(g)
 
 
 def gemm_batched(layout, As, Bs, M, N, K, outs, biases=None, residuals=None, act=0, accumulate=False):
@@ -316,15 +348,11 @@ def gemm_batched(layout, As, Bs, M, N, K, outs, biases=None, residuals=None, act
     epi = act | (EPI_BIAS if biases is not None else 0) | (EPI_RESIDUAL if residuals is not None else 0) | (EPI_ACCUMULATE if accumulate else 0)
     lda, ldb, ldc = _same_stride(As), _same_stride(Bs), _same_stride(outs)
     ldr = _same_stride(residuals) if residuals is not None else 0
-    try:
-        call("mm_gemm_batched", dt(As[0]), layout, len(As), M, N, K, _pa(As), lda, _pa(Bs), ldb, _pa(outs), ldc, _pa(biases), _pa(residuals),
-             ldr, epi, _stream())
-    except _lib.MMHipError as err:
-        if not _unsupported(err):
-            raise
-        for g in range(len(As)):
-            call("mm_gemm", dt(As[g]), layout, M, N, K, _p(As[g]), lda, _p(Bs[g]), ldb, _p(outs[g]), ldc,
-                 _p(biases[g]) if biases is not None else None, _p(residuals[g]) if residuals is not None else None, ldr, epi, _stream())
+    _grouped_or_each(len(As),
+                     lambda: call("mm_gemm_batched", dt(As[0]), layout, len(As), M, N, K, _pa(As), lda, _pa(Bs), ldb, _pa(outs), ldc, _pa(biases),
+                                  _pa(residuals), ldr, epi, _stream()),
+                     lambda g: call("mm_gemm", dt(As[g]), layout, M, N, K, _p(As[g]), lda, _p(Bs[g]), ldb, _p(outs[g]), ldc, _pat(biases, g),
+                                    _pat(residuals, g), ldr, epi, _stream()))
     return outs
 
 
@@ -350,7 +378,7 @@ def linear_act_fwd_batched(x, ws, biases, act, residual=None):
     G = len(ws)
     R, Kd = x.shape[0] // G, x.shape[1]
     N = ws[0].shape[0]
-    if x.dtype != torch.bfloat16 or R <= 16 or _os.environ.get("MM_FUSED_GELU", "1") == "0":
+    if not fused_gelu_ok(x.dtype, R):
         return None
     pre = torch.empty((G * R, N), dtype=x.dtype, device=x.device)
     y = torch.empty((G * R, N), dtype=x.dtype, device=x.device)
@@ -359,15 +387,11 @@ def linear_act_fwd_batched(x, ws, biases, act, residual=None):
     epi = act | (EPI_BIAS if biases is not None else 0) | (EPI_RESIDUAL if residual is not None else 0)
     ldx, ldw = _same_stride(xs), _same_stride(ws)
     ldr = residual.stride(0) if residual is not None else 0
-    try:
-        call("mm_gemm_act_fwd_batched", dt(x), G, R, N, Kd, _pa(xs), ldx, _pa(ws), ldw, _pa(biases), _pa(pres), pre.stride(0), _pa(ys),
-             y.stride(0), _pa(res), ldr, epi, _stream())
-    except _lib.MMHipError as err:
-        if not _unsupported(err):
-            raise
-        for g in range(G):
-            call("mm_gemm_act_fwd", dt(x), R, N, Kd, _p(xs[g]), ldx, _p(ws[g]), ldw, _p(biases[g]) if biases is not None else None,
-                 _p(pres[g]), pre.stride(0), _p(ys[g]), y.stride(0), _p(res[g]) if res is not None else None, ldr, epi, _stream())
+    _grouped_or_each(G,
+                     lambda: call("mm_gemm_act_fwd_batched", dt(x), G, R, N, Kd, _pa(xs), ldx, _pa(ws), ldw, _pa(biases), _pa(pres), pre.stride(0),
+                                  _pa(ys), y.stride(0), _pa(res), ldr, epi, _stream()),
+                     lambda g: call("mm_gemm_act_fwd", dt(x), R, N, Kd, _p(xs[g]), ldx, _p(ws[g]), ldw, _pat(biases, g), _p(pres[g]), pre.stride(0),
+                                    _p(ys[g]), y.stride(0), _pat(res, g), ldr, epi, _stream()))
     return pre, y
 
 
@@ -488,12 +512,10 @@ def embed_splice_fwd(emb, ids, proj, src_map):
 
 def embed_sort(ids, src_map, vocab, H):
     """Stable token order by id for the embedding gradient -> (order, skey) int32 (padded, see mm_embed_sort_sizes)."""
-    import ctypes
     T = ids.numel()
-    n_order, n_scr = ctypes.c_int64(0), ctypes.c_int64(0)
-    call("mm_embed_sort_sizes", T, H, ctypes.byref(n_order), ctypes.byref(n_scr))
-    order = torch.empty(n_order.value, dtype=torch.int32, device=ids.device)
-    skey = torch.empty(n_order.value, dtype=torch.int32, device=ids.device)
+    n_order, _ = _sizes("mm_embed_sort_sizes", T, H, n=2)
+    order = torch.empty(n_order, dtype=torch.int32, device=ids.device)
+    skey = torch.empty(n_order, dtype=torch.int32, device=ids.device)
     ws = torch.empty(max(T, 1), dtype=torch.int32, device=ids.device)
     call("mm_embed_sort", _p(ids), _p(src_map), T, vocab, _p(ws), _p(order), _p(skey), _stream())
     return order, skey
@@ -643,9 +665,7 @@ def rope_apply_(x, T, nheads, D, ld, cos, sin, inverse=False):
 
 def rope_append_(qkv, B, Hq, Hkv, D, cos, sin, kcache, vcache, pos):
     """decode step: RoPE q/k in place + write roped k and v to cache[:, pos] ([B, Smax, Hkv, D] contiguous in the last two)."""
-    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
-    call("mm_rope_append", dt(qkv), _p(qkv), B, Hq, Hkv, D, qkv.stride(0), _p(cos), _p(sin), _p(kcache[:, pos]), _p(vcache[:, pos]),
-         kcache.stride(0), _stream())
+    call("mm_rope_append", dt(qkv), _p(qkv), B, Hq, Hkv, D, qkv.stride(0), _p(cos), _p(sin), *_cache_rows(kcache, vcache, D, pos), _stream())
     return qkv
 
 
@@ -680,9 +700,8 @@ def qk_norm_rope_bwd(dqk, qkv, T, Hq, Hkv, D, w_q, w_k, rstd, cos, sin, dqkv, wa
 
 def qk_norm_rope_append_(qkv, B, Hq, Hkv, D, w_q, w_k, eps, cos, sin, kcache, vcache, pos):
     """decode step (Qwen3): per-head norm + RoPE of q/k in place + write the normed, roped k and v to cache[:, pos]."""
-    assert kcache.stride(3) == 1 and kcache.stride(2) == D and vcache.stride(2) == D and kcache.stride(0) == vcache.stride(0)
     call("mm_qk_norm_rope_append", dt(qkv), _p(qkv), B, Hq, Hkv, D, qkv.stride(0), _p(w_q), _p(w_k), float(eps), _p(cos), _p(sin),
-         _p(kcache[:, pos]), _p(vcache[:, pos]), kcache.stride(0), _stream())
+         *_cache_rows(kcache, vcache, D, pos), _stream())
     return qkv
 
 
@@ -714,6 +733,13 @@ def attn_bwd(q, k, v, out, dout, lse, key_mask, causal, scale, dq, dk, dv):
          *_strides3(k), *_strides3(v), _p(key_mask), int(causal), float(scale), _p(dq), _p(dk), _p(dv), _p(delta), _stream())
 
 
+def _decode_ws(q, ns):
+    """(workspace of ns partial (out, max, sum) records per query row and head, out [rows, Hq, D]) of a decode-attention launch on q"""
+    rows, Hq, D = q.shape
+    return (torch.empty(rows * Hq * ns * (D + 2), dtype=torch.float32, device=q.device),
+            torch.empty((rows, Hq, D), dtype=q.dtype, device=q.device))
+
+
 def attn_decode_supported(q_dtype, Hq, Hkv, D):
     return q_dtype == torch.bfloat16 and D in (64, 128) and Hq % Hkv == 0 and (Hq // Hkv) in (1, 2, 4, 7, 8)
 
@@ -727,8 +753,7 @@ def attn_decode(q, k, v, key_mask, scale):
     Skv, Hkv = k.shape[1], k.shape[2]
     assert q.stride(2) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     ns = _lib.lib().mm_attn_decode_splits(B, Hkv, Skv)
-    ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
-    out = torch.empty((B, Hq, D), dtype=q.dtype, device=q.device)
+    ws, out = _decode_ws(q, ns)
     # sync=None: the slices are merged by a second (tiny) launch.  The single-launch form (sync = arrival counters [B * Hkv]; the
     # slice that arrives last merges) is correct but SLOWER on MI355X in every protocol tried: __threadfence() per thread (round 2:
     # 8.2 vs 5.2 ms/token), one agent-scope release per workgroup (round 3: the partial kernel went from 18 to 75 us -- buffer_wbl2
@@ -736,7 +761,7 @@ def attn_decode(q, k, v, key_mask, scale):
     # two launches: the merging workgroup starts only when the last slice is done and reads records that come from beyond L2).
     # MM_DECODE_MERGE=fused selects it.
     sync = None
-    if _os.environ.get("MM_DECODE_MERGE", "launch") == "fused":
+    if switch("MM_DECODE_MERGE") == "fused":
         sync = _decode_sync.get(q.device)
         if sync is None or sync.numel() < B * Hkv:
             sync = _decode_sync[q.device] = torch.zeros(max(64, B * Hkv), dtype=torch.int32, device=q.device)
@@ -765,8 +790,7 @@ def attn_decode_shared(q, kp, vp, ks, vs, n, key_mask, scale, anc=None, nsplit=N
     assert key_mask is None or (tuple(key_mask.shape) == (B, Sp) and key_mask.is_contiguous())
     assert anc is None or (anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] >= Ss and anc.shape[1] >= R and anc.stride(1) == 1)
     ns = _lib.lib().mm_attn_decode_shared_splits(B, n, Hkv, Sp + Ss) if nsplit is None else int(nsplit)
-    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
-    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
+    ws, out = _decode_ws(q, ns)
     table = () if anc is None else (_p(anc), anc.stride(0))
     call("mm_attn_decode_shared" if anc is None else "mm_attn_decode_beam", dt(q), _p(q), _p(kp), _p(vp), _p(ks), _p(vs), B, n, Sp, Ss,
          Hq, Hkv, D, q.stride(0), q.stride(1), *_strides3(kp), *_strides3(vp), *_strides3(ks), *_strides3(vs), _p(key_mask), float(scale),
@@ -792,15 +816,13 @@ class BeamState:
     (mm_beam_state_layout) with a tensor view of every field, and the workspace of a step over V logits."""
 
     def __init__(self, B, n, T, V, device):
-        import ctypes
-        nb, wb = ctypes.c_int64(0), ctypes.c_int64(0)
-        call("mm_beam_state_bytes", int(B), int(n), int(T), ctypes.byref(nb))
-        call("mm_beam_ws_bytes", int(B), int(n), int(V), ctypes.byref(wb))
+        nb = _sizes("mm_beam_state_bytes", int(B), int(n), int(T))
+        wb = _sizes("mm_beam_ws_bytes", int(B), int(n), int(V))
         off = (ctypes.c_int64 * len(BEAM_FIELDS))()
         call("mm_beam_state_layout", int(B), int(n), int(T), off)
         self.B, self.n, self.T, self.V = int(B), int(n), int(T), int(V)
-        self.buf = torch.zeros(nb.value, dtype=torch.uint8, device=device)
-        self.ws = torch.empty((wb.value + 15) // 16 * 2, dtype=torch.int64, device=device)
+        self.buf = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.ws = torch.empty((wb + 15) // 16 * 2, dtype=torch.int64, device=device)
         self.next_ids = torch.empty(B * n, dtype=torch.int64, device=device)
         R = B * n
         shapes = {"tok": (T, R), "anc": (2, T, R), "fseq": (R, T), "open": (B,), "fcount": (B,), "done": (1,)}
@@ -865,8 +887,7 @@ def attn_decode_kv8(q, cache, Skv, Smax, Hkv, key_mask, scale):
     B, Hq, D = q.shape
     assert q.stride(2) == 1
     ns = _lib.lib().mm_attn_decode_splits(B, Hkv, Skv)
-    ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
-    out = torch.empty((B, Hq, D), dtype=q.dtype, device=q.device)
+    ws, out = _decode_ws(q, ns)
     call("mm_attn_decode_kv8", dt(q), _p(q), _p(cache), B, Skv, Smax, Hq, Hkv, D, q.stride(0), q.stride(1), _p(key_mask), float(scale),
          _p(out), _p(ws), ns, _stream())
     return out
@@ -898,16 +919,14 @@ def xattn_fwd(q, k, v, scale, drop_p=0.0, seed=0, offset=0):
 
 def xattn_bwd(q, k, v, out, dout, lse, scale, drop_p, seed, offset, dq, dk, dv):
     """dq/dk/dv: preallocated views with the SAME strides as q/k/v.  Deterministic (no atomics)."""
-    import ctypes
     n, Nq, H, D = q.shape
     Nkv = k.shape[1]
     assert _strides3(dq) == _strides3(q) and _strides3(dk) == _strides3(k) and _strides3(dv) == _strides3(v)
     assert dout.is_contiguous() and out.is_contiguous()
-    nb = ctypes.c_int64(0)
-    call("mm_xattn_ws_bytes", dt(q), n, Nq, Nkv, H, ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=q.device)
+    nb = _sizes("mm_xattn_ws_bytes", dt(q), n, Nq, Nkv, H)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
     call("mm_xattn_bwd", dt(q), _p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), n, Nq, Nkv, H, D, *_strides3(q), *_strides3(k),
-         *_strides3(v), float(scale), float(drop_p), int(seed), int(offset), _p(dq), _p(dk), _p(dv), _p(ws), nb.value, _stream())
+         *_strides3(v), float(scale), float(drop_p), int(seed), int(offset), _p(dq), _p(dk), _p(dv), _p(ws), nb, _stream())
 
 
 def dropout(x, p, seed, offset):
@@ -1011,7 +1030,7 @@ def ce_bwd(logits2d, V, labels, lse, loss_and_count, gscale, dlogits2d):
 def argmax_softmax(logits2d, V, temperature):
     rows = logits2d.shape[0]
     out = torch.empty(rows, dtype=torch.int64, device=logits2d.device)
-    if V >= 16384 and _os.environ.get("MM_ARGMAX_SPLIT", "1") != "0":      # long rows: the vocabulary over many workgroups
+    if V >= 16384 and _on("MM_ARGMAX_SPLIT"):      # long rows: the vocabulary over many workgroups
         nb = _lib.lib().mm_argmax_softmax_ws_bytes(rows, V)
         ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=logits2d.device)
         call("mm_argmax_softmax_split", dt(logits2d), _p(logits2d), rows, V, logits2d.stride(0), float(temperature), _p(out), _p(ws), _stream())
@@ -1028,10 +1047,7 @@ def _i64(v):
 
 def sample_ws(rows, V, device):
     """workspace of mm_sample for `rows` rows of V logits (reusable across calls of that size)."""
-    import ctypes
-    nb = ctypes.c_int64(0)
-    call("mm_sample_ws_bytes", int(rows), int(V), ctypes.byref(nb))
-    return torch.empty((nb.value + 15) // 16 * 2, dtype=torch.int64, device=device)
+    return torch.empty((_sizes("mm_sample_ws_bytes", int(rows), int(V)) + 15) // 16 * 2, dtype=torch.int64, device=device)
 
 
 def sample(logits2d, V, temperature, top_k=0, top_p=1.0, min_p=0.0, seed=0, offset=0, thresh=False, ws=None, out=None):
@@ -1059,7 +1075,6 @@ def sample_uniforms(seed, offset, rows, device="cuda"):
 def expert_fuse(x, gate, idx, mode, backward=False, E=None):
     """MoE fusion (see mm_expert_fuse).  forward: x [E, n, L] -> [n, L] (mode 0) / [n, J, L] (mode 1); backward: x = dout ->
     dX [E, n, L] (zeros outside the listed experts)."""
-    import ctypes
     J = len(idx)
     ix = (ctypes.c_int * J)(*[int(i) for i in idx])
     if not backward:
@@ -1184,8 +1199,7 @@ def attn_decode_verify(q, k, v, Q, key_mask, base, scale, nsplit=None):
     assert base.dtype == torch.int32 and base.numel() == B and base.is_contiguous()
     assert key_mask is None or (key_mask.dim() == 2 and key_mask.shape[0] == B and key_mask.is_contiguous() and key_mask.dtype == torch.int64)
     ns = _lib.lib().mm_attn_decode_verify_splits(B, Q, Hkv, Scap) if nsplit is None else int(nsplit)
-    ws = torch.empty(R * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
-    out = torch.empty((R, Hq, D), dtype=q.dtype, device=q.device)
+    ws, out = _decode_ws(q, ns)
     call("mm_attn_decode_verify", dt(q), _p(q), _p(k), _p(v), B, Q, Scap, 0 if key_mask is None else key_mask.shape[1], Hq, Hkv, D,
          q.stride(0), q.stride(1), *_strides3(k), *_strides3(v), _p(key_mask), _p(base), float(scale), _p(out), _p(ws), ns, _stream())
     return out
@@ -1303,10 +1317,7 @@ def gate_head(x: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, top_k: in
 # ------------------------------------------------------------------------------------------------ gating network, training pieces
 def bn_train_ws(M: int, C: int, device) -> torch.Tensor:
     """the fp32 workspace of bn_train_fwd / bn_train_bwd for z [M, C]."""
-    import ctypes
-    b = ctypes.c_int64(0)
-    call("mm_bn_train_ws_bytes", int(M), int(C), ctypes.byref(b))
-    return torch.empty(b.value // 4, dtype=torch.float32, device=device)
+    return torch.empty(_sizes("mm_bn_train_ws_bytes", int(M), int(C)) // 4, dtype=torch.float32, device=device)
 
 
 def bn_train_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False,
@@ -1373,18 +1384,16 @@ def maxpool2d_nhwc_bwd(x: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Te
 
 def expert_fuse_gate_bwd(x, dout, gate, idx, mode, out=None):
     """d(loss) / d(gate) of expert_fuse: x [E, n, L], dout [n, L] (mode 0) / [n, J, L] (mode 1), gate [n, E] fp32 -> fp32 [n, E]."""
-    import ctypes
     J = len(idx)
     E_, n, L = x.shape
     assert x.is_contiguous() and dout.is_contiguous() and dout.dtype == x.dtype and gate.dtype == torch.float32 and gate.is_contiguous()
     assert dout.shape == ((n, L) if mode == 0 else (n, J, L)) and gate.shape == (n, E_)
     ix = (ctypes.c_int * J)(*[int(i) for i in idx])
-    b = ctypes.c_int64(0)
-    call("mm_expert_fuse_gate_bwd_ws_bytes", dt(x), J, n, L, ctypes.byref(b))
-    ws = torch.empty(b.value // 4, dtype=torch.float32, device=x.device)
+    b = _sizes("mm_expert_fuse_gate_bwd_ws_bytes", dt(x), J, n, L)
+    ws = torch.empty(b // 4, dtype=torch.float32, device=x.device)
     if out is None:
         out = torch.empty((n, E_), dtype=torch.float32, device=x.device)
-    call("mm_expert_fuse_gate_bwd", dt(x), int(mode), _p(x), _p(dout), _p(gate), ix, J, E_, n, L, _p(out), _p(ws), b.value, _stream())
+    call("mm_expert_fuse_gate_bwd", dt(x), int(mode), _p(x), _p(dout), _p(gate), ix, J, E_, n, L, _p(out), _p(ws), b, _stream())
     return out
 
 
@@ -1405,10 +1414,7 @@ def conv2d_nhwc_dgrad(dz: torch.Tensor, wp: torch.Tensor, H: int, W: int, stride
 
 
 def conv2d_nhwc_wgrad_ws_bytes(n: int, H: int, W: int, Cin: int, Cout: int, R: int, stride: int, pad: int) -> int:
-    import ctypes
-    b = ctypes.c_int64(0)
-    call("mm_conv2d_nhwc_wgrad_ws_bytes", n, H, W, Cin, Cout, R, stride, pad, ctypes.byref(b))
-    return b.value
+    return _sizes("mm_conv2d_nhwc_wgrad_ws_bytes", n, H, W, Cin, Cout, R, stride, pad)
 
 
 def conv2d_nhwc_wgrad(dz: torch.Tensor, x: torch.Tensor, R: int, stride: int, pad: int, out: Optional[torch.Tensor] = None,

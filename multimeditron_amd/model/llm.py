@@ -138,8 +138,7 @@ class Attention(nn.Module):
             K.qk_norm_rope_fwd(qkv, B * S, Hq, Hkv, D, *self.qkn(), cos, sin, out=qkv, want_rstd=False)
         else:
             K.rope_apply_(qkv, B * S, Hq + Hkv, D, (Hq + 2 * Hkv) * D, cos, sin)
-        return (qkv[:, : Hq * D].view(B, S, Hq, D), qkv[:, Hq * D:(Hq + Hkv) * D].view(B, S, Hkv, D),
-                qkv[:, (Hq + Hkv) * D:].view(B, S, Hkv, D))
+        return Fm.qkv_views(qkv, B, S, Hq, Hkv, D)
 
     def rope_append_(self, qkv, B, cos, sin, kcache, vcache, pos):
         """A decode step's (per-head norm +) RoPE of q / k in place and the write of the new k / v rows to cache[:, pos]: one pass."""

@@ -12,6 +12,7 @@ collator's output for mock_dataset/cat.jpg.  No reference source text is copied.
 `python tools/make_golden.py gemm_plan` is a mode apart: it rewrites tests/golden/gemm_plan.jsonl (the GEMM launch decisions) from
 the built library and needs neither the reference nor a GPU (gemm_plan_table below).  `python tools/make_golden.py generate_launches`
 is another: it records generate()'s launches on a GPU into tests/golden/generate_launches.jsonl (generate_launches_table below);
+`python tools/make_golden.py train_launches` does the same for two training passes of every tiny model (train_launches_table below);
 `python tools/make_golden.py decoder_routes` records the decoder's launches per inference route, without a GPU, into
 tests/golden/decoder_routes.jsonl (decoder_routes_table below).
 
@@ -73,6 +74,25 @@ def generate_launches_table():
     print(f"generate_launches: {len(rows)} cases, {sum(len(n) for _, n in rows)} launches")
 
 
+def train_launches_table():
+    """`make_golden.py train_launches`: write tests/golden/train_launches.jsonl, the C symbols and gradient-ready calls of two
+    training passes of every tiny model (tests/train_trace.py holds the cases and the recorder; tests/test_train_launch_trace_gpu.py
+    replays them).  Needs the built library and a GPU, not the reference.  Every case is recorded twice and the two must agree.  As
+    generate_launches: run it on the revision whose launch order is the contract and commit the file as recorded."""
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    sys.path.insert(0, root)
+    from tests import train_trace as T
+    golden = os.path.join(root, "tests", "golden")
+    with tempfile.TemporaryDirectory() as tmp:
+        rows = T.record(golden, os.path.join(tmp, "a"))
+        again = T.record(golden, os.path.join(tmp, "b"))
+    assert rows == again, [a[0] for a, b in zip(rows, again) if a != b]
+    T.write(rows, golden)
+    for name, names in rows:
+        print(f"{name}: {len(names)} entries, {sum(n.startswith('ready:') for n in names)} ready, {sum('batched' in n for n in names)} grouped")
+    print(f"train_launches: {len(rows)} cases, {sum(len(n) for _, n in rows)} entries")
+
+
 def decoder_routes_table():
     """`make_golden.py decoder_routes`: write tests/golden/decoder_routes.jsonl, the C symbols CausalLM.forward queues on every
     inference route (tests/decoder_routes.py holds the cases and the recorder; tests/test_decoder_routes_cpu.py replays them).  Needs
@@ -92,6 +112,9 @@ if sys.argv[1:] == ["gemm_plan"]:
     sys.exit(0)
 if sys.argv[1:] == ["generate_launches"]:
     generate_launches_table()
+    sys.exit(0)
+if sys.argv[1:] == ["train_launches"]:
+    train_launches_table()
     sys.exit(0)
 if sys.argv[1:] == ["decoder_routes"]:
     decoder_routes_table()
