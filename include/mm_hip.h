@@ -712,6 +712,27 @@ int mm_logits_process(int dtype, const void* logits, int rows, int V, int ld, in
                       int ld_hist, const int32_t* plen, int max_plen, float repetition_penalty, int no_repeat_ngram_size,
                       int min_new_tokens, int64_t eos, const int32_t* suppress, int n_suppress, float* out, int ld_out,
                       void* stream);
+/* generate()'s classifier-free guidance (guidance_scale=; opt-in): transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor, the
+ * first processor of HF's chain, from the conditional and the unconditional logits of one step to the fp32 scores every later
+ * processor and selector reads.  cond [rows, ld_c] and uncond [rows, ld_u] (MM_BF16 / MM_F32, V valid columns; columns [V, ld) are
+ * never read): row r of uncond is the unconditional row of row r of cond.  out fp32 [rows, ld_out]; columns [V, ld_out) are never
+ * written; out overlaps neither input.
+ * Per row and per operand, in fp32: x_v = float(logit_v); lse = m + logf(sum_v expf(x_v - m)) by mm_beam_step's rule a -- per
+ * 4096-entry chunk with the chunk's own maximum, then over the chunks in chunk order with m the row's maximum --; y_v = x_v - lse.
+ *   out_v = fl(fl(scale * fl(yc_v - yu_v)) + yu_v)
+ * the three operations rounded separately, never a fused multiply-add: HF's scores = uncond + scale * (cond - uncond) on the two
+ * log_softmax rows, operation for operation (bit-equal rows of a pair give yc - yu = 0 exactly, hence out = yu at every scale).
+ * Domain: scale finite, logits finite.  A -inf or NaN logit is out of contract; it still touches nothing outside out[:, :V].
+ * Two launches (chunk maxima and sums over 2 rows x ceil(V / 4096) workgroups, then the combine over rows x ceil(V / 4096));
+ * bitwise deterministic: no atomics, no arrival counters, fixed reduction orders.  No allocation, copy or synchronisation inside
+ * (capturable).  16-byte vector loads / stores where the base and the row stride allow, scalar ones otherwise.
+ * ws: mm_cfg_ws_bytes(rows, V) bytes (the partials), 16-byte aligned.
+ * MM_ERR_ARG before any launch: another dtype, rows < 0 or > 32767, V <= 0 or V > 2^24, ld_c < V, ld_u < V, ld_out < V, a scale
+ * that is not finite, a NULL pointer (cond, uncond, out, ws; bytes of mm_cfg_ws_bytes), ws_bytes too small, out == cond or out ==
+ * uncond.  MM_ERR_ALIGN: ws not 16-byte aligned.  rows = 0: MM_OK, nothing written.                                           */
+int mm_cfg_ws_bytes(int rows, int V, int64_t* bytes);
+int mm_cfg_combine(int dtype, const void* cond, int ld_c, const void* uncond, int ld_u, int rows, int V, float scale,
+                   float* out, int ld_out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- MoE image modality: gating-weighted fusion of the experts' token features (modalities/image_modality_moe.py:163-205)
  * X [E, n, L] (L = P*C, expert-major), gate [n, E] fp32 (the gating network's softmax weights, expert order), idx[J] = the

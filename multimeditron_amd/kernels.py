@@ -1144,6 +1144,30 @@ def logits_process(logits2d, st: LogitsState, step, last_ids, eos):
     return st.out[:, :st.V]
 
 
+class GuidanceState:
+    """The device state of generate(guidance_scale=) for one call: mm_cfg_combine's workspace (the chunk partials of 2 rows log-sum-exp)
+    and the fp32 score rows [rows, V] (row stride padded to 64) the processors and selectors read.  rows = the number of
+    (conditional, unconditional) pairs."""
+
+    def __init__(self, rows, V, device):
+        self.rows, self.V = int(rows), int(V)
+        self.ws_bytes = _sizes("mm_cfg_ws_bytes", self.rows, self.V)
+        self.ws = torch.empty(max(1, (self.ws_bytes + 15) // 16) * 2, dtype=torch.int64, device=device)
+        self.ld_out = (self.V + 63) // 64 * 64
+        self.out = torch.empty((self.rows, self.ld_out), dtype=torch.float32, device=device)
+
+
+def cfg_combine(logits2d, st: GuidanceState, scale):
+    """mm_cfg_combine on ONE logits tensor [2 rows, >= V] (bf16 / fp32) of a guided decoder pass: rows [0, rows) are the conditional
+    ones, rows [rows, 2 rows) their unconditional partners -> st.out[:, :V], fp32 scores = log_softmax(uncond) + scale *
+    (log_softmax(cond) - log_softmax(uncond))."""
+    assert logits2d.stride(-1) == 1 and logits2d.shape[0] == 2 * st.rows and logits2d.shape[1] >= st.V
+    ld = logits2d.stride(0)
+    call("mm_cfg_combine", dt(logits2d), _p(logits2d), ld, _p(logits2d[st.rows:]) if st.rows else _p(logits2d), ld, st.rows, st.V,
+         float(scale), _p(st.out), st.ld_out, _p(st.ws), st.ws_bytes, _stream())
+    return st.out[:, :st.V]
+
+
 # ---- prompt-lookup speculative decoding (include/mm_hip.h: mm_lookup_draft, mm_kv_append_at, mm_lookup_accept) ----
 class LookupState:
     """The device state of generate(prompt_lookup_num_tokens=k) for one call: per row the int32 history (prompt_history's layout: the

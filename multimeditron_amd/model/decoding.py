@@ -8,6 +8,9 @@ trim.  A strategy answers only what the driver asks, in this order:
     empty(B)                 the result of max_new_tokens <= 0
     cache_args(Sp, T)        (Smax, keyword arguments) of CausalLM.new_cache for a prompt of Sp positions and T new tokens
     begin(model, cache, input_ids, mask, T)      allocate the device state, once
+    second_prefill()         asked once, between the prefill and consume(logits, 0): the arguments of a second prefill into the same
+                             cache (the unconditional prompts of classifier-free guidance), or None; with one, consume(.., 0) gets the
+                             pair (the prefill's logits, the second prefill's logits)
     consume(logits, i)       the logits of decoder pass i (0: the prefill) -> the selection, on the device
     done()                   the device flag the driver reads every sync_every passes
     feed(i)                  the arguments of decoder pass i >= 1: inputs_embeds, attention_mask, position_ids, and logits_to_keep=1
@@ -16,7 +19,7 @@ trim.  A strategy answers only what the driver asks, in this order:
     trim_eos                 whether the driver cuts the ids behind the first column at which every row has emitted eos
 
 Every pass but the prefill sits at "padded prompt length + i - 1" for every row (the reference's position quirk), or where the lookup's
-device state says."""
+device state says; the unconditional half of a guided pass sits at ITS OWN padded prompt length + i - 1."""
 import torch
 
 from .. import kernels as K
@@ -62,21 +65,65 @@ class Sampling:
     chosen, e.g. the attachment placeholder and pad ids (None or empty: off).  Compose with decode_weights, kv_cache,
     prefill_weights, num_return_sequences (every sample row keeps its own history) and every sampler path.  NOT with num_beams > 1
     (processors inside beam search act on log-probabilities inside mm_beam_step: out of scope, ValueError).  A bad value raises
-    ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids."""
+    ValueError before the modalities are encoded.  With all four off nothing changes: no launch, no buffer, the same ids.
+
+    guidance = (scale, negative_batch or None), checked by generate, else None (guidance_scale= / negative_batch=: opt-in):
+    classifier-free guidance, transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor -- the FIRST processor of HF's chain --
+    with both halves in ONE decoder pass.  Row b of the batch is paired with an unconditional row: row b of negative_batch (a collated
+    batch of the same B rows with its own input_ids / attention_mask / position_ids / processed_multimodal_inputs, e.g. the same
+    conversation without its image), or, without one, HF's default: the last id of the prompt as one position (mask 1, position 0).
+    The prefill is followed by a second prefill of the B unconditional prompts at their OWN padded length Su into rows [B, 2 B) of a
+    LayerKVCacheGuided; every later pass runs 2 B rows x 1 on one stream of the weights.  Per step, in fp32, scores =
+    log_softmax(x_u) + scale * (log_softmax(x_c) - log_softmax(x_u)) (include/mm_hip.h: mm_cfg_combine, two short launches) take the
+    place of the logits for everything that follows: the four processors (their history is the CONDITIONAL prompt's, as HF passes
+    input_ids) and greedy / torch.multinomial / the device sampler on B fp32 rows.  Both rows of a pair are fed the SAME chosen id;
+    eos bookkeeping, sync_every, the early stop and the returned [B, n_new] ids are per pair.  The conditional rows step at Sc + i - 1
+    and the unconditional ones at Su + i - 1: what generate would use for each batch alone.  The unconditional rows stream Sp + i key
+    slots (Sp = max(Sc, Su)) although only Su + i are live.  Composes with decode_weights (2 B <= 16 rows), prefill_weights (both
+    prefills), the processors and every sampler path.  NOT with num_beams > 1, num_return_sequences > 1, prompt_lookup_num_tokens
+    or kv_cache="mxfp8" (a second multi-token store into an MXFP8 cache is what LayerKVCacheMX8.accept refuses): ValueError before
+    the modalities are encoded.  guidance_scale None or 1.0 is off: no launch, no buffer, no second prefill, the same ids."""
     returns_extra, trim_eos = False, True
 
-    def __init__(self, temperature, do_sample, sampler=None, samples=1, kv_cache=None, processors=None):
+    def __init__(self, temperature, do_sample, sampler=None, samples=1, kv_cache=None, processors=None, guidance=None):
         self.temperature, self.do_sample, self.sampler = max(temperature, 1e-6), do_sample, sampler
-        self.samples, self.kv_cache, self.processors = samples, kv_cache, processors
+        self.samples, self.kv_cache, self.processors, self.guidance = samples, kv_cache, processors, guidance
+        self.negative = None
 
     def rows(self, B):
-        return B * self.samples
+        return B * self.samples * (2 if self.guidance is not None else 1)
 
     def empty(self, B):
         return torch.empty((B * self.samples, 0), dtype=torch.int64), None
 
     def cache_args(self, Sp, T):
+        if self.guidance is not None:
+            neg = self.guidance[1]
+            Sp = max(Sp, 1 if neg is None else int(neg["input_ids"].shape[1]))
+            return Sp + T, dict(guided=True, prompt_len=Sp)
         return Sp + T, (dict(samples=self.samples, prompt_len=Sp) if self.samples > 1 else dict(kv_cache=self.kv_cache))
+
+    def _begin_guidance(self, model, input_ids, mask, T):
+        """The unconditional half: its prefill's arguments, the mask [2 B, Sp + T] of the right-aligned halves, the positions."""
+        dev, (B, Sc), neg = input_ids.device, mask.shape, self.guidance[1]
+        if neg is None:                               # HF's default: the last id of the prompt, as one position
+            nmask, npos = torch.ones((B, 1), dtype=mask.dtype, device=dev), torch.zeros((B, 1), dtype=torch.long, device=dev)
+            embeds = self.emb(input_ids[:, -1:])
+        else:
+            nmask, npos = neg["attention_mask"].to(dev), neg["position_ids"].to(dev)
+            embeds = model.embed_modalities_with_text(neg["input_ids"].to(dev), neg["processed_multimodal_inputs"])
+        Su = nmask.shape[1]
+        self.negative = dict(inputs_embeds=embeds, attention_mask=nmask, position_ids=npos, logits_to_keep=1)
+        self.Sp = max(Sc, Su)
+        self.mask = torch.zeros((2 * B, self.Sp + T), dtype=mask.dtype, device=dev)
+        self.mask[:, self.Sp:] = 1
+        self.mask[:B, self.Sp - Sc:self.Sp] = mask
+        self.mask[B:, self.Sp - Su:self.Sp] = nmask
+        self.pos = torch.cat([torch.full((B, 1), Sc, dtype=torch.long, device=dev), torch.full((B, 1), Su, dtype=torch.long, device=dev)])
+        self.gs = K.GuidanceState(B, self.V, dev)
+
+    def second_prefill(self):
+        return self.negative
 
     def begin(self, model, cache, input_ids, mask, T):
         # device-resident loop state (plumbing): the growing mask is a view of one preallocated buffer
@@ -84,7 +131,9 @@ class Sampling:
         self.R = R = B * self.samples              # the rows of every buffer below and of every step after the prefill
         self.V, self.eos, self.emb = model._llm_cfg.vocab_size, model.config.eos_token_idx, model.model.get_input_embeddings()
         self.mask = mask
-        if self.samples == 1:
+        if self.guidance is not None:
+            self._begin_guidance(model, input_ids, mask, T)
+        elif self.samples == 1:
             self.mask = torch.ones((B, self.Sp + T), dtype=mask.dtype, device=dev)
             self.mask[:, :self.Sp] = mask
         self.out_ids = torch.full((R, T), self.eos, dtype=torch.int64, device=dev)
@@ -97,7 +146,11 @@ class Sampling:
             self.lp = K.LogitsState(R, self.V, dev, *self.processors, prompt_ids=input_ids, prompt_mask=mask, samples=self.samples, room=T)
 
     def consume(self, logits, i):
-        logits2d = logits[:, -1, :]                       # [rows, V] view, stride padded
+        if self.guidance is not None:                     # fp32 scores of the B pairs take the place of the logits
+            both = torch.cat([l[:, -1, :] for l in logits]) if i == 0 else logits[:, -1, :]     # plumbing: the two prefills' last rows
+            logits2d = K.cfg_combine(both, self.gs, self.guidance[0])
+        else:
+            logits2d = logits[:, -1, :]                   # [rows, V] view, stride padded
         if self.samples > 1 and i == 0:
             logits2d = logits2d.repeat_interleave(self.samples, dim=0)      # plumbing: sample j of prompt b is row b n + j
         if self.lp is not None:
@@ -116,6 +169,9 @@ class Sampling:
         return self.finished.all()
 
     def feed(self, i):
+        if self.guidance is not None:                     # both rows of a pair take the chosen id, each half at its own position
+            return dict(inputs_embeds=self.emb(self.next_ids.repeat(2).view(2 * self.R, 1)), position_ids=self.pos + (i - 1),
+                        logits_to_keep=1, attention_mask=self.mask[:, : self.Sp + i])
         nxt = self.emb(self.next_ids.view(self.R, 1))
         return dict(inputs_embeds=nxt, position_ids=_step_positions(self.R, self.Sp + i - 1, nxt.device), logits_to_keep=1,
                     attention_mask=self.mask[:, : self.Sp + i] if self.samples == 1 else self.mask)
@@ -148,6 +204,9 @@ class BeamSearch:
 
     def rows(self, B):
         return B * self.n
+
+    def second_prefill(self):
+        return None
 
     def empty(self, B):
         return torch.empty((B * self.nrs, 0), dtype=torch.int64), torch.zeros(B * self.nrs, dtype=torch.float32)
@@ -209,6 +268,9 @@ class PromptLookup:
 
     def rows(self, B):
         return B * (self.k + 1)
+
+    def second_prefill(self):
+        return None
 
     def empty(self, B):
         return torch.empty((B, 0), dtype=torch.int64), torch.zeros((B, 2), dtype=torch.int32)

@@ -548,6 +548,73 @@ class LayerKVCacheBeam(LayerKVCacheShared):
         return anc
 
 
+class LayerKVCacheGuided(LayerKVCache):
+    """The cache of generate(guidance_scale=): ONE plain LayerKVCache of 2 B rows for the B conditional sequences (rows [0, B)) and
+    their B unconditional partners (rows [B, 2 B)), whose prompts have different padded lengths Sc and Su.  It has Sp = max(Sc, Su)
+    prompt slots and room for max_new generated tokens, and takes exactly: a prefill of B rows x Sc into the empty cache (slots
+    [Sp - Sc, Sp) of rows [0, B)), then a prefill of B rows x Su (slots [Sp - Su, Sp) of rows [B, 2 B)), then steps of 2 B rows x 1.
+    Each prefill attends over its own rows alone, at its own length -- what a LayerKVCache of B rows would compute --; placing the
+    rows is device-side plumbing.  Both halves end at slot Sp, so a step is an ordinary left-padded batch of 2 B rows over Sp + i
+    keys (the base class's append and decode attention, the fused step included) under a key_mask [2 B, Sp + i] that is 0 on the
+    slots in front of the shorter half (they hold zeros).  positions() is 0 until both prefills are in: to CausalLM.forward either
+    one is a prefill into an empty cache."""
+
+    def __init__(self, B, Sp_max, max_new, Hkv, D, dtype, device):
+        super().__init__(2 * B, Sp_max + max(1, max_new), Hkv, D, dtype, device)
+        self.B, self.Sp, self.prefills = B, Sp_max, 0
+
+    def positions(self):
+        return self.len if self.prefills == 2 else 0
+
+    def append_dst(self):
+        """The base class's once both prefills are in.  None before: a one-token prompt's prefill is a decode step that `step`
+        places itself, after `accept` has seen its rows."""
+        return super().append_dst() if self.prefills == 2 else None
+
+    def accept(self, B, S):
+        if self.prefills < 2 and (B != self.B or not 1 <= S <= self.Sp):
+            raise ValueError(f"{S} new positions for {B} rows on a guided KV cache of {self.B} pairs and {self.Sp} prompt slots that holds "
+                             f"{self.prefills} of its two prefills: only the conditional prefill, then the unconditional one, each of "
+                             f"{self.B} rows and at most {self.Sp} positions, then one token per row of both halves")
+        if self.prefills == 2 and (B != 2 * self.B or S != 1 or self.len >= self.k.shape[1]):
+            raise ValueError(f"{S} new positions for {B} rows on a guided KV cache of {self.B} pairs that holds both prefills and "
+                             f"{self.len} of {self.k.shape[1]} positions: only one token for each of its {2 * self.B} rows")
+
+    def _half(self, S):
+        """(k, v, first slot) of the half the coming prefill of S positions fills."""
+        rows = slice(self.prefills * self.B, (self.prefills + 1) * self.B)
+        return self.k[rows], self.v[rows], self.Sp - S
+
+    def _filled(self):
+        self.prefills += 1
+        if self.prefills == 2:
+            self.len = self.Sp
+
+    @torch.no_grad()
+    def attend(self, qkv, cos, sin, key_mask, B, S, a: Attention):
+        if self.prefills == 2:
+            return super().attend(qkv, cos, sin, key_mask, B, S, a)
+        Hq, D = a.Hq, a.D
+        self.accept(B, S)
+        q, kn, vn = a.rope_views(qkv, cos, sin, B, S)
+        k, v, at = self._half(S)
+        k[:, at:at + S].copy_(kn)      # device-side memory plumbing
+        v[:, at:at + S].copy_(vn)
+        self._filled()
+        if S == 1 and K.attn_decode_supported(qkv.dtype, Hq, a.Hkv, D):
+            return K.attn_decode(q.view(B, Hq, D), k[:, at:at + S], v[:, at:at + S], key_mask, D ** -0.5).view(B, Hq * D)
+        return K.attn_fwd(q, k[:, at:at + S], v[:, at:at + S], key_mask, True, D ** -0.5)[0].view(B * S, Hq * D)
+
+    def step(self, qkv, cos, sin, key_mask, B, S, a: Attention, appended):
+        self.accept(B, S)
+        if self.prefills == 2:
+            return super().step(qkv, cos, sin, key_mask, B, S, a, appended)
+        k, v, at = self._half(1)       # a one-token prompt (HF's default unconditional prompt): a decode step over its own key
+        a.rope_append_(qkv, B, cos, sin, k, v, at)
+        self._filled()
+        return K.attn_decode(qkv[:, : a.Hq * a.D].view(B, a.Hq, a.D), k[:, at:at + 1], v[:, at:at + 1], key_mask, a.D ** -0.5).view(B, a.Hq * a.D)
+
+
 class LayerKVCacheLookup(LayerKVCache):
     """The cache of generate(prompt_lookup_num_tokens=k): a bf16 LayerKVCache [B, Smax, Hkv, D] whose rows advance by DIFFERENT
     amounts per verify step, so where a row stands is not a host integer: `shared.base` (int32 [B] on the device, advanced by
@@ -832,7 +899,7 @@ class CausalLM(nn.Module):
             raise ValueError(f"{name}={value!r} cannot be used: {why}")
 
     def new_cache(self, B, Smax, kv_cache: Optional[str] = None, samples: int = 1, prompt_len: Optional[int] = None, beams: int = 1,
-                  lookup: Optional[int] = None):
+                  lookup: Optional[int] = None, guided: bool = False):
         """kv_cache="mxfp8": LayerKVCacheMX8 (about half the bytes per cached position); ValueError when kv_cache_ok says it cannot.
         samples=n > 1: LayerKVCacheShared for B prompts of at most prompt_len positions and n sample rows each with room for
         Smax - prompt_len generated tokens; ValueError when samples_ok says it cannot, or together with kv_cache.
@@ -840,8 +907,18 @@ class CausalLM(nn.Module):
         step's ancestor table); ValueError when beams_ok says it cannot, or together with kv_cache or samples.
         lookup=k >= 1: LayerKVCacheLookup (prompt-lookup decoding with drafts of k tokens; Smax includes the k slots a last verify step
         may write behind the last emitted id), every layer holding the SAME `shared` object (its base / bound are the decode loop's to
-        set); ValueError when lookup_ok says it cannot, or together with kv_cache, samples or beams."""
+        set); ValueError when lookup_ok says it cannot, or together with kv_cache, samples or beams.
+        guided=True: LayerKVCacheGuided (classifier-free guidance) for B (conditional, unconditional) pairs -- 2 B rows -- of at most
+        prompt_len positions each with room for Smax - prompt_len generated tokens; ValueError together with any of the others."""
         c = self.config
+        if guided:
+            if kv_cache is not None or samples != 1 or beams != 1 or lookup is not None:
+                raise ValueError(f"guided=True with kv_cache={kv_cache!r}, samples={samples!r}, beams={beams!r}, lookup={lookup!r}: the "
+                                 "guided cache is a plain one whose rows are the two halves of every pair")
+            if prompt_len is None or not 1 <= int(prompt_len) <= Smax:
+                raise ValueError(f"guided=True needs prompt_len in [1, Smax = {Smax}], got {prompt_len!r}")
+            return [LayerKVCacheGuided(B, int(prompt_len), Smax - int(prompt_len), c.num_key_value_heads, c.head_dim, self.dtype,
+                                       self.device) for _ in range(c.num_hidden_layers)]
         val = dict(lookup=lookup, beams=beams, samples=samples, kv_cache=kv_cache)
         on = dict(lookup=lookup is not None, beams=beams != 1, samples=samples != 1, kv_cache=kv_cache is not None)
         shape = (c.num_key_value_heads, c.head_dim, self.dtype, self.device)

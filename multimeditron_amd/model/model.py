@@ -469,7 +469,8 @@ class MultiModalModelForCausalLM(nn.Module):
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                  min_new_tokens: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
-                 return_lookup_stats: bool = False, **kwargs) -> torch.Tensor:
+                 return_lookup_stats: bool = False, guidance_scale: Optional[float] = None,
+                 negative_batch: Optional[Dict[str, Any]] = None, **kwargs) -> torch.Tensor:
         """model.py:528-640: KV-cache decode.  Token choice = argmax(softmax(logits/T)) (one kernel) or a per-row
         multinomial draw; decode position = padded prompt length + i - 1 for every row (reference quirk :582-586);
         rows that already emitted eos keep emitting eos; returns [B, n_new] int64 on CPU without the prompt.
@@ -508,7 +509,15 @@ class MultiModalModelForCausalLM(nn.Module):
 
         num_return_sequences=n > 1, repetition_penalty= / no_repeat_ngram_size= / min_new_tokens= / suppress_tokens=, num_beams=n > 1 and
         prompt_lookup_num_tokens=k (each opt-in): see decoding.Sampling, decoding.BeamSearch and decoding.PromptLookup, the strategies
-        the one decode loop (_decode) runs for them."""
+        the one decode loop (_decode) runs for them.
+
+        guidance_scale=s with negative_batch= (opt-in): classifier-free guidance in ONE decoder pass per token, transformers'
+        guidance_scale / negative_prompt_ids (UnbatchedClassifierFreeGuidanceLogitsProcessor): scores = log_softmax(uncond) + s *
+        (log_softmax(cond) - log_softmax(uncond)) replace the logits in front of the processors and the selection.  negative_batch is
+        a collated batch of the same B rows (input_ids, attention_mask, position_ids, processed_multimodal_inputs; with modalities of
+        its own or none, e.g. the same conversation without its image: contrastive decoding against the language prior); None gives
+        HF's default, the last prompt id as one position.  s: a finite number, not a bool; None or 1.0 is off and nothing changes
+        (negative_batch must then be None).  See decoding.Sampling for the rows, positions and what it does not compose with."""
         n = _int_arg("num_return_sequences", num_return_sequences, 1)
         nb = _int_arg("num_beams", num_beams, 1, 16)
         pk, mg = prompt_lookup_num_tokens, max_matching_ngram_size
@@ -525,11 +534,19 @@ class MultiModalModelForCausalLM(nn.Module):
         if processors is not None:
             val["processors"] = ", ".join(k for k, v in zip(("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens"),
                                                             (processors[0] != 1.0, processors[1] > 0, processors[2] > 0, len(processors[3]) > 0)) if v)
+        guided = guidance_scale is not None and float(_number_arg("guidance_scale", guidance_scale)) != 1.0
+        if negative_batch is not None and not guided:
+            raise ValueError(f"negative_batch needs guidance_scale (a finite number other than 1.0), got guidance_scale={guidance_scale!r}")
+        on["guidance"], val["gs"] = guided, guidance_scale
+        if guided and negative_batch is not None:
+            missing = [k for k in ("input_ids", "attention_mask", "position_ids", "processed_multimodal_inputs") if k not in negative_batch]
+            if missing:
+                raise ValueError(f"negative_batch (guidance_scale={guidance_scale!r}) lacks {', '.join(missing)}: a collated batch is expected")
         if pk is not None:
             _int_arg("prompt_lookup_num_tokens", pk, 1)
             mg = _int_arg("max_matching_ngram_size", 2 if mg is None else mg, 1)
         _refuse(_REFUSALS[1:], on, val)
-        opt_in = pk is not None or nb > 1 or n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights))
+        opt_in = guided or pk is not None or nb > 1 or n > 1 or any(v is not None for v in (kv_cache, decode_weights, prefill_weights))
         B, Sp = (int(d) for d in batch["input_ids"].shape[:2]) if opt_in else (None, None)
         own = None                               # the mode's own entry of CausalLM.OPTIONS
         if pk is not None:
@@ -544,9 +561,13 @@ class MultiModalModelForCausalLM(nn.Module):
                 raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
             strategy, own = BeamSearch(nb, n, float(length_penalty), early_stopping, return_beam_scores), ("num_beams", nb)
         else:
-            strategy = Sampling(temperature, do_sample, None, n, kv_cache, processors)
+            strategy = Sampling(temperature, do_sample, None, n, kv_cache, processors,
+                                (float(guidance_scale), negative_batch) if guided else None)
             if n > 1:
                 own = ("num_return_sequences", n)
+            if guided and negative_batch is not None and tuple(negative_batch["input_ids"].shape[:1]) != (B,):
+                raise ValueError(f"negative_batch of {tuple(negative_batch['input_ids'].shape)[0]} rows with guidance_scale={guidance_scale!r} "
+                                 f"on a batch of {B}: one unconditional row per row")
         if opt_in:                               # a call without opt-ins reads neither the batch nor the decoder before _decode
             llm = self.model
             if own is not None:
@@ -554,6 +575,9 @@ class MultiModalModelForCausalLM(nn.Module):
             llm.check_option("kv_cache", kv_cache, B)
             llm.check_option("decode_weights", decode_weights, strategy.rows(B))                  # the rows of a decode step
             llm.check_option("prefill_weights", prefill_weights, B, Sp, check_grad=False)         # the loop runs under no_grad
+            if guided:                                                                            # the second prefill, at its own length
+                llm.check_option("prefill_weights", prefill_weights, B, 1 if negative_batch is None else int(negative_batch["input_ids"].shape[1]),
+                                 check_grad=False)
         if do_sample and given:
             strategy.sampler = _device_sampler(top_k, top_p, min_p, seed, generator)
         return self._decode(strategy, batch, max_new_tokens, sync_every, decode_weights, prefill_weights)
@@ -601,9 +625,12 @@ class MultiModalModelForCausalLM(nn.Module):
             cache = llm.new_cache(mask.shape[0], Smax, **kw)
             strategy.begin(self, cache, input_ids, mask, max_new_tokens)
             for i in range(max_new_tokens):
-                out = llm(past_key_values=cache, use_cache=True, **feed, **dw, **pw)
+                logits = llm(past_key_values=cache, use_cache=True, **feed, **dw, **pw).logits
+                second = strategy.second_prefill() if i == 0 else None
+                if second is not None:
+                    logits = (logits, llm(past_key_values=cache, use_cache=True, **second, **dw, **pw).logits)
                 pw = {}
-                strategy.consume(out.logits, i)
+                strategy.consume(logits, i)
                 if i + 1 == max_new_tokens:
                     break
                 if (i + 1) % max(1, sync_every) == 0 and bool(strategy.done()):      # the only host sync of the loop
@@ -650,6 +677,11 @@ _REFUSALS = (
     ("samples", "greedy", "num_return_sequences={n} needs do_sample=True: greedy decoding would return {n} identical rows"),
     ("samples", "kv_cache", "num_return_sequences={n} with kv_cache={kv_cache!r}: the shared-prefix cache is bf16 only (an MXFP8 "
                             "shared-prefix cache is out of scope)"),
+    ("guidance", "beams", "guidance_scale={gs} with num_beams={nb}: guidance inside beam search is out of scope"),
+    ("guidance", "samples", "guidance_scale={gs} with num_return_sequences={n}: guided samples over a shared prompt are out of scope"),
+    ("guidance", "lookup", "guidance_scale={gs} with prompt_lookup_num_tokens={pk}: guided verify steps are out of scope"),
+    ("guidance", "kv_cache", "guidance_scale={gs} with kv_cache={kv_cache!r}: the guided cache is bf16 only (the second prefill would be "
+                             "a multi-token store into a filled MXFP8 cache)"),
 )
 
 

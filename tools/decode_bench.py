@@ -3,6 +3,7 @@
    python tools/decode_bench.py [B] [S] [new_tokens] [--sample top_p=0.95,T=0.7] [--decode-weights mxfp8] [--kv-cache mxfp8]
                                 [--prefill-weights mxfp8] [--samples n] [--beams n]
                                 [--processors repetition_penalty=1.2,no_repeat_ngram_size=3] [--lookup K[,G]]
+                                [--guidance S[,negative=last|text]]
 --sample: the device sampler (generate(do_sample=True, ...)) with the listed settings (T, top_k, top_p, min_p, seed) instead of
 the greedy selection.  --decode-weights mxfp8: the decode steps stream the weight-only MXFP8 copies (generate(decode_weights=...));
 the copies are made by the warm-up call, outside the timed ones.  --kv-cache mxfp8: the KV cache is kept in MXFP8
@@ -28,7 +29,13 @@ scores instead of bf16 logits).  The other flags apply to both sides.
 without the lookup, alternating, best of three each after a warm-up: ms per verify iteration against ms per plain step (their ratio
 is the number that transfers), accepted drafts per iteration and tokens/s (this model's weights are random: its acceptance rate is
 whatever its loops give); then the launches alone -- mm_attn_decode_verify against mm_attn_decode over 16 layers' caches, and
-mm_lookup_draft / mm_kv_append_at / mm_lookup_accept.  --decode-weights and --prefill-weights apply to both sides."""
+mm_lookup_draft / mm_kv_append_at / mm_lookup_accept.  --decode-weights and --prefill-weights apply to both sides.
+--guidance S[,negative=last|text]: in this one process, greedy generate(guidance_scale=S) -- the conditional and the unconditional
+rows in ONE decoder pass of 2 B rows -- against plain greedy at B rows and against the two-pass form it replaces, alternating, best
+of three each after a warm-up.  negative=last (default): HF's default unconditional prompt, the last id as one position; negative=text:
+the batch without its image spans (negative_batch=).  The two-pass form is a plain step of the B prompts plus a plain step of the B
+unconditional prompts per token (each timed as a plain generate of that batch alone), reported as `2 x plain`; prefill + 1 token of
+all three.  --decode-weights and --prefill-weights apply to every side."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -84,6 +91,13 @@ LOOKUP = None
 if "--lookup" in sys.argv:
     i = sys.argv.index("--lookup")
     LOOKUP = [int(t) for t in sys.argv[i + 1].split(",")]
+    del sys.argv[i:i + 2]
+GUIDE = None
+if "--guidance" in sys.argv:
+    i = sys.argv.index("--guidance")
+    parts = sys.argv[i + 1].split(",")
+    GUIDE = (float(parts[0]), dict(kv.split("=") for kv in parts[1:]).get("negative", "last"))
+    assert GUIDE[1] in ("last", "text"), GUIDE
     del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -374,6 +388,59 @@ def compare_lookup(k, G=2):
     timed(f"mm_lookup_accept ({B} rows)", lambda i: K.lookup_accept(st, tokq))
 
 
+def compare_guidance(scale, kind):
+    kw = {"decode_weights": DW} if DW else {}
+    if PW:
+        kw["prefill_weights"] = PW
+    ids, mm = batch["input_ids"], batch["processed_multimodal_inputs"]
+    none = {"batch_idx": {}, "token_range": {}, "stacked": {}}
+    if kind == "text":                                     # the same rows without their image spans (every row loses as many positions)
+        keep = torch.ones_like(ids, dtype=torch.bool)
+        keep[mm["batch_idx"]["image"].long(), mm["token_range"]["image"].long()] = False
+        nids = ids[keep].view(B, -1)
+    else:
+        nids = ids[:, -1:]
+    Su = nids.shape[1]
+    neg = dict(input_ids=nids, attention_mask=torch.ones(B, Su, dtype=torch.long, device="cuda"),
+               position_ids=torch.arange(Su, device="cuda")[None, :].expand(B, Su).contiguous(), processed_multimodal_inputs=none)
+    sides = {"plain": lambda new: model.generate(batch, max_new_tokens=new, temperature=0.1, do_sample=False, **kw),
+             "unconditional alone": lambda new: model.generate(neg, max_new_tokens=new, temperature=0.1, do_sample=False, **kw),
+             "guided": lambda new: model.generate(batch, max_new_tokens=new, temperature=0.1, do_sample=False, guidance_scale=scale,
+                                                  negative_batch=neg if kind == "text" else None, **kw)}
+
+    def go(name, new):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = sides[name](new)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    for name in sides:
+        go(name, 2)                                        # warm-up (and the MXFP8 copies, if asked for)
+    t1, tn, shape = {k: [] for k in sides}, {k: [] for k in sides}, {}
+    for _ in range(3):                                     # alternating
+        for name in sides:
+            t1[name].append(go(name, 1)[0])
+            dt, out = go(name, N)
+            tn[name].append(dt)
+            shape[name] = tuple(out.shape)
+    first, per = {}, {}
+    for name in sides:
+        a, b = min(t1[name]), min(tn[name])
+        first[name], per[name] = a * 1e3, (b - a) / (N - 1) * 1e3
+        print(f"B={B} S={S}{' decode_weights ' + DW if DW else ''} {name} ({Su if name == 'unconditional alone' else S} prompt positions): "
+              f"prefill+1 token {first[name]:.1f} ms; decode {per[name]:.3f} ms/token (all runs "
+              f"{', '.join(f'{(y - x) / (N - 1) * 1e3:.3f}' for x, y in zip(t1[name], tn[name]))}); ids {shape[name]}", flush=True)
+    two = per["plain"] + per["unconditional alone"]
+    print(f"guidance_scale={scale} negative={kind} (Su = {Su}): guided step {per['guided']:.3f} ms = {per['guided'] / per['plain']:.2f} x plain "
+          f"({per['plain']:.3f}) = {per['guided'] / two:.2f} x `2 x plain` ({two:.3f}: a plain step of the prompts + one of the unconditional "
+          f"prompts); prefill+1 token {first['guided']:.1f} ms against {first['plain']:.1f} plain, "
+          f"{first['plain'] + first['unconditional alone']:.1f} two-pass", flush=True)
+
+
+if GUIDE:
+    compare_guidance(*GUIDE)
+    sys.exit(0)
 if LOOKUP:
     compare_lookup(*LOOKUP)
     sys.exit(0)

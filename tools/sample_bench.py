@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """mm_sample alone on the decoder's vocabulary (V = 128 258, bf16 logits) beside the greedy selection mm_argmax_softmax_split on the
 same rows, and the logits processors' launch mm_logits_process (repetition penalty 1.2, 3-gram ban, a history of 2048 + 512 ids) on
-them (run on the GPU box).  HIP events around 200 back-to-back calls after 20 warm-up calls.
+them, and classifier-free guidance's mm_cfg_combine (two launches) on 1 / 4 / 8 pairs of such rows (run on the GPU box).  HIP events
+around 200 back-to-back calls after 20 warm-up calls.
    python tools/sample_bench.py [--iters N]"""
 import argparse
 import os
@@ -59,6 +60,14 @@ def main():
         mb = rows * V * 6 / 1e6
         print(f"rows={rows:2d}  logits_process p=1.2 g=3 history {hist_len + room} {full:6.1f} us | no history (min_new_tokens only) "
               f"{copy:6.1f} us | {mb:.1f} MB of logits in and scores out, {mb / full:.2f} TB/s", flush=True)
+    # classifier-free guidance: the conditional and the unconditional rows of one logits tensor -> fp32 scores (2 launches)
+    for pairs in (1, 4, 8):
+        lg = (torch.randn(2 * pairs, ld, device="cuda") * 3).to(torch.bfloat16)[:, :V]
+        st = K.GuidanceState(pairs, V, "cuda")
+        us = timed(lambda: K.cfg_combine(lg, st, 3.0), args.iters)
+        mb = pairs * V * (2 * 2 * 2 + 4) / 1e6               # both rows read twice (bf16), the scores written once (fp32)
+        print(f"pairs={pairs:2d} ({2 * pairs:2d} rows)  cfg_combine {us:6.1f} us | {mb:.1f} MB of logits in (twice) and scores out, "
+              f"{mb / us:.2f} TB/s", flush=True)
 
 
 if __name__ == "__main__":
